@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the CURL+SAC learner hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--no-others] [--dry-run]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5|c1t] [--full] [--dump-outputs DIR] [--dry-run]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one ``CurlSacAgent.update()`` (critic + [actor/alpha + target soft
@@ -16,11 +16,24 @@ configuration (default c2 = configs[1], the one the metric is quoted on):
 With N>1 every rank does the same on its own ring shard and the gradient buckets
 are all-reduced over RCCL (weak scaling).  Prints ONE JSON line on rank 0.
 
-Without ``--config`` the line's ``metric`` / ``value`` / ``config`` are c2's and, at N = 1, the same process then
-measures c1t, c3 and c5 as well (the c2 ring is freed first) and reports them under ``other_configs`` -- each with its own
-``value``, ``ms_per_step``, ``steps``, ``roofline`` and ``cpu_baseline``; ``--no-others`` or an explicit ``--config``
-measures one configuration only.  At N > 1 only c2 is measured unless ``--others`` asks for all three (a failure in a
-secondary configuration of a multi-GPU job would take the headline line down with it).
+A plain run does only what the headline figure needs: it sets up one configuration (c2 unless ``--config`` names
+another), warms up, times exactly K updates and prints the line -- ``metric``, ``value`` (updates/s), ``unit``,
+``ms_per_step``, ``higher_is_better``, ``dtype`` and the configuration it ran.
+
+``--full`` adds everything else the benchmark measures.  Without ``--config`` the line's ``metric`` / ``value`` /
+``config`` are c2's and, at N = 1, the same process then measures c1t, c3 and c5 as well (the c2 ring is freed first) and
+reports them under ``other_configs`` -- each with its own ``value``, ``ms_per_step``, ``steps``, ``roofline`` and
+``cpu_baseline``; ``--no-others`` or an explicit ``--config`` measures one configuration only.  At N > 1 only c2 is
+measured unless ``--others`` asks for all three (a failure in a secondary configuration of a multi-GPU job would take
+the headline line down with it); ``--others`` asks for them without ``--full`` as well.  Every configuration of a
+``--full`` run also carries the roofline figures (HIP-event timing of the dominant kernel on a sample of the timed
+steps, the matrix-pipe and fp32-roofline fractions, HBM traffic and matrix-pipe busy fraction measured live by child runs
+under ``rocprofv3 --pmc`` for the headline configuration) and, at N = 1, the oracle's CPU baseline.
+
+``--dump-outputs DIR``: after the timed steps, what the last timed update computed -- the parameters it left in the
+critic, the target critic, the actor and CURL's W, log_alpha and its critic loss -- is written as ``DIR/<name>.npy``
+(float32; log_alpha float64), at most 64 MB in all (dump_outputs).  The inputs depend on the arguments only (seeded
+initialisation, ring and sampling), so two builds of the project can be compared output for output.
 
 At N > 1 BOTH data-parallel schedules are measured (``--schedule auto``, the default): the blocking one (one all-reduce
 per gradient bucket in front of its optimizer step) and the overlapped one (each bucket in two asynchronous pieces under
@@ -161,6 +174,38 @@ class NullLogger:
         pass
 
     log_histogram = log_param = log_image = log
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per array: a larger one is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(agent, batch, out_dir, step):
+    """--dump-outputs: what update() computed in its last timed step, as its caller receives it -- the parameters it
+    left in the critic, the target critic and the actor (state_dict keys and layouts), CURL's W and log_alpha, and the
+    critic loss of that step -- one ``out_dir/<name>.npy`` each, float32 (log_alpha float64).  An array of more than
+    DUMP_MAX_ELEMS elements is written flattened, as its elements at DUMP_MAX_ELEMS positions drawn by RandomState(0)
+    (sorted; the same positions for the same size).  Returns the summary the line reports."""
+    arrays = {}
+    for prefix, module in (("critic", agent.critic), ("critic_target", agent.critic_target), ("actor", agent.actor)):
+        for k, v in module.state_dict().items():
+            arrays[f"{prefix}.{k}"] = v
+    arrays["curl.W"] = agent.CURL.W
+    arrays["log_alpha"] = agent.log_alpha
+    arrays["critic_loss"] = agent._ws(batch).scalars[0]
+    os.makedirs(out_dir, exist_ok=True)
+    total, sampled = 0, []
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pos]
+            sampled.append(name)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "step": step, "arrays": len(arrays), "bytes": total, "sampled": sampled}
 
 
 def _oracle_sample(cfg, batch, calls, budget_s, threads):
@@ -383,12 +428,13 @@ class Job:
             _lib.set_trace_hook(None)
 
 
-def measure(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, overlap=None):
+def measure(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, overlap=None, dump_dir=None):
     """One configuration: build agent + ring shard, prime, warm up, time ``steps`` updates between barriers.
     Returns the result object on rank 0 (None elsewhere).  Everything it allocated is released on return.
     ``pg`` / ``n``: the process group and the number of ranks this measurement runs on (default: all of the job's;
     the sweep passes ranks 0 .. n-1 -- only they call); ``overlap``: the data-parallel schedule (None: the agent's
-    default, CURLA_DP_OVERLAP)."""
+    default, CURLA_DP_OVERLAP); ``dump_dir``: rank 0 writes the last timed update's outputs there (dump_outputs).
+    The roofline figures (and the kernel timing they need) are taken with ``--full`` only."""
     import curla_amd
     from curla_amd import ops
     args, cfg, dev, rank = job.args, CONFIGS[name], job.dev, job.rank
@@ -484,7 +530,9 @@ def measure(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, overla
         if ok:
             ev_pairs.append((e0, e1, fl, by))
         return ok
-    ops.conv_s1_fwd, ops.conv_s1_fwd2, ops.conv_s1_fwd_stack = timed_s1, timed_s1_2, timed_stack
+    if args.full:
+        ops.conv_s1_fwd, ops.conv_s1_fwd2, ops.conv_s1_fwd_stack = timed_s1, timed_s1_2, timed_stack
+    dumped = None
     try:
         # one priming update outside everything (workspaces, split-K buffers and the Adam states are allocated on
         # first use), so that even --warmup 0 times steady-state steps; then the W untimed warm-up steps
@@ -527,7 +575,10 @@ def measure(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, overla
         recording[0] = False
         job.barrier(pg, world)
         dt = time.perf_counter() - t0
-        if graphed:  # a replayed update makes no host-side launch to put events around: time the kernel on eager updates
+        if dump_dir is not None and rank == 0:
+            dumped = dump_outputs(agent, B, dump_dir, step - 1)
+        if graphed and args.full:
+            # a replayed update makes no host-side launch to put events around: time the kernel on eager updates
             agent.disable_update_graphs()
             recording[0] = True
             for _ in range(8):
@@ -584,40 +635,7 @@ def measure(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, overla
 
     out = None
     if rank == 0:
-        kflops = sum(p[2] for p in ev_pairs)
-        kbytes = sum(p[3] for p in ev_pairs)
-        kms = sum(p[0].elapsed_time(p[1]) for p in ev_pairs)
-        achieved = kflops / (kms * 1e-3) / 1e12 if kms > 0 else 0.0
         updates_per_s = world * steps / dt
-        per_update = sum(flops_per_update(cfg, first_step + i) for i in range(steps)) / steps
-        # the dominant kernel: all stride-1 forward layers of two minibatches in one launch when the batch sizes allow,
-        # else one launch per layer
-        stacked = B % job.cu_count() == 0  # (ops.stack_granule(): one workgroup per CU owns its samples)
-        # which form the stride-1 forward takes (option s1_fwd, curla_amd/csrc/conv.hip launch_rw_fwd): auto = b3, the
-        # bf16-matrix-core form with fp32 operands split into three bf16 parts (conv_rwb.h); f23 / f43 = Winograd on the
-        # f32-input MFMA
-        from curla_amd import _lib as _clib
-        s1 = "auto" if job.dry else _clib.get_option("s1_fwd")
-        kname, wino, wino_factor, mfma, peak_tf, terms = {
-            "auto": ("conv_rwb_fwd_kernel", "F(2,3)", 1.5, "bf16 MFMA 16x16x32, fp32 operands as three bf16 parts", PEAK_BF16_TFLOPS, 6),
-            "b3": ("conv_rwb_fwd_kernel", "F(2,3)", 1.5, "bf16 MFMA 16x16x32, fp32 operands as three bf16 parts", PEAK_BF16_TFLOPS, 6),
-            "f23": ("conv_rw_fwd_kernel", "F(2,3)", 1.5, "f32 MFMA 16x16x4", PEAK_F32_TFLOPS, 1),
-            "f43": ("conv_rw43_fwd_kernel", "F(4,3)", 2.0, "f32 MFMA 16x16x4", PEAK_F32_TFLOPS, 1)}[s1]
-        issued = achieved / wino_factor * terms  # what the matrix pipe executes, in its own FLOPs
-        traffic, mfma_busy, pmc_note = (None, None, "dry run") if job.dry else committed_counters(name, kname)
-        pmc_live = False
-        if (not job.dry and not args.no_live_pmc and world == 1 and name == (args.config or "c2") and with_cpu_baseline):
-            # (the headline configuration of a plain one-GPU run: counters measured live, by child runs under rocprofv3)
-            torch.cuda.empty_cache()
-            live = live_counters(name, kname)
-            if live is not None:
-                traffic, mfma_busy, pmc_note = live
-                pmc_live = True
-        opts = {} if job.dry else {k: _clib.get_option(k) for k in ("s1_fwd", "s1_wgrad", "conv1_u8", "wgrad1_u8")}
-        pipe_s = sum(matrix_pipe_seconds_per_update(cfg, first_step + i, opts) for i in range(steps)) / steps
-        clock = None if (job.dry or name != "c2") else committed_clock(kname)
-        n_launch = max(1, len(ev_pairs))
-        avg_ms = kms / n_launch
         out = {
             "metric": cfg["metric"],
             "value": updates_per_s,
@@ -636,55 +654,96 @@ def measure(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, overla
                                            "none (the reference's shipped geometry, beside BASELINE.json's)"),
                        "replay_capacity": cap * world, "shards": shards, "prefill": prefill,
                        "parallelism": f"dp{world}", "priming_updates": 1, "clock_warmup_s": args.clock_warmup_s,
-                       "update_graphs": graphed},
+                       "update_graphs": graphed, "full": bool(args.full)},
             "transitions_per_s": updates_per_s * B,
-            "conv_algorithmic_gflop_per_update": per_update / 1e9,
-            "conv_roofline_frac_whole_update": per_update * (steps / dt) / (PEAK_F32_TFLOPS * 1e12),
-            "conv_roofline_note": "SURVEY.md 8d accounting (the north star's 'fraction of the conv roofline'): direct-conv "
-                                  "FLOPs of the update / time against the 157.3 TFLOP/s fp32 peak.  Read it as the SPEED-UP "
-                                  "over what the fp32 pipe could do at best, not as a fraction bounded by 1: the kernels skip "
-                                  "work (Winograd) and run most of it on the bf16 matrix cores.  matrix_pipe_time_frac_whole_"
-                                  "update is the bounded figure",
-            "matrix_pipe_time_frac_whole_update": pipe_s / (dt / steps),
-            "matrix_pipe_time_note": "time the two matrix pipes would need at their dense peaks (bf16 2.5 PFLOP/s, f32-input "
-                                     "157.3 TFLOP/s) for the conv work as the kernels issue it (Winograd factors and bf16x3 "
-                                     "products counted, padding not) / measured time per update",
-            "roofline": {"bound": "mfma",
-                         "kernel": (f"{kname} (row-walk Winograd {wino} along x: all 3x3 s1 32->32 + bias + ReLU layers of "
-                                    f"two minibatches per launch, {mfma})")
-                                   if stacked else
-                                   f"{kname} (row-walk Winograd {wino} along x: one 3x3 s1 32->32 + bias + ReLU layer per "
-                                   f"launch, {mfma})",
-                         # The kernel is Winograd F(2,3) / F(4,3) along x: it issues 1/1.5 resp. 1/2 of the direct-
-                         # convolution FLOPs of SURVEY.md 8(d).  `achieved` / `frac` are what the matrix pipe really
-                         # executes (compare with 1.0 and with `mfma_busy_frac_pmc`); the SURVEY 8(d) accounting in
-                         # direct-conv FLOPs, which can exceed 1 because the algorithm skips work, is under `direct_equiv_*`.
-                         "achieved": issued, "peak": peak_tf, "unit": "TFLOP/s",
-                         "frac": issued / peak_tf, "traffic": traffic,
-                         "achieved_note": (f"MFMA FLOPs issued = algorithmic direct-conv FLOPs / {wino_factor} (Winograd "
-                                           f"{wino} in one dimension; strip padding not counted)"
-                                           + (f" x {terms} (six bf16 x bf16 products per fp32 product: x = xh + xm + xl exactly, the "
-                                              "three products below 2^-24 dropped), against the dense bf16 MFMA peak" if terms > 1 else "")),
-                         "direct_equiv_achieved": achieved, "direct_equiv_frac": achieved / PEAK_F32_TFLOPS,
-                         "direct_equiv_note": "direct-conv TFLOP/s of the launch and their ratio to the fp32 peak: a speed-up "
-                                              "over that pipe's best case, not a utilisation (see frac)",
-                         "in_kernel_clock": clock,
-                         "traffic_unit": "HBM bytes per launch; " + pmc_note, "pmc_measured_live": pmc_live,
-                         "algorithmic_bytes_per_launch": kbytes / n_launch,
-                         "launches": len(ev_pairs), "avg_launch_ms": avg_ms,
-                         "launch_timing": ("HIP events around the kernel's launches in 8 eager updates right after the "
-                                           "timed region (the timed updates are graph replays)" if graphed else
-                                           "HIP events around the kernel's launches inside the timed region"),
-                         "hbm_GBps": (traffic / (avg_ms * 1e-3) / 1e9) if (traffic and avg_ms > 0) else None,
-                         # the kernel's other roof: its ALGORITHMIC bytes (every activation read and written once) / its
-                         # launch time against the 8 TB/s HBM peak.  Round 6 found the time per sample the same at 1.7 and
-                         # 2.33 GHz: this, not the matrix pipe, is what bounds it (torch's streaming copy / add kernels
-                         # reach 4.8 / 6.0 TB/s on this chip: tools/hbm_mixed.py)
-                         "hbm_algorithmic_GBps": (kbytes / n_launch) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else None,
-                         "hbm_algorithmic_frac": (kbytes / n_launch) / (avg_ms * 1e-3) / 8e12 if avg_ms > 0 else None,
-                         "hbm_peak_GBps": 8000.0,
-                         "mfma_busy_frac_pmc": mfma_busy},
         }
+        if dumped is not None:
+            out["outputs"] = dumped
+        if args.full:
+            kflops = sum(p[2] for p in ev_pairs)
+            kbytes = sum(p[3] for p in ev_pairs)
+            kms = sum(p[0].elapsed_time(p[1]) for p in ev_pairs)
+            achieved = kflops / (kms * 1e-3) / 1e12 if kms > 0 else 0.0
+            per_update = sum(flops_per_update(cfg, first_step + i) for i in range(steps)) / steps
+            # the dominant kernel: all stride-1 forward layers of two minibatches in one launch when the batch sizes allow,
+            # else one launch per layer
+            stacked = B % job.cu_count() == 0  # (ops.stack_granule(): one workgroup per CU owns its samples)
+            # which form the stride-1 forward takes (option s1_fwd, curla_amd/csrc/conv.hip launch_rw_fwd): auto = b3, the
+            # bf16-matrix-core form with fp32 operands split into three bf16 parts (conv_rwb.h); f23 / f43 = Winograd on the
+            # f32-input MFMA
+            from curla_amd import _lib as _clib
+            s1 = "auto" if job.dry else _clib.get_option("s1_fwd")
+            kname, wino, wino_factor, mfma, peak_tf, terms = {
+                "auto": ("conv_rwb_fwd_kernel", "F(2,3)", 1.5, "bf16 MFMA 16x16x32, fp32 operands as three bf16 parts",
+                         PEAK_BF16_TFLOPS, 6),
+                "b3": ("conv_rwb_fwd_kernel", "F(2,3)", 1.5, "bf16 MFMA 16x16x32, fp32 operands as three bf16 parts",
+                       PEAK_BF16_TFLOPS, 6),
+                "f23": ("conv_rw_fwd_kernel", "F(2,3)", 1.5, "f32 MFMA 16x16x4", PEAK_F32_TFLOPS, 1),
+                "f43": ("conv_rw43_fwd_kernel", "F(4,3)", 2.0, "f32 MFMA 16x16x4", PEAK_F32_TFLOPS, 1)}[s1]
+            issued = achieved / wino_factor * terms  # what the matrix pipe executes, in its own FLOPs
+            traffic, mfma_busy, pmc_note = (None, None, "dry run") if job.dry else committed_counters(name, kname)
+            pmc_live = False
+            if (not job.dry and not args.no_live_pmc and world == 1 and name == (args.config or "c2") and with_cpu_baseline):
+                # (the headline configuration of a one-GPU --full run: counters measured live, by child runs under rocprofv3)
+                torch.cuda.empty_cache()
+                live = live_counters(name, kname)
+                if live is not None:
+                    traffic, mfma_busy, pmc_note = live
+                    pmc_live = True
+            opts = {} if job.dry else {k: _clib.get_option(k) for k in ("s1_fwd", "s1_wgrad", "conv1_u8", "wgrad1_u8")}
+            pipe_s = sum(matrix_pipe_seconds_per_update(cfg, first_step + i, opts) for i in range(steps)) / steps
+            clock = None if (job.dry or name != "c2") else committed_clock(kname)
+            n_launch = max(1, len(ev_pairs))
+            avg_ms = kms / n_launch
+            out.update({
+                "conv_algorithmic_gflop_per_update": per_update / 1e9,
+                "conv_roofline_frac_whole_update": per_update * (steps / dt) / (PEAK_F32_TFLOPS * 1e12),
+                "conv_roofline_note": "SURVEY.md 8d accounting (the north star's 'fraction of the conv roofline'): direct-conv "
+                                      "FLOPs of the update / time against the 157.3 TFLOP/s fp32 peak.  Read it as the SPEED-UP "
+                                      "over what the fp32 pipe could do at best, not as a fraction bounded by 1: the kernels skip "
+                                      "work (Winograd) and run most of it on the bf16 matrix cores.  matrix_pipe_time_frac_whole_"
+                                      "update is the bounded figure",
+                "matrix_pipe_time_frac_whole_update": pipe_s / (dt / steps),
+                "matrix_pipe_time_note": "time the two matrix pipes would need at their dense peaks (bf16 2.5 PFLOP/s, f32-input "
+                                         "157.3 TFLOP/s) for the conv work as the kernels issue it (Winograd factors and bf16x3 "
+                                         "products counted, padding not) / measured time per update",
+                "roofline": {"bound": "mfma",
+                             "kernel": (f"{kname} (row-walk Winograd {wino} along x: all 3x3 s1 32->32 + bias + ReLU layers of "
+                                        f"two minibatches per launch, {mfma})")
+                                       if stacked else
+                                       f"{kname} (row-walk Winograd {wino} along x: one 3x3 s1 32->32 + bias + ReLU layer per "
+                                       f"launch, {mfma})",
+                             # The kernel is Winograd F(2,3) / F(4,3) along x: it issues 1/1.5 resp. 1/2 of the direct-
+                             # convolution FLOPs of SURVEY.md 8(d).  `achieved` / `frac` are what the matrix pipe really
+                             # executes (compare with 1.0 and with `mfma_busy_frac_pmc`); the SURVEY 8(d) accounting in
+                             # direct-conv FLOPs, which can exceed 1 because the algorithm skips work, is under `direct_equiv_*`.
+                             "achieved": issued, "peak": peak_tf, "unit": "TFLOP/s",
+                             "frac": issued / peak_tf, "traffic": traffic,
+                             "achieved_note": (f"MFMA FLOPs issued = algorithmic direct-conv FLOPs / {wino_factor} (Winograd "
+                                               f"{wino} in one dimension; strip padding not counted)"
+                                               + (f" x {terms} (six bf16 x bf16 products per fp32 product: x = xh + xm + xl "
+                                                  "exactly, the three products below 2^-24 dropped), against the dense bf16 MFMA "
+                                                  "peak" if terms > 1 else "")),
+                             "direct_equiv_achieved": achieved, "direct_equiv_frac": achieved / PEAK_F32_TFLOPS,
+                             "direct_equiv_note": "direct-conv TFLOP/s of the launch and their ratio to the fp32 peak: a speed-up "
+                                                  "over that pipe's best case, not a utilisation (see frac)",
+                             "in_kernel_clock": clock,
+                             "traffic_unit": "HBM bytes per launch; " + pmc_note, "pmc_measured_live": pmc_live,
+                             "algorithmic_bytes_per_launch": kbytes / n_launch,
+                             "launches": len(ev_pairs), "avg_launch_ms": avg_ms,
+                             "launch_timing": ("HIP events around the kernel's launches in 8 eager updates right after the "
+                                               "timed region (the timed updates are graph replays)" if graphed else
+                                               "HIP events around the kernel's launches inside the timed region"),
+                             "hbm_GBps": (traffic / (avg_ms * 1e-3) / 1e9) if (traffic and avg_ms > 0) else None,
+                             # the kernel's other roof: its ALGORITHMIC bytes (every activation read and written once) / its
+                             # launch time against the 8 TB/s HBM peak.  Round 6 found the time per sample the same at 1.7 and
+                             # 2.33 GHz: this, not the matrix pipe, is what bounds it (torch's streaming copy / add kernels
+                             # reach 4.8 / 6.0 TB/s on this chip: tools/hbm_mixed.py)
+                             "hbm_algorithmic_GBps": (kbytes / n_launch) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else None,
+                             "hbm_algorithmic_frac": (kbytes / n_launch) / (avg_ms * 1e-3) / 8e12 if avg_ms > 0 else None,
+                             "hbm_peak_GBps": 8000.0,
+                             "mfma_busy_frac_pmc": mfma_busy},
+            })
         if job.dry:
             out["dry_run"] = True
             out["kernel_calls_traced"] = job.launches - launches0
@@ -728,11 +787,12 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None,
-                    help="measure this configuration only (default: c2, then c3, c5 and c1t under other_configs)")
+                    help="measure this configuration only (default: c2; with --full then c3, c5 and c1t under "
+                         "other_configs)")
     ap.add_argument("--no-others", action="store_true", help="without --config: measure c2 only")
     ap.add_argument("--others", action="store_true",
-                    help="measure c3 and c5 after c2 at N > 1 as well (default: only at N = 1 -- a multi-GPU run that "
-                         "fails in a secondary configuration would take the headline line down with it)")
+                    help="measure c3, c5 and c1t after c2, at any N (--full measures them at N = 1 only -- a multi-GPU "
+                         "run that fails in a secondary configuration would take the headline line down with it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not measure roofline.traffic / mfma_busy_frac_pmc live (child runs under rocprofv3 --pmc, ~1 "
@@ -752,11 +812,20 @@ def main():
                          "per n and a summary line")
     ap.add_argument("--dry-run", action="store_true",
                     help="gloo + launch-trace hook on the CPU: the host path of an N-rank run without a GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the other configurations (N = 1), the roofline figures "
+                         "with live PMC counters and the oracle's CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed update computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     main_cfg = args.config or "c2"
     world_env = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
-    others = [] if (args.config is not None or args.no_others or (world_env > 1 and not args.others)) else \
-        ["c3", "c5", "c1t"]
+    others = [] if (args.config is not None or args.no_others or not (args.others or (args.full and world_env == 1))) \
+        else ["c3", "c5", "c1t"]
 
     def budget(name):
         """(steps, warmup) of a configuration: the command line's for the main one and c3; c5's updates are 15x
@@ -771,12 +840,12 @@ def main():
         respawn_under_torchrun(args)
     own_stdout()
     job = Job(args)
-    cpu_bl = not args.no_cpu_baseline and job.world == 1 and not job.dry and not args.sweep
+    cpu_bl = args.full and not args.no_cpu_baseline and job.world == 1 and not job.dry and not args.sweep
     try:
         if args.sweep:
             sweep(job, main_cfg, others, budget)
             return
-        out = measure_schedules(job, main_cfg, *budget(main_cfg), cpu_bl)
+        out = measure_schedules(job, main_cfg, *budget(main_cfg), cpu_bl, dump_dir=args.dump_outputs)
         extra = {}
         for name in others:
             r = measure_schedules(job, name, *budget(name), cpu_bl)
@@ -790,21 +859,23 @@ def main():
         job.close()
 
 
-def measure_schedules(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, single_gpu_ms=None):
+def measure_schedules(job, name, steps, warmup, with_cpu_baseline, pg=None, n=None, single_gpu_ms=None, dump_dir=None):
     """measure() under the data-parallel schedule(s) ``--schedule`` asks for.  One rank (or a world of one): there is no
     schedule to choose.  ``auto`` measures blocking then overlapped -- each its own agent, ring and K timed steps -- and
     returns the faster one's line with both under ``allreduce``; an error in the second one is reported, not raised
     (the first result stands).  ``single_gpu_ms``: this job's own N = 1 time per step, when it has one (the sweep), for
-    the communication each schedule leaves exposed."""
+    the communication each schedule leaves exposed.  ``dump_dir``: passed to every schedule's measure() (the schedules
+    reduce the same elements with the same collective, so they compute the same outputs)."""
     world = job.world if n is None else n
     if not (job.distributed and (world > 1 or os.environ.get("CURLA_BENCH_FORCE_DIST") == "1")):
-        return measure(job, name, steps, warmup, with_cpu_baseline, pg, n)
+        return measure(job, name, steps, warmup, with_cpu_baseline, pg, n, dump_dir=dump_dir)
     want = job.args.schedule
     scheds = ["blocking", "overlapped"] if want == "auto" else [want]
     res = {}
     for i, sc in enumerate(scheds):
         try:
-            res[sc] = measure(job, name, steps, warmup, with_cpu_baseline and i == 0, pg, n, overlap=(sc == "overlapped"))
+            res[sc] = measure(job, name, steps, warmup, with_cpu_baseline and i == 0, pg, n, overlap=(sc == "overlapped"),
+                              dump_dir=dump_dir)
         except Exception as e:  # noqa: BLE001
             if i == 0:
                 raise

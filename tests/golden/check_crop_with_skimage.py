@@ -8,7 +8,11 @@ Build-container check only (it reads /root/reference, which never travels to the
 The conda interpreter has no torch and no kornia; ``augmentations.py`` imports both at module level but RandomCrop uses
 neither (augmentations.py:19-75: NumPy + view_as_windows only), so the two names are stubbed -- no arithmetic of the crop
 goes through a stub.  Exit status 0 = the fixture's index stream, crop bytes (sha256 + the first two crops) and centre
-crop are what the reference produces with the real library."""
+crop are what the reference produces with the real library.
+
+With ``--write`` it also records what the genuine library gave (default output shapes, the index stream, sha256 of the
+16 crops, of the first two and of the centre crop, the two library versions) in crop84_skimage.npz next to it: the
+fixture tests/test_oracle_golden.py pins crop84.npz and the oracle to, with no scikit-image and no reference at hand."""
 import hashlib
 import os
 import sys
@@ -61,6 +65,17 @@ def main():
         print(("ok   " if good else "FAIL ") + what)
         ok = ok and good
     print(f"scikit-image {skimage.__version__}, numpy {np.__version__}: crop84.npz " + ("confirmed" if ok else "DIFFERS"))
+    if "--write" in sys.argv[1:]:
+        sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
+        path = os.path.join(HERE, "crop84_skimage.npz")
+        np.savez(path, imgs_seed=g["imgs_seed"], numpy_seed=g["numpy_seed"],
+                 default_shape_84=np.array(augmentations.RandomCrop((84, 84)).output_shape, dtype=np.int64),
+                 default_shape_90_160=np.array(augmentations.RandomCrop((90, 160)).output_shape, dtype=np.int64),
+                 h1=np.asarray(calls[0], dtype=np.int64), w1=np.asarray(calls[1], dtype=np.int64),
+                 out_sha256=np.array(sha(out)), out_first2_sha256=np.array(sha(out[:2])),
+                 center_crop0_sha256=np.array(sha(aug.evaluation_augmentation(imgs[0]))),
+                 skimage_version=np.array(skimage.__version__), numpy_version=np.array(np.__version__))
+        print(f"wrote {path}")
     return 0 if ok else 1
 
 

@@ -6,7 +6,8 @@ configurations, through the self-respawn) and N = 8 (configs[1] only, through th
 N ranks came up, the ring is sharded ``capacity // N`` per rank, every rank samples from its own seed, exactly one
 JSON line is printed, it says ``n_gpus: N`` / ``dpN``, carries an all-reduce entry per gradient bucket and BOTH
 data-parallel schedules (``--schedule auto``).  ``--sweep`` (sub-groups of 1, 2, 4, 8 ranks of one 8-rank job, both
-schedules each, one line per n + a summary) is rehearsed the same way."""
+schedules each, one line per n + a summary) is rehearsed the same way, and so are the one-rank plain run (the headline
+figure only, ``--dump-outputs``) and ``--full``."""
 import json
 import os
 import socket
@@ -132,3 +133,45 @@ def test_world_size_mismatch_is_refused():
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--dry-run"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE=2" in p.stderr
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain one-rank run: the headline configuration alone, exactly ``--steps`` timed steps, none of ``--full``'s
+    figures; ``--dump-outputs`` writes what the last timed update left (float32 / float64, at most 64 MB), and the
+    same arguments give the same bytes from run to run."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run", "--capacity",
+                  "256", "--dump-outputs", str(out)])
+        runs.append((d, out))
+    d, out = runs[0]
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["full"] is False
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    for k in ("other_configs", "roofline", "cpu_baseline", "matrix_pipe_time_frac_whole_update", "allreduce"):
+        assert k not in d, k
+    assert d["kernel_calls_traced"] > 50 * (1 + 1 + 3) // 2
+    info = d["outputs"]
+    assert info["step"] == 1 + 1 + 3 - 1  # priming update, warm-up, timed steps: the last timed one
+    names = sorted(f[:-4] for f in os.listdir(out))
+    assert len(names) == info["arrays"] and all(f.endswith(".npy") for f in os.listdir(out))
+    assert {"critic_loss", "log_alpha", "curl.W", "critic.encoder.fc.weight", "actor.trunk.4.weight",
+            "critic_target.Q2.trunk.4.bias"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(out / f"{n}.npy"), np.load(runs[1][1] / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total == info["bytes"] <= 64_000_000
+    assert np.load(out / "log_alpha.npy").dtype == np.float64
+
+
+def test_full_adds_the_other_configurations_and_the_roofline():
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--dry-run", "--capacity", "256",
+              "--full"])
+    assert d["config"]["full"] is True and sorted(d["other_configs"]) == ["c1t", "c3", "c5"]
+    for r in [d] + list(d["other_configs"].values()):
+        assert r["roofline"]["bound"] == "mfma" and "matrix_pipe_time_frac_whole_update" in r
+        assert "outputs" not in r

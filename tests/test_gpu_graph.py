@@ -169,14 +169,14 @@ def test_unsupported_setups_are_refused():
 
 
 def test_bench_graphs_flag_runs_and_reports():
-    """``bench.py --graphs``: the timed updates are graph replays, the dominant kernel's HIP-event timing comes from
-    eager updates after the timed region; one JSON line, nothing else on stdout."""
+    """``bench.py --graphs --full``: the timed updates are graph replays, the dominant kernel's HIP-event timing (a
+    --full figure) comes from eager updates after the timed region; one JSON line, nothing else on stdout."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, "bench.py", "--config", "c3", "--steps", "6", "--warmup", "2", "--graphs",
+    p = subprocess.run([sys.executable, "bench.py", "--config", "c3", "--steps", "6", "--warmup", "2", "--graphs", "--full",
                         "--no-cpu-baseline", "--capacity", "4096", "--clock-warmup-s", "0"], cwd=root,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]

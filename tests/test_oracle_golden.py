@@ -44,19 +44,22 @@ def test_random_crop_bit_exact_84_to_76():
 
 def test_crop_fixture_under_the_genuine_skimage():
     """make_goldens.py records crop84.npz with ``sliding_window_view`` standing in for skimage's ``view_as_windows``
-    (this interpreter has no scikit-image).  Where the image's conda interpreter with the GENUINE scikit-image and the
-    reference are both present (the build container), the reference's RandomCrop is re-run under it and must give the
-    fixture's bytes; elsewhere (the GPU box has no /root/reference) the check is skipped."""
-    import os
-    import subprocess
-
-    import pytest
-    conda, ref = "/opt/conda/bin/python3.9", os.environ.get("CURLA_REFERENCE", "/root/reference")
-    if not (os.path.exists(conda) and os.path.exists(os.path.join(ref, "augmentations.py"))):
-        pytest.skip("needs the build container: /opt/conda (scikit-image) and /root/reference")
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "check_crop_with_skimage.py")
-    r = subprocess.run([conda, script], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "crop84.npz confirmed" in r.stdout, r.stdout + r.stderr
+    (this interpreter has no scikit-image).  crop84_skimage.npz holds what the reference's RandomCrop gives under the
+    GENUINE scikit-image on the same images and seeds (tests/golden/check_crop_with_skimage.py --write): the fixture's
+    index stream, bytes and shapes must be those, and so must the oracle's crops of the same images."""
+    g, s = load("crop84.npz"), load("crop84_skimage.npz")
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
+    assert int(s["imgs_seed"]) == int(g["imgs_seed"]) and int(s["numpy_seed"]) == int(g["numpy_seed"])
+    for k in ("default_shape_84", "default_shape_90_160", "h1", "w1"):
+        assert np.array_equal(g[k], s[k]), k
+    assert str(g["out_sha256"]) == str(s["out_sha256"])
+    assert sha(g["out_first2"]) == str(s["out_first2_sha256"])
+    assert sha(g["center_crop0"]) == str(s["center_crop0_sha256"])
+    imgs = np.random.RandomState(int(s["imgs_seed"])).randint(0, 256, (16, 9, 84, 84), dtype=np.uint8)
+    assert sha(O.random_crop(imgs, s["h1"], s["w1"], (76, 76))) == str(s["out_sha256"])
+    assert sha(O.center_crop(imgs[0], (76, 76))) == str(s["center_crop0_sha256"])
+    assert tuple(s["default_shape_84"]) == O.random_crop_output_shape((84, 84))
+    assert tuple(s["default_shape_90_160"]) == O.random_crop_output_shape((90, 160))
 
 
 def test_sample_cpc_draw_order_bit_exact():

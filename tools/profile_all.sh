@@ -9,7 +9,7 @@ O=gpurun_out; mkdir -p $O
 for CFG in c2 c3 c5 c1t; do
   echo "== $CFG"; tools/profile_config.sh $TAG $CFG 2>&1 | tail -4
 done
-python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 300 $O/${TAG}_bench_default.json; echo
+python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 300 $O/${TAG}_bench_default.json; echo
 tools/clock_reconcile.sh $TAG > $O/${TAG}_clock.log 2>&1; tail -3 $O/${TAG}_clock_reconcile.txt
 rm -f $O/fullsize_parity.txt $O/fullsize_arbiter.txt
 python -m pytest tests/test_gpu_fullsize.py -q > $O/${TAG}_fullsize_tests.log 2>&1; tail -2 $O/${TAG}_fullsize_tests.log

@@ -17,7 +17,7 @@ HASH=$($PY -c "from curla_amd import build; print(build.source_hash())")
 PSTEPS=6; PWARM=2
 if [ "$CFG" = "c5" ]; then PSTEPS=2; PWARM=1; fi
 if [[ $WHAT == *bench* ]]; then
-  $PY bench.py --config $CFG > $O/${TAG}_bench_${CFG}.json 2> $O/${TAG}_bench_${CFG}.err
+  $PY bench.py --config $CFG --full > $O/${TAG}_bench_${CFG}.json 2> $O/${TAG}_bench_${CFG}.err
   tail -1 $O/${TAG}_bench_${CFG}.json | cut -c1-400
 fi
 if [[ $WHAT == *stats* ]]; then
