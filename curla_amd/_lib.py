@@ -16,7 +16,7 @@ c_int, c_ll, c_float, c_size_t, vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_f
 c_u64 = ctypes.c_ulonglong
 c_double = ctypes.c_double
 
-ABI_VERSION = 6  # include/curla_hip.h CURLA_ABI_VERSION this table was written for
+ABI_VERSION = 7  # include/curla_hip.h CURLA_ABI_VERSION this table was written for
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/curla_hip.h
 SIGNATURES = {
@@ -35,6 +35,7 @@ SIGNATURES = {
     "curla_conv1_wgrad_slabs": [vp, c_int, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, vp,
                                 vp],
     "curla_conv3x3_s1_bwd_slabs": [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],
+    "curla_conv1_dgrad": [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_float, vp],
     "curla_wgrad_reduce_multi": [c_int, vp, vp, vp, vp, vp, vp, vp],
     "curla_conv_wgrad_workspace_floats": [c_int],
     "curla_gemm": [vp, c_int, c_int, c_ll, vp, c_int, c_int, c_ll, vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int,
@@ -90,6 +91,7 @@ SIGNATURES = {
                                    vp, vp, vp, c_int, vp],
     "curla_fc_ln_fwd_multi": [c_int, vp, c_int, c_ll, c_int, c_int, c_int, c_float, c_int, vp],
     "curla_actor_head_bwd": [vp, vp, c_int, vp, vp, c_float, vp, vp, vp, vp, c_int, c_int, c_float, c_float, vp, vp],
+    "curla_policy_head_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_float, c_float, vp, vp],
     "curla_concat": [vp, vp, c_int, c_int, c_int, vp, vp],
     "curla_split_sum": [vp, c_ll, c_int, c_int, c_int, vp, vp, vp],
     "curla_td_target": [vp, c_ll, vp, vp, vp, vp, c_float, c_int, vp, vp],

@@ -2308,3 +2308,5 @@ int curla_conv1_wgrad_slabs(const void* src, int src_kind, const int64_t* idx, c
 
 
 }  // extern "C"
+
+#include "conv1_dgrad.h"  // curla_conv1_dgrad: the observation gradient of the differentiable encoder

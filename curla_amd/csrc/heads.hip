@@ -628,6 +628,39 @@ __global__ void actor_head_bwd_kernel(const float* gpi, const float* gpi2, int g
   }
 }
 
+// general backward of the squashed-Gaussian head (curl_sac.py:20-35,87-108) for any upstream gradients of its four
+// outputs (NULL = zero): mu_out = tanh(mu), log_std = lo + (hi - lo)(tanh(raw) + 1) / 2, pi = tanh(mu + noise exp(log_std)),
+// log_pi = sum(-noise^2 / 2 - log_std) - A log(2 pi) / 2 - sum log(relu(1 - pi^2) + 1e-6); noise is a constant.
+// dmu / dpi / dlog_std are [B][A], dlog_pi [B] (the [B, 1] column); writes d[mu | raw] = dout2a [B][2A].
+__global__ void policy_head_bwd_kernel(const float* dmu, const float* dpi, const float* dlog_pi, const float* dlog_std,
+                                       const float* noise, const float* mu_t, const float* pi_t, const float* log_std,
+                                       const float* tanh_ls, int B, int A, float lo, float hi, float* dout2a) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float glp = dlog_pi ? dlog_pi[b] : 0.f;
+  const bool sampled = dpi || dlog_pi;
+  for (int a = 0; a < A; ++a) {
+    const size_t e = (size_t)b * A + a;
+    float gmu = 0.f, gls = dlog_std ? dlog_std[e] : 0.f;
+    if (dmu) {
+      const float m = mu_t[e];
+      gmu = dmu[e] * (1.f - m * m);
+    }
+    if (sampled) {
+      const float p = pi_t[e];
+      const float om = 1.f - p * p;
+      float gp = dpi ? dpi[e] : 0.f;
+      if (om > 0.f) gp += glp * (2.f * p / (om + 1e-6f));  // d/dpi of -log(relu(1 - pi^2) + 1e-6)
+      const float gu = gp * om;                               // through tanh
+      gmu += gu;
+      gls += gu * noise[e] * expf(log_std[e]) - glp;          // pi's std, and gaussian_logprob's -log_std
+    }
+    const float t = tanh_ls[e];
+    dout2a[(size_t)b * 2 * A + a] = gmu;
+    dout2a[(size_t)b * 2 * A + A + a] = gls * 0.5f * (hi - lo) * (1.f - t * t);
+  }
+}
+
 // xa[z] = [ zfeat | act ] for the twin-Q input
 __global__ void concat_kernel(const float* zf, const float* act, int B, int F, int A, float* xa) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1624,6 +1657,18 @@ int curla_actor_head_bwd(const float* gpi, const float* gpi2, int gpi_ld, const 
   return curla_launch_status();
 }
 
+int curla_policy_head_bwd(const float* dmu, const float* dpi, const float* dlog_pi, const float* dlog_std,
+                          const float* noise, const float* mu, const float* pi, const float* log_std,
+                          const float* tanh_ls, int B, int A, float log_std_min, float log_std_max, float* dtrunk_out,
+                          void* stream) {
+  CURLA_REQUIRE(tanh_ls && dtrunk_out && B > 0 && A > 0 && A <= kMaxA);
+  CURLA_REQUIRE(!dmu || mu);
+  CURLA_REQUIRE(!(dpi || dlog_pi) || (noise && pi && log_std));
+  hipLaunchKernelGGL(policy_head_bwd_kernel, dim3((B + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), dmu,
+                     dpi, dlog_pi, dlog_std, noise, mu, pi, log_std, tanh_ls, B, A, log_std_min, log_std_max, dtrunk_out);
+  return curla_launch_status();
+}
+
 int curla_concat(const float* z, const float* act, int B, int F, int A, float* xa, void* stream) {
   CURLA_REQUIRE(z && act && xa && B > 0 && F > 0 && A > 0);
   hipLaunchKernelGGL(concat_kernel, dim3((B * (F + A) + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), z,
@@ -1989,7 +2034,7 @@ int curla_nhwc_to_nchw(const float* in, float* out, int B, int H, int W, int C, 
   return curla_launch_status();
 }
 
-const char* curla_version(void) { return "curla_hip 0.6 (gfx950, abi 6)"; }
+const char* curla_version(void) { return "curla_hip 0.7 (gfx950, abi 7)"; }
 
 int curla_abi_version(void) { return CURLA_ABI_VERSION; }
 

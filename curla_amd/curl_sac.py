@@ -26,7 +26,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import autograd, ops
 from .encoder import CNNEncoder
 from .ops import ObsRef
 from .optim import FlatAdam
@@ -156,10 +156,12 @@ class Actor(nn.Module):
         self.apply(weight_init)
 
     def forward(self, obs, compute_pi=True, compute_log_pi=True, detach_encoder=False, noise=None):
-        """Inference forward on the HIP kernels; same return tuple as the
-        reference (mu, pi, log_pi, log_std) with pi/log_pi None when not asked
-        for.  ``noise`` replaces torch.randn_like (curl_sac.py:97)."""
+        """Forward on the HIP kernels; same return tuple as the reference (mu, pi, log_pi, log_std) with pi/log_pi
+        None when not asked for.  ``noise`` replaces torch.randn_like (curl_sac.py:97) and is a constant.
+        Differentiable (autograd.ActorFn) when grad mode is on and the features or a trunk parameter require grad."""
         z = self.encoder(obs, detach=detach_encoder)
+        if autograd.wants_graph(z, *self.trunk.parameters()):
+            return autograd.actor_forward(self, z, compute_pi, compute_log_pi, noise)
         B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
         dev = z.device
         h1 = torch.empty((B, H), device=dev)
@@ -225,6 +227,10 @@ class Critic(nn.Module):
     def forward(self, obs, action, detach_encoder=False):
         assert obs.size(0) == action.size(0)  # curl_sac.py:136
         z = self.encoder(obs, detach=detach_encoder)
+        if autograd.wants_graph(z, action, *self.Q1.parameters(), *self.Q2.parameters()):
+            q1, q2 = autograd.critic_forward(self, z, action)  # (differentiable: autograd.CriticFn)
+            self.outputs['q1'], self.outputs['q2'] = q1.detach(), q2.detach()
+            return q1, q2
         B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
         dev = z.device
         xa = torch.empty((B, F + A), device=dev)
@@ -259,11 +265,21 @@ class CURL(nn.Module):
         self.output_type = output_type
 
     def encode(self, x, detach=False, ema=False):
-        return self.encoder_target(x) if ema else self.encoder(x)
+        """curl_sac.py:196-209: ``ema`` runs the target encoder without grad, ``detach`` detaches the result."""
+        if ema:
+            with torch.no_grad():
+                z_out = self.encoder_target(x)
+        else:
+            z_out = self.encoder(x)
+        return z_out.detach() if detach else z_out
 
     def compute_logits(self, z_a, z_pos):
         """(B,B) logits z_a (W z_pos^T) minus the row max (curl_sac.py:211-222),
-        both products on the MFMA GEMM."""
+        both products on the MFMA GEMM; differentiable through both (autograd.CurlLogitsFn) when grad mode is on and
+        an input or W requires grad."""
+        if autograd.wants_graph(z_a, z_pos, self.W):
+            logits = autograd.CurlLogitsFn.apply(z_a.contiguous(), z_pos.contiguous(), self.W)
+            return logits - torch.max(logits, 1)[0][:, None]
         B, F = z_a.shape
         WzT = torch.empty((B, F), device=z_a.device)
         logits = torch.empty((B, B), device=z_a.device)
@@ -426,6 +442,7 @@ class CurlSacAgent(object):
             **(dict(foreach=False) if flat_actor else dict(fused=True) if self.device.type == "cuda" else {}))
         self.encoder_optimizer = adam(enc_params, cf, cg, lr=encoder_lr)
         self.cpc_optimizer = adam([self.CURL.W] + enc_params, cf, cg, lr=encoder_lr)
+        self._install_grad_views()
 
         self._workspaces = {}
         self._anchor_cache = None
@@ -517,6 +534,48 @@ class CurlSacAgent(object):
         self._la_words = self._actor_gbucket[a_sz:]
         place(actor_own, False, self._actor_flat, self._actor_gflat, 0)
         self.log_alpha.grad = torch.zeros((), device=dev, dtype=torch.float64)
+
+    def _install_grad_views(self):
+        """User autograd (autograd.py) against the flat gradient buffers.  A backward that finds a parameter's .grad
+        unset (``zero_grad()`` sets it to None) makes a fresh tensor; the hook registered here copies it into the
+        parameter's flat-buffer view and points .grad back at the view, which FlatAdam.step() requires.  Accumulation
+        into an existing view is in place anyway.  Parameters that receive no gradient keep None, so the optimizers
+        skip them as torch's Adam does.  ``zero_grad`` of the five optimizers marks the views as possibly dropped;
+        update() restores them first (_restore_grad_views) -- a flag test, not a walk, while nothing has changed."""
+        views, seen = [], set()
+        for p in [self.CURL.W, self.log_alpha, *self.critic.parameters(), *self.actor.parameters()]:
+            if id(p) not in seen and p.grad is not None:
+                seen.add(id(p))
+                views.append((p, p.grad))
+        self._grad_views = views
+        state = self._grad_state = {"dirty": False}
+
+        def make_hook(view):
+            def hook(p):
+                if p.grad is not None and p.grad is not view:
+                    if p.grad.data_ptr() != view.data_ptr():
+                        view.copy_(p.grad)
+                    p.grad = view
+            return hook
+        for p, v in views:
+            p.register_post_accumulate_grad_hook(make_hook(v))
+
+        def watch(opt):
+            inner = opt.zero_grad
+
+            def zero_grad(set_to_none=True):
+                state["dirty"] = True
+                return inner(set_to_none)
+            opt.zero_grad = zero_grad
+        for opt in self._optimizers().values():
+            watch(opt)
+
+    def _restore_grad_views(self):
+        if self._grad_state["dirty"]:
+            self._grad_state["dirty"] = False
+            for p, v in self._grad_views:
+                if p.grad is not v:
+                    p.grad = v
 
     _curl_unfused = False       # the CURL head as separate launches (set per agent from CURLA_CURL_HEAD=unfused)
     _soft_update_hint = False   # set by update() around update_critic(): a target soft update follows the critic's step
@@ -795,6 +854,7 @@ class CurlSacAgent(object):
     # ------------------------------------------------------------------ phases
     def update_critic(self, obs, action, reward, next_obs, not_done, L, step, noise=None):
         """curl_sac.py:349-371."""
+        self._restore_grad_views()
         o, no = _as_ref(obs), _as_ref(next_obs)
         B, A, H = o.B, self.action_dim, self.hidden_dim
         enc, F = self.critic.encoder, self.critic.encoder.feature_dim
@@ -907,6 +967,7 @@ class CurlSacAgent(object):
         """curl_sac.py:373-404.  Only the live gradients are produced: the
         actor's own fc/ln/trunk and log_alpha (the reference also deposits
         gradients on critic tensors that are zeroed before any step reads them)."""
+        self._restore_grad_views()
         o = _as_ref(obs)
         B, A, H = o.B, self.action_dim, self.hidden_dim
         enc, aenc, F = self.critic.encoder, self.actor.encoder, self.critic.encoder.feature_dim
@@ -1015,6 +1076,7 @@ class CurlSacAgent(object):
 
     def update_cpc(self, obs_anchor, obs_pos, cpc_kwargs, L, step):
         """curl_sac.py:406-423."""
+        self._restore_grad_views()
         oa, op_ = _as_ref(obs_anchor), _as_ref(obs_pos)
         B = oa.B
         enc, tenc, F = self.critic.encoder, self.critic_target.encoder, self.critic.encoder.feature_dim
@@ -1087,6 +1149,7 @@ class CurlSacAgent(object):
         buffer is used through the reference's ``sample_cpc()`` tensors.
         ``noise`` (parity tests): (critic-phase, actor-phase) tensors in place of the two ``torch.randn_like`` draws
         (curl_sac.py:97 via :352 and :375)."""
+        self._restore_grad_views()
         if noise is None and self._graphs is not None and self._graph_usable(replay_buffer, step, only_cpc):
             return self._update_graphed(replay_buffer, L, step)
         self._update_eager(replay_buffer, L, step, only_cpc, noise)

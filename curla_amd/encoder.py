@@ -19,7 +19,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import autograd, ops
 
 
 def tie_weights(src, trg):
@@ -255,24 +255,38 @@ class CNNEncoder(nn.Module):
         ws = self.workspace(ref.B)
         self.conv_forward(ref, ws.acts)
         if self.record_outputs:
-            for i, a in enumerate(ws.acts):
-                out = torch.empty((a.shape[0], a.shape[3], a.shape[1], a.shape[2]), device=a.device, dtype=a.dtype)
-                ops.nhwc_to_nchw(a, out)
-                self.outputs["conv%s" % (i + 1)] = out
+            self._record(ws.acts)
         return ref, ws.acts[-1]
+
+    def _record(self, acts):
+        for i, a in enumerate(acts):
+            out = torch.empty((a.shape[0], a.shape[3], a.shape[1], a.shape[2]), device=a.device, dtype=a.dtype)
+            ops.nhwc_to_nchw(a, out)
+            self.outputs["conv%s" % (i + 1)] = out
+
+    def _wants_graph(self, obs, convs=True):
+        ps = self.parameters() if convs else (self.fc.weight, self.fc.bias, self.ln.weight, self.ln.bias)
+        return autograd.wants_graph(obs, *ps)
 
     def forward_conv(self, obs):
         """encoder.py:77-90: the flattened conv features, in the reference's order -- ``conv.view(B, -1)`` of an NCHW
         tensor, i.e. (c, y, x).  (The kernels keep activations NHWC; this public method transposes a copy.  The
-        learner never calls it: ``forward`` feeds ``fc``, whose columns are stored in (y, x, c) order, directly.)"""
+        learner never calls it: ``forward`` feeds ``fc``, whose columns are stored in (y, x, c) order, directly.)
+        Differentiable (autograd.py) when grad mode is on and ``obs`` or a conv parameter requires grad."""
+        if autograd.wants_graph(obs, *[t for m in self.convs for t in (m.weight, m.bias)]):
+            return autograd.forward_conv(self, obs)
         ref, h = self._forward_conv_nhwc(obs)
         out = torch.empty((h.shape[0], h.shape[3], h.shape[1], h.shape[2]), device=h.device, dtype=h.dtype)
         ops.nhwc_to_nchw(h, out)
         return out.view(ref.B, -1)
 
     def forward(self, obs, detach=False):
-        """Inference forward (no autograd graph: training gradients are produced
-        by CurlSacAgent's explicit backward kernels).  obs: float NCHW in [0,255]."""
+        """obs: float NCHW in [0,255] or an ObsRef.  With grad mode on and ``obs`` or a parameter requiring grad the
+        same launches run inside autograd.EncoderFn (differentiable; ``detach`` stops gradients at the conv output,
+        encoder.py:92-93); otherwise no graph is built.  update() never comes through here: its gradients are
+        produced by CurlSacAgent's explicit backward kernels."""
+        if self._wants_graph(obs, convs=not detach):
+            return autograd.encoder_forward(self, obs, detach)
         ref, h = self._forward_conv_nhwc(obs)
         h = h.view(ref.B, -1)
         z = torch.empty((h.shape[0], self.feature_dim), device=h.device, dtype=torch.float32)

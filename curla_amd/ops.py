@@ -199,6 +199,14 @@ def conv1_wgrad_slabs(obs: ObsRef, g, ws, channels, scale=1.0 / 255.0):
     return n.value
 
 
+def conv1_dgrad(g, w, dobs, scale=1.0 / 255.0):
+    """Gradient w.r.t. a float NCHW observation ``dobs`` [B, C, H, W] of the first layer, from its pre-activation output
+    gradient ``g`` [B, Ho, Wo, F] (NHWC, ReLU-masked) and OIHW weight ``w``; every element of ``dobs`` is written."""
+    B, C, H, W = dobs.shape
+    _dev(g), _dev(dobs)
+    call("curla_conv1_dgrad", ptr(g), ptr(w), ptr(dobs), B, C, H, W, w.shape[0], scale, stream())
+
+
 def wgrad_reduce_multi(jobs):
     """jobs: [(slabs workspace, slab count, dw, db), ...] (<= 8): every layer's slabs summed into dW / db in ONE launch."""
     import ctypes
@@ -505,6 +513,13 @@ def actor_head_bwd(gpi, log_alpha, glp_scale, noise, pi, log_std, tanh_ls, B, A,
     else:
         g1, g2, ld = ptr(gpi), None, A
     call("curla_actor_head_bwd", g1, g2, ld, ptr(glp_rows), ptr(log_alpha), glp_scale, ptr(noise), ptr(pi),
+         ptr(log_std), ptr(tanh_ls), B, A, lo, hi, ptr(dtrunk_out), stream())
+
+
+def policy_head_bwd(dmu, dpi, dlog_pi, dlog_std, noise, mu, pi, log_std, tanh_ls, B, A, lo, hi, dtrunk_out):
+    """d(trunk output [B, 2A]) of the squashed-Gaussian head for any subset of upstream gradients (None = zero):
+    ``dmu`` / ``dpi`` / ``dlog_std`` [B, A], ``dlog_pi`` [B, 1]; the other tensors are what the forward wrote."""
+    call("curla_policy_head_bwd", ptr(dmu), ptr(dpi), ptr(dlog_pi), ptr(dlog_std), ptr(noise), ptr(mu), ptr(pi),
          ptr(log_std), ptr(tanh_ls), B, A, lo, hi, ptr(dtrunk_out), stream())
 
 

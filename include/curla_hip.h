@@ -35,9 +35,10 @@ extern "C" {
 const char* curla_version(void);
 
 /* The C ABI's number: bumped whenever an entry point's argument list changes (round 4 put dyn / dyn64 / rng_dev
- * pointers into the middle of the Adam and policy-head calls: 4 -> 5 names that).  A binding written for another
+ * pointers into the middle of the Adam and policy-head calls: 4 -> 5 names that; 7 adds the autograd path's
+ * curla_conv1_dgrad and curla_policy_head_bwd).  A binding written for another
  * number must refuse the library -- curla_amd/_lib.py does -- instead of calling with shifted arguments. */
-#define CURLA_ABI_VERSION 6
+#define CURLA_ABI_VERSION 7
 int curla_abi_version(void);
 
 /* Run-time kernel-selection options (curla_amd/csrc/options.h).  Every option's default is the measured-best path;
@@ -139,6 +140,14 @@ int curla_conv1_wgrad_slabs(const void* src, int src_kind, const int64_t* idx, c
  * the layer's input `in`) of one stride-1 layer in ONE launch: both only read the output gradient g. */
 int curla_conv3x3_s1_bwd_slabs(const float* in, const float* g, const float* w, float* gin, float* workspace, int B, int Hi,
                                int Wi, int channels, int* nslabs, void* stream);
+/* Gradient w.r.t. a float observation of the first (stride-2) layer (encoder.py:78,82: conv(obs / 255)):
+ * dobs[n][c][y][x] = scale * sum g[n][oy][ox][o] * w[o][c][ky][kx] over y = 2 oy + ky, x = 2 ox + kx.  g = the layer's
+ * pre-activation output gradient, NHWC [B][Ho][Wo][channels] (16-byte aligned; already ReLU-masked); w = OIHW weight;
+ * dobs = float NCHW [B][C][H][W], every element written (pixels no output reaches are 0).  C in {3, 6, 9, 12},
+ * channels a multiple of 4 up to 256 (32: one filter chunk per thread, others chunks of 4; csrc/conv1_dgrad.h).
+ * The differentiable encoder's input gradient (curla_amd/autograd.py); update() never calls it. */
+int curla_conv1_dgrad(const float* g, const float* w, float* dobs, int B, int C, int H, int W, int channels,
+                      float scale, void* stream);
 int curla_wgrad_reduce_multi(int njobs, const float* const* slabs, const int* nslabs, const int* nw, const int* nb,
                              float* const* dw, float* const* db, void* stream);
 /* floats of `workspace` the two wgrad entry points need (per-workgroup partial slabs) */
@@ -340,6 +349,16 @@ int curla_actor_head_bwd(const float* gpi, const float* gpi2, int gpi_ld, const 
                          float glp_scale, const float* noise, const float* pi, const float* log_std,
                          const float* tanh_ls, int B, int A, float log_std_min, float log_std_max, float* dtrunk_out,
                          void* stream);
+/* General backward of the squashed-Gaussian head (curl_sac.py:20-35 gaussian_logprob / squash, :87-108 forward): the
+ * gradient w.r.t. trunk_out [B][2A] = [mu | raw log_std] of sum(dmu*mu + dpi*pi + dlog_std*log_std) + sum_b
+ * dlog_pi[b]*log_pi[b] for the outputs curla_actor_head_fwd wrote -- mu = tanh(mu), log_std rescaled from tanh (:85-87),
+ * pi = tanh(mu + noise*std), log_pi with squash's log(relu(1 - pi^2) + 1e-6) correction (:32).  noise is a constant.
+ * Any of dmu, dpi, dlog_pi (length B), dlog_std may be NULL (= zero).  Needs tanh_ls always, mu when dmu is given, and
+ * noise / pi / log_std when dpi or dlog_pi is (the saved forward outputs).  The autograd path (curla_amd/autograd.py). */
+int curla_policy_head_bwd(const float* dmu, const float* dpi, const float* dlog_pi, const float* dlog_std,
+                          const float* noise, const float* mu, const float* pi, const float* log_std,
+                          const float* tanh_ls, int B, int A, float log_std_min, float log_std_max, float* dtrunk_out,
+                          void* stream);
 
 /* torch.cat([z, action], 1) (curl_sac.py:138) and its backward summed over the twin */
 int curla_concat(const float* z, const float* act, int B, int F, int A, float* xa, void* stream);
