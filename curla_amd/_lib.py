@@ -16,7 +16,7 @@ c_int, c_ll, c_float, c_size_t, vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_f
 c_u64 = ctypes.c_ulonglong
 c_double = ctypes.c_double
 
-ABI_VERSION = 7  # include/curla_hip.h CURLA_ABI_VERSION this table was written for
+ABI_VERSION = 8  # include/curla_hip.h CURLA_ABI_VERSION this table was written for
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/curla_hip.h
 SIGNATURES = {
@@ -102,6 +102,7 @@ SIGNATURES = {
     "curla_soft_update": [vp, vp, c_size_t, c_float, c_float, vp],
     "curla_crop_nchw": [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp],
     "curla_store_frame": [vp, vp, c_ll, c_int, c_int, c_int, vp],
+    "curla_stage_frames_u8": [vp, vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp],
     "curla_gather_stacks": [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_nhwc_to_nchw": [vp, vp, c_int, c_int, c_int, c_int, vp],
     "curla_color_jiggle": [vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],

@@ -1342,6 +1342,8 @@ __global__ void gather_stacks_kernel(const uint8_t* store, const int32_t* fid, i
   }
 }
 
+#include "stage.h"  // stage_frames_kernel: N planar frames into N ring slots, crop fused (batched acting)
+
 // NHWC float activation -> NCHW (for callers that read encoder.outputs)
 __global__ void nhwc_to_nchw_kernel(const float* in, float* out, int B, int H, int W, int C) {
   const size_t n = (size_t)B * H * W * C;
@@ -2010,6 +2012,31 @@ int curla_store_frame(const uint8_t* chw, uint8_t* frames, long long slot, int C
   return curla_launch_status();
 }
 
+int curla_stage_frames_u8(const uint8_t* nchw, uint8_t* frames, long long first_slot, int N, int C, int Hs, int Ws,
+                          int top, int left, int Hd, int Wd, void* stream) {
+  CURLA_REQUIRE(nchw && frames && first_slot >= 0 && N >= 1 && C >= 1 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0);
+  CURLA_REQUIRE(top >= 0 && left >= 0 && (long long)top + Hd <= Hs && (long long)left + Wd <= Ws);
+  const size_t npix = (size_t)N * Hd * Wd, slot = (size_t)Hd * Wd * C;
+  CURLA_REQUIRE(npix < (1ull << 31));  // (the kernels number the output pixels in 32 bits)
+  const size_t src_bytes = (size_t)N * C * Hs * Ws;
+  uint8_t* out = frames + (size_t)first_slot * slot;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool words = ((reinterpret_cast<uintptr_t>(nchw) | reinterpret_cast<uintptr_t>(out)) & 3) == 0;
+  const uint32_t np = (uint32_t)npix;
+  if (words && C == 3)
+    stage_frames_launch<3>(nchw, src_bytes, out, np, Hs, Ws, top, left, Hd, Wd, st);
+  else if (words && C == 6)
+    stage_frames_launch<6>(nchw, src_bytes, out, np, Hs, Ws, top, left, Hd, Wd, st);
+  else if (words && C == 9)
+    stage_frames_launch<9>(nchw, src_bytes, out, np, Hs, Ws, top, left, Hd, Wd, st);
+  else if (words && C == 12)
+    stage_frames_launch<12>(nchw, src_bytes, out, np, Hs, Ws, top, left, Hd, Wd, st);
+  else  // other channel counts, pointers off a dword boundary: the same bytes one by one
+    hipLaunchKernelGGL(stage_frames_bytes_kernel, dim3(nblocks(npix * C, 256, 8192)), dim3(256), 0, st, nchw, out,
+                       npix * C, C, Hs, Ws, top, left, Hd, Wd);
+  return curla_launch_status();
+}
+
 int curla_gather_stacks(const uint8_t* store, const int32_t* fid, int fid_stride, const int64_t* idx, int B, int K,
                         int H, int W, uint8_t* out, void* stream) {
   CURLA_REQUIRE(store && fid && out && B > 0 && K > 0 && H > 0 && W > 0 && fid_stride >= K);
@@ -2034,7 +2061,7 @@ int curla_nhwc_to_nchw(const float* in, float* out, int B, int H, int W, int C, 
   return curla_launch_status();
 }
 
-const char* curla_version(void) { return "curla_hip 0.7 (gfx950, abi 7)"; }
+const char* curla_version(void) { return "curla_hip 0.8 (gfx950, abi 8)"; }
 
 int curla_abi_version(void) { return CURLA_ABI_VERSION; }
 

@@ -667,6 +667,21 @@ def store_frame(chw_u8, frames, slot):
     call("curla_store_frame", ptr(chw_u8), ptr(frames), int(slot), C, H, W, stream())
 
 
+def stage_frames(nchw_u8, frames, first_slot=0, top=0, left=0):
+    """N planar frames into N ring slots in one launch, the window (top, left) fused:
+    frames[first_slot + n, y, x, c] = nchw_u8[n, c, top + y, left + x].  nchw_u8 u8 [N, C, Hs, Ws]; frames u8
+    [slots, Hd, Wd, C] (any view of a ring whose storage carries the loader's slack)."""
+    N, C, Hs, Ws = nchw_u8.shape
+    slots, Hd, Wd, Cf = frames.shape
+    _dev(nchw_u8, torch.uint8)
+    _dev(frames, torch.uint8)
+    if Cf != C or first_slot < 0 or first_slot + N > slots:
+        raise _lib.CurlaHipError(f"stage_frames: {N} frames of {C} channels from slot {first_slot} do not fit a ring of "
+                                 f"{slots} slots of {Cf} channels")
+    call("curla_stage_frames_u8", ptr(nchw_u8), ptr(frames), int(first_slot), N, C, Hs, Ws, int(top), int(left), Hd, Wd,
+         stream())
+
+
 def gather_stacks(store, fid, idx, B, out):
     """store u8 [F, H, W, 3]; fid int32 [rows, k] (a view with row stride fid.stride(0)); out u8 [B, H, W, 3k]."""
     _, H, W, _ = store.shape

@@ -36,9 +36,9 @@ const char* curla_version(void);
 
 /* The C ABI's number: bumped whenever an entry point's argument list changes (round 4 put dyn / dyn64 / rng_dev
  * pointers into the middle of the Adam and policy-head calls: 4 -> 5 names that; 7 adds the autograd path's
- * curla_conv1_dgrad and curla_policy_head_bwd).  A binding written for another
- * number must refuse the library -- curla_amd/_lib.py does -- instead of calling with shifted arguments. */
-#define CURLA_ABI_VERSION 7
+ * curla_conv1_dgrad and curla_policy_head_bwd; 8 the batched acting path's curla_stage_frames_u8).  A binding written
+ * for another number must refuse the library -- curla_amd/_lib.py does -- instead of calling with shifted arguments. */
+#define CURLA_ABI_VERSION 8
 int curla_abi_version(void);
 
 /* Run-time kernel-selection options (curla_amd/csrc/options.h).  Every option's default is the measured-best path;
@@ -488,6 +488,18 @@ int curla_sample_stage(const void* host_block, void* device_block, long long nby
 int curla_host_device_pointer(void* host, void** device);
 /* ReplayBuffer.add: one CHW uint8 observation into ring slot `slot` (utils.py:120-128) */
 int curla_store_frame(const uint8_t* chw, uint8_t* frames, long long slot, int C, int H, int W, void* stream);
+/* Acting on N observations at once (CurlSacAgent.select_actions / sample_actions; one by one: curl_sac.py:330-347 with
+ * the centre crop of augmentations.py:26-45 in front): `nchw` holds N planar uint8 frames [N][C][Hs][Ws] as the
+ * environments hand them over; the window (top, left), Hd x Wd, of each goes into ring slots first_slot ..
+ * first_slot + N - 1 of `frames` ([slot][Hd][Wd][C], what curla_conv1_fwd reads with src_kind 1):
+ *   frames[first_slot + n][y][x][c] = nchw[n][c][top + y][left + x],   0 <= y < Hd, 0 <= x < Wd.
+ * One launch replaces N curla_store_frame calls and N host-side crops and transposes.  C in {3, 6, 9, 12} with both
+ * pointers on a 4-byte boundary moves whole dwords on both sides, at any Hs, Ws, Hd, Wd, top and left; every other
+ * case gives the same bytes one at a time.  CURLA_ERR_ARG when the window reaches outside the source or N < 1 or
+ * C < 1.  Reads only the N source frames and writes only the N slots (the caller owns the ring's size and its 32
+ * bytes of loader slack). */
+int curla_stage_frames_u8(const uint8_t* nchw, uint8_t* frames, long long first_slot, int N, int C, int Hs, int Ws,
+                          int top, int left, int Hd, int Wd, void* stream);
 /* De-duplicated frame store (next_obs[t] shares k-1 of its k frames with obs[t], and equals obs[t+1]
  * inside an episode, utils.py:238-268): `store` holds every RGB frame once, uint8 [F][H][W][3]; row idx[b] (NULL: b) of
  * `fid` (int32, `fid_stride` entries per row) lists the K frame ids of a stack.  Writes the minibatch of stacks
