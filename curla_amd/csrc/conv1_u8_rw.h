@@ -16,7 +16,7 @@
 // channels and walks down: output row y needs input rows 2y, 2y+1, 2y+2, the last of which is the next row's first, so
 // a step loads and converts two new rows (2 loads, 2 E conversions) for 6 E MFMAs.  No LDS, no barrier.
 //
-// Status (rounds 3-4; since round 5 this walk is what option conv1_u8 = auto takes, see conv.hip use_rw_u8 and the bf16 form at the end
+// Status (rounds 3-4; since round 5 this walk is what option conv1_u8 = auto takes, see conv.hip select_conv1_u8_form and the bf16 form at the end
 // of this file): opt-in.  Alone -- the same ring slots re-read out of the Infinity Cache from launch to
 // launch -- it is the faster kernel (1024 samples of 76x76x9: 66-71 us against 85; 1536: 100-105 against 128).  On slots
 // drawn afresh from a ring of gigabytes for every launch, which is what update() does, it is the slower one: 114 us on
@@ -24,7 +24,7 @@
 // prefetch distance (1 / 2 / 4 steps: 90.6 / 86.4 / 88.4 us), five waves per SIMD instead of four, and pulling a
 // workgroup's crops into the L2 in one coalesced burst first (92 against 82) did not change that; the banded kernel,
 // which reads a crop once in one burst and then works out of LDS, does not see the difference -- and the default is now
-// the hybrid of the two (conv1_u8_walk_kernel in conv.hip: that staging, this loop reading from LDS).  DESIGN.md section 6.
+// the hybrid of the two (conv1_u8_walk_kernel in conv1_band.h: that staging, this loop reading from LDS).  DESIGN.md section 6.
 #pragma once
 
 namespace rw {

@@ -1302,11 +1302,11 @@ struct GemmPlan {
 // the matrix pipe.  A 128 x 64 tile (a wave: 64 x 32, six fragment reads per 48 matrix instructions) halves the LDS
 // traffic per product.
 static int gemm_mfma_opt() { return curla_opt(kOptGemmMfma); }
-static bool gemm_b3() { return gemm_mfma_opt() == 2; }
+static bool gemm_b3() { return gemm_mfma_opt() == kGemmMfmaB3; }
 
 // whether the 128 x 64 bf16x3 tile can take this product at all (whole tiles, aligned operands, no k split)
 static bool big_tile_ok(const GemmArgs& g) {
-  return gemm_mfma_opt() != 1 && g.ksplit == 1 && g.vecA && g.vecB && g.K % BK == 0 && g.K >= 4 * BK && g.M % 128 == 0 &&
+  return gemm_mfma_opt() != kGemmMfmaF32 && g.ksplit == 1 && g.vecA && g.vecB && g.K % BK == 0 && g.K >= 4 * BK && g.M % 128 == 0 &&
          g.N % 64 == 0 && !g.colsum;
 }
 static long long big_tile_count(const GemmArgs& g) { return (long long)(g.M / 128) * (g.N / 64) * g.nbatch; }
@@ -1345,10 +1345,10 @@ static int gemm_plan(GemmArgs& g, int a_kmajor, int b_kmajor, GemmPlan& p, bool 
   const int tile_opt = curla_opt(kOptGemmTile);
   bool big = big_tile_ok(g) && (force_big || big_tile_count(g) >= curla_cu_count());
   switch (tile_opt) {  // option gemm_tile (options.h; tools/gemm_shapes.py): a forced tile shape
-    case 1: tbm = 64, tbn = 64, big = false; break;
-    case 2: tbm = 64, tbn = 32, big = false; break;
-    case 3: tbm = 32, tbn = 32, big = false; break;
-    case 4: big = big_tile_ok(g); break;
+    case kGemmTile6464: tbm = 64, tbn = 64, big = false; break;
+    case kGemmTile6432: tbm = 64, tbn = 32, big = false; break;
+    case kGemmTile3232: tbm = 32, tbn = 32, big = false; break;
+    case kGemmTile12864: big = big_tile_ok(g); break;
     default: break;
   }
   if (big) {
@@ -1499,7 +1499,7 @@ int curla_linear_bwd(const float* dy, long long stride_dy, const float* x, long 
   gemm_args_plain(g2, dy, N, stride_dy, W, K, stride_W, dx, K, stride_dx, B, K, N, nbatch);
   g2.mask = mask, g2.ldmask = K, g2.sMask = stride_mask;
   GemmPlan p1, p2;
-  const bool split = curla_opt(kOptLinearBwd) == 1;  // (option linear_bwd, options.h)
+  const bool split = curla_opt(kOptLinearBwd) == kLinearBwdSplit;  // (option linear_bwd, options.h)
   // the two products' 128 x 64 tiles are counted together: one launch holds both
   const bool both_big = !split && big_tile_ok(g1) && big_tile_ok(g2) && big_tile_count(g1) + big_tile_count(g2) >= curla_cu_count();
   int rc = gemm_plan(g1, 1, 1, p1, both_big);
@@ -1620,7 +1620,7 @@ int curla_fc_fwd_multi(int nprob, const float* const* x, const float* const* W, 
     if (curla_set_dyn_lds(reinterpret_cast<const void*>(fc_fwd_kernel<NTF, NTL, B3F>), lds) != CURLA_OK) return CURLA_ERR_LAUNCH; \
     hipLaunchKernelGGL((fc_fwd_kernel<NTF, NTL, B3F>), dim3(grid), dim3(256), lds, st, g);                                \
   } while (0)
-  const bool b3 = gemm_mfma_opt() != 1;  // option gemm_mfma: f32 keeps the f32-input MFMA
+  const bool b3 = gemm_mfma_opt() != kGemmMfmaF32;  // option gemm_mfma: f32 keeps the f32-input MFMA
   if (F == 50) {
     if (b3) CURLA_FC_FWD(3, 2, true); else CURLA_FC_FWD(3, 2, false);
   } else {

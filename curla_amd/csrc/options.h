@@ -25,4 +25,16 @@ enum CurlaOpt {
   kOptCount
 };
 
+// The values of each option by name, in the order of the comments above and of the texts in options.hip's kDefs (which
+// checks the counts, k...Values, against its table)
+enum Conv1U8Opt { kConv1U8Auto, kConv1U8Hybrid, kConv1U8Band, kConv1U8Rw, kConv1U8Rwb, kConv1U8Values };
+enum Conv1F32Opt { kConv1F32Rw, kConv1F32Band, kConv1F32Values };
+enum S1FwdOpt { kS1FwdAuto, kS1FwdF23, kS1FwdF43, kS1FwdB3, kS1FwdValues };
+enum BwdSplitOpt { kBwdSplitAuto, kBwdSplitOff, kBwdSplitOn, kBwdSplitValues };
+enum GemmTileOpt { kGemmTileAuto, kGemmTile6464, kGemmTile6432, kGemmTile3232, kGemmTile12864, kGemmTileValues };
+enum LinearBwdOpt { kLinearBwdPair, kLinearBwdSplit, kLinearBwdValues };
+enum GemmMfmaOpt { kGemmMfmaAuto, kGemmMfmaF32, kGemmMfmaB3, kGemmMfmaValues };
+enum S1WgradOpt { kS1WgradAuto, kS1WgradX, kS1WgradXY, kS1WgradValues };
+enum Wgrad1U8Opt { kWgrad1U8Auto, kWgrad1U8F32, kWgrad1U8B16, kWgrad1U8Values };
+
 int curla_opt(int id);  // current value (options.hip)

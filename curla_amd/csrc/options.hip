@@ -19,7 +19,7 @@ struct OptDef {
   const char* alias[6];
 };
 
-const OptDef kDefs[kOptCount] = {
+constexpr OptDef kDefs[kOptCount] = {
     {"conv1_u8", {"auto", "hybrid", "band", "rw", "rwb", nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}},
     {"conv1_f32", {"rw", "band", nullptr}, {nullptr, nullptr, nullptr}},
     {"s1_fwd", {"auto", "f23", "f43", "b3", nullptr}, {nullptr, nullptr, nullptr, "bf16x3", nullptr}},
@@ -30,6 +30,16 @@ const OptDef kDefs[kOptCount] = {
     {"s1_wgrad", {"auto", "x", "xy", nullptr}, {nullptr, "1d", "2d", nullptr}},
     {"wgrad1_u8", {"auto", "f32", "b16", nullptr}, {nullptr, nullptr, "bf16", nullptr}},
 };
+
+// the value enumerators of options.h and the texts above cannot drift apart: same number of values per option
+constexpr int kValueCount[kOptCount] = {kConv1U8Values, kConv1F32Values, kS1FwdValues, kBwdSplitValues, kGemmTileValues,
+                                        kLinearBwdValues, kGemmMfmaValues, kS1WgradValues, kWgrad1U8Values};
+constexpr bool value_counts_match() {
+  for (int id = 0; id < kOptCount; ++id)  // (texts 0 .. n - 1, then the nullptr that ends them)
+    if (!kDefs[id].values[kValueCount[id] - 1] || kDefs[id].values[kValueCount[id]]) return false;
+  return true;
+}
+static_assert(value_counts_match(), "options.h names a different number of values than kDefs lists for some option");
 
 std::atomic<int> g_value[kOptCount];
 std::once_flag g_once;

@@ -58,7 +58,7 @@ def _one_update(aug_name, options=None, env=None, lr=0.0, steps=1):
         if aug_name == "random_crop":
             C, in_hw, out_hw = 9, (40, 44), (32, 36)
             aug = curla_amd.RandomCrop(in_hw, out_hw)
-        elif aug_name == "wide":  # rows of >= 16 pixel quads after three stride-1 layers: the F(4,3) forward by default
+        elif aug_name == "wide":  # rows of >= 16 pixel quads after three stride-1 layers: where F(4,3) wins among the f32 forms
             C, in_hw, out_hw, layers = 9, (20, 150), (16, 141), 4
             aug = curla_amd.RandomCrop(in_hw, out_hw)
         else:  # float NHWC minibatches: the colour-jittered observations of configs[4]
