@@ -16,7 +16,7 @@ c_int, c_ll, c_float, c_size_t, vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_f
 c_u64 = ctypes.c_ulonglong
 c_double = ctypes.c_double
 
-ABI_VERSION = 8  # include/curla_hip.h CURLA_ABI_VERSION this table was written for
+ABI_VERSION = 8  # include/curla_hip.h CURLA_ABI_VERSION this table was written for (additive entry points keep it)
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/curla_hip.h
 SIGNATURES = {
@@ -108,6 +108,8 @@ SIGNATURES = {
     "curla_color_jiggle": [vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_noisy_cover": [vp, vp, vp, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp],
     "curla_gather_nhwc": [vp, vp, c_int, c_int, c_int, c_int, vp, vp],
+    "curla_noisy_cover_rng": [vp, vp, c_float, c_u64, c_u64, vp, c_float, c_float, c_float, vp, c_int, c_int, c_int, c_int,
+                              c_int, c_int, vp, vp, vp],
     "curla_color_jiggle_nchw": [vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_noisy_cover_nchw": [vp, vp, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp],
     "curla_version": [],

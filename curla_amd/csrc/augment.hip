@@ -213,6 +213,76 @@ __global__ void noisy_cover_kernel(const uint8_t* frames, const int64_t* idx, co
   }
 }
 
+// noisy_cover_kernel with the noise DRAWN here instead of read (augmentations.py:157,197: RandomGaussianNoise(0, std)):
+// element i of the flat NHWC batch gets std * philox_normal(seed, offset, i) (common.h), so one thread owns one Philox
+// counter = 4 consecutive elements: 4 source bytes in (one aligned dword where the frame and its address allow), one
+// 16-byte store out -- 1 B read + 4 B written per element, where torch.randn + `* std` + noisy_cover_kernel move
+// 4 + (4 + 4) + (1 + 4 + 4).  Cover rows need no pixel coordinates: inside a frame of H W C bytes row y < top is byte
+// r < top W C and y >= H - bottom is r >= (H - bottom) W C; the colour channel is (r % C) % 3.
+// rng_dev / colors_dev != nullptr: (seed, offset) / the three colours are read from device memory when the kernel
+// RUNS (a captured graph is replayed with new values), the by-value ones are ignored.
+struct CoverDraw {
+  float std, c0, c1, c2;
+  unsigned long long seed, offset;
+  const unsigned long long* rng_dev;
+  const float* colors_dev;
+};
+
+__global__ __launch_bounds__(256) void noisy_cover_rng_kernel(const uint8_t* frames, const int64_t* idx, CoverDraw a,
+                                                                unsigned lo, unsigned hi, unsigned frame, unsigned C,
+                                                                unsigned n, float* out, float* noise_out) {
+  // v + std * z must round like the explicit-noise kernel fed noise_out (product first, then the sum): no fused
+  // multiply-add across the two
+#pragma clang fp contract(off)
+  const unsigned long long seed = a.rng_dev ? a.rng_dev[0] : a.seed, offs = a.rng_dev ? a.rng_dev[1] : a.offset;
+  const float c0 = a.colors_dev ? a.colors_dev[0] : a.c0, c1 = a.colors_dev ? a.colors_dev[1] : a.c1,
+              c2 = a.colors_dev ? a.colors_dev[2] : a.c2;
+  const unsigned groups = (n >> 2) + ((n & 3) != 0);
+  const bool vec = ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(noise_out)) & 15) == 0;  // (null: aligned)
+  for (unsigned j = blockIdx.x * 256 + threadIdx.x; j < groups; j += gridDim.x * 256) {
+    float z[4];
+    philox_normal4(seed, offs + j, z);
+    const unsigned e0 = 4 * j, cnt = min(4u, n - e0);
+    unsigned b = e0 / frame, r = e0 - b * frame;  // sample and byte inside its frame of element e0
+    const uint8_t* src = frames + (size_t)(idx ? idx[b] : (int64_t)b) * frame + r;
+    unsigned px[4], rr[4];
+    if (r + 4 <= frame && (reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+      const uint32_t d = *reinterpret_cast<const uint32_t*>(src);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) px[e] = (d >> (8 * e)) & 0xffu, rr[e] = r + e;
+    } else {  // the group straddles two samples (H W C not a multiple of 4), or the bytes are off a dword boundary
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        px[e] = 0, rr[e] = 0;
+        if ((unsigned)e < cnt) {
+          if (r == frame) r = 0, ++b, src = frames + (size_t)(idx ? idx[b] : (int64_t)b) * frame;
+          px[e] = *src++, rr[e] = r++;
+        }
+      }
+    }
+    float nz[4], o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const unsigned ch = (rr[e] % C) % 3;
+      float v = (float)px[e];
+      if (rr[e] < lo || rr[e] >= hi) v = ch == 0 ? c0 : ch == 1 ? c1 : c2;
+      nz[e] = a.std * z[e];
+      o[e] = fminf(fmaxf(v + nz[e], 0.f), 255.f);
+    }
+    if (vec && cnt == 4) {
+      *reinterpret_cast<f32x4*>(out + e0) = f32x4{o[0], o[1], o[2], o[3]};
+      if (noise_out) *reinterpret_cast<f32x4*>(noise_out + e0) = f32x4{nz[0], nz[1], nz[2], nz[3]};
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((unsigned)e < cnt) {
+          out[e0 + e] = o[e];
+          if (noise_out) noise_out[e0 + e] = nz[e];
+        }
+    }
+  }
+}
+
 // the same on the reference's tensor contract: float NCHW in [0,255] in, noise NCHW, out NCHW
 // (NoisyCover.training_augmentation(image_batch), augmentations.py:170-205; in == out is allowed)
 __global__ void noisy_cover_nchw_kernel(const float* in, const float* noise, float c0, float c1, float c2, int top,
@@ -274,6 +344,24 @@ int curla_noisy_cover(const uint8_t* frames, const int64_t* idx, const float* no
   CURLA_REQUIRE(frames && noise && out && B > 0 && C > 0 && H > 0 && W > 0 && top >= 0 && bottom >= 0);
   hipLaunchKernelGGL(noisy_cover_kernel, dim3(blocks_for((size_t)B * H * W * C)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), frames, idx, noise, c0, c1, c2, top, bottom, B, C, H, W, out);
+  return curla_launch_status();
+}
+
+int curla_noisy_cover_rng(const uint8_t* frames, const int64_t* idx, float std, unsigned long long seed,
+                          unsigned long long offset, const unsigned long long* rng_dev, float c0, float c1, float c2,
+                          const float* colors_dev, int top, int bottom, int B, int C, int H, int W, float* out,
+                          float* noise_out, void* stream) {
+  CURLA_REQUIRE(frames && out && B > 0 && C > 0 && H > 0 && W > 0 && top >= 0 && bottom >= 0);
+  CURLA_REQUIRE((reinterpret_cast<uintptr_t>(rng_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(colors_dev) & 3) == 0);
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(noise_out)) & 3) == 0);
+  const unsigned long long n = (unsigned long long)B * H * W * C;
+  if (n >= (1ull << 32)) return CURLA_ERR_UNSUPPORTED;  // (elements are numbered in 32 bits, like the policy head's)
+  const unsigned row = (unsigned)W * C;
+  const CoverDraw a{std, c0, c1, c2, seed, offset, rng_dev, colors_dev};
+  hipLaunchKernelGGL(noisy_cover_rng_kernel, dim3(blocks_for((size_t)((n + 3) / 4))), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), frames, idx, a, (unsigned)(top < H ? top : H) * row,
+                     (unsigned)(bottom < H ? H - bottom : 0) * row, (unsigned)H * row, (unsigned)C, (unsigned)n, out,
+                     noise_out);
   return curla_launch_status();
 }
 

@@ -103,3 +103,44 @@ static inline int curla_set_dyn_lds(const void* fn, size_t bytes) {
   } while (0)
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- counter-based normal draws (policy head, heads.hip; NoisyCover, augment.hip): ONE definition, so that both
+// translation units number and round the stream alike ----
+__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long ctr, unsigned (&out)[4]) {
+  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1, c3 = (unsigned)p0, c0 = n0, c2 = n2;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+// standard normal number i of the stream: Box-Muller on two of the four 32-bit outputs of counter i / 4
+__device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned long long offset, unsigned i) {
+  unsigned r[4];
+  philox4x32_10(seed, offset + (i >> 2), r);
+  const unsigned a = r[(i & 2)], b = r[(i & 2) + 1];
+  const float u1 = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
+  const float u2 = (float)(b >> 8) * (1.0f / 16777216.0f);          // [0, 1)
+  const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.283185307179586f * u2;
+  return (i & 1) ? rad * sinf(ang) : rad * cosf(ang);
+}
+
+// the four normals 4 j .. 4 j + 3 of the stream (all of counter offset + j) at the cost of one Philox evaluation:
+// out[e] is philox_normal(seed, offset, 4 j + e), the same expressions on the same inputs
+__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned long long ctr, float (&out)[4]) {
+  unsigned r[4];
+  philox4x32_10(seed, ctr, r);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const unsigned a = r[2 * h], b = r[2 * h + 1];
+    const float u1 = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
+    const float u2 = (float)(b >> 8) * (1.0f / 16777216.0f);          // [0, 1)
+    const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.283185307179586f * u2;
+    out[2 * h] = rad * cosf(ang), out[2 * h + 1] = rad * sinf(ang);
+  }
+}

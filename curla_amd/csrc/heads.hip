@@ -284,30 +284,7 @@ struct HeadArgs {
   const unsigned long long* rng_dev;
 };
 
-__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long ctr, unsigned (&out)[4]) {
-  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1, c3 = (unsigned)p0, c0 = n0, c2 = n2;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-  out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
-}
-
-// standard normal number i of the stream: Box-Muller on two of the four 32-bit outputs of counter i / 4
-__device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned long long offset, unsigned i) {
-  unsigned r[4];
-  philox4x32_10(seed, offset + (i >> 2), r);
-  const unsigned a = r[(i & 2)], b = r[(i & 2) + 1];
-  const float u1 = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-  const float u2 = (float)(b >> 8) * (1.0f / 16777216.0f);          // [0, 1)
-  const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.283185307179586f * u2;
-  return (i & 1) ? rad * sinf(ang) : rad * cosf(ang);
-}
-
+// (philox4x32_10 / philox_normal: common.h, shared with the noisy-cover kernel of augment.hip)
 __device__ __forceinline__ void actor_head_one(float mu, float raw, int b, int a, const HeadArgs& hd, float& lp,
                                                float& corr) {
   const int A = hd.A;

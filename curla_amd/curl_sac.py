@@ -1335,13 +1335,21 @@ class CurlSacAgent(object):
         captured kernels read on the device: the minibatch's indices / crop offsets (as before), the Philox stream
         position of each policy-noise draw and every optimizer's two step-dependent Adam factors (curla_hip.h: the
         ``rng_dev`` / ``dyn`` arguments); the block's staging kernel is the first node of the graph.
+        A ``ReplayBuffer(..., staged_aug=True)`` with ColorJiggle or NoisyCover is covered the same way: the host draws
+        the three tensors' parameters per replay (``draw_aug``: torch's CPU generator / NumPy, in the eager order; for
+        NoisyCover also the Philox positions of the three in-kernel noise draws, taken from the device generator IN
+        FRONT of the two policy draws, as an eager staged update takes them) and writes them into the block behind the
+        indices; the jitter / cover launches are nodes that read the block's device copy.  A ``dedup_frames`` buffer
+        needs no flag: its gather_stacks launches are nodes that read the frame-id table when the graph runs.
+        (ColorJiggle's arithmetic stays PARITY UNPINNED, graphed or not: augmentations.py.)
         ``depth`` graphs are captured per kind, each with its own pinned block, and used in rotation: the host may then
         prepare update n + 2 depth - 1 while the GPU still reads the block of update n (with one graph per kind it would
         wait for the replay two updates back before every update).
         Results are bit-identical to the eager path (tests/test_gpu_graph.py).  Steps the graphs do not cover run
         eagerly, in any mix: logging steps (``step % log_interval == 0``: they compute extra scalars), histogram /
-        image recording steps, ``only_cpc``, float augmentations (ColorJiggle / NoisyCover stage their parameters per
-        call), other replay buffers, data-parallel runs on a backend other than RCCL.  Data-parallel updates over RCCL
+        image recording steps, ``only_cpc``, other replay buffers, data-parallel runs on a backend other than RCCL.  A
+        float augmentation on a buffer built WITHOUT ``staged_aug=True`` is refused here (its parameters go through a
+        pinned block and a copy of their own per call).  Data-parallel updates over RCCL
         ARE captured, collectives included (round 5; the replica check stays on the host, in front of the replay).
         Values the graphs hold as kernel arguments (discount, taus, betas / eps, detach_encoder, the update
         frequencies, the data-parallel group and schedule) are fingerprinted at capture: editing one of them drops the
@@ -1351,7 +1359,9 @@ class CurlSacAgent(object):
             raise RuntimeError("update graphs need the HIP device")
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
             raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
-                             "(uint8-ring minibatches only: RandomCrop or identity, plain storage)")
+                             "(covered: RandomCrop or identity, plain or dedup_frames storage; ColorJiggle / NoisyCover "
+                             "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
+                             "CURLA_STAGE_COPY=1)")
         opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer)
         if not all(isinstance(o, FlatAdam) and "step" not in vars(o) for o in opts) or \
                 type(self.log_alpha_optimizer) is not torch.optim.Adam or self._noise_launch:
@@ -1471,8 +1481,8 @@ class CurlSacAgent(object):
         B = rb.batch_size
         if st["graph"] is None:
             # capture FIRST, commit the host's bookkeeping (NumPy draw, generator offset, step counts) only once the
-            # capture has succeeded: nothing inside the captured region draws from NumPy or moves the generator
-            # (draw_indices / _graph_tail run after it), so a capture that raises (a first-use attribute call after an
+            # capture has succeeded: nothing inside the captured region draws from NumPy, torch's CPU generator or
+            # moves the device generator (draw_indices / draw_aug / _graph_tail run after it), so a capture that raises (a first-use attribute call after an
             # option change, a HIP call from another thread) has touched only the phase-to-phase hints below, which are
             # reset, and this update runs eagerly
             blk = rb.graph_block(st["slot"])
@@ -1522,9 +1532,12 @@ class CurlSacAgent(object):
                 return self._update_eager(rb, L, step)
             st["graph"] = graph
             self._graph_key_at_capture = key
+        # the eager order of host draws: indices, then the three tensors' augmentation parameters (staged_aug: NoisyCover
+        # reserves its noise counters on the device generator here), then the policy draws of _graph_tail
         idxs, offs = rb.draw_indices()
+        aug = rb.draw_aug()
         tail = self._graph_tail(kind, B)
-        blk = rb.graph_write(st["slot"], idxs, offs, tail)
+        blk = rb.graph_write(st["slot"], idxs, offs, tail, aug)
         if self._dp_active and self._dp_check_every > 0 and step % self._dp_check_every == 0:
             self.check_replicas()
         st["graph"].replay()

@@ -704,6 +704,18 @@ def noisy_cover(frames, idx, noise, colors, top, bottom, B, out):
          int(top), int(bottom), B, C, H, W, ptr(out), stream())
 
 
+def noisy_cover_rng(frames, idx, std, rng, colors, top, bottom, B, out, noise_out=None):
+    """noisy_cover with the noise drawn inside the launch.  ``rng`` = (seed, offset[, device address]) as for
+    actor_head_fwd: the caller owns the offset bookkeeping (ceil(B H W C / 4) counters per call).  ``colors``: three
+    numbers, or the device address of three floats that the kernel reads when it runs."""
+    _, H, W, C = frames.shape
+    by_value = not isinstance(colors, int)
+    c = [float(v) for v in colors] if by_value else [0.0, 0.0, 0.0]
+    call("curla_noisy_cover_rng", ptr(frames), ptr(idx), float(std), int(rng[0]) & (2 ** 64 - 1), int(rng[1]),
+         rng[2] if len(rng) > 2 else None, c[0], c[1], c[2], None if by_value else colors, int(top), int(bottom), B, C, H,
+         W, ptr(out), ptr(noise_out), stream())
+
+
 def color_jiggle_nchw(x, params, order, out):
     B, C, H, W = x.shape
     call("curla_color_jiggle_nchw", ptr(_dev(x)), ptr(params), ptr(order), B, C, H, W, ptr(_dev(out)), stream())

@@ -16,6 +16,11 @@ ONE new frame instead of 2k -- 63.5 KB -> 21 KB per transition at 84x84x9,
 339 KB -> 85 KB at 168x168x12.  Sharing is detected from the bytes handed to
 ``add`` (hash, then full comparison), never assumed, so sampled pixels are the
 reference's whatever the caller does.
+
+``staged_aug=True`` (float augmentations) sends the random parameters of a minibatch's three tensors along in the
+index block instead of through a pinned block and a copy of their own per tensor, and lets NoisyCover draw its noise
+inside the cover kernel: with it -- and for ``dedup_frames`` without it -- the minibatch can be a node of a captured
+update graph (``graph_supported``).
 """
 import collections
 import os
@@ -193,7 +198,7 @@ class ReplayBuffer(object):
     EVENT_EVERY = 8     # index uploads per recorded event (16 pinned slots)
 
     def __init__(self, obs_shape, action_shape, capacity, batch_size, device, augmentor, transform=None,
-                 dedup_frames=False, frame_capacity=None):
+                 dedup_frames=False, frame_capacity=None, staged_aug=False):
         self.capacity = capacity
         self.batch_size = batch_size
         self.device = torch.device(device)
@@ -206,6 +211,16 @@ class ReplayBuffer(object):
         frame = c * h * w
         A = int(np.prod(action_shape))
         self.dedup_frames = bool(dedup_frames)
+        # float augmentations only: the parameters travel in the index block, NoisyCover's noise is drawn in the kernel
+        self.staged_aug = bool(staged_aug) and self._is_float_aug()
+        if self.staged_aug and isinstance(augmentor, augmentations.NoisyCover):
+            if c * h * w * batch_size >= 2 ** 32:
+                raise ValueError("staged_aug: the in-kernel noise numbers a minibatch tensor's elements in 32 bits")
+            try:
+                self._noise_generator().get_offset()
+            except (AttributeError, RuntimeError) as e:
+                raise ValueError("staged_aug=True with NoisyCover draws its noise from the Philox stream of the HIP "
+                                 f"device's torch generator, which exposes no offset here ({e!r})") from e
         if self.dedup_frames:
             if c % 3 != 0:
                 raise ValueError("dedup_frames needs stacked RGB frames (channels a multiple of 3)")
@@ -282,7 +297,9 @@ class ReplayBuffer(object):
         # (an event record is a packet of its own in the stream, ~5 us: one per EVENT_EVERY uses, and a slot is
         # re-written only after the first event recorded at or after its last use has completed)
         self._n_slots, self._slot_use = 16, 0
-        nbytes = 2 * B * 8 + B * 4 * 6  # frame indices (obs | next_obs) + the six crop-offset rows
+        # frame indices (obs | next_obs) + the six crop-offset rows (+ staged_aug: the three tensors' parameters)
+        self._layout = self.block_layout()
+        nbytes = self._layout["nbytes"]
         self._h_index = torch.empty((self._n_slots, nbytes), dtype=torch.uint8, pin_memory=pin)
         self._slot_events = {}
         # pinned slots are read by the GPU in place (ops.sample_stage): no copy-engine transfer in front of an update
@@ -466,15 +483,20 @@ class ReplayBuffer(object):
             raise NotImplementedError("unknown augmentation object: %r" % (self.augmentor,))
         return idxs, offs
 
-    def _float_augmented(self, ring, idx, out=None):
+    def _float_augmented(self, ring, idx, out=None, staged=None):
         """One augmented float NHWC minibatch [B, H, W, C] from ``ring`` rows ``idx`` (None: rows 0..B-1)
-        (utils.py:168-182 branch: the torch/kornia augmentations)."""
+        (utils.py:168-182 branch: the torch/kornia augmentations).  ``staged`` (staged_aug): the tensor's parameters
+        are already on the device, in the minibatch's block (_aug_args) -- nothing is drawn, allocated or copied here."""
         B = self.batch_size
         c, h, w = self.obs_shape
         if out is None:
             out = torch.empty((B, h, w, c), dtype=torch.float32, device=self.device)
         aug = self.augmentor
-        if isinstance(aug, augmentations.ColorJiggle):
+        if staged is not None and isinstance(aug, augmentations.ColorJiggle):
+            ops.color_jiggle(ring, idx, staged[0], staged[1], B, out)
+        elif staged is not None:
+            ops.noisy_cover_rng(ring, idx, aug.std, (0, 0, staged[1]), staged[0], aug.top, aug.bottom, B, out)
+        elif isinstance(aug, augmentations.ColorJiggle):
             params, order = aug.draw_params(B * (c // 3))
             # one pinned staging block, one asynchronous copy: a `.to(device)` of a pageable tensor makes the host wait
             # until the stream has drained (two of them per call left ~60 us of idle GPU around every jitter launch)
@@ -495,6 +517,89 @@ class ReplayBuffer(object):
 
     def _is_float_aug(self):
         return isinstance(self.augmentor, (augmentations.ColorJiggle, augmentations.NoisyCover))
+
+    def _staged_args(self):
+        """Per tensor (obs, next_obs, pos): the staged parameters in the current sample slot's device block, or None."""
+        if not self.staged_aug:
+            return [None, None, None]
+        return [self._aug_args(self._d_index[self._sample_slot], j) for j in range(3)]
+
+    def block_layout(self):
+        """Byte offsets inside a minibatch's block -- the ONE place that knows them.  Every block starts with
+        idx int64 [2B] | crop offsets int32 [6][B] (_fill_index_block).  ``staged_aug`` appends the parameters of the
+        three tensors (obs, next_obs, pos), ``aug_stride`` bytes each:
+          ColorJiggle  params float [B k][4] (apply, contrast, saturation, hue) | order int32 [4]
+          NoisyCover   colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2]   (8-byte aligned)
+        ``nbytes`` is what a rotating sample slot stages per minibatch; the block of a captured update graph carries
+        GRAPH_TAIL more bytes of per-update control values behind it (at ``tail``; ``graph_nbytes`` in all)."""
+        B = self.batch_size
+        lay = dict(idx=0, offs=2 * B * 8, aug=None, aug_stride=0, aug_order=None, aug_rng=None)
+        n = 2 * B * 8 + 6 * B * 4
+        if self.staged_aug:
+            if isinstance(self.augmentor, augmentations.ColorJiggle):
+                n_par = 16 * B * (self.obs_shape[0] // 3)
+                lay.update(aug=n, aug_stride=n_par + 16, aug_order=n_par)
+            else:
+                lay.update(aug=n, aug_stride=32, aug_rng=16)
+            n += 3 * lay["aug_stride"]
+        assert n % 8 == 0
+        lay.update(nbytes=n, tail=n, graph_nbytes=n + self.GRAPH_TAIL)
+        return lay
+
+    def _noise_generator(self):
+        """The torch generator of the HIP device: staged NoisyCover takes (seed, Philox counter) of its in-kernel noise
+        from it, exactly as the policy-noise draws do (CurlSacAgent._noise) -- one non-overlapping counter sequence."""
+        if self.device.type != "cuda":
+            raise RuntimeError("no HIP device generator on a %s buffer" % self.device.type)
+        return torch.cuda.default_generators[self.device.index if self.device.index is not None
+                                             else torch.cuda.current_device()]
+
+    def draw_aug(self):
+        """(staged_aug) The host draws of the three tensors' augmentations, obs then next_obs then pos -- what the
+        default path draws one tensor at a time (utils.py:173-182): ``ColorJiggle.draw_params`` from torch's CPU
+        generator, ``NoisyCover.draw_colors`` from NumPy.  NoisyCover also reserves the tensor's ceil(n / 4) Philox
+        counters by moving the device generator's offset on by 4 ceil(n / 4), as CurlSacAgent._noise does.  None when
+        nothing is staged."""
+        if not self.staged_aug:
+            return None
+        B = self.batch_size
+        c, h, w = self.obs_shape
+        aug, out = self.augmentor, []
+        for _ in range(3):
+            if isinstance(aug, augmentations.ColorJiggle):
+                out.append(aug.draw_params(B * (c // 3)))
+            else:
+                colors = aug.draw_colors()
+                gen = self._noise_generator()
+                off, n = gen.get_offset(), B * c * h * w
+                gen.set_offset(off + 4 * ((n + 3) // 4))
+                out.append((colors, gen.initial_seed() & (2 ** 64 - 1), off // 4))
+        return out
+
+    def _fill_aug(self, host, aug):
+        """draw_aug()'s values into a pinned block (block_layout)."""
+        lay = self._layout
+        for j, item in enumerate(aug):
+            a = lay["aug"] + j * lay["aug_stride"]
+            if lay["aug_order"] is not None:
+                params, order = item
+                host[a:a + lay["aug_order"]].view(torch.float32).copy_(params.reshape(-1))
+                host[a + lay["aug_order"]:a + lay["aug_stride"]].view(torch.int32).copy_(order)
+            else:
+                colors, seed, ctr = item
+                host[a:a + 12].view(torch.float32).copy_(torch.tensor([float(v) for v in colors]))
+                host[a + lay["aug_rng"]:a + 32].view(torch.int64).copy_(
+                    torch.from_numpy(np.array([seed, ctr], dtype=np.uint64).view(np.int64)))
+
+    def _aug_args(self, dev, j):
+        """What the augmentation kernel of tensor j reads from the device copy ``dev`` of a block: ColorJiggle
+        (params [B k, 4], order [4]) as tensors, NoisyCover (colours, (seed, counter)) as device addresses."""
+        lay = self._layout
+        a = lay["aug"] + j * lay["aug_stride"]
+        if lay["aug_order"] is not None:
+            return (dev[a:a + lay["aug_order"]].view(torch.float32).view(-1, 4),
+                    dev[a + lay["aug_order"]:a + lay["aug_stride"]].view(torch.int32))
+        return dev.data_ptr() + a, dev.data_ptr() + a + lay["aug_rng"]
 
     def _fill_index_block(self, host, idxs, offs):
         """A minibatch's indices and crop offsets in the layout the kernels read:
@@ -518,9 +623,9 @@ class ReplayBuffer(object):
         off = [d32[(j // 2 + 3 * (j % 2)) * B:(j // 2 + 3 * (j % 2) + 1) * B] for j in range(6)]
         return d64[:B], off, (d64, d32[:2 * B], d32[3 * B:5 * B])
 
-    def _upload_indices(self, idxs, offs):
-        """Copy a minibatch's indices and crop offsets into the next device sample slot; returns the slot's
-        (guard, idx view [B] int64, offsets view [6, B] int32)."""
+    def _upload_indices(self, idxs, offs, aug=None):
+        """Copy a minibatch's indices and crop offsets (and, staged_aug, its augmentation parameters ``aug``) into the
+        next device sample slot; returns the slot's (guard, idx view [B] int64, offsets view [6, B] int32)."""
         B = self.batch_size
         u, every = self._slot_use, self.EVENT_EVERY
         self._slot_use = u + 1
@@ -534,6 +639,8 @@ class ReplayBuffer(object):
                 del self._slot_events[old]
         host = self._h_index[k]
         self._fill_index_block(host, idxs, offs)
+        if aug is not None:
+            self._fill_aug(host, aug)
         s = self._sample_slot = (self._sample_slot + 1) % self.N_SAMPLE_SLOTS
         self._sample_gen[s] += 1
         dst = self._d_index[s]
@@ -594,11 +701,16 @@ class ReplayBuffer(object):
     GRAPH_TAIL = 80  # u64[4] (seed, critic-noise offset, seed, actor-noise offset) | f64[2] log_alpha | f32[8] four Adams
 
     def graph_supported(self):
-        """Graph replay covers the uint8-ring minibatches (RandomCrop / identity, plain storage, one allocation for both
-        rings, pinned index slots read in place); the float augmentations stage their parameters through per-call
-        pinned blocks and stay eager."""
-        return (self.device.type == "cuda" and not self._is_float_aug() and not self.dedup_frames
-                and self._both is not None and self._h_index_dev is not None)
+        """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
+        ones (RandomCrop / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
+        are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover constructed with
+        ``staged_aug=True`` (either storage).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
+        through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""
+        if self.device.type != "cuda" or self._h_index_dev is None:
+            return False
+        if self._is_float_aug():
+            return self.staged_aug
+        return self.dedup_frames or self._both is not None
 
     def graph_block(self, slot):
         if not hasattr(self, "_graph_blocks"):
@@ -606,27 +718,63 @@ class ReplayBuffer(object):
         g = self._graph_blocks.get(slot)
         if g is None:
             B, A = self.batch_size, self._n_act
-            nb = self._h_index.shape[1] + self.GRAPH_TAIL
-            host = torch.zeros(nb, dtype=torch.uint8, pin_memory=True)
+            lay = self._layout
+            nb = lay["graph_nbytes"]
+            host = torch.zeros(nb, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
             g = dict(host=host, host_dev=ops.host_device_pointer(host), dev=torch.zeros(nb, dtype=torch.uint8, device=self.device),
                      scal=torch.empty(B * (A + 2), dtype=torch.float32, device=self.device), event=None,
-                     tail=self._h_index.shape[1])
+                     tail=lay["tail"], guards=[])
+            # A replayed graph writes to the SAME addresses every time, so the minibatch tensors that the rotating
+            # sample slots / the allocator provide per call are buffers of the graph slot here (allocated now, before
+            # the capture): the gathered uint8 stacks of the de-duplicated store, the float NHWC tensors of an
+            # augmentation.  Each sits between guard bytes (tests/test_gpu_graph_aug.py).
+            frame = self._frame
+            if self.dedup_frames:
+                (g["mb_u8"],) = self._guarded([2 * B * frame + 32], g["guards"])  # (+32: the loaders' slack, as a ring)
+                g["ar2"] = torch.arange(2 * B, device=self.device, dtype=torch.int64)
+            if self._is_float_aug():
+                c, h, w = self.obs_shape
+                both, pos = self._guarded([4 * 2 * B * frame, 4 * B * frame], g["guards"])
+                g["both_f32"] = both.view(torch.float32).view(2 * B, h, w, c)
+                g["pos_f32"] = pos.view(torch.float32).view(B, h, w, c)
             self._graph_blocks[slot] = g
         return g
 
-    def graph_write(self, slot, idxs, offs, tail):
-        """Host side of one graphed update: the minibatch's indices / offsets and the control tail (80 bytes) into the
-        slot's pinned block -- after the previous replay that reads this block has finished."""
+    GUARD, GUARD_BYTE = 256, 0xA5
+
+    def _guarded(self, sizes, guards):
+        """Zeroed uint8 device buffers of ``sizes`` bytes in one allocation, GUARD bytes of GUARD_BYTE in front of,
+        between and behind them (each buffer starts 256-byte aligned); the guard views are appended to ``guards``."""
+        G = self.GUARD
+        padded = [(n + G - 1) // G * G for n in sizes]
+        store = torch.full((G + sum(p + G for p in padded),), self.GUARD_BYTE, dtype=torch.uint8, device=self.device)
+        out, at = [], G
+        guards.append(store[:G])
+        for n, pn in zip(sizes, padded):
+            out.append(store[at:at + n].zero_())
+            guards.append(store[at + n:at + pn + G])
+            at += pn + G
+        return out
+
+    def graph_write(self, slot, idxs, offs, tail, aug=None):
+        """Host side of one graphed update: the minibatch's indices / offsets, the augmentation parameters
+        (``aug`` = draw_aug(), staged_aug) and the control tail (80 bytes) into the slot's pinned block -- after the
+        previous replay that reads this block has finished."""
         g = self.graph_block(slot)
         if g["event"] is not None:
             g["event"].synchronize()
         self._fill_index_block(g["host"], idxs, offs)
+        if aug is not None:
+            self._fill_aug(g["host"], aug)
         g["host"][g["tail"]:].copy_(torch.from_numpy(np.frombuffer(bytearray(tail), dtype=np.uint8)))
         return g
 
     def graph_refs(self, slot):
         """Device side, called while the graph is being captured: the staging launch (pinned block -> device block +
-        the transitions' scalars) and the sample_cpc 6-tuple with handles into the slot's device block."""
+        the transitions' scalars), for the de-duplicated store the two gather_stacks launches (they read ``_fid`` when
+        the graph is replayed), for a staged float augmentation the three jitter / cover launches (they read their
+        parameters from the device block), and the sample_cpc 6-tuple with handles into the slot's buffers.  Nothing
+        here draws a random number."""
         g = self.graph_block(slot)
         B, A = self.batch_size, self._n_act
         buf = g["scal"]
@@ -634,11 +782,25 @@ class ReplayBuffer(object):
                          buf[B * A + B:])
         d_idx, off, (idx2, h2, w2) = self._index_views(g["dev"])
         crop = tuple(self.augmentor.output_shape)
-        both = self._both
-        obses = ops.ObsRef.from_ring(both, idx2[:B], off[0], off[1], B, crop, None)
-        next_obses = ops.ObsRef.from_ring(both, idx2[B:], off[2], off[3], B, crop, None)
-        pos = ops.ObsRef.from_ring(both, idx2[:B], off[4], off[5], B, crop, None)
-        obses.pair = (ops.ObsRef.from_ring(both, idx2, h2, w2, 2 * B, crop, None), next_obses)
+        c, h, w = self.obs_shape
+        both, rows = None if self.dedup_frames else self._both, d_idx
+        if self.dedup_frames:
+            both, rows = g["mb_u8"][:2 * B * self._frame].view(2 * B, h, w, c), None
+            for j in range(2):
+                ops.gather_stacks(self.frames, self._fid[:, j, :], d_idx, B, both[j * B:(j + 1) * B])
+            idx2 = g["ar2"]
+        if self._is_float_aug():
+            ring_o, ring_n = (both[:B], both[B:]) if self.dedup_frames else (self.obses, self.next_obses)
+            fb, fp = g["both_f32"], g["pos_f32"]
+            obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, fb[:B], self._aug_args(g["dev"], 0)))
+            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows, fb[B:], self._aug_args(g["dev"], 1)))
+            pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, fp, self._aug_args(g["dev"], 2)))
+            obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
+        else:
+            obses = ops.ObsRef.from_ring(both, idx2[:B], off[0], off[1], B, crop, None)
+            next_obses = ops.ObsRef.from_ring(both, idx2[B:], off[2], off[3], B, crop, None)
+            pos = ops.ObsRef.from_ring(both, idx2[:B], off[4], off[5], B, crop, None)
+            obses.pair = (ops.ObsRef.from_ring(both, idx2, h2, w2, 2 * B, crop, None), next_obses)
         act, rew, nd = buf[:B * A].view((B,) + tuple(self.actions.shape[1:])), buf[B * A:B * A + B].view(B, 1), \
             buf[B * A + B:].view(B, 1)
         return obses, act, rew, next_obses, nd, dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
@@ -651,7 +813,7 @@ class ReplayBuffer(object):
         one raises)."""
         self._require_cuda()
         idxs, offs = indices if indices is not None else self.draw_indices()
-        guard, d_idx, off = self._upload_indices(idxs, offs)
+        guard, d_idx, off = self._upload_indices(idxs, offs, self.draw_aug())
         B = self.batch_size
         crop = tuple(self.augmentor.output_shape)
         ring_o, ring_n, rows = self._sources(d_idx)
@@ -660,9 +822,10 @@ class ReplayBuffer(object):
             # next_obs are written into the two halves of one [2B] tensor (ObsRef.pair, see below)
             c, h, w = self.obs_shape
             both = torch.empty((2 * B, h, w, c), dtype=torch.float32, device=self.device)
-            obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, out=both[:B]))
-            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows, out=both[B:]))
-            pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows))
+            st = self._staged_args()
+            obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, both[:B], st[0]))
+            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows, both[B:], st[1]))
+            pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, None, st[2]))
             obses.pair = (ops.ObsRef.from_nhwc(both), next_obses)
         else:
             idx2, h2, w2 = self._pair_views
@@ -693,16 +856,17 @@ class ReplayBuffer(object):
         in [0,255] on the device (materialised by one crop kernel per tensor)."""
         self._require_cuda()
         idxs, offs = indices if indices is not None else self.draw_indices()
-        _, d_idx, off = self._upload_indices(idxs, offs)
+        _, d_idx, off = self._upload_indices(idxs, offs, self.draw_aug())
         B = self.batch_size
         c = self.obs_shape[0]
         oh, ow = self.augmentor.output_shape
         ring_o, ring_n, rows = self._sources(d_idx)
+        st = self._staged_args()
         outs = []
         for ring, j in ((ring_o, 0), (ring_n, 1), (ring_o, 2)):
             t = torch.empty((B, c, oh, ow), dtype=torch.float32, device=self.device)
             if self._is_float_aug():
-                ops.nhwc_to_nchw(self._float_augmented(ring, rows), t)
+                ops.nhwc_to_nchw(self._float_augmented(ring, rows, None, st[j]), t)
             else:
                 ops.crop_nchw(ring, rows, off[2 * j], off[2 * j + 1], B, (oh, ow), out_f32=t)
             outs.append(t)

@@ -37,7 +37,11 @@ const char* curla_version(void);
 /* The C ABI's number: bumped whenever an entry point's argument list changes (round 4 put dyn / dyn64 / rng_dev
  * pointers into the middle of the Adam and policy-head calls: 4 -> 5 names that; 7 adds the autograd path's
  * curla_conv1_dgrad and curla_policy_head_bwd; 8 the batched acting path's curla_stage_frames_u8).  A binding written
- * for another number must refuse the library -- curla_amd/_lib.py does -- instead of calling with shifted arguments. */
+ * for another number must refuse the library -- curla_amd/_lib.py does -- instead of calling with shifted arguments.
+ * curla_noisy_cover_rng is a purely ADDITIVE entry point: no existing argument list moves, so a version-8 binding
+ * calls a library that has it exactly as before and the number stays 8; a binding that needs it and meets an older
+ * version-8 library fails at symbol lookup (curla_amd/_lib.py resolves every name when it loads), loudly, not with
+ * shifted arguments. */
 #define CURLA_ABI_VERSION 8
 int curla_abi_version(void);
 
@@ -461,6 +465,20 @@ int curla_color_jiggle(const uint8_t* frames, const int64_t* idx, const float* p
 int curla_noisy_cover(const uint8_t* frames, const int64_t* idx, const float* noise, float c0, float c1, float c2,
                       int top, int bottom, int B, int C, int H, int W, float* out, void* stream);
 int curla_gather_nhwc(const uint8_t* frames, const int64_t* idx, int B, int C, int H, int W, float* out, void* stream);
+/* curla_noisy_cover with the noise drawn INSIDE the launch (augmentations.py:157,197: kornia's
+ * RandomGaussianNoise(mean 0, std) applied after the cover is painted) -- no B H W C float noise tensor is written by
+ * one launch and read back by the next.  Element i of the flat NHWC batch gets std * z_i, z_i = Box-Muller on outputs
+ * (i % 4) & 2, + 1 of Philox4x32-10 with key `seed` and counter `offset + i / 4` (cos for even i, sin for odd): the
+ * policy head's stream (curla_actor_head_fwd_rng).  The caller advances `offset` by ceil(B H W C / 4) per call.
+ * rng_dev != NULL (8-byte aligned device memory): seed = rng_dev[0], offset = rng_dev[1] are read when the kernel RUNS
+ * and the by-value pair is ignored; colors_dev != NULL (3 floats of device memory): likewise for (c0, c1, c2) -- a
+ * captured hipGraph is replayed with new values.  noise_out (optional, NULL in production; float NHWC): receives
+ * std * z_i, so that out equals curla_noisy_cover fed noise_out bit for bit.  Everything else as curla_noisy_cover.
+ * B H W C >= 2^32: CURLA_ERR_UNSUPPORTED (elements are numbered in 32 bits).  PARITY UNPINNED for the noise stream. */
+int curla_noisy_cover_rng(const uint8_t* frames, const int64_t* idx, float std, unsigned long long seed,
+                          unsigned long long offset, const unsigned long long* rng_dev, float c0, float c1, float c2,
+                          const float* colors_dev, int top, int bottom, int B, int C, int H, int W, float* out,
+                          float* noise_out, void* stream);
 /* The two augmentations on the reference's own tensor contract -- what ColorJiggle.training_augmentation(image_batch)
  * and NoisyCover.training_augmentation(image_batch) take and return (augmentations.py:105-136,170-205): float NCHW
  * [B][C][H][W] in [0,255], same arithmetic as the ring forms above; `out` may alias `in`. */
