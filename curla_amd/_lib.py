@@ -112,6 +112,7 @@ SIGNATURES = {
                               c_int, c_int, vp, vp, vp],
     "curla_color_jiggle_nchw": [vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_noisy_cover_nchw": [vp, vp, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp],
+    "curla_random_shift_u8": [vp, vp, c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp],
     "curla_version": [],
     "curla_abi_version": [],
     "curla_set_option": [ctypes.c_char_p, ctypes.c_char_p],

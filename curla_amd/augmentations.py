@@ -78,6 +78,44 @@ class RandomCrop(IdentityAugmentation):
         return out
 
 
+class RandomShift(IdentityAugmentation):
+    """Beyond the reference: the random shift of DrQ / DrQ-v2.  Every frame is padded by ``pad`` pixels on each side
+    with its edge pixels repeated, then a window of the ORIGINAL size is cut at a random offset (dy, dx) in
+    [0, 2 pad]^2, one draw per sample shared by all channels of the stack:
+        out[c][y][x] = in[c][clamp(y + dy - pad, 0, H - 1)][clamp(x + dx - pad, 0, W - 1)]
+    The full field of view and the frame size are kept (``output_shape == input_shape``; not a ``RandomCrop``: nothing
+    is centre-cropped at evaluation time).  On the learner path the pixels are moved by ``curla_random_shift_u8`` and
+    stay uint8 (ReplayBuffer); the offsets are drawn on the host from NumPy's global stream, like RandomCrop's."""
+
+    def __init__(self, input_shape, pad=4):
+        super().__init__(input_shape)
+        if isinstance(pad, bool) or not isinstance(pad, (int, np.integer)) or pad < 0:
+            raise ValueError("RandomShift: pad must be an int >= 0, got %r" % (pad,))
+        self.pad = int(pad)
+
+    def draw_offsets(self, n):
+        """Two RNG draws, dy then dx, each in [0, 2 pad] (in the style of RandomCrop.draw_offsets)."""
+        dy = np.random.randint(0, 2 * self.pad + 1, n)
+        dx = np.random.randint(0, 2 * self.pad + 1, n)
+        return dy, dx
+
+    def shift(self, image_batch, dy, dx):
+        """The shift of a (B, C, H, W) array by given per-sample offsets, on the host."""
+        h, w = image_batch.shape[2:]
+        out = np.empty_like(image_batch)
+        for b in range(image_batch.shape[0]):
+            ys = np.clip(np.arange(h) + int(dy[b]) - self.pad, 0, h - 1)
+            xs = np.clip(np.arange(w) + int(dx[b]) - self.pad, 0, w - 1)
+            out[b] = image_batch[b][:, ys[:, None], xs[None, :]]
+        return out
+
+    def training_augmentation(self, image_batch):
+        """Host-side shift of a (B, C, H, W) NumPy array, for callers outside the fused path."""
+        image_batch = np.asarray(image_batch)
+        dy, dx = self.draw_offsets(image_batch.shape[0])
+        return self.shift(image_batch, dy, dx)
+
+
 class ColorJiggle(IdentityAugmentation):
     """augmentations.py:78-136: every RGB frame of the stack is jittered independently with probability
     0.85 -- contrast U(0.8,1.2), saturation U(0.5,1.5), hue U(-0.5,0.5) turns, brightness 0 -- the four
@@ -150,8 +188,8 @@ class NoisyCover(IdentityAugmentation):
         return out
 
 
-def make_augmentor(name, input_shape, output_shape=None):
-    """augmentations.py:208-221."""
+def make_augmentor(name, input_shape, output_shape=None, *, pad=4):
+    """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding; beyond the reference)."""
     print(f'CHOSEN AUGMENTATION: {name}')
     if name == 'identity':
         return IdentityAugmentation(input_shape)
@@ -161,4 +199,6 @@ def make_augmentor(name, input_shape, output_shape=None):
         return ColorJiggle(input_shape)
     if name == 'noisy_cover':
         return NoisyCover(input_shape)
+    if name == 'random_shift':
+        return RandomShift(input_shape, pad)
     raise ValueError('augmentation is not supported: %s' % name)

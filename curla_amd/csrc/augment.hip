@@ -312,6 +312,103 @@ __global__ void gather_nhwc_kernel(const uint8_t* frames, const int64_t* idx, in
   }
 }
 
+// ---- RandomShift (beyond the reference: the pad-and-crop shift of DrQ / DrQ-v2) ----
+// out[s][y][x][c] = in[row(s)][clamp(y + dy[s] - pad, 0, H - 1)][clamp(x + dx[s] - pad, 0, W - 1)][c], uint8 NHWC in and
+// out: a frame padded by `pad` replicated edge pixels on every side, then an H x W window cut at (dy, dx).  A byte
+// mover (roof: HBM).  A thread owns 16 consecutive output bytes of a sample (one 16-byte store); grid row = sample, so
+// the only division is r / (W C) once per group.  The shift is the same for every channel, so in bytes it is
+// (dx - pad) C along a row and byte b of an output row comes from byte b + (dx - pad) C of the source row wherever
+// that lies inside the row: a group that sits in ONE output row and whose 16 source bytes need no x-clamp is one
+// unaligned 16-byte load (it cannot leave the source row, hence not the ring).  Row clamping only picks the source
+// row.  Groups that straddle two rows or touch the replicated left / right pixels walk their bytes ((y, x, c) are
+// stepped, not divided); so does every group when a frame is not a whole number of 16-byte groups or `out` is off
+// the 16-byte grid (vec == false: byte stores, the last group of a sample is short).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+struct ShiftGeom {
+  int H, W, C, oy, ox;  // oy / ox = dy - pad / dx - pad of the sample
+  unsigned rb, frame;   // bytes of a row / of a frame
+};
+
+// one group, byte by byte: (y, x, c) of its first byte are stepped through the 16 bytes, each read at its clamped source
+__device__ __forceinline__ void shift_group_bytes(const uint8_t* src, uint8_t* dst, const ShiftGeom& q, unsigned r,
+                                                  bool vec) {
+  const unsigned cnt = min(16u, q.frame - r);
+  const unsigned y = r / q.rb;
+  const int xb = (int)(r - y * q.rb);
+  int yy = (int)y, x = xb / q.C, c = xb - x * q.C;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (unsigned e = 0; e < 16; ++e) {
+    if (e < cnt) {
+      const int ys = min(max(yy + q.oy, 0), q.H - 1), xs = min(max(x + q.ox, 0), q.W - 1);
+      const uint8_t b = src[(size_t)ys * q.rb + (unsigned)(xs * q.C + c)];
+      if (vec)
+        w[e >> 2] |= (uint32_t)b << (8 * (e & 3));
+      else
+        dst[r + e] = b;
+      if (++c == q.C) {
+        c = 0;
+        if (++x == q.W) x = 0, ++yy;
+      }
+    }
+  }
+  if (vec) *reinterpret_cast<u32x4*>(dst + r) = u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// A thread takes SHIFT_UNROLL groups per trip, a grid stride apart, and issues the loads of all its fast groups before
+// the first store: a wave has up to 4 KiB in flight.  Measured: what sets the time is not the
+// fast path but the byte-wise groups -- a wave that holds one runs the 16 byte loads for it, and at rows of 756 bytes
+// (84 x 84 x 9: 47.25 groups) every wave holds a row-straddling group.
+constexpr int SHIFT_UNROLL = 4;
+
+__global__ __launch_bounds__(256) void random_shift_u8_kernel(const uint8_t* frames, const int64_t* idx, int period,
+                                                                const int32_t* dy, const int32_t* dx, int pad, int n,
+                                                                int H, int W, int C, unsigned groups, bool vec,
+                                                                uint8_t* out) {
+  ShiftGeom q;
+  q.H = H, q.W = W, q.C = C, q.rb = (unsigned)W * C, q.frame = (unsigned)H * q.rb;
+  const unsigned stride = gridDim.x * 256;
+  for (int s = blockIdx.y; s < n; s += gridDim.y) {
+    const int p = s % period;
+    const int64_t row = idx ? idx[p] : (int64_t)p;
+    // (offsets outside [0, 2 pad] are clamped into it: whatever the block holds, every read stays inside the frame)
+    q.oy = min(max(dy[s], 0), 2 * pad) - pad, q.ox = min(max(dx[s], 0), 2 * pad) - pad;
+    const int sx = q.ox * C;
+    const uint8_t* src = frames + (size_t)row * q.frame;
+    uint8_t* dst = out + (size_t)s * q.frame;
+    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += SHIFT_UNROLL * stride) {
+      u32x4 v[SHIFT_UNROLL];
+      bool fast[SHIFT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < SHIFT_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        fast[u] = false;
+        if (vec && g < groups) {
+          const unsigned r = 16 * g;
+          const unsigned y = r / q.rb;
+          const int xb = (int)(r - y * q.rb);
+          if (xb + 16 <= (int)q.rb && xb + sx >= 0 && xb + sx + 16 <= (int)q.rb) {
+            const int ys = min(max((int)y + q.oy, 0), H - 1);
+            __builtin_memcpy(&v[u], src + (size_t)ys * q.rb + (xb + sx), 16);  // one unaligned global_load_dwordx4
+            fast[u] = true;
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < SHIFT_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        if (g < groups) {
+          if (fast[u])
+            *reinterpret_cast<u32x4*>(dst + 16 * g) = v[u];
+          else
+            shift_group_bytes(src, dst, q, 16 * g, vec);
+        }
+      }
+    }
+  }
+}
+
 inline int blocks_for(size_t n) {
   size_t b = (n + 255) / 256;
   return (int)(b < 8192 ? b : 8192);
@@ -378,6 +475,23 @@ int curla_noisy_cover_nchw(const float* in, const float* noise, float c0, float 
   CURLA_REQUIRE(in && noise && out && B > 0 && C > 0 && H > 0 && W > 0 && top >= 0 && bottom >= 0);
   hipLaunchKernelGGL(noisy_cover_nchw_kernel, dim3(blocks_for((size_t)B * H * W * C)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), in, noise, c0, c1, c2, top, bottom, B, C, H, W, out);
+  return curla_launch_status();
+}
+
+int curla_random_shift_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* dy, const int32_t* dx,
+                          int pad, int n, int C, int H, int W, uint8_t* out, void* stream) {
+  CURLA_REQUIRE(frames && dy && dx && out && n > 0 && period > 0 && pad >= 0 && C > 0 && H > 0 && W > 0);
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 3) == 0 &&
+                (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  const long long frame = (long long)H * W * C;
+  // (bytes inside a frame and the byte shift (dx - pad) C are 32-bit quantities in the kernel)
+  if (frame >= (1LL << 31) - 16 || 2LL * pad * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;
+  const bool vec = frame % 16 == 0 && aligned16(out);
+  const unsigned groups = (unsigned)((frame + 15) / 16);
+  const unsigned gx = (groups + 1023) / 1024;  // (256 threads of SHIFT_UNROLL = 4 groups)
+  const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
+  hipLaunchKernelGGL(random_shift_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period,
+                     dy, dx, pad, n, H, W, C, groups, vec, out);
   return curla_launch_status();
 }
 

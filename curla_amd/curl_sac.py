@@ -1359,7 +1359,8 @@ class CurlSacAgent(object):
             raise RuntimeError("update graphs need the HIP device")
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
             raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
-                             "(covered: RandomCrop or identity, plain or dedup_frames storage; ColorJiggle / NoisyCover "
+                             "(covered: RandomCrop, RandomShift or identity, plain storage with both rings in one "
+                             "allocation or dedup_frames storage; ColorJiggle / NoisyCover "
                              "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
                              "CURLA_STAGE_COPY=1)")
         opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer)

@@ -688,6 +688,20 @@ def gather_stacks(store, fid, idx, B, out):
     call("curla_gather_stacks", ptr(store), ptr(fid), fid.stride(0), ptr(idx), B, fid.shape[1], H, W, ptr(out), stream())
 
 
+def random_shift_u8(frames, idx, period, dy, dx, pad, n, out):
+    """RandomShift of n samples (curla_random_shift_u8): frames u8 [rows, H, W, C]; sample s reads row idx[s % period]
+    (idx None: s % period) shifted by (dy[s], dx[s]) - pad with edge pixels repeated; out u8 [n, H, W, C]."""
+    _, H, W, C = frames.shape
+    _dev(frames, torch.uint8), _dev(out, torch.uint8), _dev(dy, torch.int32), _dev(dx, torch.int32)
+    if idx is not None:
+        _dev(idx, torch.int64)
+    if tuple(out.shape) != (n, H, W, C) or dy.numel() < n or dx.numel() < n or (idx is not None and idx.numel() < min(period, n)):
+        raise _lib.CurlaHipError(f"random_shift_u8: out {tuple(out.shape)} / {dy.numel()}, {dx.numel()} offsets do not "
+                                 f"fit {n} samples of {(H, W, C)}")
+    call("curla_random_shift_u8", ptr(frames), ptr(idx), int(period), ptr(dy), ptr(dx), int(pad), int(n), C, H, W,
+         ptr(out), stream())
+
+
 def nhwc_to_nchw(x, out):
     B, H, W, C = x.shape
     call("curla_nhwc_to_nchw", ptr(x), ptr(out), B, H, W, C, stream())

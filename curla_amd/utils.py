@@ -232,6 +232,8 @@ class ReplayBuffer(object):
                 + self.N_SAMPLE_SLOTS * 2 * batch_size * frame
         else:
             total_bytes = 2 * capacity * frame + capacity * (4 * A + 8)
+        if self._is_shift():  # the shifted minibatches (obs | next_obs | pos) of the sample slots
+            total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * frame + 32)
         if self.device.type == "cuda":
             free, _ = torch.cuda.mem_get_info(self.device)
             if total_bytes > free:
@@ -315,6 +317,14 @@ class ReplayBuffer(object):
         if self.dedup_frames:
             # (obs stacks | next_obs stacks) of a minibatch, contiguous: also one [2B] ring for ObsRef.pair
             self._mb_store = torch.zeros((self.N_SAMPLE_SLOTS, 2 * B * frame + 32), dtype=torch.uint8, device=dev)
+        if self._is_shift():
+            # RandomShift: a minibatch's shifted frames, uint8 [3B][H][W][C] = (obs | next_obs | pos) + 32 B of slack
+            # like a ring, per sample slot (each slot starts on a 256-byte boundary: the shift kernel then stores
+            # 16 bytes per lane).  Downstream it IS a ring: rows 0..3B-1, zero crop offsets -- static tensors.
+            stride = (3 * B * frame + 32 + 255) // 256 * 256
+            self._shift_store = torch.zeros((self.N_SAMPLE_SLOTS, stride), dtype=torch.uint8, device=dev)
+            self._shift_rows = torch.arange(3 * B, dtype=torch.int64, device=dev)
+            self._shift_zero = torch.zeros(3 * B, dtype=torch.int32, device=dev)
 
     # ------------------------------------------------------------------ writing
     def _stage_scalars(self, row, action, reward, done):
@@ -466,15 +476,18 @@ class ReplayBuffer(object):
     def _is_crop(self):
         return isinstance(self.augmentor, augmentations.RandomCrop)
 
+    def _is_shift(self):
+        return isinstance(self.augmentor, augmentations.RandomShift)
+
     def draw_indices(self):
         """Host RNG draws of sample_cpc, in the reference's order (utils.py:147 then
         augmentations.py:66-67 for obs, next_obs, pos).  Returns (idxs, offsets) with
         offsets an int32 array [6, B] = h1/w1 of obs, next_obs, pos (zeros when the
-        augmentation is not RandomCrop)."""
+        augmentation is neither RandomCrop nor RandomShift, whose (dy, dx) pairs take the same places)."""
         B = self.batch_size
         idxs = np.random.randint(0, self.capacity if self.full else self.idx, size=B)
         offs = np.zeros((6, B), dtype=np.int32)
-        if self._is_crop():
+        if self._is_crop() or self._is_shift():
             for j in range(3):
                 h1, w1 = self.augmentor.draw_offsets(B)
                 offs[2 * j], offs[2 * j + 1] = h1, w1
@@ -694,6 +707,38 @@ class ReplayBuffer(object):
         self._mb_both = both
         return views[0], views[1], None
 
+    def _shift_minibatch(self, dev_block, both, rows2, ring_o, ring_n, rows, store):
+        """RandomShift: the frames of a minibatch, shifted by the (dy, dx) of ``dev_block`` (a device index block:
+        the h rows of obs, next_obs, pos are one int32 run of 3B, the w rows the next), into ``store``
+        (uint8, 3B frames + slack) as obs | next_obs | pos; returns the [3B][H][W][C] view.  ``both`` (a [2 * rows] ring
+        holding obs frames then next_obs frames, read at the 2B indices ``rows2`` or, None, at 0..2B-1): ONE launch,
+        pos reading the obs rows again (period 2B).  Without it (rings in two allocations) one launch per tensor from
+        ``ring_o`` / ``ring_n`` at ``rows``."""
+        B = self.batch_size
+        c, h, w = self.obs_shape
+        pad = self.augmentor.pad
+        out = store[:3 * B * self._frame].view(3 * B, h, w, c)
+        d32 = dev_block[2 * B * 8:2 * B * 8 + 6 * B * 4].view(torch.int32)
+        dy, dx = d32[:3 * B], d32[3 * B:]
+        if both is not None:
+            ops.random_shift_u8(both, rows2, 2 * B, dy, dx, pad, 3 * B, out)
+        else:
+            for j, ring in enumerate((ring_o, ring_n, ring_o)):
+                ops.random_shift_u8(ring, rows, B, dy[j * B:(j + 1) * B], dx[j * B:(j + 1) * B], pad, B,
+                                    out[j * B:(j + 1) * B])
+        return out
+
+    def _shift_refs(self, shifted, guard):
+        """(obs, next_obs, pos) handles over a shifted minibatch: an ordinary uint8 ring of 3B rows, nothing left to
+        crop; obs carries the (obs | next_obs) pair of 2B rows."""
+        B = self.batch_size
+        hw = tuple(self.augmentor.output_shape)
+        ar, z = self._shift_rows, self._shift_zero
+        obses, next_obses, pos = (ops.ObsRef.from_ring(shifted, ar[j * B:(j + 1) * B], z[:B], z[:B], B, hw, guard)
+                                  for j in range(3))
+        obses.pair = (ops.ObsRef.from_ring(shifted, ar[:2 * B], z[:2 * B], z[:2 * B], 2 * B, hw, guard), next_obses)
+        return obses, next_obses, pos
+
     # ---- dedicated sample slots of captured update graphs (CurlSacAgent.enable_update_graphs) ---------------------
     # A captured graph replays the SAME pointers: its minibatch block lives in its own pinned host slot and its own
     # device block, never in the rotating ones above.  Behind the indices the block carries GRAPH_TAIL bytes of per-update
@@ -702,7 +747,7 @@ class ReplayBuffer(object):
 
     def graph_supported(self):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
-        ones (RandomCrop / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
+        ones (RandomCrop / RandomShift / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
         are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover constructed with
         ``staged_aug=True`` (either storage).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
         through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""
@@ -732,6 +777,8 @@ class ReplayBuffer(object):
             if self.dedup_frames:
                 (g["mb_u8"],) = self._guarded([2 * B * frame + 32], g["guards"])  # (+32: the loaders' slack, as a ring)
                 g["ar2"] = torch.arange(2 * B, device=self.device, dtype=torch.int64)
+            if self._is_shift():  # the shifted (obs | next_obs | pos) frames, + the loaders' slack
+                (g["shift_u8"],) = self._guarded([3 * B * frame + 32], g["guards"])
             if self._is_float_aug():
                 c, h, w = self.obs_shape
                 both, pos = self._guarded([4 * 2 * B * frame, 4 * B * frame], g["guards"])
@@ -772,7 +819,8 @@ class ReplayBuffer(object):
     def graph_refs(self, slot):
         """Device side, called while the graph is being captured: the staging launch (pinned block -> device block +
         the transitions' scalars), for the de-duplicated store the two gather_stacks launches (they read ``_fid`` when
-        the graph is replayed), for a staged float augmentation the three jitter / cover launches (they read their
+        the graph is replayed), for RandomShift the shift launch (it reads its offsets from the device block), for a
+        staged float augmentation the three jitter / cover launches (they read their
         parameters from the device block), and the sample_cpc 6-tuple with handles into the slot's buffers.  Nothing
         here draws a random number."""
         g = self.graph_block(slot)
@@ -796,6 +844,10 @@ class ReplayBuffer(object):
             next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows, fb[B:], self._aug_args(g["dev"], 1)))
             pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, fp, self._aug_args(g["dev"], 2)))
             obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
+        elif self._is_shift():  # one shift launch behind the staging (and the gathers); the offsets are the block's
+            shifted = self._shift_minibatch(g["dev"], both, None if self.dedup_frames else idx2, None, None, None,
+                                            g["shift_u8"])
+            obses, next_obses, pos = self._shift_refs(shifted, None)
         else:
             obses = ops.ObsRef.from_ring(both, idx2[:B], off[0], off[1], B, crop, None)
             next_obses = ops.ObsRef.from_ring(both, idx2[B:], off[2], off[3], B, crop, None)
@@ -804,6 +856,14 @@ class ReplayBuffer(object):
         act, rew, nd = buf[:B * A].view((B,) + tuple(self.actions.shape[1:])), buf[B * A:B * A + B].view(B, 1), \
             buf[B * A + B:].view(B, 1)
         return obses, act, rew, next_obses, nd, dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
+
+    def _shifted(self, ring_o, ring_n, rows):
+        """RandomShift: the current sample slot's minibatch, shifted into the slot's scratch (after _upload_indices and
+        _sources)."""
+        s = self._sample_slot
+        both = self._mb_both if self.dedup_frames else self._both
+        rows2 = None if self.dedup_frames else self._pair_views[0]
+        return self._shift_minibatch(self._d_index[s], both, rows2, ring_o, ring_n, rows, self._shift_store[s])
 
     def sample_cpc_refs(self, indices=None):
         """The fused form of sample_cpc: same 6-tuple, but obs / next_obs / pos are
@@ -827,6 +887,8 @@ class ReplayBuffer(object):
             next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows, both[B:], st[1]))
             pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, None, st[2]))
             obses.pair = (ops.ObsRef.from_nhwc(both), next_obses)
+        elif self._is_shift():
+            obses, next_obses, pos = self._shift_refs(self._shifted(ring_o, ring_n, rows), guard)
         else:
             idx2, h2, w2 = self._pair_views
             both = self._mb_both if self.dedup_frames else self._both
@@ -863,9 +925,13 @@ class ReplayBuffer(object):
         ring_o, ring_n, rows = self._sources(d_idx)
         st = self._staged_args()
         outs = []
+        shifted = self._shifted(ring_o, ring_n, rows) if self._is_shift() else None
         for ring, j in ((ring_o, 0), (ring_n, 1), (ring_o, 2)):
             t = torch.empty((B, c, oh, ow), dtype=torch.float32, device=self.device)
-            if self._is_float_aug():
+            if shifted is not None:  # the shifted frames as they are: rows j B .. of the scratch, zero offsets
+                z = self._shift_zero[:B]
+                ops.crop_nchw(shifted, self._shift_rows[j * B:(j + 1) * B], z, z, B, (oh, ow), out_f32=t)
+            elif self._is_float_aug():
                 ops.nhwc_to_nchw(self._float_augmented(ring, rows, None, st[j]), t)
             else:
                 ops.crop_nchw(ring, rows, off[2 * j], off[2 * j + 1], B, (oh, ow), out_f32=t)

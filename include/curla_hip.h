@@ -526,6 +526,20 @@ int curla_stage_frames_u8(const uint8_t* nchw, uint8_t* frames, long long first_
 int curla_gather_stacks(const uint8_t* store, const int32_t* fid, int fid_stride, const int64_t* idx, int B, int K,
                         int H, int W, uint8_t* out, void* stream);
 int curla_nhwc_to_nchw(const float* in, float* out, int B, int H, int W, int C, void* stream);
+/* RandomShift, the pad-and-crop shift of DrQ / DrQ-v2 (beyond the reference: its augmentations.py has no such class).
+ * Every frame is padded by `pad` pixels on each side with its edge pixels repeated, then an H x W window is cut at the
+ * sample's (dy, dx), 0 <= dy, dx <= 2 pad -- all channels of a stack share the draw:
+ *   out[s][y][x][c] = frames[row(s)][clamp(y + dy[s] - pad, 0, H - 1)][clamp(x + dx[s] - pad, 0, W - 1)][c],  0 <= s < n
+ * uint8 NHWC in ([rows][H][W][C]) and out ([n][H][W][C]): a shifted minibatch is still a uint8 ring, read by
+ * curla_conv1_fwd (src_kind 1) with zero crop offsets; like a ring, `out` needs 32 bytes of slack behind it for that.
+ * row(s) = idx[s % period] (idx NULL: s % period): with period = 2 B over a block's (obs rows | next_obs rows) run one
+ * launch of n = 3 B serves obs, next_obs and pos, which reads the obs rows again.  dy / dx: int32 [n] (values outside
+ * [0, 2 pad] are clamped into it).  A frame of a multiple of 16 bytes with `out` on a 16-byte boundary moves 16 bytes
+ * per lane (one unaligned load where the group lies in one row and needs no x-clamp); every other case gives the same
+ * bytes one at a time.  Additive like curla_noisy_cover_rng: CURLA_ABI_VERSION stays 8.  CURLA_ERR_UNSUPPORTED when
+ * H W C or 2 pad C does not fit 31 / 30 bits. */
+int curla_random_shift_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* dy, const int32_t* dx,
+                          int pad, int n, int C, int H, int W, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
