@@ -1243,6 +1243,69 @@ __global__ void sample_stage_kernel(const unsigned long long* host, unsigned lon
     nd[b] = v;
 }
 
+// n-step return of sample b, which starts at ring row r0 (beyond the reference; DrQ-v2's multi-step TD target): walk
+// forward while the continuity flag of the current row is set, at most n - 1 times,
+//   R = reward[r0]; g = 1;  per step: r = (r + 1) % capacity; g = g * gamma; R = R + g * reward[r]
+// in fp32 with every product and sum rounded on its own (contraction is switched off for this function -- hipcc's
+// default would fuse g * reward into the sum, and HIP's __fmul_rn / __fadd_rn are plain operators that fuse as well:
+// the NumPy restatement of the tests gives the same bits).  Hands the TD kernels reward = R and
+// not_done = not_done[r_last] * g, and the bootstrap row r_last twice: as capacity + r_last in word B + b of the block
+// (the double ring's next_obs half) and as r_last in next_row[b].
+__device__ __forceinline__ void nstep_compose_one(const float* sc, const uint8_t* cont, long long capacity, int n,
+                                                  float gamma, int A, long long r0, int b, int B,
+                                                  unsigned long long* dev, unsigned long long* next_row, float* rew,
+                                                  float* nd) {
+#pragma clang fp contract(off)
+  const size_t ld = (size_t)A + 2;
+  float R = sc[(size_t)r0 * ld + A], g = 1.f;
+  long long r = r0;
+  for (int m = 1; m < n && cont[r]; ++m) {
+    r = r + 1 == capacity ? 0 : r + 1;
+    g = g * gamma;
+    const float term = g * sc[(size_t)r * ld + A];
+    R = R + term;
+  }
+  rew[b] = R;
+  nd[b] = sc[(size_t)r * ld + A + 1] * g;
+  dev[B + b] = (unsigned long long)(capacity + r);
+  next_row[b] = (unsigned long long)r;
+}
+
+// The composition on a block that is already on the device (idx = its first B words): one thread per scalar of a
+// sample as in gather_transition_scalars_kernel -- the action's threads copy action[r0], the reward's thread walks.
+__global__ void nstep_compose_kernel(unsigned long long* dev, int nr_word, const float* sc, const uint8_t* cont,
+                                     long long capacity, int n, float gamma, int B, int A, float* act, float* rew,
+                                     float* nd) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * (A + 2)) return;
+  const int b = i / (A + 2), c = i - b * (A + 2);
+  const long long r0 = (long long)dev[b];
+  if (c < A)
+    act[(size_t)b * A + c] = sc[(size_t)r0 * (A + 2) + c];
+  else if (c == A)
+    nstep_compose_one(sc, cont, capacity, n, gamma, A, r0, b, B, dev, dev + nr_word, rew, nd);
+}
+
+// sample_stage_kernel + the composition in one launch.  The copy leaves out the words the composition writes
+// (B .. 2B - 1 and the B words of next_row): each of them has exactly one writer, sample b's reward thread, which
+// reads its row index from the pinned block with the same system-scope load as the copy -- nothing in the launch
+// reads a word that another thread of it writes.
+__global__ void sample_stage_nstep_kernel(const unsigned long long* host, unsigned long long* dev, int nwords,
+                                          int nr_word, const float* sc, const uint8_t* cont, long long capacity, int n,
+                                          float gamma, int B, int A, float* act, float* rew, float* nd) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nwords && !(i >= B && i < 2 * B) && !(i >= nr_word && i < nr_word + B))
+    dev[i] = __hip_atomic_load(host + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (i >= B * (A + 2)) return;
+  const int b = i / (A + 2), c = i - b * (A + 2);
+  if (c > A) return;
+  const long long r0 = (long long)__hip_atomic_load(host + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (c < A)
+    act[(size_t)b * A + c] = sc[(size_t)r0 * (A + 2) + c];
+  else
+    nstep_compose_one(sc, cont, capacity, n, gamma, A, r0, b, B, dev, dev + nr_word, rew, nd);
+}
+
 // out[b][c][i][j] = (float) frames[idx[b]][h1[b]+i][w1[b]+j][c]          (augmentations.py:47-75 + utils.py:161)
 __global__ void crop_nchw_kernel(const uint8_t* frames, const int64_t* idx, const int32_t* h1, const int32_t* w1,
                                  int B, int C, int Hs, int Ws, int Hc, int Wc, float* out_f32, uint8_t* out_u8) {
@@ -1971,6 +2034,35 @@ int curla_sample_stage(const void* host_block, void* device_block, long long nby
   hipLaunchKernelGGL(sample_stage_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned long long*>(host_block), static_cast<unsigned long long*>(device_block),
                      nwords, scalars, B, A, action, reward, not_done);
+  return curla_launch_status();
+}
+
+int curla_nstep_compose(void* device_block, long long next_row_offset, const float* scalars, const uint8_t* cont,
+                        long long capacity, int n, float discount, int B, int A, float* action, float* reward,
+                        float* not_done, void* stream) {
+  CURLA_REQUIRE(device_block && scalars && cont && action && reward && not_done && B > 0 && A > 0);
+  CURLA_REQUIRE(n >= 1 && capacity >= 1 && (uintptr_t)device_block % 8 == 0);
+  CURLA_REQUIRE(next_row_offset % 8 == 0 && next_row_offset >= 2LL * B * 8 && next_row_offset < (1LL << 30));
+  hipLaunchKernelGGL(nstep_compose_kernel, dim3((B * (A + 2) + 255) / 256), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<unsigned long long*>(device_block),
+                     (int)(next_row_offset / 8), scalars, cont, capacity, n, discount, B, A, action, reward, not_done);
+  return curla_launch_status();
+}
+
+int curla_sample_stage_nstep(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
+                             const float* scalars, const uint8_t* cont, long long capacity, int n, float discount, int B,
+                             int A, float* action, float* reward, float* not_done, void* stream) {
+  CURLA_REQUIRE(host_block && device_block && scalars && cont && action && reward && not_done && B > 0 && A > 0);
+  CURLA_REQUIRE(n >= 1 && capacity >= 1);
+  CURLA_REQUIRE(nbytes % 8 == 0 && nbytes < (1LL << 30));
+  CURLA_REQUIRE(next_row_offset % 8 == 0 && next_row_offset >= 2LL * B * 8 && next_row_offset + 8LL * B <= nbytes);
+  CURLA_REQUIRE(((uintptr_t)host_block | (uintptr_t)device_block) % 8 == 0);
+  const int nwords = (int)(nbytes / 8);
+  const int nthreads = nwords > B * (A + 2) ? nwords : B * (A + 2);
+  hipLaunchKernelGGL(sample_stage_nstep_kernel, dim3((nthreads + 255) / 256), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned long long*>(host_block),
+                     static_cast<unsigned long long*>(device_block), nwords, (int)(next_row_offset / 8), scalars, cont,
+                     capacity, n, discount, B, A, action, reward, not_done);
   return curla_launch_status();
 }
 

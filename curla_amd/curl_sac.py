@@ -1271,9 +1271,17 @@ class CurlSacAgent(object):
         ``noise`` (parity tests): (critic-phase, actor-phase) tensors in place of the two ``torch.randn_like`` draws
         (curl_sac.py:97 via :352 and :375)."""
         self._restore_grad_views()
+        self._check_n_step(replay_buffer)
         if noise is None and self._graphs is not None and self._graph_usable(replay_buffer, step, only_cpc):
             return self._update_graphed(replay_buffer, L, step)
         self._update_eager(replay_buffer, L, step, only_cpc, noise)
+
+    def _check_n_step(self, replay_buffer):
+        """An n-step buffer composes its rewards with ITS discount and the TD kernels bootstrap with the agent's: the
+        two must be one number, or the target is neither's."""
+        if getattr(replay_buffer, "n_step", 1) > 1 and replay_buffer.discount != self.discount:
+            raise ValueError("replay_buffer.discount = %r (n_step = %d) differs from the agent's discount = %r"
+                             % (replay_buffer.discount, replay_buffer.n_step, self.discount))
 
     def _update_eager(self, replay_buffer, L, step, only_cpc=False, noise=None):
         if hasattr(replay_buffer, "sample_cpc_refs"):
@@ -1352,8 +1360,9 @@ class CurlSacAgent(object):
         pinned block and a copy of their own per call).  Data-parallel updates over RCCL
         ARE captured, collectives included (round 5; the replica check stays on the host, in front of the replay).
         Values the graphs hold as kernel arguments (discount, taus, betas / eps, detach_encoder, the update
-        frequencies, the data-parallel group and schedule) are fingerprinted at capture: editing one of them drops the
-        graphs and they are captured again; so does ``load_checkpoint``.  A capture that raises leaves the agent's
+        frequencies, the data-parallel group and schedule, ``n_step`` and ``discount`` of an n-step replay buffer) are
+        fingerprinted at capture: editing one of them drops the graphs and they are captured again; so does
+        ``load_checkpoint``.  A capture that raises leaves the agent's
         state untouched and that update runs eagerly."""
         if self.device.type != "cuda":
             raise RuntimeError("update graphs need the HIP device")
@@ -1407,7 +1416,13 @@ class CurlSacAgent(object):
                 bool(self.pixel_sac), float(self.target_entropy), float(self.actor.log_std_min),
                 float(self.actor.log_std_max), self.actor_update_freq, self.critic_target_update_freq,
                 self.cpc_update_freq, self._dp_active, self._dp_overlap, id(self._dp_group) if self._dp_active else 0,
-                hyper)
+                hyper, self._graph_rb_key())
+
+    def _graph_rb_key(self):
+        """(n_step, discount) of the graphs' replay buffer: its staging launch holds both by value."""
+        rb = getattr(self, "_graph_rb", None)
+        n = getattr(rb, "n_step", 1)
+        return (n, float(rb.discount)) if n > 1 else (1, None)
 
     def _graph_tail(self, kind, B):
         """The 80 control bytes of one graphed update (ReplayBuffer.GRAPH_TAIL) -- and the host-side bookkeeping of
@@ -1466,6 +1481,7 @@ class CurlSacAgent(object):
             self._graph_key_at_capture = None
 
     def _update_graphed(self, rb, L, step):
+        self._check_n_step(rb)
         key = self._graph_key()
         if self._graphs and key != self._graph_key_at_capture:
             self._drop_graphs()  # a value the graphs hold as a kernel argument has been edited since the capture

@@ -656,6 +656,19 @@ def sample_stage(host_dev_ptr, dev_block, nbytes, sc, B, A, act, rew, nd):
     call("curla_sample_stage", host_dev_ptr, ptr(dev_block), nbytes, ptr(sc), B, A, ptr(act), ptr(rew), ptr(nd), stream())
 
 
+def nstep_compose(dev_block, next_row_off, sc, cont, capacity, n, discount, B, A, act, rew, nd):
+    """n-step reward / not_done / bootstrap rows of a minibatch whose index block is already on the device
+    (curla_hip.h: curla_nstep_compose)."""
+    call("curla_nstep_compose", ptr(dev_block), int(next_row_off), ptr(sc), ptr(cont), int(capacity), int(n),
+         float(discount), B, A, ptr(act), ptr(rew), ptr(nd), stream())
+
+
+def sample_stage_nstep(host_dev_ptr, dev_block, nbytes, next_row_off, sc, cont, capacity, n, discount, B, A, act, rew, nd):
+    """sample_stage with the n-step composition in the same launch."""
+    call("curla_sample_stage_nstep", host_dev_ptr, ptr(dev_block), nbytes, int(next_row_off), ptr(sc), ptr(cont),
+         int(capacity), int(n), float(discount), B, A, ptr(act), ptr(rew), ptr(nd), stream())
+
+
 def crop_nchw(frames, idx, h1, w1, B, crop_hw, out_f32=None, out_u8=None):
     _, Hs, Ws, C = frames.shape
     call("curla_crop_nchw", ptr(frames), ptr(idx), ptr(h1), ptr(w1), B, C, Hs, Ws, crop_hw[0], crop_hw[1],

@@ -40,6 +40,13 @@ except ImportError:  # pragma: no cover
         return zlib.crc32(buf) | (zlib.adler32(buf) << 32)
 
 
+def _checked_discount(d):
+    """``discount`` of an n-step ReplayBuffer as a float; ValueError unless it is a number in (0, 1]."""
+    if isinstance(d, bool) or not isinstance(d, (int, float, np.floating, np.integer)) or not 0.0 < float(d) <= 1.0:
+        raise ValueError("n_step > 1 needs discount, a float in (0, 1] (the agent's), got %r" % (d,))
+    return float(d)
+
+
 def _lib_tracing():
     from . import _lib
     return _lib._trace_hook is not None
@@ -192,13 +199,28 @@ class _FrameStore:
 
 
 class ReplayBuffer(object):
-    """Buffer to store environment transitions (utils.py:80-236), HBM-resident."""
+    """Buffer to store environment transitions (utils.py:80-236), HBM-resident.
+
+    ``n_step=n > 1`` (beyond the reference; DrQ-v2 uses 3) makes every sample an n-step transition: reward becomes
+    ``sum_{k<m} discount^k r_{t+k}``, not_done ``not_done_{t+m-1} discount^(m-1)`` and next_obs the one of row
+    ``t+m-1``, ``m <= n`` being the steps the episode still has from row t on -- so the learner's unchanged
+    ``reward + not_done * discount * (...)`` is the n-step TD target.  ``discount`` is then required and must be the
+    agent's (``CurlSacAgent.update`` checks it); it is a plain attribute, read at every sample.  Which row continues
+    which is detected from the data handed to ``add`` (a per-row flag ``cont``): row i continues into row i + 1 when
+    that was the very next add, ``done`` was false and row i's ``next_obs`` equals row i + 1's ``obs`` byte for byte --
+    a time-limit truncation or a reset breaks the chain without a change to ``add``'s signature.  A caller that
+    interleaves several environments into one buffer therefore gets a break at every switch, i.e. 1-step targets.
+    ``n_step=1`` (default) is the reference's buffer: nothing is allocated, launched or laid out differently."""
 
     N_SAMPLE_SLOTS = 2  # minibatches whose references may be alive at once (the current one + one drawn ahead)
     EVENT_EVERY = 8     # index uploads per recorded event (16 pinned slots)
 
     def __init__(self, obs_shape, action_shape, capacity, batch_size, device, augmentor, transform=None,
-                 dedup_frames=False, frame_capacity=None, staged_aug=False):
+                 dedup_frames=False, frame_capacity=None, staged_aug=False, n_step=1, discount=None):
+        if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or n_step < 1:
+            raise ValueError("n_step must be an int >= 1, got %r" % (n_step,))
+        self.n_step = int(n_step)
+        self.discount = _checked_discount(discount) if self.n_step > 1 else discount
         self.capacity = capacity
         self.batch_size = batch_size
         self.device = torch.device(device)
@@ -234,6 +256,8 @@ class ReplayBuffer(object):
             total_bytes = 2 * capacity * frame + capacity * (4 * A + 8)
         if self._is_shift():  # the shifted minibatches (obs | next_obs | pos) of the sample slots
             total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * frame + 32)
+        if self.n_step > 1:  # the continuity flags
+            total_bytes += capacity
         if self.device.type == "cuda":
             free, _ = torch.cuda.mem_get_info(self.device)
             if total_bytes > free:
@@ -286,13 +310,24 @@ class ReplayBuffer(object):
         self._sc_off = (n_stage + 15) & ~15
         self._hdr = 4 * (2 * self._k) if self.dedup_frames else 0  # frame-id row in front of the scalars
         blk = self._sc_off + self._hdr + 4 * (A + 2)
+        if self.n_step > 1:
+            # cont[i] = 1: row (i + 1) % capacity continues row i's episode (class docstring).  The flags of the previous
+            # row and of the new one (always 0) ride behind the scalars of the add block; the host keeps a mirror and
+            # what it needs of the previous add to evaluate the rule.
+            self._cont = torch.zeros(capacity, dtype=torch.uint8, device=dev)
+            self._cont_h = np.zeros(capacity, dtype=np.uint8)
+            self._cont_off = blk
+            blk += 4
+            self._last_row = None   # the row the latest add wrote
+            self._last_nd = False   # ... its stored not_done == 1
+            self._last_next = None  # ... its next_obs bytes (plain ring; the frame store compares frame ids)
         self._n_add, self._add_slot = 4, 0
         self._h_add = torch.empty((self._n_add, blk), dtype=torch.uint8, pin_memory=pin)
         self._h_add_np = self._h_add.numpy()
         self._add_events = [None] * self._n_add
         self._d_add = torch.empty(blk, dtype=torch.uint8, device=dev)
         self._d_add_frames = self._d_add[:2 * frame].view(2, frame)
-        self._d_add_sc = self._d_add[self._sc_off + self._hdr:].view(torch.float32)
+        self._d_add_sc = self._d_add[self._sc_off + self._hdr:self._sc_off + self._hdr + 4 * (A + 2)].view(torch.float32)
         B = batch_size
         # the host may run several updates ahead of the GPU: a small ring of pinned slots, each guarded by an
         # event, keeps an index upload's source intact until its async copy has executed
@@ -329,11 +364,40 @@ class ReplayBuffer(object):
     # ------------------------------------------------------------------ writing
     def _stage_scalars(self, row, action, reward, done):
         A = self._n_act
-        sc = row[self._sc_off + self._hdr:].view(np.float32)
+        at = self._sc_off + self._hdr
+        sc = row[at:at + 4 * (A + 2)].view(np.float32)
         sc[:A] = np.asarray(action, dtype=np.float32).reshape(-1)
         sc[A] = float(reward)
         sc[A + 1] = float(not done)
         return sc
+
+    def _stage_cont(self, row, i, continues, not_done):
+        """n-step bookkeeping of an add to row ``i``: ``continues`` = the new obs is the previous add's next_obs, byte
+        for byte.  Sets the host flags (previous row by the rule, new row 0), puts the two bytes into the pinned add
+        block ``row`` and returns the previous row (None: there is none to re-evaluate)."""
+        p = self._last_row
+        if p is not None and ((p + 1) % self.capacity != i or p == i):
+            p = None
+        flag = 0
+        if p is not None:
+            flag = int(bool(continues) and self._last_nd)
+            self._cont_h[p] = flag
+        self._cont_h[i] = 0
+        row[self._cont_off], row[self._cont_off + 1] = flag, 0
+        self._last_row, self._last_nd = i, bool(not_done)
+        return p
+
+    def _store_cont(self, i, p):
+        """Device side of _stage_cont, stream-ordered behind the add block's copy: one 2-byte copy (two of one byte
+        where the pair straddles the ring's end)."""
+        o = self._cont_off
+        if p is None:
+            self._cont[i:i + 1].copy_(self._d_add[o + 1:o + 2])
+        elif p + 1 == i:
+            self._cont[p:i + 1].copy_(self._d_add[o:o + 2])
+        else:
+            self._cont[p:p + 1].copy_(self._d_add[o:o + 1])
+            self._cont[i:i + 1].copy_(self._d_add[o + 1:o + 2])
 
     def _next_add_slot(self):
         k = self._add_slot
@@ -355,6 +419,12 @@ class ReplayBuffer(object):
         row[:fr] = np.asarray(obs, dtype=np.uint8).reshape(-1)
         row[fr:2 * fr] = np.asarray(next_obs, dtype=np.uint8).reshape(-1)
         sc = self._stage_scalars(row, action, reward, done)
+        if self.n_step > 1:  # one comparison of a frame on the host, against the copy kept of the previous next_obs
+            same = self._last_next is not None and np.array_equal(row[:fr], self._last_next)
+            prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0)
+            if self._last_next is None:
+                self._last_next = np.empty(fr, dtype=np.uint8)
+            self._last_next[:] = row[fr:2 * fr]
         if self.device.type == "cuda":
             self._d_add.copy_(self._h_add[k], non_blocking=True)
             ev = torch.cuda.Event()
@@ -363,12 +433,17 @@ class ReplayBuffer(object):
             ops.store_frame(self._d_add_frames[0], self.obses, i)
             ops.store_frame(self._d_add_frames[1], self.next_obses, i)
             self._sc[i].copy_(self._d_add_sc)
+            if self.n_step > 1:
+                self._store_cont(i, prev)
         else:  # host-side bookkeeping only (index logic tests); pixels are still stored, HWC
             c, h, w = self.obs_shape
             blk = self._h_add[k]
             self.obses[i] = blk[:fr].view(c, h, w).permute(1, 2, 0)
             self.next_obses[i] = blk[fr:2 * fr].view(c, h, w).permute(1, 2, 0)
             self._sc[i] = torch.from_numpy(sc.copy())
+            if self.n_step > 1:
+                for r in (i,) if prev is None else (prev, i):
+                    self._cont[r] = int(self._cont_h[r])
         self._advance(1)
 
     def _advance(self, n):
@@ -421,9 +496,14 @@ class ReplayBuffer(object):
                     new.append(fid)
                 st.refs[fid] += 1
             ids[j] = fid
+        if self.n_step > 1:  # equal bytes have equal frame ids: the new obs row against the previous next_obs row
+            p = self._last_row
+            same = p is not None and p != i and np.array_equal(ids[:K], self._fid_h[p, 1])
         self._fid_h[i] = ids.reshape(2, K)
         row[self._sc_off:self._sc_off + self._hdr].view(np.int32)[:] = ids
         sc = self._stage_scalars(row, action, reward, done)
+        if self.n_step > 1:
+            prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0)
         if self.device.type == "cuda":
             n = len(new) * f3
             if n:
@@ -436,12 +516,43 @@ class ReplayBuffer(object):
                 ops.store_frame(self._d_add[j * f3:(j + 1) * f3], self.frames, fid)
             self._fid[i].view(-1).copy_(self._d_add[self._sc_off:self._sc_off + self._hdr].view(torch.int32))
             self._sc[i].copy_(self._d_add_sc)
+            if self.n_step > 1:
+                self._store_cont(i, prev)
         else:  # host-side bookkeeping only
             for j, fid in enumerate(new):
                 self.frames[fid] = torch.from_numpy(row[j * f3:(j + 1) * f3].reshape(3, h, w).copy()).permute(1, 2, 0)
             self._fid[i] = torch.from_numpy(ids.reshape(2, K).copy())
             self._sc[i] = torch.from_numpy(sc.copy())
+            if self.n_step > 1:
+                for r in (i,) if prev is None else (prev, i):
+                    self._cont[r] = int(self._cont_h[r])
         self._advance(1)
+
+    def _cont_rows(self, first, obs, nxt, not_done):
+        """n-step bookkeeping of a bulk write (add_batch, load): transitions ``obs`` / ``nxt`` ((m, C, H, W) uint8 host
+        arrays) with ``not_done`` (m values) go to rows first, first + 1, ... (mod capacity), in this order -- the rule
+        of add() applied to the arrays, the pair (previous add, first element) included."""
+        m = len(obs)
+        if m == 0:
+            return
+        obs = np.asarray(obs, dtype=np.uint8).reshape(m, -1)
+        nxt = np.asarray(nxt, dtype=np.uint8).reshape(m, -1)
+        nd = np.asarray(not_done, dtype=np.float32).reshape(m) == 1.0
+        cap = self.capacity
+        rows = (first + np.arange(m)) % cap
+        flags = np.zeros(m, dtype=np.uint8)
+        flags[:-1] = (nxt[:-1] == obs[1:]).all(axis=1) & nd[:-1]
+        touched = rows
+        p = self._last_row
+        if p is not None and (p + 1) % cap == rows[0] and m < cap:  # (m >= cap: the batch overwrites row p itself)
+            self._cont_h[p] = int(self._last_nd and self._last_next is not None
+                                  and np.array_equal(self._last_next, obs[0]))
+            touched = np.concatenate([[p], rows])
+        self._cont_h[rows] = flags  # (a row written twice keeps its last flag)
+        self._last_row, self._last_nd = int(rows[-1]), bool(nd[-1])
+        self._last_next = nxt[-1].copy()
+        touched = np.unique(touched)
+        self._cont[torch.from_numpy(touched).to(self.device)] = torch.from_numpy(self._cont_h[touched]).to(self.device)
 
     def add_batch(self, obses, actions, rewards, next_obses, dones):
         """Bulk fill (benchmarks / buffer load): N transitions, observations as
@@ -466,6 +577,8 @@ class ReplayBuffer(object):
                                                     device=self.device)
             nd = 1.0 - np.asarray(dones[s:e], dtype=np.float32).reshape(m, 1)
             self.not_dones[slots_d] = torch.as_tensor(nd, device=self.device)
+            if self.n_step > 1:
+                self._cont_rows(self.idx, obses[s:e], next_obses[s:e], nd)
             self._advance(m)
 
     def frames_in_use(self):
@@ -543,6 +656,7 @@ class ReplayBuffer(object):
         three tensors (obs, next_obs, pos), ``aug_stride`` bytes each:
           ColorJiggle  params float [B k][4] (apply, contrast, saturation, hue) | order int32 [4]
           NoisyCover   colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2]   (8-byte aligned)
+        ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
         ``nbytes`` is what a rotating sample slot stages per minibatch; the block of a captured update graph carries
         GRAPH_TAIL more bytes of per-update control values behind it (at ``tail``; ``graph_nbytes`` in all)."""
         B = self.batch_size
@@ -556,6 +670,9 @@ class ReplayBuffer(object):
                 lay.update(aug=n, aug_stride=32, aug_rng=16)
             n += 3 * lay["aug_stride"]
         assert n % 8 == 0
+        if self.n_step > 1:  # next_row int64 [B]: the bootstrap rows without the double ring's offset (device-written)
+            lay["next_row"] = n
+            n += 8 * B
         lay.update(nbytes=n, tail=n, graph_nbytes=n + self.GRAPH_TAIL)
         return lay
 
@@ -659,12 +776,18 @@ class ReplayBuffer(object):
         dst = self._d_index[s]
         self._staged = self._h_index_dev is not None
         if self._staged:  # index block and the transitions' scalars in one launch, the block read from the pinned slot
-            B, A = self.batch_size, self._n_act
-            buf = self._d_scal[s]
-            ops.sample_stage(self._h_index_dev[k], dst, host.numel(), self._sc, B, A, buf[:B * A], buf[B * A:B * A + B],
-                             buf[B * A + B:])
+            self._stage(self._h_index_dev[k], dst, host.numel(), self._d_scal[s])
         else:
             dst.copy_(host, non_blocking=True)
+            if self.n_step > 1 and (self.device.type == "cuda" or _lib_tracing()):
+                # the bootstrap rows must be in the block before anything reads pixels: gather and compose here
+                B, A = self.batch_size, self._n_act
+                buf = self._d_scal[s]
+                out = buf[:B * A], buf[B * A:B * A + B], buf[B * A + B:]
+                ops.gather_transition_scalars(self._sc, dst[:B * 8].view(torch.int64), B, A, *out)
+                ops.nstep_compose(dst, self._layout["next_row"], self._sc, self._cont, self.capacity, self.n_step,
+                                  self._nstep_discount(), B, A, *out)
+                self._staged = True  # (_scalars: already gathered)
         if self.device.type == "cuda" and u % every == every - 1:
             ev = torch.cuda.Event()
             ev.record()
@@ -672,6 +795,29 @@ class ReplayBuffer(object):
         guard = (self._sample_gen, s, self._sample_gen[s])
         d_idx, off, self._pair_views = self._index_views(dst)
         return guard, d_idx, off
+
+    def _nstep_discount(self):
+        """``discount`` as the kernels take it: read at every sample, so an edit of the attribute is seen."""
+        return _checked_discount(self.discount)
+
+    def _stage(self, host_dev, dev, nbytes, scal):
+        """The staging launch of a minibatch: pinned block -> device block + the transitions' scalars into ``scal``;
+        with n_step > 1 the n-step composition happens in the same launch."""
+        B, A = self.batch_size, self._n_act
+        out = scal[:B * A], scal[B * A:B * A + B], scal[B * A + B:]
+        if self.n_step > 1:
+            ops.sample_stage_nstep(host_dev, dev, nbytes, self._layout["next_row"], self._sc, self._cont, self.capacity,
+                                   self.n_step, self._nstep_discount(), B, A, *out)
+        else:
+            ops.sample_stage(host_dev, dev, nbytes, self._sc, B, A, *out)
+
+    def _next_rows(self, dev, d_idx):
+        """The rows of ONE ring that a minibatch's next_obs come from: the sampled rows ``d_idx``, or with n_step > 1
+        the bootstrap rows that the composition wrote into the device block ``dev`` (block_layout: next_row)."""
+        if self.n_step == 1:
+            return d_idx
+        at = self._layout["next_row"]
+        return dev[at:at + 8 * self.batch_size].view(torch.int64)
 
     def _scalars(self, d_idx):
         """actions [B, ...], rewards [B, 1], not_dones [B, 1] of the sampled transitions (utils.py:159-166): one
@@ -702,18 +848,19 @@ class ReplayBuffer(object):
         mb = self._mb_store[self._sample_slot]
         both = mb[:2 * B * self._frame].view(2 * B, h, w, c)
         views = [both[:B], both[B:]]
+        rows = d_idx, self._next_rows(self._d_index[self._sample_slot], d_idx)  # (n_step: next_obs of the bootstrap rows)
         for j in range(2):
-            ops.gather_stacks(self.frames, self._fid[:, j, :], d_idx, B, views[j])
+            ops.gather_stacks(self.frames, self._fid[:, j, :], rows[j], B, views[j])
         self._mb_both = both
         return views[0], views[1], None
 
-    def _shift_minibatch(self, dev_block, both, rows2, ring_o, ring_n, rows, store):
+    def _shift_minibatch(self, dev_block, both, rows2, ring_o, ring_n, rows, store, rows_n=None):
         """RandomShift: the frames of a minibatch, shifted by the (dy, dx) of ``dev_block`` (a device index block:
         the h rows of obs, next_obs, pos are one int32 run of 3B, the w rows the next), into ``store``
         (uint8, 3B frames + slack) as obs | next_obs | pos; returns the [3B][H][W][C] view.  ``both`` (a [2 * rows] ring
         holding obs frames then next_obs frames, read at the 2B indices ``rows2`` or, None, at 0..2B-1): ONE launch,
         pos reading the obs rows again (period 2B).  Without it (rings in two allocations) one launch per tensor from
-        ``ring_o`` / ``ring_n`` at ``rows``."""
+        ``ring_o`` / ``ring_n`` at ``rows`` (``ring_n`` at ``rows_n`` where given: n_step)."""
         B = self.batch_size
         c, h, w = self.obs_shape
         pad = self.augmentor.pad
@@ -724,8 +871,8 @@ class ReplayBuffer(object):
             ops.random_shift_u8(both, rows2, 2 * B, dy, dx, pad, 3 * B, out)
         else:
             for j, ring in enumerate((ring_o, ring_n, ring_o)):
-                ops.random_shift_u8(ring, rows, B, dy[j * B:(j + 1) * B], dx[j * B:(j + 1) * B], pad, B,
-                                    out[j * B:(j + 1) * B])
+                ops.random_shift_u8(ring, rows_n if j == 1 and rows_n is not None else rows, B, dy[j * B:(j + 1) * B],
+                                    dx[j * B:(j + 1) * B], pad, B, out[j * B:(j + 1) * B])
         return out
 
     def _shift_refs(self, shifted, guard):
@@ -826,22 +973,23 @@ class ReplayBuffer(object):
         g = self.graph_block(slot)
         B, A = self.batch_size, self._n_act
         buf = g["scal"]
-        ops.sample_stage(g["host_dev"], g["dev"], g["host"].numel(), self._sc, B, A, buf[:B * A], buf[B * A:B * A + B],
-                         buf[B * A + B:])
+        self._stage(g["host_dev"], g["dev"], g["host"].numel(), buf)  # (n_step: reads ``cont`` when the graph runs)
         d_idx, off, (idx2, h2, w2) = self._index_views(g["dev"])
+        rows_n = self._next_rows(g["dev"], d_idx)
         crop = tuple(self.augmentor.output_shape)
         c, h, w = self.obs_shape
         both, rows = None if self.dedup_frames else self._both, d_idx
         if self.dedup_frames:
             both, rows = g["mb_u8"][:2 * B * self._frame].view(2 * B, h, w, c), None
             for j in range(2):
-                ops.gather_stacks(self.frames, self._fid[:, j, :], d_idx, B, both[j * B:(j + 1) * B])
+                ops.gather_stacks(self.frames, self._fid[:, j, :], (d_idx, rows_n)[j], B, both[j * B:(j + 1) * B])
             idx2 = g["ar2"]
+            rows_n = None
         if self._is_float_aug():
             ring_o, ring_n = (both[:B], both[B:]) if self.dedup_frames else (self.obses, self.next_obses)
             fb, fp = g["both_f32"], g["pos_f32"]
             obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, fb[:B], self._aug_args(g["dev"], 0)))
-            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows, fb[B:], self._aug_args(g["dev"], 1)))
+            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows_n, fb[B:], self._aug_args(g["dev"], 1)))
             pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, fp, self._aug_args(g["dev"], 2)))
             obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
         elif self._is_shift():  # one shift launch behind the staging (and the gathers); the offsets are the block's
@@ -863,7 +1011,8 @@ class ReplayBuffer(object):
         s = self._sample_slot
         both = self._mb_both if self.dedup_frames else self._both
         rows2 = None if self.dedup_frames else self._pair_views[0]
-        return self._shift_minibatch(self._d_index[s], both, rows2, ring_o, ring_n, rows, self._shift_store[s])
+        rows_n = None if rows is None else self._next_rows(self._d_index[s], rows)
+        return self._shift_minibatch(self._d_index[s], both, rows2, ring_o, ring_n, rows, self._shift_store[s], rows_n)
 
     def sample_cpc_refs(self, indices=None):
         """The fused form of sample_cpc: same 6-tuple, but obs / next_obs / pos are
@@ -877,6 +1026,8 @@ class ReplayBuffer(object):
         B = self.batch_size
         crop = tuple(self.augmentor.output_shape)
         ring_o, ring_n, rows = self._sources(d_idx)
+        # next_obs reads its ring at the bootstrap rows (n_step; the frame store has gathered them already)
+        rows_n = None if rows is None else self._next_rows(self._d_index[self._sample_slot], rows)
         if self._is_float_aug():
             # obs, next_obs and pos (= a copy of obs) are augmented independently (utils.py:173-182); obs and
             # next_obs are written into the two halves of one [2B] tensor (ObsRef.pair, see below)
@@ -884,7 +1035,7 @@ class ReplayBuffer(object):
             both = torch.empty((2 * B, h, w, c), dtype=torch.float32, device=self.device)
             st = self._staged_args()
             obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, both[:B], st[0]))
-            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows, both[B:], st[1]))
+            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows_n, both[B:], st[1]))
             pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, None, st[2]))
             obses.pair = (ops.ObsRef.from_nhwc(both), next_obses)
         elif self._is_shift():
@@ -894,7 +1045,7 @@ class ReplayBuffer(object):
             both = self._mb_both if self.dedup_frames else self._both
             if both is None:  # (rings in two allocations: second half would not start on a dword)
                 obses = ops.ObsRef.from_ring(ring_o, rows, off[0], off[1], B, crop, guard)
-                next_obses = ops.ObsRef.from_ring(ring_n, rows, off[2], off[3], B, crop, guard)
+                next_obses = ops.ObsRef.from_ring(ring_n, rows_n, off[2], off[3], B, crop, guard)
                 pos = ops.ObsRef.from_ring(ring_o, rows, off[4], off[5], B, crop, guard)
             else:
                 # every handle indexes the ONE ring that holds obs frames then next_obs frames, so that any two of
@@ -922,11 +1073,13 @@ class ReplayBuffer(object):
         B = self.batch_size
         c = self.obs_shape[0]
         oh, ow = self.augmentor.output_shape
-        ring_o, ring_n, rows = self._sources(d_idx)
+        ring_o, ring_n, rows_o = self._sources(d_idx)
+        rows_n = None if rows_o is None else self._next_rows(self._d_index[self._sample_slot], rows_o)
         st = self._staged_args()
         outs = []
-        shifted = self._shifted(ring_o, ring_n, rows) if self._is_shift() else None
+        shifted = self._shifted(ring_o, ring_n, rows_o) if self._is_shift() else None
         for ring, j in ((ring_o, 0), (ring_n, 1), (ring_o, 2)):
+            rows = rows_n if j == 1 else rows_o
             t = torch.empty((B, c, oh, ow), dtype=torch.float32, device=self.device)
             if shifted is not None:  # the shifted frames as they are: rows j B .. of the scratch, zero offsets
                 z = self._shift_zero[:B]
@@ -991,6 +1144,8 @@ class ReplayBuffer(object):
             self.next_obses[lo:hi] = to_ring(nxt)
             for dst, src in ((self.actions, act), (self.rewards, rew), (self.not_dones, nd)):
                 dst[lo:hi] = torch.as_tensor(src).to(self.device)
+            if self.n_step > 1:  # the flags are rebuilt from the payload, never stored
+                self._cont_rows(lo, obs, nxt, nd)
             self.idx = hi
 
     def __len__(self):

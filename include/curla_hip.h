@@ -502,6 +502,28 @@ int curla_gather_transition_scalars(const float* scalars, const int64_t* idx, in
  * copy-engine transfer in the stream.  The host buffer must stay untouched until the launch has executed. */
 int curla_sample_stage(const void* host_block, void* device_block, long long nbytes, const float* scalars, int B, int A,
                        float* action, float* reward, float* not_done, void* stream);
+/* n-step returns (beyond the reference: ReplayBuffer(n_step=n), the multi-step TD target of DrQ-v2).  `cont`: one
+ * uint8 per ring row, 1 when row (r + 1) % capacity continues row r's episode.  For sample b, starting at ring row
+ * r0 = idx[b] (the block's first B int64), in fp32, every product and sum rounded on its own (no FMA), in this order:
+ *   R = reward[r0]; g = 1; r = r0; m = 1
+ *   while m < n and cont[r]:  r = (r + 1) % capacity; g = g * discount; R = R + g * reward[r]; m += 1
+ *   reward[b] = R;  not_done[b] = not_done[r] * g;  action[b][:] = action[r0][:]
+ *   block int64 [B + b] = capacity + r   (the bootstrap frame's row in the double ring, next_obs half)
+ *   block int64 [next_row_offset / 8 + b] = r
+ * so that reward + not_done * discount * (...) of the TD kernels is the n-step target; n = 1 gives what
+ * curla_gather_transition_scalars gives and idx + capacity.  curla_nstep_compose works on a `device_block` that has
+ * been staged already (its words B .. 2B - 1 and the next_row words are overwritten, nothing else of it is);
+ * curla_sample_stage_nstep is curla_sample_stage with the composition in the same launch (the copy leaves out the
+ * words the composition writes; the row indices are read from the pinned block).  CURLA_ERR_ARG on a NULL pointer,
+ * n < 1, capacity < 1, a next_row_offset that is not a multiple of 8, overlaps the 2 B index words or (staging form)
+ * does not leave room for B words inside nbytes.  Rows are not range-checked: idx[b] in [0, capacity), as for the
+ * gathers above.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_nstep_compose(void* device_block, long long next_row_offset, const float* scalars, const uint8_t* cont,
+                        long long capacity, int n, float discount, int B, int A, float* action, float* reward,
+                        float* not_done, void* stream);
+int curla_sample_stage_nstep(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
+                             const float* scalars, const uint8_t* cont, long long capacity, int n, float discount, int B,
+                             int A, float* action, float* reward, float* not_done, void* stream);
 /* device-visible address of a pinned (hipHostMalloc'd / registered) host pointer; CURLA_ERR_ARG if it is not */
 int curla_host_device_pointer(void* host, void** device);
 /* ReplayBuffer.add: one CHW uint8 observation into ring slot `slot` (utils.py:120-128) */
