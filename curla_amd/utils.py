@@ -17,10 +17,11 @@ ONE new frame instead of 2k -- 63.5 KB -> 21 KB per transition at 84x84x9,
 ``add`` (hash, then full comparison), never assumed, so sampled pixels are the
 reference's whatever the caller does.
 
-``staged_aug=True`` (float augmentations) sends the random parameters of a minibatch's three tensors along in the
-index block instead of through a pinned block and a copy of their own per tensor, and lets NoisyCover draw its noise
-inside the cover kernel: with it -- and for ``dedup_frames`` without it -- the minibatch can be a node of a captured
-update graph (``graph_supported``).
+``staged_aug=True`` (float augmentations) sends the random parameters of a
+minibatch's three tensors along in the index block instead of through a pinned
+block and a copy of their own per tensor, and lets NoisyCover draw its noise
+inside the cover kernel: with it -- and for ``dedup_frames`` without it -- the
+minibatch can be a node of a captured update graph (``graph_supported``).
 """
 import collections
 import os
@@ -198,6 +199,10 @@ class _FrameStore:
                     del self.recent[h]
 
 
+# what ReplayBuffer._sources returns
+_Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off dy dx")
+
+
 class ReplayBuffer(object):
     """Buffer to store environment transitions (utils.py:80-236), HBM-resident.
 
@@ -214,6 +219,10 @@ class ReplayBuffer(object):
 
     N_SAMPLE_SLOTS = 2  # minibatches whose references may be alive at once (the current one + one drawn ahead)
     EVENT_EVERY = 8     # index uploads per recorded event (16 pinned slots)
+    # The block of a captured update graph carries GRAPH_TAIL bytes of per-update control values behind the indices:
+    # u64[4] (seed, critic-noise offset, seed, actor-noise offset) | f64[2] log_alpha | f32[8] four Adams
+    GRAPH_TAIL = 80
+    GUARD, GUARD_BYTE = 256, 0xA5  # around a graph slot's minibatch buffers (_guarded)
 
     def __init__(self, obs_shape, action_shape, capacity, batch_size, device, augmentor, transform=None,
                  dedup_frames=False, frame_capacity=None, staged_aug=False, n_step=1, discount=None):
@@ -326,7 +335,8 @@ class ReplayBuffer(object):
         self._h_add_np = self._h_add.numpy()
         self._add_events = [None] * self._n_add
         self._d_add = torch.empty(blk, dtype=torch.uint8, device=dev)
-        self._d_add_frames = self._d_add[:2 * frame].view(2, frame)
+        # the staged frames (plain: the two stacks; frame store: up to 2k RGB frames) as views made once
+        self._d_add_frames = self._d_add[:2 * frame].view(-1, 3 * h * w if self.dedup_frames else frame).unbind(0)
         self._d_add_sc = self._d_add[self._sc_off + self._hdr:self._sc_off + self._hdr + 4 * (A + 2)].view(torch.float32)
         B = batch_size
         # the host may run several updates ahead of the GPU: a small ring of pinned slots, each guarded by an
@@ -342,7 +352,6 @@ class ReplayBuffer(object):
         # pinned slots are read by the GPU in place (ops.sample_stage): no copy-engine transfer in front of an update
         self._h_index_dev = ([ops.host_device_pointer(self._h_index[k]) for k in range(self._n_slots)]
                              if pin and os.environ.get("CURLA_STAGE_COPY", "0") != "1" else None)
-        self._staged = False
         # every minibatch gets its own device index block (and, de-duplicated, its own assembled stacks), so the
         # references of one sample stay valid while the next one is drawn (N_SAMPLE_SLOTS alive at a time)
         self._d_index = torch.empty((self.N_SAMPLE_SLOTS, nbytes), dtype=torch.uint8, device=dev)
@@ -360,6 +369,21 @@ class ReplayBuffer(object):
             self._shift_store = torch.zeros((self.N_SAMPLE_SLOTS, stride), dtype=torch.uint8, device=dev)
             self._shift_rows = torch.arange(3 * B, dtype=torch.int64, device=dev)
             self._shift_zero = torch.zeros(3 * B, dtype=torch.int32, device=dev)
+        # A slot = the buffers ONE minibatch is assembled in (_assemble): ``dev`` the device block, ``scal`` the
+        # transitions' scalars and ``scalars`` its (actions, rewards, not_dones) views, ``mb_u8`` the gathered stacks +
+        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the shifted frames (RandomShift), ``both_f32`` / ``pos_f32``
+        # the float tensors (absent here: allocated per call).  The rotating slots are views of the stores above; a
+        # captured update graph has slots of its own with the same keys (graph_block).
+        ar2 = torch.arange(2 * B, dtype=torch.int64, device=dev) if self.dedup_frames else None
+        self._sample_slots = []
+        for s in range(self.N_SAMPLE_SLOTS):
+            slot = dict(dev=self._d_index[s], scal=self._d_scal[s], scalars=self._scalar_views(self._d_scal[s]))
+            if self.dedup_frames:
+                slot.update(mb_u8=self._mb_store[s], ar2=ar2)
+            if self._is_shift():
+                slot["shift_u8"] = self._shift_store[s]
+            self._sample_slots.append(slot)
+        self._graph_blocks = {}
 
     # ------------------------------------------------------------------ writing
     def _stage_scalars(self, row, action, reward, done):
@@ -419,27 +443,40 @@ class ReplayBuffer(object):
         row[:fr] = np.asarray(obs, dtype=np.uint8).reshape(-1)
         row[fr:2 * fr] = np.asarray(next_obs, dtype=np.uint8).reshape(-1)
         sc = self._stage_scalars(row, action, reward, done)
+        prev = None
         if self.n_step > 1:  # one comparison of a frame on the host, against the copy kept of the previous next_obs
             same = self._last_next is not None and np.array_equal(row[:fr], self._last_next)
             prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0)
             if self._last_next is None:
                 self._last_next = np.empty(fr, dtype=np.uint8)
             self._last_next[:] = row[fr:2 * fr]
+        self._commit_add(k, i, sc, prev, [(self._d_add, self._h_add[k])], [(self.obses, i), (self.next_obses, i)])
+
+    def _commit_add(self, k, i, sc, prev, copies, frames):
+        """What add() and _add_dedup() share once pinned block ``k`` is staged for row ``i``: the async ``copies``
+        (device view, pinned view) and the event that guards the block, one store_frame per (ring, ring row) of
+        ``frames`` -- the j-th staged frame goes to the j-th entry --, the frame-id row (frame store), the scalar row
+        ``sc`` and the continuity flags (``prev``: _stage_cont)."""
         if self.device.type == "cuda":
-            self._d_add.copy_(self._h_add[k], non_blocking=True)
+            for dst, src in copies:
+                dst.copy_(src, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             self._add_events[k] = ev
-            ops.store_frame(self._d_add_frames[0], self.obses, i)
-            ops.store_frame(self._d_add_frames[1], self.next_obses, i)
+            for j, (ring, row) in enumerate(frames):
+                ops.store_frame(self._d_add_frames[j], ring, row)
+            if self.dedup_frames:
+                self._fid[i].view(-1).copy_(self._d_add[self._sc_off:self._sc_off + self._hdr].view(torch.int32))
             self._sc[i].copy_(self._d_add_sc)
             if self.n_step > 1:
                 self._store_cont(i, prev)
         else:  # host-side bookkeeping only (index logic tests); pixels are still stored, HWC
-            c, h, w = self.obs_shape
-            blk = self._h_add[k]
-            self.obses[i] = blk[:fr].view(c, h, w).permute(1, 2, 0)
-            self.next_obses[i] = blk[fr:2 * fr].view(c, h, w).permute(1, 2, 0)
+            h, w = self.obs_shape[1:]
+            n = self._d_add_frames[0].numel()
+            for j, (ring, row) in enumerate(frames):
+                ring[row] = self._h_add[k, j * n:(j + 1) * n].view(-1, h, w).permute(1, 2, 0)
+            if self.dedup_frames:
+                self._fid[i] = torch.from_numpy(self._fid_h[i].copy())
             self._sc[i] = torch.from_numpy(sc.copy())
             if self.n_step > 1:
                 for r in (i,) if prev is None else (prev, i):
@@ -502,31 +539,12 @@ class ReplayBuffer(object):
         self._fid_h[i] = ids.reshape(2, K)
         row[self._sc_off:self._sc_off + self._hdr].view(np.int32)[:] = ids
         sc = self._stage_scalars(row, action, reward, done)
-        if self.n_step > 1:
-            prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0)
-        if self.device.type == "cuda":
-            n = len(new) * f3
-            if n:
-                self._d_add[:n].copy_(self._h_add[slot, :n], non_blocking=True)
-            self._d_add[self._sc_off:].copy_(self._h_add[slot, self._sc_off:], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._add_events[slot] = ev
-            for j, fid in enumerate(new):
-                ops.store_frame(self._d_add[j * f3:(j + 1) * f3], self.frames, fid)
-            self._fid[i].view(-1).copy_(self._d_add[self._sc_off:self._sc_off + self._hdr].view(torch.int32))
-            self._sc[i].copy_(self._d_add_sc)
-            if self.n_step > 1:
-                self._store_cont(i, prev)
-        else:  # host-side bookkeeping only
-            for j, fid in enumerate(new):
-                self.frames[fid] = torch.from_numpy(row[j * f3:(j + 1) * f3].reshape(3, h, w).copy()).permute(1, 2, 0)
-            self._fid[i] = torch.from_numpy(ids.reshape(2, K).copy())
-            self._sc[i] = torch.from_numpy(sc.copy())
-            if self.n_step > 1:
-                for r in (i,) if prev is None else (prev, i):
-                    self._cont[r] = int(self._cont_h[r])
-        self._advance(1)
+        prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0) if self.n_step > 1 else None
+        # two partial copies: the new frames (if any), then frame ids | scalars | flags
+        n = len(new) * f3
+        copies = [(self._d_add[:n], self._h_add[slot, :n])] if n else []
+        copies.append((self._d_add[self._sc_off:], self._h_add[slot, self._sc_off:]))
+        self._commit_add(slot, i, sc, prev, copies, [(self.frames, fid) for fid in new])
 
     def _cont_rows(self, first, obs, nxt, not_done):
         """n-step bookkeeping of a bulk write (add_batch, load): transitions ``obs`` / ``nxt`` ((m, C, H, W) uint8 host
@@ -609,10 +627,12 @@ class ReplayBuffer(object):
             raise NotImplementedError("unknown augmentation object: %r" % (self.augmentor,))
         return idxs, offs
 
-    def _float_augmented(self, ring, idx, out=None, staged=None):
-        """One augmented float NHWC minibatch [B, H, W, C] from ``ring`` rows ``idx`` (None: rows 0..B-1)
-        (utils.py:168-182 branch: the torch/kornia augmentations).  ``staged`` (staged_aug): the tensor's parameters
-        are already on the device, in the minibatch's block (_aug_args) -- nothing is drawn, allocated or copied here."""
+    def _float_augmented(self, ring, idx, dev, j, out=None):
+        """Tensor ``j`` (0 obs, 1 next_obs, 2 pos) of a minibatch as an augmented float NHWC tensor [B, H, W, C] from
+        ``ring`` rows ``idx`` (None: rows 0..B-1) (utils.py:168-182 branch: the torch/kornia augmentations).  With
+        staged_aug the tensor's parameters are already on the device, in the minibatch's block ``dev`` (_aug_args) --
+        nothing is drawn, allocated or copied here."""
+        staged = self._aug_args(dev, j) if self.staged_aug else None
         B = self.batch_size
         c, h, w = self.obs_shape
         if out is None:
@@ -644,24 +664,18 @@ class ReplayBuffer(object):
     def _is_float_aug(self):
         return isinstance(self.augmentor, (augmentations.ColorJiggle, augmentations.NoisyCover))
 
-    def _staged_args(self):
-        """Per tensor (obs, next_obs, pos): the staged parameters in the current sample slot's device block, or None."""
-        if not self.staged_aug:
-            return [None, None, None]
-        return [self._aug_args(self._d_index[self._sample_slot], j) for j in range(3)]
-
     def block_layout(self):
         """Byte offsets inside a minibatch's block -- the ONE place that knows them.  Every block starts with
-        idx int64 [2B] | crop offsets int32 [6][B] (_fill_index_block).  ``staged_aug`` appends the parameters of the
-        three tensors (obs, next_obs, pos), ``aug_stride`` bytes each:
+        idx int64 [2B] | crop offsets int32 [6][B] at ``offs`` .. ``offs_end`` (_fill_index_block).  ``staged_aug``
+        appends the parameters of the three tensors (obs, next_obs, pos), ``aug_stride`` bytes each:
           ColorJiggle  params float [B k][4] (apply, contrast, saturation, hue) | order int32 [4]
           NoisyCover   colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2]   (8-byte aligned)
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
         ``nbytes`` is what a rotating sample slot stages per minibatch; the block of a captured update graph carries
         GRAPH_TAIL more bytes of per-update control values behind it (at ``tail``; ``graph_nbytes`` in all)."""
         B = self.batch_size
-        lay = dict(idx=0, offs=2 * B * 8, aug=None, aug_stride=0, aug_order=None, aug_rng=None)
         n = 2 * B * 8 + 6 * B * 4
+        lay = dict(idx=0, offs=2 * B * 8, offs_end=n, aug=None, aug_stride=0, aug_order=None, aug_rng=None)
         if self.staged_aug:
             if isinstance(self.augmentor, augmentations.ColorJiggle):
                 n_par = 16 * B * (self.obs_shape[0] // 3)
@@ -736,27 +750,18 @@ class ReplayBuffer(object):
         idx [B] | idx + capacity [B] (the same transitions in the next_obs half of the double ring) | h1 of obs,
         next_obs, pos | w1 of obs, next_obs, pos -- so that (obs, next_obs) is ONE run of 2B frame indices, 2B row
         offsets and 2B column offsets."""
-        B = self.batch_size
-        i64 = host[:2 * B * 8].view(torch.int64)
+        B, lay = self.batch_size, self._layout
+        i64 = host[lay["idx"]:lay["offs"]].view(torch.int64)
         i64[:B].copy_(torch.from_numpy(np.ascontiguousarray(idxs, dtype=np.int64)))
         i64[B:].copy_(i64[:B] + self.capacity)
-        o32 = host[2 * B * 8:2 * B * 8 + 6 * B * 4].view(torch.int32).view(6, B)
+        o32 = host[lay["offs"]:lay["offs_end"]].view(torch.int32).view(6, B)
         offs = np.ascontiguousarray(offs, dtype=np.int32)
         o32.copy_(torch.from_numpy(np.ascontiguousarray(offs[[0, 2, 4, 1, 3, 5]])))
 
-    def _index_views(self, dst):
-        """(idx [B] int64, the six offset rows, the 2B-long (idx, h1, w1) views) of a device index block."""
-        B = self.batch_size
-        d64 = dst[:2 * B * 8].view(torch.int64)
-        d32 = dst[2 * B * 8:2 * B * 8 + 6 * B * 4].view(torch.int32)
-        # off[2j] / off[2j+1] = h1 / w1 of tensor j (obs, next_obs, pos); pair = the 2B-long views
-        off = [d32[(j // 2 + 3 * (j % 2)) * B:(j // 2 + 3 * (j % 2) + 1) * B] for j in range(6)]
-        return d64[:B], off, (d64, d32[:2 * B], d32[3 * B:5 * B])
-
     def _upload_indices(self, idxs, offs, aug=None):
-        """Copy a minibatch's indices and crop offsets (and, staged_aug, its augmentation parameters ``aug``) into the
-        next device sample slot; returns the slot's (guard, idx view [B] int64, offsets view [6, B] int32)."""
-        B = self.batch_size
+        """A minibatch's indices and crop offsets (and, staged_aug, its augmentation parameters ``aug``) into the next
+        rotating slot's device block, the transitions' scalars (n_step: composed) into its scalar buffer; returns the
+        slot and the guard of handles into it."""
         u, every = self._slot_use, self.EVENT_EVERY
         self._slot_use = u + 1
         k = u % self._n_slots
@@ -773,106 +778,95 @@ class ReplayBuffer(object):
             self._fill_aug(host, aug)
         s = self._sample_slot = (self._sample_slot + 1) % self.N_SAMPLE_SLOTS
         self._sample_gen[s] += 1
-        dst = self._d_index[s]
-        self._staged = self._h_index_dev is not None
-        if self._staged:  # index block and the transitions' scalars in one launch, the block read from the pinned slot
-            self._stage(self._h_index_dev[k], dst, host.numel(), self._d_scal[s])
+        slot = self._sample_slots[s]
+        dst = slot["dev"]
+        if self._h_index_dev is not None:  # block and scalars in one launch, the block read from the pinned slot
+            self._stage(self._h_index_dev[k], dst, host.numel(), slot["scalars"])
         else:
             dst.copy_(host, non_blocking=True)
-            if self.n_step > 1 and (self.device.type == "cuda" or _lib_tracing()):
-                # the bootstrap rows must be in the block before anything reads pixels: gather and compose here
-                B, A = self.batch_size, self._n_act
-                buf = self._d_scal[s]
-                out = buf[:B * A], buf[B * A:B * A + B], buf[B * A + B:]
-                ops.gather_transition_scalars(self._sc, dst[:B * 8].view(torch.int64), B, A, *out)
-                ops.nstep_compose(dst, self._layout["next_row"], self._sc, self._cont, self.capacity, self.n_step,
-                                  self._nstep_discount(), B, A, *out)
-                self._staged = True  # (_scalars: already gathered)
+            if self.device.type == "cuda" or _lib_tracing():
+                B, A, lay = self.batch_size, self._n_act, self._layout
+                out = slot["scalars"]
+                ops.gather_transition_scalars(self._sc, dst[lay["idx"]:lay["idx"] + 8 * B].view(torch.int64), B, A, *out)
+                if self.n_step > 1:  # the bootstrap rows must be in the block before anything reads pixels
+                    ops.nstep_compose(dst, lay["next_row"], self._sc, self._cont, self.capacity, self.n_step,
+                                      self._nstep_discount(), B, A, *out)
         if self.device.type == "cuda" and u % every == every - 1:
             ev = torch.cuda.Event()
             ev.record()
             self._slot_events[u // every] = ev
-        guard = (self._sample_gen, s, self._sample_gen[s])
-        d_idx, off, self._pair_views = self._index_views(dst)
-        return guard, d_idx, off
+        return slot, (self._sample_gen, s, self._sample_gen[s])
 
     def _nstep_discount(self):
         """``discount`` as the kernels take it: read at every sample, so an edit of the attribute is seen."""
         return _checked_discount(self.discount)
 
-    def _stage(self, host_dev, dev, nbytes, scal):
-        """The staging launch of a minibatch: pinned block -> device block + the transitions' scalars into ``scal``;
-        with n_step > 1 the n-step composition happens in the same launch."""
+    def _scalar_views(self, scal):
+        """actions [B, ...], rewards [B, 1], not_dones [B, 1] (utils.py:159-166) inside a slot's scalar buffer (made
+        once per slot: ``scalars``)."""
         B, A = self.batch_size, self._n_act
-        out = scal[:B * A], scal[B * A:B * A + B], scal[B * A + B:]
+        return (scal[:B * A].view((B,) + tuple(self.actions.shape[1:])), scal[B * A:B * A + B].view(B, 1),
+                scal[B * A + B:].view(B, 1))
+
+    def _stage(self, host_dev, dev, nbytes, out):
+        """The staging launch of a minibatch: pinned block -> device block + the transitions' scalars into ``out``
+        (_scalar_views); with n_step > 1 the n-step composition happens in the same launch."""
+        B, A = self.batch_size, self._n_act
         if self.n_step > 1:
             ops.sample_stage_nstep(host_dev, dev, nbytes, self._layout["next_row"], self._sc, self._cont, self.capacity,
                                    self.n_step, self._nstep_discount(), B, A, *out)
         else:
             ops.sample_stage(host_dev, dev, nbytes, self._sc, B, A, *out)
 
-    def _next_rows(self, dev, d_idx):
-        """The rows of ONE ring that a minibatch's next_obs come from: the sampled rows ``d_idx``, or with n_step > 1
-        the bootstrap rows that the composition wrote into the device block ``dev`` (block_layout: next_row)."""
-        if self.n_step == 1:
-            return d_idx
-        at = self._layout["next_row"]
-        return dev[at:at + 8 * self.batch_size].view(torch.int64)
-
-    def _scalars(self, d_idx):
-        """actions [B, ...], rewards [B, 1], not_dones [B, 1] of the sampled transitions (utils.py:159-166): one
-        gather kernel into this sample slot's buffer (valid as long as the slot's pixel handles are)."""
-        B, A = self.batch_size, self._n_act
-        buf = self._d_scal[self._sample_slot]
-        act, rew, nd = buf[:B * A].view((B,) + tuple(self.actions.shape[1:])), buf[B * A:B * A + B].view(B, 1), \
-            buf[B * A + B:].view(B, 1)
-        if self._staged:  # gathered by the launch that staged the indices (_upload_indices)
-            self._staged = False
-        elif self.device.type == "cuda" or _lib_tracing():
-            ops.gather_transition_scalars(self._sc, d_idx, B, A, act, rew, nd)
-        return act, rew, nd
-
     def _require_cuda(self):
         from . import _lib
         if self.device.type != "cuda" and _lib._trace_hook is None:
             raise RuntimeError("sampling pixels needs the HIP device: curla_amd has no CPU fallback for the learner path")
 
-    def _sources(self, d_idx):
-        """(obs ring, next_obs ring, row index tensor or None) the loaders read a minibatch from.  Plain storage:
-        the two rings, indexed by the sampled slots.  De-duplicated storage: the k frames of every sampled stack
-        are first assembled into this sample slot's [B][H][W][3k] uint8 buffers (one gather kernel per tensor)."""
-        if not self.dedup_frames:
-            return self.obses, self.next_obses, d_idx
-        B = self.batch_size
-        c, h, w = self.obs_shape
-        mb = self._mb_store[self._sample_slot]
-        both = mb[:2 * B * self._frame].view(2 * B, h, w, c)
-        views = [both[:B], both[B:]]
-        rows = d_idx, self._next_rows(self._d_index[self._sample_slot], d_idx)  # (n_step: next_obs of the bootstrap rows)
-        for j in range(2):
-            ops.gather_stacks(self.frames, self._fid[:, j, :], rows[j], B, views[j])
-        self._mb_both = both
-        return views[0], views[1], None
+    def _sources(self, slot):
+        """Where the loaders read the minibatch of ``slot`` from -- which storage, which rows for next_obs: decided
+        here and nowhere else.  Returns a _Sources:
+          tensors  (ring, rows) of obs, next_obs, pos: ONE ring each, ``rows`` int64 [B] or None for rows 0..B-1;
+                   next_obs at the sampled rows, or with n_step > 1 at the bootstrap rows that the composition wrote into
+                   the block (block_layout: next_row)
+          off      the six offset rows: off[2j] / off[2j+1] = h1 / w1 of tensor j
+          both     the ring of obs frames then next_obs frames in which (obs | next_obs) is ONE run of 2B rows ``idx2``
+                   (None: rows 0..2B-1) with offsets ``h2`` / ``w2``; None when the rings are two allocations
+          dy, dx   the h rows of obs, next_obs, pos as one int32 run of 3B, and the w rows (RandomShift's offsets)
+        Plain storage reads the rings at the sampled rows.  The frame store first assembles the k frames of every
+        sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor)."""
+        B, lay, dev = self.batch_size, self._layout, slot["dev"]
+        d64 = dev[lay["idx"]:lay["offs"]].view(torch.int64)
+        d32 = dev[lay["offs"]:lay["offs_end"]].view(torch.int32)
+        off = [d32[(j // 2 + 3 * (j % 2)) * B:(j // 2 + 3 * (j % 2) + 1) * B] for j in range(6)]
+        rows = d64[:B]
+        rows_n = rows if self.n_step == 1 else dev[lay["next_row"]:lay["next_row"] + 8 * B].view(torch.int64)
+        if self.dedup_frames:
+            c, h, w = self.obs_shape
+            both = slot["mb_u8"][:2 * B * self._frame].view(2 * B, h, w, c)
+            rings, idx2 = (both[:B], both[B:]), None
+            for j, r in enumerate((rows, rows_n)):
+                ops.gather_stacks(self.frames, self._fid[:, j, :], r, B, rings[j])
+            rows = rows_n = None
+        else:
+            both, rings, idx2 = self._both, (self.obses, self.next_obses), d64
+        return _Sources(both, idx2, d32[:2 * B], d32[3 * B:5 * B], ((rings[0], rows), (rings[1], rows_n), (rings[0], rows)),
+                        off, d32[:3 * B], d32[3 * B:])
 
-    def _shift_minibatch(self, dev_block, both, rows2, ring_o, ring_n, rows, store, rows_n=None):
-        """RandomShift: the frames of a minibatch, shifted by the (dy, dx) of ``dev_block`` (a device index block:
-        the h rows of obs, next_obs, pos are one int32 run of 3B, the w rows the next), into ``store``
-        (uint8, 3B frames + slack) as obs | next_obs | pos; returns the [3B][H][W][C] view.  ``both`` (a [2 * rows] ring
-        holding obs frames then next_obs frames, read at the 2B indices ``rows2`` or, None, at 0..2B-1): ONE launch,
-        pos reading the obs rows again (period 2B).  Without it (rings in two allocations) one launch per tensor from
-        ``ring_o`` / ``ring_n`` at ``rows`` (``ring_n`` at ``rows_n`` where given: n_step)."""
+    def _shift(self, slot, src):
+        """RandomShift: the frames of a minibatch (``src``: _sources), shifted by (dy, dx), into the slot's scratch as
+        obs | next_obs | pos; returns the [3B][H][W][C] view.  With ``both`` ONE launch, pos reading the obs rows again
+        (period 2B); with the rings in two allocations one launch per tensor."""
         B = self.batch_size
         c, h, w = self.obs_shape
         pad = self.augmentor.pad
-        out = store[:3 * B * self._frame].view(3 * B, h, w, c)
-        d32 = dev_block[2 * B * 8:2 * B * 8 + 6 * B * 4].view(torch.int32)
-        dy, dx = d32[:3 * B], d32[3 * B:]
-        if both is not None:
-            ops.random_shift_u8(both, rows2, 2 * B, dy, dx, pad, 3 * B, out)
+        out = slot["shift_u8"][:3 * B * self._frame].view(3 * B, h, w, c)
+        if src.both is not None:
+            ops.random_shift_u8(src.both, src.idx2, 2 * B, src.dy, src.dx, pad, 3 * B, out)
         else:
-            for j, ring in enumerate((ring_o, ring_n, ring_o)):
-                ops.random_shift_u8(ring, rows_n if j == 1 and rows_n is not None else rows, B, dy[j * B:(j + 1) * B],
-                                    dx[j * B:(j + 1) * B], pad, B, out[j * B:(j + 1) * B])
+            for j, (ring, rows) in enumerate(src.tensors):
+                ops.random_shift_u8(ring, rows, B, src.dy[j * B:(j + 1) * B], src.dx[j * B:(j + 1) * B], pad, B,
+                                    out[j * B:(j + 1) * B])
         return out
 
     def _shift_refs(self, shifted, guard):
@@ -886,12 +880,49 @@ class ReplayBuffer(object):
         obses.pair = (ops.ObsRef.from_ring(shifted, ar[:2 * B], z[:2 * B], z[:2 * B], 2 * B, hw, guard), next_obses)
         return obses, next_obses, pos
 
+    def _assemble(self, slot, guard):
+        """The (obs, next_obs, pos) handles of the minibatch whose block and scalars are staged in ``slot`` -- a rotating
+        slot (sample_cpc_refs; ``guard`` from _upload_indices) or a captured graph's (graph_refs; ``guard`` None), whose
+        launches then write to fixed addresses: the
+        gathers of the frame store (_sources), then by augmentation ring handles (nothing is launched: the first conv
+        layer gathers and crops), the shift launch(es), or the three jitter / cover launches."""
+        B = self.batch_size
+        src = self._sources(slot)
+        both, idx2, tensors, off = src.both, src.idx2, src.tensors, src.off
+        if self._is_float_aug():
+            # obs, next_obs and pos (= a copy of obs) are augmented independently (utils.py:173-182); obs and
+            # next_obs are written into the two halves of one [2B] tensor (ObsRef.pair, see below)
+            c, h, w = self.obs_shape
+            fb = slot.get("both_f32")
+            if fb is None:
+                fb = torch.empty((2 * B, h, w, c), dtype=torch.float32, device=self.device)
+            outs = fb[:B], fb[B:], slot.get("pos_f32")
+            obses, next_obses, pos = (ops.ObsRef.from_nhwc(self._float_augmented(ring, rows, slot["dev"], j, outs[j]))
+                                      for j, (ring, rows) in enumerate(tensors))
+            obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
+        elif self._is_shift():
+            obses, next_obses, pos = self._shift_refs(self._shift(slot, src), guard)
+        else:
+            crop = tuple(self.augmentor.output_shape)
+            if both is not None:
+                # every handle indexes the ONE ring that holds obs frames then next_obs frames, so that any two of
+                # them can share a first-layer launch (ops.conv1_fwd2), and (obs | next_obs) is itself a handle of
+                # 2B frames: the critic phase runs both through the online convs in one launch per layer
+                # (curl_sac.py:350-358)
+                if idx2 is None:
+                    idx2 = slot["ar2"]
+                tensors = (both, idx2[:B]), (both, idx2[B:]), (both, idx2[:B])
+            # (else rings in two allocations -- the second half would not start on a dword: no pair)
+            obses, next_obses, pos = (ops.ObsRef.from_ring(ring, rows, off[2 * j], off[2 * j + 1], B, crop, guard)
+                                      for j, (ring, rows) in enumerate(tensors))
+            if both is not None:
+                obses.pair = (ops.ObsRef.from_ring(both, idx2, src.h2, src.w2, 2 * B, crop, guard), next_obses)
+        return obses, next_obses, pos
+
     # ---- dedicated sample slots of captured update graphs (CurlSacAgent.enable_update_graphs) ---------------------
     # A captured graph replays the SAME pointers: its minibatch block lives in its own pinned host slot and its own
     # device block, never in the rotating ones above.  Behind the indices the block carries GRAPH_TAIL bytes of per-update
     # control values (RNG stream positions, Adam step factors) that the graph's kernels read from the device copy.
-    GRAPH_TAIL = 80  # u64[4] (seed, critic-noise offset, seed, actor-noise offset) | f64[2] log_alpha | f32[8] four Adams
-
     def graph_supported(self):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
         ones (RandomCrop / RandomShift / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
@@ -905,8 +936,6 @@ class ReplayBuffer(object):
         return self.dedup_frames or self._both is not None
 
     def graph_block(self, slot):
-        if not hasattr(self, "_graph_blocks"):
-            self._graph_blocks = {}
         g = self._graph_blocks.get(slot)
         if g is None:
             B, A = self.batch_size, self._n_act
@@ -916,6 +945,7 @@ class ReplayBuffer(object):
             g = dict(host=host, host_dev=ops.host_device_pointer(host), dev=torch.zeros(nb, dtype=torch.uint8, device=self.device),
                      scal=torch.empty(B * (A + 2), dtype=torch.float32, device=self.device), event=None,
                      tail=lay["tail"], guards=[])
+            g["scalars"] = self._scalar_views(g["scal"])
             # A replayed graph writes to the SAME addresses every time, so the minibatch tensors that the rotating
             # sample slots / the allocator provide per call are buffers of the graph slot here (allocated now, before
             # the capture): the gathered uint8 stacks of the de-duplicated store, the float NHWC tensors of an
@@ -933,8 +963,6 @@ class ReplayBuffer(object):
                 g["pos_f32"] = pos.view(torch.float32).view(B, h, w, c)
             self._graph_blocks[slot] = g
         return g
-
-    GUARD, GUARD_BYTE = 256, 0xA5
 
     def _guarded(self, sizes, guards):
         """Zeroed uint8 device buffers of ``sizes`` bytes in one allocation, GUARD bytes of GUARD_BYTE in front of,
@@ -971,48 +999,10 @@ class ReplayBuffer(object):
         parameters from the device block), and the sample_cpc 6-tuple with handles into the slot's buffers.  Nothing
         here draws a random number."""
         g = self.graph_block(slot)
-        B, A = self.batch_size, self._n_act
-        buf = g["scal"]
-        self._stage(g["host_dev"], g["dev"], g["host"].numel(), buf)  # (n_step: reads ``cont`` when the graph runs)
-        d_idx, off, (idx2, h2, w2) = self._index_views(g["dev"])
-        rows_n = self._next_rows(g["dev"], d_idx)
-        crop = tuple(self.augmentor.output_shape)
-        c, h, w = self.obs_shape
-        both, rows = None if self.dedup_frames else self._both, d_idx
-        if self.dedup_frames:
-            both, rows = g["mb_u8"][:2 * B * self._frame].view(2 * B, h, w, c), None
-            for j in range(2):
-                ops.gather_stacks(self.frames, self._fid[:, j, :], (d_idx, rows_n)[j], B, both[j * B:(j + 1) * B])
-            idx2 = g["ar2"]
-            rows_n = None
-        if self._is_float_aug():
-            ring_o, ring_n = (both[:B], both[B:]) if self.dedup_frames else (self.obses, self.next_obses)
-            fb, fp = g["both_f32"], g["pos_f32"]
-            obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, fb[:B], self._aug_args(g["dev"], 0)))
-            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows_n, fb[B:], self._aug_args(g["dev"], 1)))
-            pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, fp, self._aug_args(g["dev"], 2)))
-            obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
-        elif self._is_shift():  # one shift launch behind the staging (and the gathers); the offsets are the block's
-            shifted = self._shift_minibatch(g["dev"], both, None if self.dedup_frames else idx2, None, None, None,
-                                            g["shift_u8"])
-            obses, next_obses, pos = self._shift_refs(shifted, None)
-        else:
-            obses = ops.ObsRef.from_ring(both, idx2[:B], off[0], off[1], B, crop, None)
-            next_obses = ops.ObsRef.from_ring(both, idx2[B:], off[2], off[3], B, crop, None)
-            pos = ops.ObsRef.from_ring(both, idx2[:B], off[4], off[5], B, crop, None)
-            obses.pair = (ops.ObsRef.from_ring(both, idx2, h2, w2, 2 * B, crop, None), next_obses)
-        act, rew, nd = buf[:B * A].view((B,) + tuple(self.actions.shape[1:])), buf[B * A:B * A + B].view(B, 1), \
-            buf[B * A + B:].view(B, 1)
+        self._stage(g["host_dev"], g["dev"], g["host"].numel(), g["scalars"])  # (n_step: reads ``cont`` when the graph runs)
+        obses, next_obses, pos = self._assemble(g, None)
+        act, rew, nd = g["scalars"]
         return obses, act, rew, next_obses, nd, dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
-
-    def _shifted(self, ring_o, ring_n, rows):
-        """RandomShift: the current sample slot's minibatch, shifted into the slot's scratch (after _upload_indices and
-        _sources)."""
-        s = self._sample_slot
-        both = self._mb_both if self.dedup_frames else self._both
-        rows2 = None if self.dedup_frames else self._pair_views[0]
-        rows_n = None if rows is None else self._next_rows(self._d_index[s], rows)
-        return self._shift_minibatch(self._d_index[s], both, rows2, ring_o, ring_n, rows, self._shift_store[s], rows_n)
 
     def sample_cpc_refs(self, indices=None):
         """The fused form of sample_cpc: same 6-tuple, but obs / next_obs / pos are
@@ -1022,45 +1012,9 @@ class ReplayBuffer(object):
         one raises)."""
         self._require_cuda()
         idxs, offs = indices if indices is not None else self.draw_indices()
-        guard, d_idx, off = self._upload_indices(idxs, offs, self.draw_aug())
-        B = self.batch_size
-        crop = tuple(self.augmentor.output_shape)
-        ring_o, ring_n, rows = self._sources(d_idx)
-        # next_obs reads its ring at the bootstrap rows (n_step; the frame store has gathered them already)
-        rows_n = None if rows is None else self._next_rows(self._d_index[self._sample_slot], rows)
-        if self._is_float_aug():
-            # obs, next_obs and pos (= a copy of obs) are augmented independently (utils.py:173-182); obs and
-            # next_obs are written into the two halves of one [2B] tensor (ObsRef.pair, see below)
-            c, h, w = self.obs_shape
-            both = torch.empty((2 * B, h, w, c), dtype=torch.float32, device=self.device)
-            st = self._staged_args()
-            obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, both[:B], st[0]))
-            next_obses = ops.ObsRef.from_nhwc(self._float_augmented(ring_n, rows_n, both[B:], st[1]))
-            pos = ops.ObsRef.from_nhwc(self._float_augmented(ring_o, rows, None, st[2]))
-            obses.pair = (ops.ObsRef.from_nhwc(both), next_obses)
-        elif self._is_shift():
-            obses, next_obses, pos = self._shift_refs(self._shifted(ring_o, ring_n, rows), guard)
-        else:
-            idx2, h2, w2 = self._pair_views
-            both = self._mb_both if self.dedup_frames else self._both
-            if both is None:  # (rings in two allocations: second half would not start on a dword)
-                obses = ops.ObsRef.from_ring(ring_o, rows, off[0], off[1], B, crop, guard)
-                next_obses = ops.ObsRef.from_ring(ring_n, rows_n, off[2], off[3], B, crop, guard)
-                pos = ops.ObsRef.from_ring(ring_o, rows, off[4], off[5], B, crop, guard)
-            else:
-                # every handle indexes the ONE ring that holds obs frames then next_obs frames, so that any two of
-                # them can share a first-layer launch (ops.conv1_fwd2), and (obs | next_obs) is itself a handle of
-                # 2B frames: the critic phase runs both through the online convs in one launch per layer
-                # (curl_sac.py:350-358)
-                if self.dedup_frames:
-                    if getattr(self, "_ar2", None) is None:
-                        self._ar2 = torch.arange(2 * B, device=self.device, dtype=torch.int64)
-                    idx2 = self._ar2
-                obses = ops.ObsRef.from_ring(both, idx2[:B], off[0], off[1], B, crop, guard)
-                next_obses = ops.ObsRef.from_ring(both, idx2[B:], off[2], off[3], B, crop, guard)
-                pos = ops.ObsRef.from_ring(both, idx2[:B], off[4], off[5], B, crop, guard)
-                obses.pair = (ops.ObsRef.from_ring(both, idx2, h2, w2, 2 * B, crop, guard), next_obses)
-        actions, rewards, not_dones = self._scalars(d_idx)
+        slot, guard = self._upload_indices(idxs, offs, self.draw_aug())
+        obses, next_obses, pos = self._assemble(slot, guard)
+        actions, rewards, not_dones = slot["scalars"]  # (valid as long as the pixel handles are)
         cpc_kwargs = dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
         return obses, actions, rewards, next_obses, not_dones, cpc_kwargs
 
@@ -1069,28 +1023,26 @@ class ReplayBuffer(object):
         in [0,255] on the device (materialised by one crop kernel per tensor)."""
         self._require_cuda()
         idxs, offs = indices if indices is not None else self.draw_indices()
-        _, d_idx, off = self._upload_indices(idxs, offs, self.draw_aug())
+        slot, _ = self._upload_indices(idxs, offs, self.draw_aug())
         B = self.batch_size
         c = self.obs_shape[0]
         oh, ow = self.augmentor.output_shape
-        ring_o, ring_n, rows_o = self._sources(d_idx)
-        rows_n = None if rows_o is None else self._next_rows(self._d_index[self._sample_slot], rows_o)
-        st = self._staged_args()
+        src = self._sources(slot)
+        shifted = self._shift(slot, src) if self._is_shift() else None
         outs = []
-        shifted = self._shifted(ring_o, ring_n, rows_o) if self._is_shift() else None
-        for ring, j in ((ring_o, 0), (ring_n, 1), (ring_o, 2)):
-            rows = rows_n if j == 1 else rows_o
+        for j, (ring, rows) in enumerate(src.tensors):
             t = torch.empty((B, c, oh, ow), dtype=torch.float32, device=self.device)
             if shifted is not None:  # the shifted frames as they are: rows j B .. of the scratch, zero offsets
                 z = self._shift_zero[:B]
                 ops.crop_nchw(shifted, self._shift_rows[j * B:(j + 1) * B], z, z, B, (oh, ow), out_f32=t)
             elif self._is_float_aug():
-                ops.nhwc_to_nchw(self._float_augmented(ring, rows, None, st[j]), t)
+                ops.nhwc_to_nchw(self._float_augmented(ring, rows, slot["dev"], j), t)
             else:
-                ops.crop_nchw(ring, rows, off[2 * j], off[2 * j + 1], B, (oh, ow), out_f32=t)
+                ops.crop_nchw(ring, rows, src.off[2 * j], src.off[2 * j + 1], B, (oh, ow), out_f32=t)
             outs.append(t)
         obses, next_obses, pos = outs
-        actions, rewards, not_dones = (t.clone() for t in self._scalars(d_idx))  # fresh tensors, like the reference's
+        # fresh tensors, like the reference's
+        actions, rewards, not_dones = (t.clone() for t in slot["scalars"])
         cpc_kwargs = dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
         return obses, actions, rewards, next_obses, not_dones, cpc_kwargs
 
