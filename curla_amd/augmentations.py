@@ -116,6 +116,55 @@ class RandomShift(IdentityAugmentation):
         return self.shift(image_batch, dy, dx)
 
 
+class RandomCutout(IdentityAugmentation):
+    """Beyond the reference: the cutout (``color=False``) and cutout-color (``color=True``) of RAD.  One box per sample,
+    shared by all frames of the stack, is painted black or in one random RGB colour onto an otherwise untouched frame:
+        out[c][y][x] = colour[c % 3]   if y0 <= y < y0 + bh and x0 <= x < x0 + bw,   in[c][y][x] otherwise
+    with bh, bw in [min_cut, max_cut] and the box always inside the frame (``output_shape == input_shape``; evaluation
+    is the identity).  This is a clean restatement, not a port: RAD's own code reuses one draw for both the position and
+    the size of its box, a quirk that is not reproduced here.  On the learner path the boxes are painted by
+    ``curla_cutout_u8`` and the minibatch stays uint8 (ReplayBuffer); boxes and colours are drawn on the host from
+    NumPy's global stream."""
+
+    def __init__(self, input_shape, min_cut=10, max_cut=30, color=False):
+        super().__init__(input_shape)
+        for name, v in (("min_cut", min_cut), ("max_cut", max_cut)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("RandomCutout: %s must be an int, got %r" % (name, v))
+        # (bh | bw << 16 travels as one non-negative int32 of the minibatch's block: a side has 15 bits)
+        if not 1 <= min_cut <= max_cut <= min(min(self.input_shape), 0x7FFF):
+            raise ValueError("RandomCutout: need 1 <= min_cut <= max_cut <= min(H, W), got min_cut=%r max_cut=%r for %r"
+                             % (min_cut, max_cut, self.input_shape))
+        self.min_cut, self.max_cut, self.color = int(min_cut), int(max_cut), bool(color)
+
+    def draw_boxes(self, n):
+        """The RNG draws of n boxes, in this order: bh, bw in [min_cut, max_cut], then y0 in [0, H - bh] and x0 in
+        [0, W - bw] (array upper bounds), then -- ``color=True`` only -- rgb in [0, 255], shape (n, 3).  Returns
+        (y0, x0, bh, bw, rgb); rgb is None for the black cutout, which draws nothing for it."""
+        h, w = self.input_shape
+        bh = np.random.randint(self.min_cut, self.max_cut + 1, n)
+        bw = np.random.randint(self.min_cut, self.max_cut + 1, n)
+        y0 = np.random.randint(0, h - bh + 1)
+        x0 = np.random.randint(0, w - bw + 1)
+        rgb = np.random.randint(0, 256, (n, 3)) if self.color else None
+        return y0, x0, bh, bw, rgb
+
+    @staticmethod
+    def cut(image_batch, y0, x0, bh, bw, rgb=None):
+        """The cutout of a (B, C, H, W) array with given per-sample boxes, on the host; ``rgb`` (B, 3) or None = black."""
+        out = np.array(image_batch, copy=True)
+        chan = np.arange(out.shape[1]) % 3
+        for b in range(out.shape[0]):
+            colour = np.zeros(3, dtype=out.dtype) if rgb is None else np.asarray(rgb[b]).astype(out.dtype)
+            out[b, :, int(y0[b]):int(y0[b]) + int(bh[b]), int(x0[b]):int(x0[b]) + int(bw[b])] = colour[chan][:, None, None]
+        return out
+
+    def training_augmentation(self, image_batch):
+        """Host-side cutout of a (B, C, H, W) NumPy array, for callers outside the fused path."""
+        image_batch = np.asarray(image_batch)
+        return self.cut(image_batch, *self.draw_boxes(image_batch.shape[0]))
+
+
 class ColorJiggle(IdentityAugmentation):
     """augmentations.py:78-136: every RGB frame of the stack is jittered independently with probability
     0.85 -- contrast U(0.8,1.2), saturation U(0.5,1.5), hue U(-0.5,0.5) turns, brightness 0 -- the four
@@ -188,8 +237,9 @@ class NoisyCover(IdentityAugmentation):
         return out
 
 
-def make_augmentor(name, input_shape, output_shape=None, *, pad=4):
-    """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding; beyond the reference)."""
+def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30):
+    """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding) and 'cutout' / 'cutout_color' (``min_cut``,
+    ``max_cut``: the range of a box side) -- all three beyond the reference."""
     print(f'CHOSEN AUGMENTATION: {name}')
     if name == 'identity':
         return IdentityAugmentation(input_shape)
@@ -201,4 +251,6 @@ def make_augmentor(name, input_shape, output_shape=None, *, pad=4):
         return NoisyCover(input_shape)
     if name == 'random_shift':
         return RandomShift(input_shape, pad)
+    if name in ('cutout', 'cutout_color'):
+        return RandomCutout(input_shape, min_cut, max_cut, color=name == 'cutout_color')
     raise ValueError('augmentation is not supported: %s' % name)

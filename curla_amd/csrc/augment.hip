@@ -409,6 +409,147 @@ __global__ __launch_bounds__(256) void random_shift_u8_kernel(const uint8_t* fra
   }
 }
 
+// ---- RandomCutout (beyond the reference: RAD's cutout / cutout-color) ----
+// out[s][y][x][c] = colour(s)[c % 3] inside the sample's box [y0, y0 + bh) x [x0, x0 + bw), frames[row(s)][y][x][c]
+// elsewhere; uint8 NHWC in and out, all frames of a stack share the box.  Like the shift a byte mover whose thread owns
+// 16 consecutive output bytes of a sample, but the source of a group is simply the same 16 bytes of the source frame:
+// no address depends on the box (it is clamped into the frame besides), so whatever the block holds nothing is read or
+// written outside a frame.  A group wholly outside the box is one 16-byte load and one 16-byte store; a group wholly
+// inside is a store of the colour pattern without a load; a group that crosses a box edge (or straddles rows of which
+// the box touches one) loads its 16 bytes like an outside group and replaces the bytes inside the box in registers
+// (cut_blend) -- arithmetic only, no byte-wise memory access: in the shift kernel the byte loads of such groups set the
+// time.  Byte-wise loads and stores are left to frames that are no whole number of groups and to an
+// `out` off the 16-byte grid (vec == false), as there.
+struct CutGeom {
+  unsigned rb, frame;  // bytes of a row / of a frame
+  int C, y0, y1;       // box rows [y0, y1)
+  unsigned xb0, xb1;   // box columns in bytes of a row [xb0, xb1)
+  uint32_t col[3];
+};
+
+__device__ __forceinline__ bool cut_inside(const CutGeom& q, int yy, unsigned xb) {
+  return yy >= q.y0 && yy < q.y1 && xb >= q.xb0 && xb < q.xb1;
+}
+
+__device__ __forceinline__ uint32_t cut_colour(const CutGeom& q, int c3) {  // (selects: no runtime-indexed array)
+  return c3 == 0 ? q.col[0] : c3 == 1 ? q.col[1] : q.col[2];
+}
+
+// the 16 bytes `v` of the group at byte r = y rb + xb with the bytes inside the box replaced by their colour:
+// (row, byte in row, channel) are stepped, not divided
+__device__ __forceinline__ u32x4 cut_blend(const CutGeom& q, u32x4 v, unsigned y, unsigned xb) {
+  int yy = (int)y, c = (int)(xb % (unsigned)q.C), c3 = c % 3;
+  uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int sh = 8 * (e & 3);
+    if (cut_inside(q, yy, xb)) w[e >> 2] = (w[e >> 2] & ~(0xffu << sh)) | (cut_colour(q, c3) << sh);
+    if (++c3 == 3) c3 = 0;
+    if (++c == q.C) c = 0, c3 = 0;
+    if (++xb == q.rb) xb = 0, ++yy;  // (rb is a multiple of C: c is 0 here)
+  }
+  return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// one (possibly short) group byte by byte: frames of no whole number of groups, `out` off the 16-byte grid
+__device__ __forceinline__ void cut_group_bytes(const uint8_t* src, uint8_t* dst, const CutGeom& q, unsigned r) {
+  const unsigned cnt = min(16u, q.frame - r);
+  const unsigned y = r / q.rb;
+  unsigned xb = r - y * q.rb;
+  int yy = (int)y, c = (int)(xb % (unsigned)q.C), c3 = c % 3;
+  for (unsigned e = 0; e < cnt; ++e) {
+    dst[r + e] = cut_inside(q, yy, xb) ? (uint8_t)cut_colour(q, c3) : src[r + e];
+    if (++c3 == 3) c3 = 0;
+    if (++c == q.C) c = 0, c3 = 0;
+    if (++xb == q.rb) xb = 0, ++yy;
+  }
+}
+
+constexpr int CUT_UNROLL = 4;  // groups per thread and trip, their loads issued before the first store (as SHIFT_UNROLL)
+
+__global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, const int64_t* idx, int period,
+                                                          const int32_t* y0, const int32_t* x0, const int32_t* size,
+                                                          const int32_t* rgb, int n, int H, int W, int C,
+                                                          unsigned groups, bool vec, uint8_t* out) {
+  CutGeom q;
+  q.C = C, q.rb = (unsigned)W * C, q.frame = (unsigned)H * q.rb;
+  const bool c3ok = C % 3 == 0;  // then a byte's colour is (byte offset in row) % 3 and the pattern runs on across rows
+  const unsigned stride = gridDim.x * 256;
+  for (int s = blockIdx.y; s < n; s += gridDim.y) {
+    const int p = s % period;
+    const int64_t row = idx ? idx[p] : (int64_t)p;
+    // whatever the block holds is clamped: the box lies inside the frame (an empty one is a plain copy)
+    const uint32_t sz = (uint32_t)size[s], colour = (uint32_t)rgb[s];
+    const int yc = min(max(y0[s], 0), H), xc = min(max(x0[s], 0), W);
+    const int bh = min((int)(sz & 0xffffu), H - yc), bw = min((int)(sz >> 16), W - xc);
+    const bool empty = bh == 0 || bw == 0;
+    q.y0 = yc, q.y1 = empty ? yc : yc + bh;
+    q.xb0 = (unsigned)(xc * C), q.xb1 = (unsigned)((xc + bw) * C);
+    q.col[0] = colour & 0xffu, q.col[1] = (colour >> 8) & 0xffu, q.col[2] = (colour >> 16) & 0xffu;
+    // the pattern of a group whose first byte has (byte offset in row) % 3 == k is {pat[k], pat[k + 1], pat[k + 2], pat[k]}
+    // (indices mod 3): pat[m] = colours m, m + 1, m + 2, m
+    uint32_t pat[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+      pat[m] = q.col[m] | (q.col[(m + 1) % 3] << 8) | (q.col[(m + 2) % 3] << 16) | (q.col[m] << 24);
+    const uint8_t* src = frames + (size_t)row * q.frame;
+    uint8_t* dst = out + (size_t)s * q.frame;
+    if (!vec) {
+      for (unsigned g = blockIdx.x * 256 + threadIdx.x; g < groups; g += stride) cut_group_bytes(src, dst, q, 16 * g);
+      continue;
+    }
+    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += CUT_UNROLL * stride) {
+      u32x4 v[CUT_UNROLL];
+      int kind[CUT_UNROLL];  // 0 outside the box, 1 inside, 2 both
+      unsigned gy[CUT_UNROLL], gxb[CUT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < CUT_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        kind[u] = 0, gy[u] = 0, gxb[u] = 0;
+        v[u] = u32x4{0u, 0u, 0u, 0u};
+        if (g < groups) {
+          const unsigned r = 16 * g;
+          const unsigned y = r / q.rb, xb = r - y * q.rb;
+          gy[u] = y, gxb[u] = xb;
+          const unsigned last = xb + 15;  // the group's last byte, counted from the start of row y
+          if (empty) {
+            kind[u] = 0;
+          } else if (last < q.rb) {  // one row
+            const bool in_rows = (int)y >= q.y0 && (int)y < q.y1;
+            if (!in_rows || last < q.xb0 || xb >= q.xb1) kind[u] = 0;
+            else kind[u] = (xb >= q.xb0 && last < q.xb1) ? 1 : 2;
+          } else if (last < 2 * q.rb) {  // rows y and y + 1
+            const unsigned last2 = last - q.rb;
+            const bool in0 = (int)y >= q.y0 && (int)y < q.y1, in1 = (int)y + 1 >= q.y0 && (int)y + 1 < q.y1;
+            if ((!in0 || xb >= q.xb1) && (!in1 || last2 < q.xb0)) kind[u] = 0;
+            else kind[u] = (in0 && in1 && q.xb0 == 0 && q.xb1 == q.rb) ? 1 : 2;
+          } else {  // rows shorter than a group
+            const unsigned ylast = (r + 15) / q.rb;
+            kind[u] = ((int)ylast < q.y0 || (int)y >= q.y1) ? 0 : 2;
+          }
+          if (kind[u] != 1) __builtin_memcpy(&v[u], src + r, 16);  // inside the frame: frame % 16 == 0
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < CUT_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        if (g < groups) {
+          u32x4 o = v[u];
+          if (kind[u] == 1 && c3ok) {
+            const unsigned k = gxb[u] % 3;
+            const uint32_t a = k == 0 ? pat[0] : k == 1 ? pat[1] : pat[2], b = k == 0 ? pat[1] : k == 1 ? pat[2] : pat[0],
+                           c = k == 0 ? pat[2] : k == 1 ? pat[0] : pat[1];
+            o = u32x4{a, b, c, a};
+          } else if (kind[u] != 0) {
+            o = cut_blend(q, o, gy[u], gxb[u]);
+          }
+          *reinterpret_cast<u32x4*>(dst + 16 * g) = o;
+        }
+      }
+    }
+  }
+}
+
 inline int blocks_for(size_t n) {
   size_t b = (n + 255) / 256;
   return (int)(b < 8192 ? b : 8192);
@@ -492,6 +633,23 @@ int curla_random_shift_u8(const uint8_t* frames, const int64_t* idx, int period,
   const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
   hipLaunchKernelGGL(random_shift_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period,
                      dy, dx, pad, n, H, W, C, groups, vec, out);
+  return curla_launch_status();
+}
+
+int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* y0, const int32_t* x0,
+                    const int32_t* size, const int32_t* rgb, int n, int C, int H, int W, uint8_t* out, void* stream) {
+  CURLA_REQUIRE(frames && y0 && x0 && size && rgb && out && n > 0 && period > 0 && C > 0 && H > 0 && W > 0);
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(y0) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(size) |
+                  reinterpret_cast<uintptr_t>(rgb)) & 3) == 0 && (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  const long long frame = (long long)H * W * C;
+  if (frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;  // (bytes inside a frame are 32-bit quantities in the kernel)
+  const bool vec = frame % 16 == 0 && aligned16(out);
+  const unsigned groups = (unsigned)((frame + 15) / 16);
+  const unsigned per_block = vec ? 256 * CUT_UNROLL : 256;
+  const unsigned gx = (groups + per_block - 1) / per_block;
+  const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
+  hipLaunchKernelGGL(cutout_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period, y0, x0,
+                     size, rgb, n, H, W, C, groups, vec, out);
   return curla_launch_status();
 }
 

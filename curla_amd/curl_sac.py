@@ -1368,7 +1368,7 @@ class CurlSacAgent(object):
             raise RuntimeError("update graphs need the HIP device")
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
             raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
-                             "(covered: RandomCrop, RandomShift or identity, plain storage with both rings in one "
+                             "(covered: RandomCrop, RandomShift, RandomCutout or identity, plain storage with both rings in one "
                              "allocation or dedup_frames storage; ColorJiggle / NoisyCover "
                              "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
                              "CURLA_STAGE_COPY=1)")

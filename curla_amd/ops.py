@@ -715,6 +715,24 @@ def random_shift_u8(frames, idx, period, dy, dx, pad, n, out):
          ptr(out), stream())
 
 
+def cutout_u8(frames, idx, period, y0, x0, size, rgb, n, out):
+    """RandomCutout of n samples (curla_cutout_u8): frames u8 [rows, H, W, C]; sample s is row idx[s % period] (idx None:
+    s % period) with the box of (y0[s], x0[s]) and size[s] = bh | bw << 16 painted in rgb[s] = r | g << 8 | b << 16 (all
+    int32 [n]; clamped into the frame by the kernel); out u8 [n, H, W, C]."""
+    _, H, W, C = frames.shape
+    _dev(frames, torch.uint8), _dev(out, torch.uint8)
+    for t in (y0, x0, size, rgb):
+        _dev(t, torch.int32)
+    if idx is not None:
+        _dev(idx, torch.int64)
+    if tuple(out.shape) != (n, H, W, C) or min(t.numel() for t in (y0, x0, size, rgb)) < n or \
+            (idx is not None and idx.numel() < min(period, n)):
+        raise _lib.CurlaHipError(f"cutout_u8: out {tuple(out.shape)} / {y0.numel()}, {x0.numel()}, {size.numel()}, "
+                                 f"{rgb.numel()} box words do not fit {n} samples of {(H, W, C)}")
+    call("curla_cutout_u8", ptr(frames), ptr(idx), int(period), ptr(y0), ptr(x0), ptr(size), ptr(rgb), int(n), C, H, W,
+         ptr(out), stream())
+
+
 def nhwc_to_nchw(x, out):
     B, H, W, C = x.shape
     call("curla_nhwc_to_nchw", ptr(x), ptr(out), B, H, W, C, stream())

@@ -200,7 +200,7 @@ class _FrameStore:
 
 
 # what ReplayBuffer._sources returns
-_Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off dy dx")
+_Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off dy dx size rgb")
 
 
 class ReplayBuffer(object):
@@ -263,7 +263,7 @@ class ReplayBuffer(object):
                 + self.N_SAMPLE_SLOTS * 2 * batch_size * frame
         else:
             total_bytes = 2 * capacity * frame + capacity * (4 * A + 8)
-        if self._is_shift():  # the shifted minibatches (obs | next_obs | pos) of the sample slots
+        if self._has_scratch():  # the shifted / cut minibatches (obs | next_obs | pos) of the sample slots
             total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * frame + 32)
         if self.n_step > 1:  # the continuity flags
             total_bytes += capacity
@@ -361,17 +361,18 @@ class ReplayBuffer(object):
         if self.dedup_frames:
             # (obs stacks | next_obs stacks) of a minibatch, contiguous: also one [2B] ring for ObsRef.pair
             self._mb_store = torch.zeros((self.N_SAMPLE_SLOTS, 2 * B * frame + 32), dtype=torch.uint8, device=dev)
-        if self._is_shift():
-            # RandomShift: a minibatch's shifted frames, uint8 [3B][H][W][C] = (obs | next_obs | pos) + 32 B of slack
-            # like a ring, per sample slot (each slot starts on a 256-byte boundary: the shift kernel then stores
-            # 16 bytes per lane).  Downstream it IS a ring: rows 0..3B-1, zero crop offsets -- static tensors.
+        if self._has_scratch():
+            # RandomShift / RandomCutout: a minibatch's shifted (cut) frames, uint8 [3B][H][W][C] = (obs | next_obs | pos)
+            # + 32 B of slack like a ring, per sample slot (each slot starts on a 256-byte boundary: the shift / cutout
+            # kernel then stores 16 bytes per lane).  Downstream it IS a ring: rows 0..3B-1, zero crop offsets -- static
+            # tensors.  (Both augmentations use the names the shift gave the scratch.)
             stride = (3 * B * frame + 32 + 255) // 256 * 256
             self._shift_store = torch.zeros((self.N_SAMPLE_SLOTS, stride), dtype=torch.uint8, device=dev)
             self._shift_rows = torch.arange(3 * B, dtype=torch.int64, device=dev)
             self._shift_zero = torch.zeros(3 * B, dtype=torch.int32, device=dev)
         # A slot = the buffers ONE minibatch is assembled in (_assemble): ``dev`` the device block, ``scal`` the
         # transitions' scalars and ``scalars`` its (actions, rewards, not_dones) views, ``mb_u8`` the gathered stacks +
-        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the shifted frames (RandomShift), ``both_f32`` / ``pos_f32``
+        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the shifted / cut frames (RandomShift, RandomCutout), ``both_f32`` / ``pos_f32``
         # the float tensors (absent here: allocated per call).  The rotating slots are views of the stores above; a
         # captured update graph has slots of its own with the same keys (graph_block).
         ar2 = torch.arange(2 * B, dtype=torch.int64, device=dev) if self.dedup_frames else None
@@ -380,7 +381,7 @@ class ReplayBuffer(object):
             slot = dict(dev=self._d_index[s], scal=self._d_scal[s], scalars=self._scalar_views(self._d_scal[s]))
             if self.dedup_frames:
                 slot.update(mb_u8=self._mb_store[s], ar2=ar2)
-            if self._is_shift():
+            if self._has_scratch():
                 slot["shift_u8"] = self._shift_store[s]
             self._sample_slots.append(slot)
         self._graph_blocks = {}
@@ -610,13 +611,32 @@ class ReplayBuffer(object):
     def _is_shift(self):
         return isinstance(self.augmentor, augmentations.RandomShift)
 
+    def _is_cutout(self):
+        return isinstance(self.augmentor, augmentations.RandomCutout)
+
+    def _has_scratch(self):
+        """The augmentations whose minibatch is written, still uint8, into a scratch of the sample slot by one launch
+        behind the staging launch (_scratch_aug) and read from there as an ordinary ring."""
+        return self._is_shift() or self._is_cutout()
+
     def draw_indices(self):
         """Host RNG draws of sample_cpc, in the reference's order (utils.py:147 then
         augmentations.py:66-67 for obs, next_obs, pos).  Returns (idxs, offsets) with
         offsets an int32 array [6, B] = h1/w1 of obs, next_obs, pos (zeros when the
-        augmentation is neither RandomCrop nor RandomShift, whose (dy, dx) pairs take the same places)."""
+        augmentation is neither RandomCrop nor RandomShift, whose (dy, dx) pairs take the same places).  A RandomCutout
+        returns int32 [12, B]: rows 2j, 2j + 1 = (y0, x0) of tensor j's boxes in those places, rows 6 + 2j, 6 + 2j + 1 its
+        packed sizes bh | bw << 16 and colours r | g << 8 | b << 16 (0 for the black cutout), drawn by ``draw_boxes(B)``
+        for obs, next_obs, pos."""
         B = self.batch_size
         idxs = np.random.randint(0, self.capacity if self.full else self.idx, size=B)
+        if self._is_cutout():
+            offs = np.zeros((12, B), dtype=np.int32)
+            for j in range(3):
+                y0, x0, bh, bw, rgb = self.augmentor.draw_boxes(B)
+                offs[2 * j], offs[2 * j + 1], offs[6 + 2 * j] = y0, x0, bh | (bw << 16)
+                if rgb is not None:
+                    offs[6 + 2 * j + 1] = rgb[:, 0] | (rgb[:, 1] << 8) | (rgb[:, 2] << 16)
+            return idxs, offs
         offs = np.zeros((6, B), dtype=np.int32)
         if self._is_crop() or self._is_shift():
             for j in range(3):
@@ -670,6 +690,8 @@ class ReplayBuffer(object):
         appends the parameters of the three tensors (obs, next_obs, pos), ``aug_stride`` bytes each:
           ColorJiggle  params float [B k][4] (apply, contrast, saturation, hue) | order int32 [4]
           NoisyCover   colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2]   (8-byte aligned)
+        A RandomCutout appends ``cut`` int32 [2][3B] at ``offs_end``: the packed box sizes of obs | next_obs | pos, then
+        their colour words -- contiguous runs for one launch of n = 3B.
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
         ``nbytes`` is what a rotating sample slot stages per minibatch; the block of a captured update graph carries
         GRAPH_TAIL more bytes of per-update control values behind it (at ``tail``; ``graph_nbytes`` in all)."""
@@ -683,6 +705,9 @@ class ReplayBuffer(object):
             else:
                 lay.update(aug=n, aug_stride=32, aug_rng=16)
             n += 3 * lay["aug_stride"]
+        if self._is_cutout():
+            lay["cut"] = n
+            n += 2 * 3 * B * 4
         assert n % 8 == 0
         if self.n_step > 1:  # next_row int64 [B]: the bootstrap rows without the double ring's offset (device-written)
             lay["next_row"] = n
@@ -756,7 +781,12 @@ class ReplayBuffer(object):
         i64[B:].copy_(i64[:B] + self.capacity)
         o32 = host[lay["offs"]:lay["offs_end"]].view(torch.int32).view(6, B)
         offs = np.ascontiguousarray(offs, dtype=np.int32)
+        if "cut" in lay and len(offs) != 12:
+            raise ValueError("a RandomCutout buffer's block takes offsets of 12 rows (draw_indices), got %d" % len(offs))
         o32.copy_(torch.from_numpy(np.ascontiguousarray(offs[[0, 2, 4, 1, 3, 5]])))
+        if "cut" in lay:  # sizes of obs | next_obs | pos, then their colours
+            c32 = host[lay["cut"]:lay["cut"] + 24 * B].view(torch.int32).view(6, B)
+            c32.copy_(torch.from_numpy(np.ascontiguousarray(offs[[6, 8, 10, 7, 9, 11]])))
 
     def _upload_indices(self, idxs, offs, aug=None):
         """A minibatch's indices and crop offsets (and, staged_aug, its augmentation parameters ``aug``) into the next
@@ -832,7 +862,9 @@ class ReplayBuffer(object):
           off      the six offset rows: off[2j] / off[2j+1] = h1 / w1 of tensor j
           both     the ring of obs frames then next_obs frames in which (obs | next_obs) is ONE run of 2B rows ``idx2``
                    (None: rows 0..2B-1) with offsets ``h2`` / ``w2``; None when the rings are two allocations
-          dy, dx   the h rows of obs, next_obs, pos as one int32 run of 3B, and the w rows (RandomShift's offsets)
+          dy, dx   the h rows of obs, next_obs, pos as one int32 run of 3B, and the w rows (RandomShift's offsets,
+                   RandomCutout's y0 / x0)
+          size, rgb  the packed box sizes and the colour words of obs, next_obs, pos, 3B each (RandomCutout; else None)
         Plain storage reads the rings at the sampled rows.  The frame store first assembles the k frames of every
         sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor)."""
         B, lay, dev = self.batch_size, self._layout, slot["dev"]
@@ -850,28 +882,40 @@ class ReplayBuffer(object):
             rows = rows_n = None
         else:
             both, rings, idx2 = self._both, (self.obses, self.next_obses), d64
+        size = rgb = None
+        if "cut" in lay:
+            c32 = dev[lay["cut"]:lay["cut"] + 24 * B].view(torch.int32)
+            size, rgb = c32[:3 * B], c32[3 * B:]
         return _Sources(both, idx2, d32[:2 * B], d32[3 * B:5 * B], ((rings[0], rows), (rings[1], rows_n), (rings[0], rows)),
-                        off, d32[:3 * B], d32[3 * B:])
+                        off, d32[:3 * B], d32[3 * B:], size, rgb)
 
-    def _shift(self, slot, src):
-        """RandomShift: the frames of a minibatch (``src``: _sources), shifted by (dy, dx), into the slot's scratch as
-        obs | next_obs | pos; returns the [3B][H][W][C] view.  With ``both`` ONE launch, pos reading the obs rows again
-        (period 2B); with the rings in two allocations one launch per tensor."""
+    def _scratch_aug(self, slot, src):
+        """RandomShift / RandomCutout: the frames of a minibatch (``src``: _sources), shifted by (dy, dx) resp. with the
+        boxes painted, into the slot's scratch as obs | next_obs | pos; returns the [3B][H][W][C] view.  With ``both``
+        ONE launch, pos reading the obs rows again (period 2B); with the rings in two allocations one launch per
+        tensor."""
         B = self.batch_size
         c, h, w = self.obs_shape
-        pad = self.augmentor.pad
         out = slot["shift_u8"][:3 * B * self._frame].view(3 * B, h, w, c)
+        if self._is_shift():
+            pad = self.augmentor.pad
+
+            def launch(ring, rows, period, lo, hi):
+                ops.random_shift_u8(ring, rows, period, src.dy[lo:hi], src.dx[lo:hi], pad, hi - lo, out[lo:hi])
+        else:
+            def launch(ring, rows, period, lo, hi):
+                ops.cutout_u8(ring, rows, period, src.dy[lo:hi], src.dx[lo:hi], src.size[lo:hi], src.rgb[lo:hi], hi - lo,
+                              out[lo:hi])
         if src.both is not None:
-            ops.random_shift_u8(src.both, src.idx2, 2 * B, src.dy, src.dx, pad, 3 * B, out)
+            launch(src.both, src.idx2, 2 * B, 0, 3 * B)
         else:
             for j, (ring, rows) in enumerate(src.tensors):
-                ops.random_shift_u8(ring, rows, B, src.dy[j * B:(j + 1) * B], src.dx[j * B:(j + 1) * B], pad, B,
-                                    out[j * B:(j + 1) * B])
+                launch(ring, rows, B, j * B, (j + 1) * B)
         return out
 
     def _shift_refs(self, shifted, guard):
-        """(obs, next_obs, pos) handles over a shifted minibatch: an ordinary uint8 ring of 3B rows, nothing left to
-        crop; obs carries the (obs | next_obs) pair of 2B rows."""
+        """(obs, next_obs, pos) handles over a shifted / cut minibatch: an ordinary uint8 ring of 3B rows, nothing left
+        to crop; obs carries the (obs | next_obs) pair of 2B rows."""
         B = self.batch_size
         hw = tuple(self.augmentor.output_shape)
         ar, z = self._shift_rows, self._shift_zero
@@ -885,7 +929,7 @@ class ReplayBuffer(object):
         slot (sample_cpc_refs; ``guard`` from _upload_indices) or a captured graph's (graph_refs; ``guard`` None), whose
         launches then write to fixed addresses: the
         gathers of the frame store (_sources), then by augmentation ring handles (nothing is launched: the first conv
-        layer gathers and crops), the shift launch(es), or the three jitter / cover launches."""
+        layer gathers and crops), the shift / cutout launch(es), or the three jitter / cover launches."""
         B = self.batch_size
         src = self._sources(slot)
         both, idx2, tensors, off = src.both, src.idx2, src.tensors, src.off
@@ -900,8 +944,8 @@ class ReplayBuffer(object):
             obses, next_obses, pos = (ops.ObsRef.from_nhwc(self._float_augmented(ring, rows, slot["dev"], j, outs[j]))
                                       for j, (ring, rows) in enumerate(tensors))
             obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
-        elif self._is_shift():
-            obses, next_obses, pos = self._shift_refs(self._shift(slot, src), guard)
+        elif self._has_scratch():
+            obses, next_obses, pos = self._shift_refs(self._scratch_aug(slot, src), guard)
         else:
             crop = tuple(self.augmentor.output_shape)
             if both is not None:
@@ -925,7 +969,7 @@ class ReplayBuffer(object):
     # control values (RNG stream positions, Adam step factors) that the graph's kernels read from the device copy.
     def graph_supported(self):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
-        ones (RandomCrop / RandomShift / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
+        ones (RandomCrop / RandomShift / RandomCutout / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
         are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover constructed with
         ``staged_aug=True`` (either storage).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
         through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""
@@ -954,7 +998,7 @@ class ReplayBuffer(object):
             if self.dedup_frames:
                 (g["mb_u8"],) = self._guarded([2 * B * frame + 32], g["guards"])  # (+32: the loaders' slack, as a ring)
                 g["ar2"] = torch.arange(2 * B, device=self.device, dtype=torch.int64)
-            if self._is_shift():  # the shifted (obs | next_obs | pos) frames, + the loaders' slack
+            if self._has_scratch():  # the shifted / cut (obs | next_obs | pos) frames, + the loaders' slack
                 (g["shift_u8"],) = self._guarded([3 * B * frame + 32], g["guards"])
             if self._is_float_aug():
                 c, h, w = self.obs_shape
@@ -994,7 +1038,8 @@ class ReplayBuffer(object):
     def graph_refs(self, slot):
         """Device side, called while the graph is being captured: the staging launch (pinned block -> device block +
         the transitions' scalars), for the de-duplicated store the two gather_stacks launches (they read ``_fid`` when
-        the graph is replayed), for RandomShift the shift launch (it reads its offsets from the device block), for a
+        the graph is replayed), for RandomShift / RandomCutout the shift / cutout launch (it reads its offsets, boxes and
+        colours from the device block), for a
         staged float augmentation the three jitter / cover launches (they read their
         parameters from the device block), and the sample_cpc 6-tuple with handles into the slot's buffers.  Nothing
         here draws a random number."""
@@ -1028,7 +1073,7 @@ class ReplayBuffer(object):
         c = self.obs_shape[0]
         oh, ow = self.augmentor.output_shape
         src = self._sources(slot)
-        shifted = self._shift(slot, src) if self._is_shift() else None
+        shifted = self._scratch_aug(slot, src) if self._has_scratch() else None
         outs = []
         for j, (ring, rows) in enumerate(src.tensors):
             t = torch.empty((B, c, oh, ow), dtype=torch.float32, device=self.device)

@@ -562,6 +562,19 @@ int curla_nhwc_to_nchw(const float* in, float* out, int B, int H, int W, int C, 
  * H W C or 2 pad C does not fit 31 / 30 bits. */
 int curla_random_shift_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* dy, const int32_t* dx,
                           int pad, int n, int C, int H, int W, uint8_t* out, void* stream);
+/* RandomCutout, the cutout / cutout-color of RAD (beyond the reference: its augmentations.py has no such class).  One
+ * box per sample, shared by all channels of a stack, is painted onto an otherwise untouched frame:
+ *   out[s][y][x][c] = colour(s)[c % 3]           if y0c <= y < y0c + bhc and x0c <= x < x0c + bwc,
+ *                     frames[row(s)][y][x][c]    otherwise,                                            0 <= s < n
+ * uint8 NHWC in ([rows][H][W][C]) and out ([n][H][W][C], 32 bytes of slack behind it like a ring), row(s) = idx[s % period]
+ * (idx NULL: s % period) as for curla_random_shift_u8.  y0 / x0: int32 [n], the box's first row / column; size: int32 [n],
+ * bh | bw << 16; rgb: int32 [n], r | g << 8 | b << 16 (the top byte is ignored; 0 = black).  Whatever they hold is clamped
+ * in the kernel: y0c = clamp(y0, 0, H), bhc = clamp(bh, 0, H - y0c), likewise in x -- an empty box is a plain copy, every
+ * output byte is written exactly once and no address depends on the box.  A frame of a multiple of 16 bytes with `out` on
+ * a 16-byte boundary moves 16 bytes per lane (no load for a group inside the box); every other case gives the same bytes
+ * one at a time.  Any C > 0.  Additive: CURLA_ABI_VERSION stays 8.  CURLA_ERR_UNSUPPORTED when H W C does not fit 31 bits. */
+int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* y0, const int32_t* x0,
+                    const int32_t* size, const int32_t* rgb, int n, int C, int H, int W, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
