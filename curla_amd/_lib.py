@@ -114,6 +114,8 @@ SIGNATURES = {
                               c_int, c_int, vp, vp, vp],
     "curla_color_jiggle_nchw": [vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_noisy_cover_nchw": [vp, vp, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp],
+    "curla_random_conv": [vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],
+    "curla_random_conv_nchw": [vp, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_random_shift_u8": [vp, vp, c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp],
     "curla_cutout_u8": [vp, vp, c_int, vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_version": [],

@@ -18,7 +18,7 @@ def _device_batch(image_batch, input_shape):
                          % (input_shape[0], input_shape[1], getattr(image_batch, "shape", type(image_batch))))
     from . import _lib
     if not image_batch.is_cuda and _lib._trace_hook is None:
-        raise RuntimeError("ColorJiggle / NoisyCover run on the HIP device only: curla_amd has no CPU path")
+        raise RuntimeError("ColorJiggle / NoisyCover / RandomConv run on the HIP device only: curla_amd has no CPU path")
     return image_batch.float().contiguous()
 
 
@@ -165,6 +165,76 @@ class RandomCutout(IdentityAugmentation):
         return self.cut(image_batch, *self.draw_boxes(image_batch.shape[0]))
 
 
+class RandomConv(IdentityAugmentation):
+    """Beyond the reference: the random convolution of RAD (``random_convolution``) and of Lee et al., "Network
+    Randomization".  Every sample's RGB frames go through one freshly drawn 3x3, 3 -> 3 channel filter, shared by all
+    frames of the stack -- colours and textures change, layout does not:
+        out[3 f + co][y][x] = sum over ci, ky, kx of  w[co][ci][ky][kx] * in[3 f + ci][y + ky - 1][x + kx - 1]
+    a cross-correlation (no kernel flip) with ``in`` taken as 0 outside the frame.  Input is the stored bytes as floats in
+    [0, 255]; the output is float on the same scale and NOT clamped (RAD does not clamp).  ``output_shape ==
+    input_shape``; evaluation is the identity.  ``p`` is the probability that a sample is convolved at all (Lee et al. mix
+    in clean samples): a sample that is not gets the identity filter, which returns its bytes exactly.  A clean
+    restatement, not a port of RAD's code.  On the learner path the frames are convolved straight from the ring by
+    ``curla_random_conv`` into the float NHWC minibatch (ReplayBuffer, like ColorJiggle); the weights are drawn on the host
+    from torch's CPU generator."""
+
+    def __init__(self, input_shape, p=1.0):
+        super().__init__(input_shape)
+        if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("RandomConv: p must be a number in [0, 1], got %r" % (p,))
+        self.p = float(p)
+
+    @staticmethod
+    def identity_filter():
+        """float32 [3, 3, 3, 3]: w[c][c][1][1] = 1, 0 elsewhere."""
+        import torch
+        w = torch.zeros(3, 3, 3, 3, dtype=torch.float32)
+        for c in range(3):
+            w[c, c, 1, 1] = 1.0
+        return w
+
+    def draw_weights(self, n):
+        """float32 [n, 3, 3, 3, 3] = w[sample][co][ci][ky][kx] from torch's CPU generator, in this order: first
+        ``torch.randn(n, 3, 3, 3, 3) * sqrt(2 / 54)`` (Xavier-normal for fan-in = fan-out = 27, RAD's initialisation);
+        then -- ``p < 1`` only -- ``torch.rand(n) < p``, and the rows that lose this draw become the identity filter.
+        With ``p == 1`` exactly one generator call is made."""
+        import torch
+        w = torch.randn(n, 3, 3, 3, 3, dtype=torch.float32) * np.sqrt(2.0 / 54.0)
+        if self.p < 1.0:
+            keep = torch.rand(n) < self.p
+            w[~keep] = self.identity_filter()
+        return w
+
+    @staticmethod
+    def conv(image_batch, weights):
+        """The convolution of a (B, 3k, H, W) array with given per-sample weights (B, 3, 3, 3, 3) (or (B, 81)), on the
+        host in float64: the formula of the class docstring, term by term."""
+        x = np.asarray(image_batch, dtype=np.float64)
+        B, C, H, W = x.shape
+        w = np.asarray(weights, dtype=np.float64).reshape(B, 3, 3, 3, 3)
+        k = C // 3
+        xp = np.zeros((B, k, 3, H + 2, W + 2), dtype=np.float64)
+        xp[:, :, :, 1:-1, 1:-1] = x.reshape(B, k, 3, H, W)
+        out = np.zeros((B, k, 3, H, W), dtype=np.float64)
+        for ky in range(3):
+            for kx in range(3):
+                out += np.einsum("boc,bfchw->bfohw", w[:, :, :, ky, kx], xp[:, :, :, ky:ky + H, kx:kx + W])
+        return out.reshape(B, C, H, W)
+
+    def training_augmentation(self, image_batch, weights=None):
+        """On the reference's tensor contract, as ColorJiggle's: a float (B, 3k, H, W) device tensor in [0, 255] in, the
+        convolved batch out, always a new tensor (``curla_random_conv_nchw``: the same arithmetic ``ReplayBuffer`` applies
+        straight from the ring).  ``weights`` (B, 3, 3, 3, 3) replaces the draw (tests)."""
+        import torch
+        from . import ops
+        x = _device_batch(image_batch, self.input_shape)
+        if weights is None:
+            weights = self.draw_weights(x.shape[0])
+        out = torch.empty_like(x)
+        ops.random_conv_nchw(x, torch.as_tensor(weights).to(x.device, torch.float32).contiguous(), out)
+        return out
+
+
 class ColorJiggle(IdentityAugmentation):
     """augmentations.py:78-136: every RGB frame of the stack is jittered independently with probability
     0.85 -- contrast U(0.8,1.2), saturation U(0.5,1.5), hue U(-0.5,0.5) turns, brightness 0 -- the four
@@ -237,9 +307,10 @@ class NoisyCover(IdentityAugmentation):
         return out
 
 
-def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30):
-    """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding) and 'cutout' / 'cutout_color' (``min_cut``,
-    ``max_cut``: the range of a box side) -- all three beyond the reference."""
+def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30, conv_p=1.0):
+    """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding), 'cutout' / 'cutout_color' (``min_cut``,
+    ``max_cut``: the range of a box side) and 'random_conv' (``conv_p``: the probability that a sample is convolved) --
+    all four beyond the reference."""
     print(f'CHOSEN AUGMENTATION: {name}')
     if name == 'identity':
         return IdentityAugmentation(input_shape)
@@ -253,4 +324,6 @@ def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, m
         return RandomShift(input_shape, pad)
     if name in ('cutout', 'cutout_color'):
         return RandomCutout(input_shape, min_cut, max_cut, color=name == 'cutout_color')
+    if name == 'random_conv':
+        return RandomConv(input_shape, conv_p)
     raise ValueError('augmentation is not supported: %s' % name)

@@ -550,6 +550,189 @@ __global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, c
   }
 }
 
+// ---- RandomConv (beyond the reference: the random convolution of RAD / "Network Randomization") ----
+// out[s][y][x][3 f + co] = sum over ci, ky, kx of w[s][co][ci][ky][kx] * in[row(s)][y + ky - 1][x + kx - 1][3 f + ci], `in`
+// zero outside the frame; one weight set per sample, shared by its frames; uint8 NHWC in, float NHWC out, not clamped.
+// Every accumulator is ONE fmaf chain from 0 over (ky, kx, ci) in that order -- the NCHW kernel below runs the same chain,
+// so the two agree bit for bit, and a filter of zeros and ones returns bytes exactly.
+//
+// Tiling.  A workgroup owns RC_TILE = 1024 consecutive pixels [p0, p0 + 1024) of ONE sample's flattened frame (thread t:
+// pixels p0 + t + 256 i, so a wave's lanes are 64 neighbouring pixels).  Their 3x3 windows lie in pixels
+// [p0 - W - 1, p0 + 1024 + W + 1) clipped to the frame, and in NHWC that is ONE contiguous run of bytes of the gathered
+// row: it is copied to LDS once, as aligned 16-byte groups (byte-wise only at its two ends, so nothing before or behind
+// the run -- hence the frame -- is read), and all nine reads of an input pixel are served from there.  Global traffic is
+// (1024 + 2 W + 2) / 1024 of the frame's bytes (1.33 x at W = 168), a fifth of what is written.  The LDS image keeps the
+// bytes' position on the 16-byte grid of global memory; a pixel's 3 KG bytes are read as the dwords that hold them
+// and shifted into place (v_alignbit), which serves every C, also those whose pixels are no whole dwords (C = 9).
+// The C floats of a pixel leave through LDS too, so that a wave stores whole lines (see the store below).
+// The 81 weights are uniform over the workgroup: read once, into registers (scalar registers where the compiler can).
+// Borders: which taps are inside the frame is decided from (y, x); a tap outside reads nothing of the frame -- its address
+// is that of a run of zero bytes in front of the LDS image, so it contributes x = 0 through the same instructions (no
+// branch and no select per tap, and no lane mask per tap to keep alive across the pixel loop).
+constexpr int RC_TILE = 1024;
+
+// acc = fma(w, x, acc) with the workgroup-uniform weight taken from a SCALAR register.  Written as an instruction because
+// the compiler, given fmaf, pairs the chains into packed FMAs whose operand pairs push the 81 weights out of the scalar
+// file (a v_readlane per FMA in the pixel loop) or, with the weights in vector registers, double them to 162 registers;
+// a packed f32 FMA issues no faster than two plain ones here.  The same IEEE fused multiply-add either way.
+__device__ __forceinline__ void rc_fmac(float& acc, float w, float x) {
+  asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "s"(w), "v"(x));
+}
+
+template <int KG>  // frames of a pixel convolved at a time: the whole stack (K = KG <= 4), or one by one (KG = 1, any K)
+__global__ __launch_bounds__(256) void random_conv_kernel(const uint8_t* __restrict__ frames,
+                                                            const int64_t* __restrict__ idx,
+                                                            const float* __restrict__ weights, int B, int K, int H, int W,
+                                                            float* __restrict__ out, unsigned stage_off) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t rc_tile[];
+  constexpr int NB = 3 * KG;          // bytes / accumulators of a group
+  constexpr int NW = (NB + 3) / 4;    // dwords of NB bytes in place
+  constexpr int ND = (NB + 3 + 3) / 4;  // dwords that hold NB bytes starting 0..3 bytes into the first
+  const int C = 3 * K, HW = H * W;
+  // LDS: `zero` bytes of 0 (3 K + 16 rounded up to 16: what the read of an outside tap at any frame offset touches), then
+  // the image
+  const unsigned zero = (3u * (unsigned)K + 16u + 15u) & ~15u;
+  uint8_t* tile8 = reinterpret_cast<uint8_t*>(rc_tile) + zero;
+  for (unsigned j = threadIdx.x; j < zero / 4; j += 256) rc_tile[j] = 0u;
+  const int p0 = blockIdx.x * RC_TILE;
+  const int lo = max(p0 - W - 1, 0), hi = min(p0 + RC_TILE + W + 1, HW);  // the pixels staged: [lo, hi)
+  const unsigned nbytes = (unsigned)(hi - lo) * (unsigned)C;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int64_t fi = idx ? idx[b] : (int64_t)b;
+    const uint8_t* g0 = frames + ((size_t)fi * HW + lo) * C;
+    const unsigned mis = (unsigned)(reinterpret_cast<uintptr_t>(g0) & 15);  // LDS byte mis + j = g0[j]
+    const unsigned head = mis ? min(16u - mis, nbytes) : 0u;                // bytes in front of the first whole group
+    const unsigned nfull = (nbytes - head) >> 4;
+    const unsigned tail0 = head + 16 * nfull;
+    for (unsigned g = threadIdx.x; g < nfull; g += 256)
+      *reinterpret_cast<u32x4*>(tile8 + mis + head + 16 * g) = *reinterpret_cast<const u32x4*>(g0 + head + 16 * g);
+    if (threadIdx.x < head) tile8[mis + threadIdx.x] = g0[threadIdx.x];
+    if (threadIdx.x < nbytes - tail0) tile8[mis + tail0 + threadIdx.x] = g0[tail0 + threadIdx.x];
+    float w[81];
+#pragma unroll
+    for (int i = 0; i < 81; ++i) w[i] = weights[(size_t)b * 81 + i];
+    __syncthreads();
+#pragma unroll 1
+    for (int i = 0; i < RC_TILE / 256; ++i) {
+      const int p_raw = p0 + (int)threadIdx.x + 256 * i;
+      const int pw0 = p_raw & ~63;             // the wave's first pixel (p0 is a multiple of 64)
+      if (pw0 >= HW) break;                    // (whole waves past the image leave; a partly covered wave stays whole:
+      const int p = p_raw < HW ? p_raw : HW - 1;  //  its lanes past the image redo the last pixel and help with the stores)
+      const int y = p / W, x = p - y * W;
+      unsigned tap[9];  // LDS byte address of each tap's pixel (inside: it lies in [lo, hi)), or 0: the zeros
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const bool inside = (unsigned)(y + ky - 1) < (unsigned)H && (unsigned)(x + kx - 1) < (unsigned)W;
+          tap[3 * ky + kx] = inside ? zero + mis + (unsigned)(p + (ky - 1) * W + (kx - 1) - lo) * (unsigned)C : 0u;
+        }
+#pragma unroll 1
+      for (int f0 = 0; f0 < K; f0 += KG) {
+        float acc[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[j] = 0.f;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            const unsigned a = tap[3 * ky + kx] + 3u * (unsigned)f0;
+            const unsigned sh = 8 * (a & 3);
+            uint32_t d[NW + 1];
+            d[NW] = 0u;
+#pragma unroll
+            for (int m = 0; m < ND; ++m) d[m] = rc_tile[(a >> 2) + m];
+            float xin[NB];
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+              const uint32_t word = (uint32_t)((((uint64_t)d[j / 4 + 1] << 32) | d[j / 4]) >> sh);
+              xin[j] = (float)((word >> (8 * (j % 4))) & 0xffu);
+            }
+#pragma unroll
+            for (int fr = 0; fr < KG; ++fr)
+#pragma unroll
+              for (int co = 0; co < 3; ++co)
+#pragma unroll
+                for (int ci = 0; ci < 3; ++ci)
+                  rc_fmac(acc[3 * fr + co], w[((co * 3 + ci) * 3 + ky) * 3 + kx], xin[3 * fr + ci]);
+          }
+        }
+        if (stage_off) {
+          // (K == KG: the lane holds its pixel's C floats.)  Stored directly, a wave's store instruction would write NB
+          // floats per lane 4 C bytes apart -- a fraction of every line per instruction.  Through LDS instead, as in the
+          // jitter kernel: the wave's pixels are ONE run of the output, stored in whole 16-byte chunks, lane l the chunks
+          // l, l + 64, ... (dwords where the run is off the 16-byte grid, and for what is left of a short last wave).
+          float* mine = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(rc_tile) + stage_off) + (threadIdx.x >> 6) * (64 * NB);
+          const int lane = threadIdx.x & 63;
+          if (KG == 4) {
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+              *reinterpret_cast<f32x4*>(mine + lane * NB + 4 * u) = f32x4{acc[4 * u], acc[4 * u + 1], acc[4 * u + 2], acc[4 * u + 3]};
+          } else {
+#pragma unroll
+            for (int j = 0; j < NB; ++j) mine[lane * NB + j] = acc[j];
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          const int total = min(64, HW - pw0) * NB;  // floats of this wave inside the image (> 0)
+          float* wave_out = out + ((size_t)b * HW + pw0) * NB;
+          const int nvec = (reinterpret_cast<uintptr_t>(wave_out) & 15) == 0 ? total >> 2 : 0;
+          for (int c = lane; c < nvec; c += 64)
+            *reinterpret_cast<f32x4*>(wave_out + 4 * c) = *reinterpret_cast<const f32x4*>(mine + 4 * c);
+          for (int e = 4 * nvec + lane; e < total; e += 64) wave_out[e] = mine[e];
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the next pixel's floats go where these are being read)
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        } else if (p_raw < HW) {  // stacks of more than 4 frames, frame by frame
+          float* dst = out + ((size_t)b * HW + p) * C + 3 * f0;
+#pragma unroll
+          for (int j = 0; j < NB; ++j) dst[j] = acc[j];
+        }
+      }
+    }
+    __syncthreads();  // (the next sample's tile goes where this one's is still being read)
+  }
+}
+
+// the same on the reference's tensor contract: float NCHW in and out, one grid row per RGB frame (so the weights are
+// uniform over a workgroup here too); the taps come from global memory (L1 / L2 serve the re-reads) -- not the learner path
+__global__ __launch_bounds__(256) void random_conv_nchw_kernel(const float* __restrict__ in,
+                                                                 const float* __restrict__ weights, int n_img, int K, int H,
+                                                                 int W, float* __restrict__ out) {
+  const int HW = H * W;
+  for (int img = blockIdx.y; img < n_img; img += gridDim.y) {
+    float w[81];
+#pragma unroll
+    for (int i = 0; i < 81; ++i) w[i] = weights[(size_t)(img / K) * 81 + i];
+    const float* src = in + (size_t)img * 3 * HW;
+    float* dst = out + (size_t)img * 3 * HW;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+      const int y = p / W, x = p - y * W;
+      float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const bool inside = (unsigned)(y + ky - 1) < (unsigned)H && (unsigned)(x + kx - 1) < (unsigned)W;
+          float xin[3] = {0.f, 0.f, 0.f};
+          if (inside) {
+#pragma unroll
+            for (int ci = 0; ci < 3; ++ci) xin[ci] = src[(size_t)ci * HW + (p + (ky - 1) * W + (kx - 1))];
+          }
+#pragma unroll
+          for (int co = 0; co < 3; ++co)
+#pragma unroll
+            for (int ci = 0; ci < 3; ++ci)
+              acc[co] = fmaf(w[((co * 3 + ci) * 3 + ky) * 3 + kx], xin[ci], acc[co]);
+        }
+      }
+#pragma unroll
+      for (int co = 0; co < 3; ++co) dst[(size_t)co * HW + p] = acc[co];
+    }
+  }
+}
+
 inline int blocks_for(size_t n) {
   size_t b = (n + 255) / 256;
   return (int)(b < 8192 ? b : 8192);
@@ -650,6 +833,42 @@ int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const
   const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
   hipLaunchKernelGGL(cutout_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period, y0, x0,
                      size, rgb, n, H, W, C, groups, vec, out);
+  return curla_launch_status();
+}
+
+int curla_random_conv(const uint8_t* frames, const int64_t* idx, const float* weights, int B, int C, int H, int W,
+                      float* out, void* stream) {
+  CURLA_REQUIRE(frames && weights && out && B > 0 && C > 0 && C % 3 == 0 && H > 0 && W > 0);
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(out)) & 3) == 0 &&
+                (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  const long long frame = (long long)H * W * C;
+  if (frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;  // (pixels and bytes inside a frame are 32-bit quantities in the kernel)
+  // the zeros of the outside taps, the staged run of (RC_TILE + 2 W + 2) pixels, up to 15 bytes in front of it (its place
+  // on the 16-byte grid) and the dwords a read of the last pixel may touch behind it
+  // ... and, for stacks of up to 4 frames, the four waves' output runs of 64 pixels (the stores go through LDS)
+  const int K = C / 3;
+  const long long image = ((C + 16 + 15) / 16 * 16) + (((long long)RC_TILE + 2LL * W + 2) * C + 15 + 16 + 15) / 16 * 16;
+  const long long lds = image + (K <= 4 ? 4LL * 64 * C * 4 : 0);
+  if (lds > 64 * 1024) return CURLA_ERR_UNSUPPORTED;  // (rows of more than ~1700 pixels at C = 12)
+  const unsigned stage_off = K <= 4 ? (unsigned)image : 0u;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)(((long long)H * W + RC_TILE - 1) / RC_TILE), B < 65535 ? B : 65535);
+  if (K == 4) hipLaunchKernelGGL(random_conv_kernel<4>, grid, dim3(256), (size_t)lds, st, frames, idx, weights, B, K, H, W, out, stage_off);
+  else if (K == 3) hipLaunchKernelGGL(random_conv_kernel<3>, grid, dim3(256), (size_t)lds, st, frames, idx, weights, B, K, H, W, out, stage_off);
+  else if (K == 2) hipLaunchKernelGGL(random_conv_kernel<2>, grid, dim3(256), (size_t)lds, st, frames, idx, weights, B, K, H, W, out, stage_off);
+  else hipLaunchKernelGGL(random_conv_kernel<1>, grid, dim3(256), (size_t)lds, st, frames, idx, weights, B, K, H, W, out, stage_off);
+  return curla_launch_status();
+}
+
+int curla_random_conv_nchw(const float* in, const float* weights, int B, int C, int H, int W, float* out, void* stream) {
+  CURLA_REQUIRE(in && weights && out && in != out && B > 0 && C > 0 && C % 3 == 0 && H > 0 && W > 0);
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(out)) & 3) == 0);
+  const long long n_img = (long long)B * (C / 3);
+  if ((long long)H * W * C >= (1LL << 31) - 16 || n_img >= (1LL << 31)) return CURLA_ERR_UNSUPPORTED;
+  const long long gx = ((long long)H * W + 255) / 256;
+  const dim3 grid((unsigned)(gx < 65535 ? gx : 65535), (unsigned)(n_img < 65535 ? n_img : 65535));
+  hipLaunchKernelGGL(random_conv_nchw_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), in, weights, (int)n_img,
+                     C / 3, H, W, out);
   return curla_launch_status();
 }
 

@@ -1343,11 +1343,11 @@ class CurlSacAgent(object):
         captured kernels read on the device: the minibatch's indices / crop offsets (as before), the Philox stream
         position of each policy-noise draw and every optimizer's two step-dependent Adam factors (curla_hip.h: the
         ``rng_dev`` / ``dyn`` arguments); the block's staging kernel is the first node of the graph.
-        A ``ReplayBuffer(..., staged_aug=True)`` with ColorJiggle or NoisyCover is covered the same way: the host draws
+        A ``ReplayBuffer(..., staged_aug=True)`` with ColorJiggle, NoisyCover or RandomConv is covered the same way: the host draws
         the three tensors' parameters per replay (``draw_aug``: torch's CPU generator / NumPy, in the eager order; for
         NoisyCover also the Philox positions of the three in-kernel noise draws, taken from the device generator IN
         FRONT of the two policy draws, as an eager staged update takes them) and writes them into the block behind the
-        indices; the jitter / cover launches are nodes that read the block's device copy.  A ``dedup_frames`` buffer
+        indices; the jitter / cover / convolution launches are nodes that read the block's device copy.  A ``dedup_frames`` buffer
         needs no flag: its gather_stacks launches are nodes that read the frame-id table when the graph runs.
         (ColorJiggle's arithmetic stays PARITY UNPINNED, graphed or not: augmentations.py.)
         ``depth`` graphs are captured per kind, each with its own pinned block, and used in rotation: the host may then
@@ -1369,7 +1369,7 @@ class CurlSacAgent(object):
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
             raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
                              "(covered: RandomCrop, RandomShift, RandomCutout or identity, plain storage with both rings in one "
-                             "allocation or dedup_frames storage; ColorJiggle / NoisyCover "
+                             "allocation or dedup_frames storage; ColorJiggle / NoisyCover / RandomConv "
                              "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
                              "CURLA_STAGE_COPY=1)")
         opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer)

@@ -772,6 +772,34 @@ def noisy_cover_nchw(x, noise, colors, top, bottom, out):
          int(top), int(bottom), B, C, H, W, ptr(_dev(out)), stream())
 
 
+def random_conv(frames, idx, weights, B, out):
+    """RandomConv of B samples (curla_random_conv): frames u8 [rows, H, W, C]; sample b is row idx[b] (idx None: b)
+    through the 3x3, 3 -> 3 channel filter weights[b] (float, 81 per sample: [co][ci][ky][kx]), shared by its C / 3 frames,
+    zero padding 1; out float [B, H, W, C], not clamped."""
+    _, H, W, C = frames.shape
+    _dev(frames, torch.uint8), _dev(out), _dev(weights)
+    if idx is not None:
+        _dev(idx, torch.int64)
+    if tuple(out.shape) != (B, H, W, C) or weights.numel() < 81 * B or (idx is not None and idx.numel() < B):
+        raise _lib.CurlaHipError(f"random_conv: out {tuple(out.shape)} / {weights.numel()} weights do not fit {B} samples "
+                                 f"of {(H, W, C)}")
+    call("curla_random_conv", ptr(frames), ptr(idx), ptr(weights), B, C, H, W, ptr(out), stream())
+
+
+def random_conv_nchw(x, weights, out):
+    """The same on float NCHW tensors (curla_random_conv_nchw).  The kernel reads neighbouring pixels: ``out`` must not
+    share memory with ``x``."""
+    B, C, H, W = x.shape
+    _dev(x), _dev(out), _dev(weights)
+    if tuple(out.shape) != tuple(x.shape) or weights.numel() < 81 * B:
+        raise _lib.CurlaHipError(f"random_conv_nchw: out {tuple(out.shape)} / {weights.numel()} weights do not fit x "
+                                 f"{tuple(x.shape)}")
+    n = 4 * x.numel()
+    if x.data_ptr() < out.data_ptr() + n and out.data_ptr() < x.data_ptr() + n:
+        raise _lib.CurlaHipError("random_conv_nchw: out overlaps x (a 3x3 window reads neighbours: no in-place form)")
+    call("curla_random_conv_nchw", ptr(x), ptr(weights), B, C, H, W, ptr(out), stream())
+
+
 def gather_nhwc(frames, idx, B, out):
     _, H, W, C = frames.shape
     call("curla_gather_nhwc", ptr(frames), ptr(idx), B, C, H, W, ptr(out), stream())

@@ -17,10 +17,10 @@ ONE new frame instead of 2k -- 63.5 KB -> 21 KB per transition at 84x84x9,
 ``add`` (hash, then full comparison), never assumed, so sampled pixels are the
 reference's whatever the caller does.
 
-``staged_aug=True`` (float augmentations) sends the random parameters of a
-minibatch's three tensors along in the index block instead of through a pinned
-block and a copy of their own per tensor, and lets NoisyCover draw its noise
-inside the cover kernel: with it -- and for ``dedup_frames`` without it -- the
+``staged_aug=True`` (float augmentations: ColorJiggle, NoisyCover, RandomConv)
+sends the random parameters of a minibatch's three tensors along in the index
+block instead of through a pinned block and a copy of their own per tensor, and
+lets NoisyCover draw its noise inside the cover kernel: with it -- and for ``dedup_frames`` without it -- the
 minibatch can be a node of a captured update graph (``graph_supported``).
 """
 import collections
@@ -642,8 +642,7 @@ class ReplayBuffer(object):
             for j in range(3):
                 h1, w1 = self.augmentor.draw_offsets(B)
                 offs[2 * j], offs[2 * j + 1] = h1, w1
-        elif not isinstance(self.augmentor, (augmentations.ColorJiggle, augmentations.NoisyCover)) and \
-                type(self.augmentor) is not augmentations.IdentityAugmentation:
+        elif not self._is_float_aug() and type(self.augmentor) is not augmentations.IdentityAugmentation:
             raise NotImplementedError("unknown augmentation object: %r" % (self.augmentor,))
         return idxs, offs
 
@@ -660,6 +659,8 @@ class ReplayBuffer(object):
         aug = self.augmentor
         if staged is not None and isinstance(aug, augmentations.ColorJiggle):
             ops.color_jiggle(ring, idx, staged[0], staged[1], B, out)
+        elif staged is not None and isinstance(aug, augmentations.RandomConv):
+            ops.random_conv(ring, idx, staged, B, out)
         elif staged is not None:
             ops.noisy_cover_rng(ring, idx, aug.std, (0, 0, staged[1]), staged[0], aug.top, aug.bottom, B, out)
         elif isinstance(aug, augmentations.ColorJiggle):
@@ -673,6 +674,12 @@ class ReplayBuffer(object):
             stage[n4:] = order
             d = stage.to(self.device, non_blocking=True)
             ops.color_jiggle(ring, idx, d[:n4].view(torch.float32).view(params.shape), d[n4:], B, out)
+        elif isinstance(aug, augmentations.RandomConv):
+            weights = aug.draw_weights(B)
+            # (one pinned staging block, one asynchronous copy, as above)
+            stage = torch.empty(weights.shape, dtype=torch.float32, pin_memory=self.device.type == "cuda")
+            stage.copy_(weights)
+            ops.random_conv(ring, idx, stage.to(self.device, non_blocking=True), B, out)
         elif isinstance(aug, augmentations.NoisyCover):
             colors = aug.draw_colors()
             noise = torch.randn((B, h, w, c), device=self.device) * aug.std
@@ -682,7 +689,7 @@ class ReplayBuffer(object):
         return out
 
     def _is_float_aug(self):
-        return isinstance(self.augmentor, (augmentations.ColorJiggle, augmentations.NoisyCover))
+        return isinstance(self.augmentor, (augmentations.ColorJiggle, augmentations.NoisyCover, augmentations.RandomConv))
 
     def block_layout(self):
         """Byte offsets inside a minibatch's block -- the ONE place that knows them.  Every block starts with
@@ -690,6 +697,8 @@ class ReplayBuffer(object):
         appends the parameters of the three tensors (obs, next_obs, pos), ``aug_stride`` bytes each:
           ColorJiggle  params float [B k][4] (apply, contrast, saturation, hue) | order int32 [4]
           NoisyCover   colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2]   (8-byte aligned)
+          RandomConv   weights float [B][81] | 4 bytes of padding when B is odd (``aug_weights`` = 324 B, the bytes of the
+                       weights; a key only this layout has -- the stride keeps ``nbytes`` a multiple of 8)
         A RandomCutout appends ``cut`` int32 [2][3B] at ``offs_end``: the packed box sizes of obs | next_obs | pos, then
         their colour words -- contiguous runs for one launch of n = 3B.
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
@@ -702,6 +711,8 @@ class ReplayBuffer(object):
             if isinstance(self.augmentor, augmentations.ColorJiggle):
                 n_par = 16 * B * (self.obs_shape[0] // 3)
                 lay.update(aug=n, aug_stride=n_par + 16, aug_order=n_par)
+            elif isinstance(self.augmentor, augmentations.RandomConv):
+                lay.update(aug=n, aug_stride=(324 * B + 7) // 8 * 8, aug_weights=324 * B)
             else:
                 lay.update(aug=n, aug_stride=32, aug_rng=16)
             n += 3 * lay["aug_stride"]
@@ -726,7 +737,7 @@ class ReplayBuffer(object):
     def draw_aug(self):
         """(staged_aug) The host draws of the three tensors' augmentations, obs then next_obs then pos -- what the
         default path draws one tensor at a time (utils.py:173-182): ``ColorJiggle.draw_params`` from torch's CPU
-        generator, ``NoisyCover.draw_colors`` from NumPy.  NoisyCover also reserves the tensor's ceil(n / 4) Philox
+        generator (``RandomConv.draw_weights`` likewise), ``NoisyCover.draw_colors`` from NumPy.  NoisyCover also reserves the tensor's ceil(n / 4) Philox
         counters by moving the device generator's offset on by 4 ceil(n / 4), as CurlSacAgent._noise does.  None when
         nothing is staged."""
         if not self.staged_aug:
@@ -737,6 +748,8 @@ class ReplayBuffer(object):
         for _ in range(3):
             if isinstance(aug, augmentations.ColorJiggle):
                 out.append(aug.draw_params(B * (c // 3)))
+            elif isinstance(aug, augmentations.RandomConv):
+                out.append(aug.draw_weights(B))
             else:
                 colors = aug.draw_colors()
                 gen = self._noise_generator()
@@ -754,6 +767,8 @@ class ReplayBuffer(object):
                 params, order = item
                 host[a:a + lay["aug_order"]].view(torch.float32).copy_(params.reshape(-1))
                 host[a + lay["aug_order"]:a + lay["aug_stride"]].view(torch.int32).copy_(order)
+            elif lay.get("aug_weights") is not None:
+                host[a:a + lay["aug_weights"]].view(torch.float32).copy_(item.reshape(-1))
             else:
                 colors, seed, ctr = item
                 host[a:a + 12].view(torch.float32).copy_(torch.tensor([float(v) for v in colors]))
@@ -762,12 +777,15 @@ class ReplayBuffer(object):
 
     def _aug_args(self, dev, j):
         """What the augmentation kernel of tensor j reads from the device copy ``dev`` of a block: ColorJiggle
-        (params [B k, 4], order [4]) as tensors, NoisyCover (colours, (seed, counter)) as device addresses."""
+        (params [B k, 4], order [4]) as tensors, RandomConv its weights [B, 81] as a tensor, NoisyCover (colours,
+        (seed, counter)) as device addresses."""
         lay = self._layout
         a = lay["aug"] + j * lay["aug_stride"]
         if lay["aug_order"] is not None:
             return (dev[a:a + lay["aug_order"]].view(torch.float32).view(-1, 4),
                     dev[a + lay["aug_order"]:a + lay["aug_stride"]].view(torch.int32))
+        if lay.get("aug_weights") is not None:
+            return dev[a:a + lay["aug_weights"]].view(torch.float32).view(-1, 81)
         return dev.data_ptr() + a, dev.data_ptr() + a + lay["aug_rng"]
 
     def _fill_index_block(self, host, idxs, offs):
@@ -929,7 +947,7 @@ class ReplayBuffer(object):
         slot (sample_cpc_refs; ``guard`` from _upload_indices) or a captured graph's (graph_refs; ``guard`` None), whose
         launches then write to fixed addresses: the
         gathers of the frame store (_sources), then by augmentation ring handles (nothing is launched: the first conv
-        layer gathers and crops), the shift / cutout launch(es), or the three jitter / cover launches."""
+        layer gathers and crops), the shift / cutout launch(es), or the three jitter / cover / convolution launches."""
         B = self.batch_size
         src = self._sources(slot)
         both, idx2, tensors, off = src.both, src.idx2, src.tensors, src.off
@@ -970,7 +988,7 @@ class ReplayBuffer(object):
     def graph_supported(self):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
         ones (RandomCrop / RandomShift / RandomCutout / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
-        are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover constructed with
+        are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover / RandomConv constructed with
         ``staged_aug=True`` (either storage).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
         through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""
         if self.device.type != "cuda" or self._h_index_dev is None:
@@ -1040,7 +1058,7 @@ class ReplayBuffer(object):
         the transitions' scalars), for the de-duplicated store the two gather_stacks launches (they read ``_fid`` when
         the graph is replayed), for RandomShift / RandomCutout the shift / cutout launch (it reads its offsets, boxes and
         colours from the device block), for a
-        staged float augmentation the three jitter / cover launches (they read their
+        staged float augmentation the three jitter / cover / convolution launches (they read their
         parameters from the device block), and the sample_cpc 6-tuple with handles into the slot's buffers.  Nothing
         here draws a random number."""
         g = self.graph_block(slot)

@@ -486,6 +486,24 @@ int curla_color_jiggle_nchw(const float* in, const float* params, const int32_t*
                             float* out, void* stream);
 int curla_noisy_cover_nchw(const float* in, const float* noise, float c0, float c1, float c2, int top, int bottom,
                            int B, int C, int H, int W, float* out, void* stream);
+/* RandomConv (beyond the reference: the random convolution of RAD and of Lee et al., "Network Randomization").  Every
+ * sample's k = C / 3 RGB frames go through ONE 3x3, 3 -> 3 channel filter weights[b][co][ci][ky][kx] (float [B][81], 4-byte
+ * aligned, device memory -- read when the kernel RUNS, so a captured hipGraph is replayed with new values):
+ *   out[b][y][x][3 f + co] = sum over ci, ky, kx of  w[co][ci][ky][kx] * in[b][y + ky - 1][x + kx - 1][3 f + ci]
+ * cross-correlation (no flip), `in` = 0 outside the frame, the stored bytes as floats in [0,255]; the result is NOT clamped.
+ * Each output is one float32 fused-multiply-add chain from 0 over (ky, kx, ci), ky slowest: a filter of zeros and ones
+ * returns bytes exactly, and the two forms below agree bit for bit.  In general |out - exact| <= g sum |w_i| |x_i| with
+ * g = 27 u / (1 - 27 u), u = 2^-24.
+ * curla_random_conv: uint8 NHWC ring rows idx[b] (idx == NULL: rows 0..B-1), as curla_color_jiggle takes them, to float
+ * NHWC [B][H][W][C]; nothing outside the B frames is read.  Frames of 2^31 - 16 bytes or more, and rows so long that
+ * the LDS image of (1024 + 2 W + 2) C bytes and the staged output of 1024 C bytes exceed 64 KiB (W > ~1700 at C = 12):
+ * CURLA_ERR_UNSUPPORTED.
+ * curla_random_conv_nchw: the reference's tensor contract, float NCHW in and out (RandomConv.training_augmentation).
+ * Unlike the jitter this kernel reads a pixel's NEIGHBOURS: `out` must NOT alias or overlap `in` (in == out:
+ * CURLA_ERR_ARG; a partial overlap is not detected).  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_random_conv(const uint8_t* frames, const int64_t* idx, const float* weights, int B, int C, int H, int W,
+                      float* out, void* stream);
+int curla_random_conv_nchw(const float* in, const float* weights, int B, int C, int H, int W, float* out, void* stream);
 
 /* ---- replay ring helpers ---- */
 /* float/uint8 NCHW crops exactly as sample_cpc returns them (utils.py:151-166) */
