@@ -165,6 +165,65 @@ class RandomCutout(IdentityAugmentation):
         return self.cut(image_batch, *self.draw_boxes(image_batch.shape[0]))
 
 
+class RandomTranslate(IdentityAugmentation):
+    """Beyond the reference: the translate of RAD.  The H x W frame is placed at a random position (ty, tx) on a black
+    canvas of ``output_shape = (Ho, Wo)`` (``None``: (H + 8, W + 8), a margin of 4 per side like RandomShift's default
+    pad), one draw per sample shared by all channels of the stack:
+        out[c][y][x] = in[c][y - ty][x - tx]   if 0 <= y - ty < H and 0 <= x - tx < W,   0 otherwise
+    with ty in [0, Ho - H] and tx in [0, Wo - W].  Every source pixel is kept and none is invented; the minibatch frame is
+    LARGER than the stored frame, and the encoder is built for (C, Ho, Wo).  Evaluation centres the frame on the canvas.
+    A clean restatement of RAD's ``random_translate`` / ``center_translate``, not a port.  On the learner path the pixels
+    are moved by ``curla_translate_u8`` and stay uint8 (ReplayBuffer); the offsets are drawn on the host from NumPy's
+    global stream, like RandomCrop's."""
+
+    def __init__(self, input_shape, output_shape=None):
+        for name, shape in (("input_shape", input_shape), ("output_shape", output_shape)):
+            if shape is None:
+                continue
+            if len(shape) != 2:
+                raise ValueError("RandomTranslate: %s must be 2D, got %r" % (name, shape))
+            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in shape):
+                raise ValueError("RandomTranslate: %s must hold ints, got %r" % (name, shape))
+        if output_shape is None:
+            output_shape = tuple(x + 8 for x in input_shape)
+        super().__init__(tuple(int(x) for x in input_shape))
+        self.output_shape = tuple(int(x) for x in output_shape)
+        if self.output_shape[0] < self.input_shape[0] or self.output_shape[1] < self.input_shape[1]:
+            raise ValueError("RandomTranslate: the canvas %r must be no smaller than the frame %r"
+                             % (self.output_shape, self.input_shape))
+
+    def draw_offsets(self, n):
+        """Two RNG draws, ty then tx, in [0, Ho - H] and [0, Wo - W] (in the style of RandomShift.draw_offsets)."""
+        ty = np.random.randint(0, self.output_shape[0] - self.input_shape[0] + 1, n)
+        tx = np.random.randint(0, self.output_shape[1] - self.input_shape[1] + 1, n)
+        return ty, tx
+
+    def translate(self, image_batch, ty, tx):
+        """A (B, C, H, W) array placed at given per-sample offsets on zero canvases (B, C, Ho, Wo), on the host."""
+        h, w = image_batch.shape[2:]
+        out = np.zeros(image_batch.shape[:2] + self.output_shape, dtype=image_batch.dtype)
+        for b in range(image_batch.shape[0]):
+            out[b, :, int(ty[b]):int(ty[b]) + h, int(tx[b]):int(tx[b]) + w] = image_batch[b]
+        return out
+
+    def training_augmentation(self, image_batch):
+        """Host-side translate of a (B, C, H, W) NumPy array, for callers outside the fused path."""
+        image_batch = np.asarray(image_batch)
+        ty, tx = self.draw_offsets(image_batch.shape[0])
+        return self.translate(image_batch, ty, tx)
+
+    def evaluation_augmentation(self, image):
+        """A (C, H, W) image centred on a zero canvas (C, Ho, Wo) of its dtype (an odd margin leaves the larger part
+        below / to the right); an image that already has the canvas size is returned as it is."""
+        if tuple(image.shape[-2:]) == self.output_shape:
+            return image
+        h, w = image.shape[-2:]
+        top, left = (self.output_shape[0] - h) // 2, (self.output_shape[1] - w) // 2
+        out = np.zeros(tuple(image.shape[:-2]) + self.output_shape, dtype=image.dtype)
+        out[..., top:top + h, left:left + w] = image
+        return out
+
+
 class RandomConv(IdentityAugmentation):
     """Beyond the reference: the random convolution of RAD (``random_convolution``) and of Lee et al., "Network
     Randomization".  Every sample's RGB frames go through one freshly drawn 3x3, 3 -> 3 channel filter, shared by all
@@ -309,8 +368,8 @@ class NoisyCover(IdentityAugmentation):
 
 def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30, conv_p=1.0):
     """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding), 'cutout' / 'cutout_color' (``min_cut``,
-    ``max_cut``: the range of a box side) and 'random_conv' (``conv_p``: the probability that a sample is convolved) --
-    all four beyond the reference."""
+    ``max_cut``: the range of a box side), 'random_conv' (``conv_p``: the probability that a sample is convolved) and
+    'translate' (``output_shape``: its canvas, None = 8 pixels more per side length) -- all five beyond the reference."""
     print(f'CHOSEN AUGMENTATION: {name}')
     if name == 'identity':
         return IdentityAugmentation(input_shape)
@@ -326,4 +385,6 @@ def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, m
         return RandomCutout(input_shape, min_cut, max_cut, color=name == 'cutout_color')
     if name == 'random_conv':
         return RandomConv(input_shape, conv_p)
+    if name == 'translate':
+        return RandomTranslate(input_shape, output_shape)
     raise ValueError('augmentation is not supported: %s' % name)

@@ -550,6 +550,156 @@ __global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, c
   }
 }
 
+// ---- RandomTranslate (beyond the reference: RAD's translate) ----
+// out[s][y][x][c] = frames[row(s)][y - ty][x - tx][c] where 0 <= y - ty < H and 0 <= x - tx < W, 0 elsewhere: the H x W
+// frame placed at (ty, tx) on a black Ho x Wo canvas; uint8 NHWC in and out, all channels of a stack share the offset
+// (clamped into [0, Ho - H] x [0, Wo - W]).  The first of these byte movers whose output frame is larger than its source
+// frame: a thread owns 16 consecutive OUTPUT bytes of a sample (one 16-byte store), grid row = sample.  In output order
+// the bytes of an output row that lie inside the image are ONE run, bytes [tx C, tx C + W C) of the row, and along such a
+// run the source address steps with the output address.  So per output row that a group touches (two at most where rows
+// are no shorter than a group) there is at most one run [lo, hi) of the group's bytes, with group byte e = source-frame
+// byte base + e: ONE unaligned 16-byte load at base, masked to [lo, hi).  The three kinds of groups are then one code:
+//   margin  no run: a store of zeros, nothing is loaded;
+//   inside  one run [0, 16): the load is stored as it is;
+//   mixed   (crosses the image's left / right edge or straddles two output rows) one or two runs: the loads are masked
+//           and OR-ed in registers -- no byte-wise memory access (in the shift kernel the byte loads of such groups set
+//           the time).
+// `base` may lie up to 15 bytes in front of the source frame (the image's first row behind a left margin) or less than 16
+// bytes in front of its end: the load address is clamped into [0, frame - 16] and the 16 bytes are shifted by the
+// difference, so nothing outside the source frame is read -- ring row 0 has nothing in front of it, and the slack behind
+// a ring is not relied on.  Where the canvas is no wider than the frame (Wo == W) the runs of two rows are one run of the
+// source and take one load.  Groups that touch three or more rows (rows shorter than a group) walk their rows in a loop
+// with the same run arithmetic.  Byte-wise loads and stores are left to output frames of no whole number of groups, an
+// `out` off the 16-byte grid and source frames shorter than a group (vec == false), as in the shift and the cutout.
+typedef unsigned __int128 u128;
+
+struct TrGeom {
+  int H, ty, txb;           // image rows [ty, ty + H) of the canvas, image columns in bytes of an output row from txb on
+  int srb, orb;             // bytes of a source row / of an output row
+  unsigned sframe, oframe;  // bytes of a source frame / of an output frame
+};
+
+// The run of output row yy inside a group: `rel` = the group byte at which row yy starts (negative: the row started in
+// front of the group).  Group bytes [lo, hi) are the row's bytes inside the image, group byte e is source-frame byte
+// base + e.  False: row yy has no image byte in the group.
+__device__ __forceinline__ bool tr_run(const TrGeom& q, int yy, int rel, int& lo, int& hi, int& base) {
+  lo = max(rel + q.txb, 0), hi = min(rel + q.txb + q.srb, 16);
+  base = (yy - q.ty) * q.srb - rel - q.txb;
+  return yy >= q.ty && yy < q.ty + q.H && lo < hi;
+}
+
+// The 16-byte load of a run, at its address clamped into the source frame; returns lo | hi << 8 | (d + 16) << 16 (never 0:
+// hi >= 1), d = the bytes the load sits in front of (d > 0) or behind (d < 0) `base`.  Every byte of [lo, hi) is in the
+// load: base + e is a byte of the frame, and the clamp moves the address only as far as the frame's ends.
+__device__ __forceinline__ int tr_load(const uint8_t* src, const TrGeom& q, int lo, int hi, int base, u32x4& v) {
+  const int a = min(max(base, 0), (int)q.sframe - 16);
+  __builtin_memcpy(&v, src + a, 16);  // one unaligned global_load_dwordx4
+  return lo | (hi << 8) | ((base - a + 16) << 16);
+}
+
+// the loaded bytes moved to their places in the group (only the runs at the two ends of a frame are shifted), all
+// others zero
+__device__ __forceinline__ u128 tr_place(u32x4 v, int meta) {
+  const int lo = meta & 0xff, hi = (meta >> 8) & 0xff, d = (meta >> 16) - 16;
+  u128 x = __builtin_bit_cast(u128, v);
+  if (d > 0) x >>= 8 * d;
+  if (d < 0) x <<= -8 * d;
+  if (hi - lo < 16) x &= (~(u128)0 >> (8 * (16 - (hi - lo)))) << (8 * lo);
+  return x;
+}
+
+// a group that touches three or more output rows (rows shorter than a group): its rows one by one
+__device__ __forceinline__ u128 tr_group_rows(const uint8_t* src, const TrGeom& q, unsigned r) {
+  const unsigned y = r / (unsigned)q.orb;
+  u128 o = 0;
+  int yy = (int)y;
+  for (int rel = (int)(y * (unsigned)q.orb) - (int)r; rel < 16; rel += q.orb, ++yy) {
+    int lo, hi, base;
+    if (tr_run(q, yy, rel, lo, hi, base)) {
+      u32x4 v;
+      const int meta = tr_load(src, q, lo, hi, base, v);
+      o |= tr_place(v, meta);
+    }
+  }
+  return o;
+}
+
+// one (possibly short) group byte by byte: (row, byte in row) are stepped, not divided
+__device__ __forceinline__ void tr_group_bytes(const uint8_t* src, uint8_t* dst, const TrGeom& q, unsigned r) {
+  const unsigned cnt = min(16u, q.oframe - r);
+  const unsigned y = r / (unsigned)q.orb;
+  int yy = (int)y, xb = (int)(r - y * (unsigned)q.orb);
+  for (unsigned e = 0; e < cnt; ++e) {
+    const bool inside = yy >= q.ty && yy < q.ty + q.H && xb >= q.txb && xb < q.txb + q.srb;
+    dst[r + e] = inside ? src[(size_t)(yy - q.ty) * q.srb + (unsigned)(xb - q.txb)] : (uint8_t)0;
+    if (++xb == q.orb) xb = 0, ++yy;
+  }
+}
+
+constexpr int TR_UNROLL = 4;  // groups per thread and trip, their loads issued before the first store (as SHIFT_UNROLL)
+
+__global__ __launch_bounds__(256) void translate_u8_kernel(const uint8_t* frames, const int64_t* idx, int period,
+                                                             const int32_t* ty, const int32_t* tx, int n, int H, int W,
+                                                             int C, int Ho, int Wo, unsigned groups, bool vec,
+                                                             uint8_t* out) {
+  TrGeom q;
+  q.H = H, q.srb = W * C, q.orb = Wo * C, q.sframe = (unsigned)H * q.srb, q.oframe = (unsigned)Ho * q.orb;
+  const bool flat = q.srb == q.orb;  // no margin left or right: the image rows follow one another in the output too
+  const unsigned stride = gridDim.x * 256;
+  for (int s = blockIdx.y; s < n; s += gridDim.y) {
+    const int p = s % period;
+    const int64_t row = idx ? idx[p] : (int64_t)p;
+    // (offsets outside their ranges are clamped into them: whatever the block holds, the image lies on the canvas)
+    q.ty = min(max(ty[s], 0), Ho - H), q.txb = min(max(tx[s], 0), Wo - W) * C;
+    const uint8_t* src = frames + (size_t)row * q.sframe;
+    uint8_t* dst = out + (size_t)s * q.oframe;
+    if (!vec) {
+      for (unsigned g = blockIdx.x * 256 + threadIdx.x; g < groups; g += stride) tr_group_bytes(src, dst, q, 16 * g);
+      continue;
+    }
+    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += TR_UNROLL * stride) {
+      u32x4 v[TR_UNROLL][2];
+      int meta[TR_UNROLL][2];  // of the runs of the group's first and second row; 0: no run
+      bool rows3[TR_UNROLL];   // the group touches three or more rows
+#pragma unroll
+      for (int u = 0; u < TR_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        meta[u][0] = meta[u][1] = 0, rows3[u] = false;
+        v[u][0] = v[u][1] = u32x4{0u, 0u, 0u, 0u};
+        if (g < groups) {
+          const unsigned r = 16 * g;
+          const unsigned y = r / (unsigned)q.orb;
+          const int xb = (int)(r - y * (unsigned)q.orb);
+          if (xb + 15 >= 2 * q.orb) {
+            rows3[u] = true;
+          } else {
+            int lo0, hi0, b0, lo1, hi1, b1;
+            const bool r0 = tr_run(q, (int)y, -xb, lo0, hi0, b0);
+            bool r1 = tr_run(q, (int)y + 1, q.orb - xb, lo1, hi1, b1);  // (a group inside one row: lo1 >= 16, no run)
+            if (flat && r0 && r1) hi0 = hi1, r1 = false;                // b1 == b0, lo1 == hi0: one run of the source
+            if (r0) meta[u][0] = tr_load(src, q, lo0, hi0, b0, v[u][0]);
+            if (r1) meta[u][1] = tr_load(src, q, lo1, hi1, b1, v[u][1]);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < TR_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        if (g < groups) {
+          u128 o = 0;
+          if (rows3[u]) {
+            o = tr_group_rows(src, q, 16 * g);
+          } else {
+            if (meta[u][0]) o = tr_place(v[u][0], meta[u][0]);
+            if (meta[u][1]) o |= tr_place(v[u][1], meta[u][1]);
+          }
+          *reinterpret_cast<u32x4*>(dst + 16 * g) = __builtin_bit_cast(u32x4, o);
+        }
+      }
+    }
+  }
+}
+
 // ---- RandomConv (beyond the reference: the random convolution of RAD / "Network Randomization") ----
 // out[s][y][x][3 f + co] = sum over ci, ky, kx of w[s][co][ci][ky][kx] * in[row(s)][y + ky - 1][x + kx - 1][3 f + ci], `in`
 // zero outside the frame; one weight set per sample, shared by its frames; uint8 NHWC in, float NHWC out, not clamped.
@@ -833,6 +983,25 @@ int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const
   const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
   hipLaunchKernelGGL(cutout_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period, y0, x0,
                      size, rgb, n, H, W, C, groups, vec, out);
+  return curla_launch_status();
+}
+
+int curla_translate_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* ty, const int32_t* tx, int n,
+                       int C, int H, int W, int Ho, int Wo, uint8_t* out, void* stream) {
+  CURLA_REQUIRE(frames && ty && tx && out && n > 0 && period > 0 && C > 0 && H > 0 && W > 0 && Ho >= H && Wo >= W);
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(ty) | reinterpret_cast<uintptr_t>(tx)) & 3) == 0 &&
+                (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  const long long sframe = (long long)H * W * C, oframe = (long long)Ho * Wo * C;
+  // (bytes inside an output frame, hence inside a source frame and the byte offset tx C, are 32-bit quantities in the
+  // kernel, and so is twice an output row: the run arithmetic reaches 2 Wo C)
+  if (oframe >= (1LL << 31) - 16 || (long long)Wo * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;
+  const bool vec = oframe % 16 == 0 && aligned16(out) && sframe >= 16;  // (a load of 16 bytes must fit the source frame)
+  const unsigned groups = (unsigned)((oframe + 15) / 16);
+  const unsigned per_block = vec ? 256 * TR_UNROLL : 256;
+  const unsigned gx = (groups + per_block - 1) / per_block;
+  const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
+  hipLaunchKernelGGL(translate_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period, ty,
+                     tx, n, H, W, C, Ho, Wo, groups, vec, out);
   return curla_launch_status();
 }
 

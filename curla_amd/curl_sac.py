@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import autograd, ops
-from .augmentations import RandomCrop
+from .augmentations import RandomCrop, RandomTranslate
 from .encoder import CNNEncoder
 from .ops import ObsRef
 from .optim import FlatAdam
@@ -769,14 +769,31 @@ class CurlSacAgent(object):
     def _act_windows(self):
         """Frame sizes the batched acting calls take -> origin of the window the encoder reads: its own size (the
         whole frame) and, under a RandomCrop, the crop's input size (the centre window of
-        RandomCrop.evaluation_augmentation, augmentations.py:26-45)."""
+        RandomCrop.evaluation_augmentation, augmentations.py:26-45).  Under a RandomTranslate also the translate's input
+        size, with None for an origin: such frames are no window of anything, they are centred on a black canvas as
+        RandomTranslate.evaluation_augmentation does (_act_centred), whatever the margins (0 and 1 included)."""
         h, w = self.image_shape
         windows = {(h, w): (0, 0)}
         aug = self.augmentor
-        if isinstance(aug, RandomCrop) and tuple(aug.output_shape) == (h, w):
+        if isinstance(aug, (RandomCrop, RandomTranslate)) and tuple(aug.output_shape) == (h, w):
             H, W = aug.input_shape
-            windows.setdefault((H, W), ((H - h) // 2, (W - w) // 2))
+            windows.setdefault((H, W), ((H - h) // 2, (W - w) // 2) if isinstance(aug, RandomCrop) else None)
         return windows
+
+    def _act_centred(self, x, shape):
+        """(RandomTranslate) N frames of the translate's input size, each centred on a zero canvas of the encoder's size
+        exactly as ``evaluation_augmentation`` centres one: host arrays with NumPy, tensors with torch where they are.
+        Not a hot path: acting on frames of the encoder's own size stages them as before."""
+        N, C, H, W = shape
+        h, w = self.image_shape
+        top, left = (h - H) // 2, (w - W) // 2
+        if torch.is_tensor(x):
+            out = torch.zeros((N, C, h, w), dtype=x.dtype, device=x.device)
+        else:
+            x = np.stack(x) if isinstance(x, list) else x
+            out = np.zeros((N, C, h, w), dtype=x.dtype)
+        out[:, :, top:top + H, left:left + W] = x
+        return out, (N, C, h, w), (0, 0)
 
     def _act_batch_args(self, obs, noise):
         """Argument checks of select_actions / sample_actions (they come before anything touches the device).
@@ -805,7 +822,10 @@ class CurlSacAgent(object):
         if self.device.type != "cuda" and _lib._trace_hook is None:
             raise RuntimeError("CurlSacAgent.select_actions / sample_actions need a CUDA/HIP device: the acting path "
                                "has no CPU fallback")
-        return x, shape, windows[shape[2:]]
+        window = windows[shape[2:]]
+        if window is None:
+            return self._act_centred(x, shape)
+        return x, shape, window
 
     def _stage_obs_batch(self, x, shape, window):
         """N observations for the actor.  uint8 frames go planar, as they are, into a pinned block (one contiguous
@@ -861,7 +881,8 @@ class CurlSacAgent(object):
         means.  ``obs``: a uint8 array (N, C, H, W), a sequence of N uint8 (C, H, W) frames or a uint8 CUDA tensor
         (the fast route, _stage_obs_batch); anything else (float arrays) goes the reference's float route.  (H, W) is
         the encoder's input size or -- under a RandomCrop -- the crop's input size, whose centre window is then cut
-        inside the staging launch; any other size raises ValueError.  Returns a NumPy array (one device -> host
+        inside the staging launch, or -- under a RandomTranslate -- the translate's input size, which is then centred on
+        a black canvas like ``evaluation_augmentation`` does; any other size raises ValueError.  Returns a NumPy array (one device -> host
         copy, one synchronisation), or with ``as_tensor`` the device tensor without synchronising; that tensor is
         storage of its own, which later acting calls do not touch.  Builds no autograd graph, draws no random
         numbers, and leaves the update's workspaces, index blocks and captured graphs alone."""
@@ -1368,7 +1389,7 @@ class CurlSacAgent(object):
             raise RuntimeError("update graphs need the HIP device")
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
             raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
-                             "(covered: RandomCrop, RandomShift, RandomCutout or identity, plain storage with both rings in one "
+                             "(covered: RandomCrop, RandomShift, RandomCutout, RandomTranslate or identity, plain storage with both rings in one "
                              "allocation or dedup_frames storage; ColorJiggle / NoisyCover / RandomConv "
                              "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
                              "CURLA_STAGE_COPY=1)")

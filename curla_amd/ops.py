@@ -733,6 +733,22 @@ def cutout_u8(frames, idx, period, y0, x0, size, rgb, n, out):
          ptr(out), stream())
 
 
+def translate_u8(frames, idx, period, ty, tx, n, out):
+    """RandomTranslate of n samples (curla_translate_u8): frames u8 [rows, H, W, C]; sample s is row idx[s % period] (idx
+    None: s % period) placed at (ty[s], tx[s]) (int32 [n]; clamped onto the canvas by the kernel) on a black canvas; out
+    u8 [n, Ho, Wo, C] with Ho >= H and Wo >= W."""
+    _, H, W, C = frames.shape
+    _dev(frames, torch.uint8), _dev(out, torch.uint8), _dev(ty, torch.int32), _dev(tx, torch.int32)
+    if idx is not None:
+        _dev(idx, torch.int64)
+    if out.dim() != 4 or out.shape[0] != n or out.shape[3] != C or out.shape[1] < H or out.shape[2] < W or \
+            ty.numel() < n or tx.numel() < n or (idx is not None and idx.numel() < min(period, n)):
+        raise _lib.CurlaHipError(f"translate_u8: out {tuple(out.shape)} / {ty.numel()}, {tx.numel()} offsets do not fit "
+                                 f"{n} samples of {(H, W, C)} on a canvas no smaller than the frame")
+    call("curla_translate_u8", ptr(frames), ptr(idx), int(period), ptr(ty), ptr(tx), int(n), C, H, W, int(out.shape[1]),
+         int(out.shape[2]), ptr(out), stream())
+
+
 def nhwc_to_nchw(x, out):
     B, H, W, C = x.shape
     call("curla_nhwc_to_nchw", ptr(x), ptr(out), B, H, W, C, stream())

@@ -263,8 +263,8 @@ class ReplayBuffer(object):
                 + self.N_SAMPLE_SLOTS * 2 * batch_size * frame
         else:
             total_bytes = 2 * capacity * frame + capacity * (4 * A + 8)
-        if self._has_scratch():  # the shifted / cut minibatches (obs | next_obs | pos) of the sample slots
-            total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * frame + 32)
+        if self._has_scratch():  # the shifted / cut / translated minibatches (obs | next_obs | pos) of the sample slots
+            total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * self._scratch_frame() + 32)
         if self.n_step > 1:  # the continuity flags
             total_bytes += capacity
         if self.device.type == "cuda":
@@ -362,17 +362,19 @@ class ReplayBuffer(object):
             # (obs stacks | next_obs stacks) of a minibatch, contiguous: also one [2B] ring for ObsRef.pair
             self._mb_store = torch.zeros((self.N_SAMPLE_SLOTS, 2 * B * frame + 32), dtype=torch.uint8, device=dev)
         if self._has_scratch():
-            # RandomShift / RandomCutout: a minibatch's shifted (cut) frames, uint8 [3B][H][W][C] = (obs | next_obs | pos)
-            # + 32 B of slack like a ring, per sample slot (each slot starts on a 256-byte boundary: the shift / cutout
+            # RandomShift / RandomCutout / RandomTranslate: a minibatch's shifted (cut, translated) frames, uint8
+            # [3B][Ho][Wo][C] = (obs | next_obs | pos) -- (Ho, Wo) = the augmentor's output_shape, (H, W) but for a
+            # translate -- + 32 B of slack like a ring, per sample slot (each slot starts on a 256-byte boundary: the
             # kernel then stores 16 bytes per lane).  Downstream it IS a ring: rows 0..3B-1, zero crop offsets -- static
-            # tensors.  (Both augmentations use the names the shift gave the scratch.)
-            stride = (3 * B * frame + 32 + 255) // 256 * 256
+            # tensors.  (All three augmentations use the names the shift gave the scratch.)
+            stride = (3 * B * self._scratch_frame() + 32 + 255) // 256 * 256
             self._shift_store = torch.zeros((self.N_SAMPLE_SLOTS, stride), dtype=torch.uint8, device=dev)
             self._shift_rows = torch.arange(3 * B, dtype=torch.int64, device=dev)
             self._shift_zero = torch.zeros(3 * B, dtype=torch.int32, device=dev)
         # A slot = the buffers ONE minibatch is assembled in (_assemble): ``dev`` the device block, ``scal`` the
         # transitions' scalars and ``scalars`` its (actions, rewards, not_dones) views, ``mb_u8`` the gathered stacks +
-        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the shifted / cut frames (RandomShift, RandomCutout), ``both_f32`` / ``pos_f32``
+        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the shifted / cut / translated frames (RandomShift, RandomCutout,
+        # RandomTranslate), ``both_f32`` / ``pos_f32``
         # the float tensors (absent here: allocated per call).  The rotating slots are views of the stores above; a
         # captured update graph has slots of its own with the same keys (graph_block).
         ar2 = torch.arange(2 * B, dtype=torch.int64, device=dev) if self.dedup_frames else None
@@ -614,16 +616,26 @@ class ReplayBuffer(object):
     def _is_cutout(self):
         return isinstance(self.augmentor, augmentations.RandomCutout)
 
+    def _is_translate(self):
+        return isinstance(self.augmentor, augmentations.RandomTranslate)
+
     def _has_scratch(self):
         """The augmentations whose minibatch is written, still uint8, into a scratch of the sample slot by one launch
         behind the staging launch (_scratch_aug) and read from there as an ordinary ring."""
-        return self._is_shift() or self._is_cutout()
+        return self._is_shift() or self._is_cutout() or self._is_translate()
+
+    def _scratch_frame(self):
+        """Bytes of a frame of the scratch: a MINIBATCH frame (C, Ho, Wo), (Ho, Wo) the augmentor's output_shape.  Only a
+        RandomTranslate makes it differ from a stored frame (``_frame``: the rings, add, save / load, the frame store)."""
+        oh, ow = self.augmentor.output_shape
+        return self.obs_shape[0] * oh * ow
 
     def draw_indices(self):
         """Host RNG draws of sample_cpc, in the reference's order (utils.py:147 then
         augmentations.py:66-67 for obs, next_obs, pos).  Returns (idxs, offsets) with
         offsets an int32 array [6, B] = h1/w1 of obs, next_obs, pos (zeros when the
-        augmentation is neither RandomCrop nor RandomShift, whose (dy, dx) pairs take the same places).  A RandomCutout
+        augmentation is neither RandomCrop nor RandomShift / RandomTranslate, whose (dy, dx) / (ty, tx) pairs take the
+        same places).  A RandomCutout
         returns int32 [12, B]: rows 2j, 2j + 1 = (y0, x0) of tensor j's boxes in those places, rows 6 + 2j, 6 + 2j + 1 its
         packed sizes bh | bw << 16 and colours r | g << 8 | b << 16 (0 for the black cutout), drawn by ``draw_boxes(B)``
         for obs, next_obs, pos."""
@@ -638,7 +650,7 @@ class ReplayBuffer(object):
                     offs[6 + 2 * j + 1] = rgb[:, 0] | (rgb[:, 1] << 8) | (rgb[:, 2] << 16)
             return idxs, offs
         offs = np.zeros((6, B), dtype=np.int32)
-        if self._is_crop() or self._is_shift():
+        if self._is_crop() or self._is_shift() or self._is_translate():
             for j in range(3):
                 h1, w1 = self.augmentor.draw_offsets(B)
                 offs[2 * j], offs[2 * j + 1] = h1, w1
@@ -881,7 +893,7 @@ class ReplayBuffer(object):
           both     the ring of obs frames then next_obs frames in which (obs | next_obs) is ONE run of 2B rows ``idx2``
                    (None: rows 0..2B-1) with offsets ``h2`` / ``w2``; None when the rings are two allocations
           dy, dx   the h rows of obs, next_obs, pos as one int32 run of 3B, and the w rows (RandomShift's offsets,
-                   RandomCutout's y0 / x0)
+                   RandomCutout's y0 / x0, RandomTranslate's ty / tx)
           size, rgb  the packed box sizes and the colour words of obs, next_obs, pos, 3B each (RandomCutout; else None)
         Plain storage reads the rings at the sampled rows.  The frame store first assembles the k frames of every
         sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor)."""
@@ -908,14 +920,18 @@ class ReplayBuffer(object):
                         off, d32[:3 * B], d32[3 * B:], size, rgb)
 
     def _scratch_aug(self, slot, src):
-        """RandomShift / RandomCutout: the frames of a minibatch (``src``: _sources), shifted by (dy, dx) resp. with the
-        boxes painted, into the slot's scratch as obs | next_obs | pos; returns the [3B][H][W][C] view.  With ``both``
-        ONE launch, pos reading the obs rows again (period 2B); with the rings in two allocations one launch per
-        tensor."""
+        """RandomShift / RandomCutout / RandomTranslate: the frames of a minibatch (``src``: _sources), shifted by (dy, dx)
+        resp. with the boxes painted resp. placed at (ty, tx) on the canvas, into the slot's scratch as obs | next_obs |
+        pos; returns the [3B][Ho][Wo][C] view ((Ho, Wo) = output_shape: (H, W) but for a translate).  With ``both`` ONE
+        launch, pos reading the obs rows again (period 2B); with the rings in two allocations one launch per tensor."""
         B = self.batch_size
-        c, h, w = self.obs_shape
-        out = slot["shift_u8"][:3 * B * self._frame].view(3 * B, h, w, c)
-        if self._is_shift():
+        c = self.obs_shape[0]
+        oh, ow = self.augmentor.output_shape
+        out = slot["shift_u8"][:3 * B * self._scratch_frame()].view(3 * B, oh, ow, c)
+        if self._is_translate():
+            def launch(ring, rows, period, lo, hi):
+                ops.translate_u8(ring, rows, period, src.dy[lo:hi], src.dx[lo:hi], hi - lo, out[lo:hi])
+        elif self._is_shift():
             pad = self.augmentor.pad
 
             def launch(ring, rows, period, lo, hi):
@@ -932,8 +948,8 @@ class ReplayBuffer(object):
         return out
 
     def _shift_refs(self, shifted, guard):
-        """(obs, next_obs, pos) handles over a shifted / cut minibatch: an ordinary uint8 ring of 3B rows, nothing left
-        to crop; obs carries the (obs | next_obs) pair of 2B rows."""
+        """(obs, next_obs, pos) handles over a shifted / cut / translated minibatch: an ordinary uint8 ring of 3B rows of
+        ``output_shape``, nothing left to crop; obs carries the (obs | next_obs) pair of 2B rows."""
         B = self.batch_size
         hw = tuple(self.augmentor.output_shape)
         ar, z = self._shift_rows, self._shift_zero
@@ -947,7 +963,7 @@ class ReplayBuffer(object):
         slot (sample_cpc_refs; ``guard`` from _upload_indices) or a captured graph's (graph_refs; ``guard`` None), whose
         launches then write to fixed addresses: the
         gathers of the frame store (_sources), then by augmentation ring handles (nothing is launched: the first conv
-        layer gathers and crops), the shift / cutout launch(es), or the three jitter / cover / convolution launches."""
+        layer gathers and crops), the shift / cutout / translate launch(es), or the three jitter / cover / convolution launches."""
         B = self.batch_size
         src = self._sources(slot)
         both, idx2, tensors, off = src.both, src.idx2, src.tensors, src.off
@@ -987,7 +1003,7 @@ class ReplayBuffer(object):
     # control values (RNG stream positions, Adam step factors) that the graph's kernels read from the device copy.
     def graph_supported(self):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
-        ones (RandomCrop / RandomShift / RandomCutout / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
+        ones (RandomCrop / RandomShift / RandomCutout / RandomTranslate / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
         are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover / RandomConv constructed with
         ``staged_aug=True`` (either storage).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
         through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""
@@ -1016,8 +1032,8 @@ class ReplayBuffer(object):
             if self.dedup_frames:
                 (g["mb_u8"],) = self._guarded([2 * B * frame + 32], g["guards"])  # (+32: the loaders' slack, as a ring)
                 g["ar2"] = torch.arange(2 * B, device=self.device, dtype=torch.int64)
-            if self._has_scratch():  # the shifted / cut (obs | next_obs | pos) frames, + the loaders' slack
-                (g["shift_u8"],) = self._guarded([3 * B * frame + 32], g["guards"])
+            if self._has_scratch():  # the shifted / cut / translated (obs | next_obs | pos) frames, + the loaders' slack
+                (g["shift_u8"],) = self._guarded([3 * B * self._scratch_frame() + 32], g["guards"])
             if self._is_float_aug():
                 c, h, w = self.obs_shape
                 both, pos = self._guarded([4 * 2 * B * frame, 4 * B * frame], g["guards"])
@@ -1056,8 +1072,8 @@ class ReplayBuffer(object):
     def graph_refs(self, slot):
         """Device side, called while the graph is being captured: the staging launch (pinned block -> device block +
         the transitions' scalars), for the de-duplicated store the two gather_stacks launches (they read ``_fid`` when
-        the graph is replayed), for RandomShift / RandomCutout the shift / cutout launch (it reads its offsets, boxes and
-        colours from the device block), for a
+        the graph is replayed), for RandomShift / RandomCutout / RandomTranslate the shift / cutout / translate launch (it
+        reads its offsets, boxes and colours from the device block), for a
         staged float augmentation the three jitter / cover / convolution launches (they read their
         parameters from the device block), and the sample_cpc 6-tuple with handles into the slot's buffers.  Nothing
         here draws a random number."""

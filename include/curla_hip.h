@@ -593,6 +593,22 @@ int curla_random_shift_u8(const uint8_t* frames, const int64_t* idx, int period,
  * one at a time.  Any C > 0.  Additive: CURLA_ABI_VERSION stays 8.  CURLA_ERR_UNSUPPORTED when H W C does not fit 31 bits. */
 int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* y0, const int32_t* x0,
                     const int32_t* size, const int32_t* rgb, int n, int C, int H, int W, uint8_t* out, void* stream);
+/* RandomTranslate, the translate of RAD (beyond the reference: its augmentations.py has no such class).  The H x W frame is
+ * placed at the sample's (ty, tx) on a black Ho x Wo canvas, Ho >= H and Wo >= W -- all channels of a stack share the draw,
+ * every source pixel is kept and none is invented:
+ *   out[s][y][x][c] = frames[row(s)][y - tyc][x - txc][c]   if 0 <= y - tyc < H and 0 <= x - txc < W,
+ *                     0                                     otherwise,                                  0 <= s < n
+ * uint8 NHWC in ([rows][H][W][C]) and out ([n][Ho][Wo][C], 32 bytes of slack behind it like a ring: a translated minibatch
+ * is a uint8 ring of larger frames), row(s) = idx[s % period] (idx NULL: s % period) as for curla_random_shift_u8.
+ * ty / tx: int32 [n]; whatever they hold is clamped in the kernel, tyc = clamp(ty, 0, Ho - H), txc = clamp(tx, 0, Wo - W):
+ * every output byte is written exactly once, nothing is read outside the source frame (neither in front of it nor in the
+ * slack behind a ring) and nothing is written outside `out`.  An output frame of a multiple of 16 bytes with `out` on a
+ * 16-byte boundary (and a source frame of at least 16 bytes) moves 16 bytes per lane: no load for a group in the margin,
+ * one unaligned load for a group inside the image, at most two loads combined in registers for a group that crosses an
+ * image edge or straddles two rows; every other case gives the same bytes one at a time.  Any C > 0.  Additive:
+ * CURLA_ABI_VERSION stays 8.  CURLA_ERR_UNSUPPORTED when Ho Wo C does not fit 31 bits or a row Wo C does not fit 30. */
+int curla_translate_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* ty, const int32_t* tx, int n,
+                       int C, int H, int W, int Ho, int Wo, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
