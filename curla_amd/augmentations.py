@@ -5,13 +5,18 @@ offsets are drawn with ``np.random.randint`` exactly as augmentations.py:66-67
 does, so a seeded run picks the same windows); the pixel movement itself is
 fused into the first conv kernel's load (curla_amd/csrc/conv.hip) or, for
 callers that want tensors, done by ``curla_crop_nchw``.
+
+Every class also tells ``ReplayBuffer`` how a minibatch of its kind is sampled (``sample_kind`` and the methods listed
+at ``IdentityAugmentation``; DESIGN.md, "Adding an augmentation"): the buffer asks the object, never what class it is.
 """
 import numpy as np
+import torch
+
+from . import ops
 
 
 def _device_batch(image_batch, input_shape):
     """The float NCHW device tensor the augmentation kernels take; anything else is an error (no CPU path)."""
-    import torch
     if not (torch.is_tensor(image_batch) and image_batch.dim() == 4 and image_batch.shape[1] % 3 == 0
             and tuple(image_batch.shape[2:]) == tuple(input_shape)):
         raise ValueError("expected a (B, 3*frame_stack, %d, %d) tensor, got %r"
@@ -35,6 +40,35 @@ class IdentityAugmentation:
 
     def training_augmentation(self, image_batch):
         return image_batch
+
+    # ---- what ReplayBuffer asks of an augmentation.  Every class states its ``sample_kind``:
+    #   "ring"     nothing is launched: the first conv layer gathers the stored frames and crops ``output_shape``
+    #   "scratch"  ONE launch, ``scratch_launch(ring, rows, period, words, n, out)``, writes n uint8 frames of
+    #              ``output_shape`` into the sample slot's scratch, which is then read as a ring with zero offsets;
+    #              sample s is row rows[s % period] (rows None: s % period), ``words`` its ``index_rows`` int32 runs [n]
+    #   "float"    one launch per tensor, ``launch(ring, rows, B, out, staged=None)``, into float NHWC ``out``; it draws
+    #              and uploads its parameters itself (one pinned block, one asynchronous copy) unless ``staged`` hands
+    #              them over.  With ``staged_aug`` they travel in the minibatch's block instead, ``staged_layout(B,
+    #              obs_shape)`` -> (bytes per tensor, the block_layout keys of the fields inside them): ``draw_staged(B,
+    #              obs_shape, noise_generator)`` draws one tensor's, ``fill_staged(host, at, drawn)`` writes them at byte
+    #              ``at`` of a host copy of the block and ``staged_args(dev, at, B, obs_shape)`` reads ``staged`` back
+    #              from there in the device copy.
+    # Any kind may draw ``index_rows`` (0, 2 or 4) int32 words per sample and tensor on the host, ``draw_index_words(n)``:
+    # the first two travel as the block's offset rows, the other two behind them (block_layout: ``cut``).
+    index_rows = 0
+
+    @property
+    def sample_kind(self):
+        """The identity is a "ring"; a subclass inherits no kind from it -- it declares its own (the seven below do, and
+        their subclasses inherit that) or is unknown to ReplayBuffer (None: draw_indices raises)."""
+        return "ring" if type(self) is IdentityAugmentation else None
+
+    def draw_index_words(self, n):
+        """``index_rows`` integer arrays [n], drawn from NumPy's global stream for one tensor of a minibatch."""
+        return ()
+
+    def check_staged(self, n, noise_generator):
+        """("float") ValueError when ``staged_aug`` cannot serve minibatch tensors of n elements."""
 
 
 class RandomCrop(IdentityAugmentation):
@@ -65,6 +99,11 @@ class RandomCrop(IdentityAugmentation):
         h1 = np.random.randint(0, crop_max_h, n)
         w1 = np.random.randint(0, crop_max_w, n)
         return h1, w1
+
+    sample_kind, index_rows = "ring", 2
+
+    def draw_index_words(self, n):
+        return self.draw_offsets(n)
 
     def training_augmentation(self, image_batch):
         """Host-side crop of a (B, C, H, W) array, for callers outside the fused
@@ -98,6 +137,15 @@ class RandomShift(IdentityAugmentation):
         dy = np.random.randint(0, 2 * self.pad + 1, n)
         dx = np.random.randint(0, 2 * self.pad + 1, n)
         return dy, dx
+
+    sample_kind, index_rows = "scratch", 2
+
+    def draw_index_words(self, n):
+        return self.draw_offsets(n)
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        dy, dx = words
+        ops.random_shift_u8(ring, rows, period, dy, dx, self.pad, n, out)
 
     def shift(self, image_batch, dy, dx):
         """The shift of a (B, C, H, W) array by given per-sample offsets, on the host."""
@@ -149,6 +197,18 @@ class RandomCutout(IdentityAugmentation):
         rgb = np.random.randint(0, 256, (n, 3)) if self.color else None
         return y0, x0, bh, bw, rgb
 
+    sample_kind, index_rows = "scratch", 4
+
+    def draw_index_words(self, n):
+        """``draw_boxes(n)`` as the kernel takes it: y0, x0, the packed sizes bh | bw << 16 and the colour words
+        r | g << 8 | b << 16 (0 for the black cutout)."""
+        y0, x0, bh, bw, rgb = self.draw_boxes(n)
+        return y0, x0, bh | (bw << 16), 0 if rgb is None else rgb[:, 0] | (rgb[:, 1] << 8) | (rgb[:, 2] << 16)
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        y0, x0, size, rgb = words
+        ops.cutout_u8(ring, rows, period, y0, x0, size, rgb, n, out)
+
     @staticmethod
     def cut(image_batch, y0, x0, bh, bw, rgb=None):
         """The cutout of a (B, C, H, W) array with given per-sample boxes, on the host; ``rgb`` (B, 3) or None = black."""
@@ -198,6 +258,15 @@ class RandomTranslate(IdentityAugmentation):
         tx = np.random.randint(0, self.output_shape[1] - self.input_shape[1] + 1, n)
         return ty, tx
 
+    sample_kind, index_rows = "scratch", 2
+
+    def draw_index_words(self, n):
+        return self.draw_offsets(n)
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        ty, tx = words
+        ops.translate_u8(ring, rows, period, ty, tx, n, out)
+
     def translate(self, image_batch, ty, tx):
         """A (B, C, H, W) array placed at given per-sample offsets on zero canvases (B, C, Ho, Wo), on the host."""
         h, w = image_batch.shape[2:]
@@ -246,7 +315,6 @@ class RandomConv(IdentityAugmentation):
     @staticmethod
     def identity_filter():
         """float32 [3, 3, 3, 3]: w[c][c][1][1] = 1, 0 elsewhere."""
-        import torch
         w = torch.zeros(3, 3, 3, 3, dtype=torch.float32)
         for c in range(3):
             w[c, c, 1, 1] = 1.0
@@ -257,12 +325,35 @@ class RandomConv(IdentityAugmentation):
         ``torch.randn(n, 3, 3, 3, 3) * sqrt(2 / 54)`` (Xavier-normal for fan-in = fan-out = 27, RAD's initialisation);
         then -- ``p < 1`` only -- ``torch.rand(n) < p``, and the rows that lose this draw become the identity filter.
         With ``p == 1`` exactly one generator call is made."""
-        import torch
         w = torch.randn(n, 3, 3, 3, 3, dtype=torch.float32) * np.sqrt(2.0 / 54.0)
         if self.p < 1.0:
             keep = torch.rand(n) < self.p
             w[~keep] = self.identity_filter()
         return w
+
+    sample_kind = "float"
+
+    def staged_layout(self, B, obs_shape):
+        """weights float [B][81] | 4 bytes of padding when B is odd (the block stays a multiple of 8 bytes)."""
+        return (324 * B + 7) // 8 * 8, dict(aug_weights=324 * B)
+
+    def draw_staged(self, B, obs_shape, noise_generator):
+        return self.draw_weights(B)
+
+    def fill_staged(self, host, at, drawn):
+        host[at:at + 4 * drawn.numel()].view(torch.float32).copy_(drawn.reshape(-1))
+
+    def staged_args(self, dev, at, B, obs_shape):
+        return dev[at:at + 324 * B].view(torch.float32).view(-1, 81)
+
+    def launch(self, ring, rows, B, out, staged=None):
+        if staged is None:
+            weights = self.draw_weights(B)
+            # (one pinned staging block, one asynchronous copy, as ColorJiggle's)
+            stage = torch.empty(weights.shape, dtype=torch.float32, pin_memory=out.is_cuda)
+            stage.copy_(weights)
+            staged = stage.to(out.device, non_blocking=True)
+        ops.random_conv(ring, rows, staged, B, out)
 
     @staticmethod
     def conv(image_batch, weights):
@@ -284,8 +375,6 @@ class RandomConv(IdentityAugmentation):
         """On the reference's tensor contract, as ColorJiggle's: a float (B, 3k, H, W) device tensor in [0, 255] in, the
         convolved batch out, always a new tensor (``curla_random_conv_nchw``: the same arithmetic ``ReplayBuffer`` applies
         straight from the ring).  ``weights`` (B, 3, 3, 3, 3) replaces the draw (tests)."""
-        import torch
-        from . import ops
         x = _device_batch(image_batch, self.input_shape)
         if weights is None:
             weights = self.draw_weights(x.shape[0])
@@ -308,7 +397,6 @@ class ColorJiggle(IdentityAugmentation):
 
     def draw_params(self, n_images):
         """(params [n_images, 4] = apply, contrast, saturation, hue in radians; order [4])."""
-        import torch
         apply = (torch.rand(n_images) < self.p).float()
         con = torch.empty(n_images).uniform_(1 - self.contrast, 1 + self.contrast)
         sat = torch.empty(n_images).uniform_(1 - self.saturation, 1 + self.saturation)
@@ -316,14 +404,45 @@ class ColorJiggle(IdentityAugmentation):
         order = torch.randperm(4).int()
         return torch.stack([apply, con, sat, hue], 1).contiguous(), order
 
+    sample_kind = "float"
+
+    def staged_layout(self, B, obs_shape):
+        """params float [B k][4] | order int32 [4]."""
+        n_par = 16 * B * (obs_shape[0] // 3)
+        return n_par + 16, dict(aug_order=n_par)
+
+    def draw_staged(self, B, obs_shape, noise_generator):
+        return self.draw_params(B * (obs_shape[0] // 3))
+
+    def fill_staged(self, host, at, drawn):
+        params, order = drawn
+        n_par = 4 * params.numel()
+        host[at:at + n_par].view(torch.float32).copy_(params.reshape(-1))
+        host[at + n_par:at + n_par + 16].view(torch.int32).copy_(order)
+
+    def staged_args(self, dev, at, B, obs_shape):
+        n_par = 16 * B * (obs_shape[0] // 3)
+        return dev[at:at + n_par].view(torch.float32).view(-1, 4), dev[at + n_par:at + n_par + 16].view(torch.int32)
+
+    def launch(self, ring, rows, B, out, staged=None):
+        if staged is None:
+            params, order = self.draw_params(B * (out.shape[3] // 3))
+            # one pinned staging block, one asynchronous copy: a `.to(device)` of a pageable tensor makes the host wait
+            # until the stream has drained (two of them per call left ~60 us of idle GPU around every jitter launch)
+            n4 = params.numel()
+            stage = torch.empty(n4 + 4, dtype=torch.int32, pin_memory=out.is_cuda)
+            stage[:n4] = params.reshape(-1).view(torch.int32)
+            stage[n4:] = order
+            d = stage.to(out.device, non_blocking=True)
+            staged = d[:n4].view(torch.float32).view(params.shape), d[n4:]
+        ops.color_jiggle(ring, rows, staged[0], staged[1], B, out)
+
     def training_augmentation(self, image_batch, params=None, order=None):
         """augmentations.py:105-136 on the reference's tensor contract: a float (B, 3k, H, W) device tensor in
         [0,255] in, the jittered batch out -- the same kernel arithmetic ``ReplayBuffer`` applies straight from
         the ring.  A new tensor is returned (the reference scales its argument in place by 1/255 and returns a
         fresh tensor; callers only use the return value, utils.py:174-182).  ``params`` / ``order`` replace
         the random draws (tests)."""
-        import torch
-        from . import ops
         x = _device_batch(image_batch, self.input_shape)
         B, C = x.shape[:2]
         if params is None:
@@ -350,12 +469,52 @@ class NoisyCover(IdentityAugmentation):
     def draw_colors(self):
         return [np.random.randint(0, 255) for _ in range(3)]
 
+    sample_kind = "float"
+
+    def check_staged(self, n, noise_generator):
+        if n >= 2 ** 32:
+            raise ValueError("staged_aug: the in-kernel noise numbers a minibatch tensor's elements in 32 bits")
+        try:
+            noise_generator().get_offset()
+        except (AttributeError, RuntimeError) as e:
+            raise ValueError("staged_aug=True with NoisyCover draws its noise from the Philox stream of the HIP "
+                             f"device's torch generator, which exposes no offset here ({e!r})") from e
+
+    def staged_layout(self, B, obs_shape):
+        """colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2], 8-byte aligned."""
+        return 32, dict(aug_rng=16)
+
+    def draw_staged(self, B, obs_shape, noise_generator):
+        """The colours, and (seed, counter) of the noise the kernel draws: the tensor's ceil(n / 4) Philox counters are
+        reserved by moving the device generator's offset on by 4 ceil(n / 4), as CurlSacAgent._noise does."""
+        colors = self.draw_colors()
+        gen = noise_generator()
+        off, n = gen.get_offset(), B * int(np.prod(obs_shape))
+        gen.set_offset(off + 4 * ((n + 3) // 4))
+        return colors, gen.initial_seed() & (2 ** 64 - 1), off // 4
+
+    def fill_staged(self, host, at, drawn):
+        colors, seed, ctr = drawn
+        host[at:at + 12].view(torch.float32).copy_(torch.tensor([float(v) for v in colors]))
+        host[at + 16:at + 32].view(torch.int64).copy_(
+            torch.from_numpy(np.array([seed, ctr], dtype=np.uint64).view(np.int64)))
+
+    def staged_args(self, dev, at, B, obs_shape):
+        """Device addresses of the colours and of (seed, counter): the kernel reads both when it runs."""
+        return dev.data_ptr() + at, dev.data_ptr() + at + 16
+
+    def launch(self, ring, rows, B, out, staged=None):
+        if staged is None:
+            colors = self.draw_colors()
+            noise = torch.randn(tuple(out.shape), device=out.device) * self.std
+            ops.noisy_cover(ring, rows, noise, colors, self.top, self.bottom, B, out)
+        else:
+            ops.noisy_cover_rng(ring, rows, self.std, (0, 0, staged[1]), staged[0], self.top, self.bottom, B, out)
+
     def training_augmentation(self, image_batch, colors=None, noise=None):
         """augmentations.py:170-205 on the reference's tensor contract (float (B, 3k, H, W) device tensor in
         [0,255]); returns a new tensor (the reference paints the cover into its argument in place and returns a
         fresh noisy tensor).  ``colors`` / ``noise`` replace the random draws (tests)."""
-        import torch
-        from . import ops
         x = _device_batch(image_batch, self.input_shape)
         if colors is None:
             colors = self.draw_colors()

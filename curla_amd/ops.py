@@ -701,16 +701,25 @@ def gather_stacks(store, fid, idx, B, out):
     call("curla_gather_stacks", ptr(store), ptr(fid), fid.stride(0), ptr(idx), B, fid.shape[1], H, W, ptr(out), stream())
 
 
+def _check_scratch_u8(op, frames, idx, period, words, n, out, fits, what):
+    """What the uint8 scratch augmentations check alike: frames and out uint8, ``words`` int32 runs of at least n, idx int64
+    of at least min(period, n) (or None), and ``fits``, the op's own verdict on the shape of out."""
+    _dev(frames, torch.uint8), _dev(out, torch.uint8)
+    for t in words:
+        _dev(t, torch.int32)
+    if idx is not None:
+        _dev(idx, torch.int64)
+    if not fits or min(t.numel() for t in words) < n or (idx is not None and idx.numel() < min(period, n)):
+        raise _lib.CurlaHipError(f"{op}: out {tuple(out.shape)} / {', '.join(str(t.numel()) for t in words)} {what[0]} do "
+                                 f"not fit {n} samples of {tuple(frames.shape[1:])}{what[1]}")
+
+
 def random_shift_u8(frames, idx, period, dy, dx, pad, n, out):
     """RandomShift of n samples (curla_random_shift_u8): frames u8 [rows, H, W, C]; sample s reads row idx[s % period]
     (idx None: s % period) shifted by (dy[s], dx[s]) - pad with edge pixels repeated; out u8 [n, H, W, C]."""
     _, H, W, C = frames.shape
-    _dev(frames, torch.uint8), _dev(out, torch.uint8), _dev(dy, torch.int32), _dev(dx, torch.int32)
-    if idx is not None:
-        _dev(idx, torch.int64)
-    if tuple(out.shape) != (n, H, W, C) or dy.numel() < n or dx.numel() < n or (idx is not None and idx.numel() < min(period, n)):
-        raise _lib.CurlaHipError(f"random_shift_u8: out {tuple(out.shape)} / {dy.numel()}, {dx.numel()} offsets do not "
-                                 f"fit {n} samples of {(H, W, C)}")
+    _check_scratch_u8("random_shift_u8", frames, idx, period, (dy, dx), n, out, tuple(out.shape) == (n, H, W, C),
+                      ("offsets", ""))
     call("curla_random_shift_u8", ptr(frames), ptr(idx), int(period), ptr(dy), ptr(dx), int(pad), int(n), C, H, W,
          ptr(out), stream())
 
@@ -720,15 +729,8 @@ def cutout_u8(frames, idx, period, y0, x0, size, rgb, n, out):
     s % period) with the box of (y0[s], x0[s]) and size[s] = bh | bw << 16 painted in rgb[s] = r | g << 8 | b << 16 (all
     int32 [n]; clamped into the frame by the kernel); out u8 [n, H, W, C]."""
     _, H, W, C = frames.shape
-    _dev(frames, torch.uint8), _dev(out, torch.uint8)
-    for t in (y0, x0, size, rgb):
-        _dev(t, torch.int32)
-    if idx is not None:
-        _dev(idx, torch.int64)
-    if tuple(out.shape) != (n, H, W, C) or min(t.numel() for t in (y0, x0, size, rgb)) < n or \
-            (idx is not None and idx.numel() < min(period, n)):
-        raise _lib.CurlaHipError(f"cutout_u8: out {tuple(out.shape)} / {y0.numel()}, {x0.numel()}, {size.numel()}, "
-                                 f"{rgb.numel()} box words do not fit {n} samples of {(H, W, C)}")
+    _check_scratch_u8("cutout_u8", frames, idx, period, (y0, x0, size, rgb), n, out, tuple(out.shape) == (n, H, W, C),
+                      ("box words", ""))
     call("curla_cutout_u8", ptr(frames), ptr(idx), int(period), ptr(y0), ptr(x0), ptr(size), ptr(rgb), int(n), C, H, W,
          ptr(out), stream())
 
@@ -738,13 +740,9 @@ def translate_u8(frames, idx, period, ty, tx, n, out):
     None: s % period) placed at (ty[s], tx[s]) (int32 [n]; clamped onto the canvas by the kernel) on a black canvas; out
     u8 [n, Ho, Wo, C] with Ho >= H and Wo >= W."""
     _, H, W, C = frames.shape
-    _dev(frames, torch.uint8), _dev(out, torch.uint8), _dev(ty, torch.int32), _dev(tx, torch.int32)
-    if idx is not None:
-        _dev(idx, torch.int64)
-    if out.dim() != 4 or out.shape[0] != n or out.shape[3] != C or out.shape[1] < H or out.shape[2] < W or \
-            ty.numel() < n or tx.numel() < n or (idx is not None and idx.numel() < min(period, n)):
-        raise _lib.CurlaHipError(f"translate_u8: out {tuple(out.shape)} / {ty.numel()}, {tx.numel()} offsets do not fit "
-                                 f"{n} samples of {(H, W, C)} on a canvas no smaller than the frame")
+    fits = out.dim() == 4 and out.shape[0] == n and out.shape[3] == C and out.shape[1] >= H and out.shape[2] >= W
+    _check_scratch_u8("translate_u8", frames, idx, period, (ty, tx), n, out, fits,
+                      ("offsets", " on a canvas no smaller than the frame"))
     call("curla_translate_u8", ptr(frames), ptr(idx), int(period), ptr(ty), ptr(tx), int(n), C, H, W, int(out.shape[1]),
          int(out.shape[2]), ptr(out), stream())
 

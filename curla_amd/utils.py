@@ -30,7 +30,7 @@ import random
 import numpy as np
 import torch
 
-from . import augmentations, ops
+from . import ops
 
 try:  # 64-bit frame fingerprints for the de-duplicating store (~10 GB/s); zlib is the slower stand-in
     from xxhash import xxh3_64_intdigest as _fingerprint
@@ -200,7 +200,7 @@ class _FrameStore:
 
 
 # what ReplayBuffer._sources returns
-_Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off dy dx size rgb")
+_Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off words")
 
 
 class ReplayBuffer(object):
@@ -242,16 +242,16 @@ class ReplayBuffer(object):
         frame = c * h * w
         A = int(np.prod(action_shape))
         self.dedup_frames = bool(dedup_frames)
+        # How a minibatch of this augmentation is sampled -- "ring", "scratch" or "float" -- and the int32 words it draws
+        # per sample and tensor: the object says (the protocol at IdentityAugmentation).  None: an object that says nothing
+        # (draw_indices raises).
+        self._kind = getattr(augmentor, "sample_kind", None)
+        self._index_rows = augmentor.index_rows if self._kind else 0
+        assert self._kind in ("ring", "scratch", "float", None) and self._index_rows in (0, 2, 4)
         # float augmentations only: the parameters travel in the index block, NoisyCover's noise is drawn in the kernel
-        self.staged_aug = bool(staged_aug) and self._is_float_aug()
-        if self.staged_aug and isinstance(augmentor, augmentations.NoisyCover):
-            if c * h * w * batch_size >= 2 ** 32:
-                raise ValueError("staged_aug: the in-kernel noise numbers a minibatch tensor's elements in 32 bits")
-            try:
-                self._noise_generator().get_offset()
-            except (AttributeError, RuntimeError) as e:
-                raise ValueError("staged_aug=True with NoisyCover draws its noise from the Philox stream of the HIP "
-                                 f"device's torch generator, which exposes no offset here ({e!r})") from e
+        self.staged_aug = bool(staged_aug) and self._kind == "float"
+        if self.staged_aug:
+            augmentor.check_staged(c * h * w * batch_size, self._noise_generator)
         if self.dedup_frames:
             if c % 3 != 0:
                 raise ValueError("dedup_frames needs stacked RGB frames (channels a multiple of 3)")
@@ -263,7 +263,7 @@ class ReplayBuffer(object):
                 + self.N_SAMPLE_SLOTS * 2 * batch_size * frame
         else:
             total_bytes = 2 * capacity * frame + capacity * (4 * A + 8)
-        if self._has_scratch():  # the shifted / cut / translated minibatches (obs | next_obs | pos) of the sample slots
+        if self._kind == "scratch":  # the augmented minibatches (obs | next_obs | pos) of the sample slots
             total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * self._scratch_frame() + 32)
         if self.n_step > 1:  # the continuity flags
             total_bytes += capacity
@@ -361,20 +361,18 @@ class ReplayBuffer(object):
         if self.dedup_frames:
             # (obs stacks | next_obs stacks) of a minibatch, contiguous: also one [2B] ring for ObsRef.pair
             self._mb_store = torch.zeros((self.N_SAMPLE_SLOTS, 2 * B * frame + 32), dtype=torch.uint8, device=dev)
-        if self._has_scratch():
-            # RandomShift / RandomCutout / RandomTranslate: a minibatch's shifted (cut, translated) frames, uint8
-            # [3B][Ho][Wo][C] = (obs | next_obs | pos) -- (Ho, Wo) = the augmentor's output_shape, (H, W) but for a
-            # translate -- + 32 B of slack like a ring, per sample slot (each slot starts on a 256-byte boundary: the
-            # kernel then stores 16 bytes per lane).  Downstream it IS a ring: rows 0..3B-1, zero crop offsets -- static
-            # tensors.  (All three augmentations use the names the shift gave the scratch.)
+        if self._kind == "scratch":
+            # The scratch of a "scratch" augmentation: a minibatch's augmented frames, uint8 [3B][Ho][Wo][C] = (obs |
+            # next_obs | pos) -- (Ho, Wo) = the augmentor's output_shape -- + 32 B of slack like a ring, per sample slot
+            # (each slot starts on a 256-byte boundary: the kernel then stores 16 bytes per lane).  Downstream it IS a
+            # ring: rows 0..3B-1, zero crop offsets -- static tensors.
             stride = (3 * B * self._scratch_frame() + 32 + 255) // 256 * 256
             self._shift_store = torch.zeros((self.N_SAMPLE_SLOTS, stride), dtype=torch.uint8, device=dev)
             self._shift_rows = torch.arange(3 * B, dtype=torch.int64, device=dev)
             self._shift_zero = torch.zeros(3 * B, dtype=torch.int32, device=dev)
         # A slot = the buffers ONE minibatch is assembled in (_assemble): ``dev`` the device block, ``scal`` the
         # transitions' scalars and ``scalars`` its (actions, rewards, not_dones) views, ``mb_u8`` the gathered stacks +
-        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the shifted / cut / translated frames (RandomShift, RandomCutout,
-        # RandomTranslate), ``both_f32`` / ``pos_f32``
+        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the frames of a "scratch" augmentation, ``both_f32`` / ``pos_f32``
         # the float tensors (absent here: allocated per call).  The rotating slots are views of the stores above; a
         # captured update graph has slots of its own with the same keys (graph_block).
         ar2 = torch.arange(2 * B, dtype=torch.int64, device=dev) if self.dedup_frames else None
@@ -383,7 +381,7 @@ class ReplayBuffer(object):
             slot = dict(dev=self._d_index[s], scal=self._d_scal[s], scalars=self._scalar_views(self._d_scal[s]))
             if self.dedup_frames:
                 slot.update(mb_u8=self._mb_store[s], ar2=ar2)
-            if self._has_scratch():
+            if self._kind == "scratch":
                 slot["shift_u8"] = self._shift_store[s]
             self._sample_slots.append(slot)
         self._graph_blocks = {}
@@ -607,23 +605,6 @@ class ReplayBuffer(object):
         return self.frame_capacity - len(self._store.free), self.frame_capacity
 
     # ------------------------------------------------------------------ sampling
-    def _is_crop(self):
-        return isinstance(self.augmentor, augmentations.RandomCrop)
-
-    def _is_shift(self):
-        return isinstance(self.augmentor, augmentations.RandomShift)
-
-    def _is_cutout(self):
-        return isinstance(self.augmentor, augmentations.RandomCutout)
-
-    def _is_translate(self):
-        return isinstance(self.augmentor, augmentations.RandomTranslate)
-
-    def _has_scratch(self):
-        """The augmentations whose minibatch is written, still uint8, into a scratch of the sample slot by one launch
-        behind the staging launch (_scratch_aug) and read from there as an ordinary ring."""
-        return self._is_shift() or self._is_cutout() or self._is_translate()
-
     def _scratch_frame(self):
         """Bytes of a frame of the scratch: a MINIBATCH frame (C, Ho, Wo), (Ho, Wo) the augmentor's output_shape.  Only a
         RandomTranslate makes it differ from a stored frame (``_frame``: the rings, add, save / load, the frame store)."""
@@ -631,31 +612,20 @@ class ReplayBuffer(object):
         return self.obs_shape[0] * oh * ow
 
     def draw_indices(self):
-        """Host RNG draws of sample_cpc, in the reference's order (utils.py:147 then
-        augmentations.py:66-67 for obs, next_obs, pos).  Returns (idxs, offsets) with
-        offsets an int32 array [6, B] = h1/w1 of obs, next_obs, pos (zeros when the
-        augmentation is neither RandomCrop nor RandomShift / RandomTranslate, whose (dy, dx) / (ty, tx) pairs take the
-        same places).  A RandomCutout
-        returns int32 [12, B]: rows 2j, 2j + 1 = (y0, x0) of tensor j's boxes in those places, rows 6 + 2j, 6 + 2j + 1 its
-        packed sizes bh | bw << 16 and colours r | g << 8 | b << 16 (0 for the black cutout), drawn by ``draw_boxes(B)``
-        for obs, next_obs, pos."""
+        """Host RNG draws of sample_cpc, in the reference's order (utils.py:147 then augmentations.py:66-67 for obs,
+        next_obs, pos).  Returns (idxs, offsets) with offsets an int32 array [6, B]: rows 2j, 2j + 1 = the first two words
+        the augmentation draws for tensor j (``draw_index_words``: h1 / w1 of a RandomCrop, (dy, dx) / (ty, tx) of a
+        RandomShift / RandomTranslate, (y0, x0) of a RandomCutout's boxes; zeros when it draws none).  An augmentation of
+        four words -- RandomCutout -- returns int32 [12, B], rows 6 + 2j, 6 + 2j + 1 = the other two (its packed sizes
+        and colours)."""
         B = self.batch_size
         idxs = np.random.randint(0, self.capacity if self.full else self.idx, size=B)
-        if self._is_cutout():
-            offs = np.zeros((12, B), dtype=np.int32)
-            for j in range(3):
-                y0, x0, bh, bw, rgb = self.augmentor.draw_boxes(B)
-                offs[2 * j], offs[2 * j + 1], offs[6 + 2 * j] = y0, x0, bh | (bw << 16)
-                if rgb is not None:
-                    offs[6 + 2 * j + 1] = rgb[:, 0] | (rgb[:, 1] << 8) | (rgb[:, 2] << 16)
-            return idxs, offs
-        offs = np.zeros((6, B), dtype=np.int32)
-        if self._is_crop() or self._is_shift() or self._is_translate():
-            for j in range(3):
-                h1, w1 = self.augmentor.draw_offsets(B)
-                offs[2 * j], offs[2 * j + 1] = h1, w1
-        elif not self._is_float_aug() and type(self.augmentor) is not augmentations.IdentityAugmentation:
+        if self._kind is None:
             raise NotImplementedError("unknown augmentation object: %r" % (self.augmentor,))
+        offs = np.zeros((12 if self._index_rows > 2 else 6, B), dtype=np.int32)
+        for j in range(3):
+            for r, word in enumerate(self.augmentor.draw_index_words(B)):
+                offs[6 * (r // 2) + 2 * j + r % 2] = word
         return idxs, offs
 
     def _float_augmented(self, ring, idx, dev, j, out=None):
@@ -663,56 +633,25 @@ class ReplayBuffer(object):
         ``ring`` rows ``idx`` (None: rows 0..B-1) (utils.py:168-182 branch: the torch/kornia augmentations).  With
         staged_aug the tensor's parameters are already on the device, in the minibatch's block ``dev`` (_aug_args) --
         nothing is drawn, allocated or copied here."""
-        staged = self._aug_args(dev, j) if self.staged_aug else None
         B = self.batch_size
         c, h, w = self.obs_shape
         if out is None:
             out = torch.empty((B, h, w, c), dtype=torch.float32, device=self.device)
-        aug = self.augmentor
-        if staged is not None and isinstance(aug, augmentations.ColorJiggle):
-            ops.color_jiggle(ring, idx, staged[0], staged[1], B, out)
-        elif staged is not None and isinstance(aug, augmentations.RandomConv):
-            ops.random_conv(ring, idx, staged, B, out)
-        elif staged is not None:
-            ops.noisy_cover_rng(ring, idx, aug.std, (0, 0, staged[1]), staged[0], aug.top, aug.bottom, B, out)
-        elif isinstance(aug, augmentations.ColorJiggle):
-            params, order = aug.draw_params(B * (c // 3))
-            # one pinned staging block, one asynchronous copy: a `.to(device)` of a pageable tensor makes the host wait
-            # until the stream has drained (two of them per call left ~60 us of idle GPU around every jitter launch)
-            n4 = params.numel()
-            cuda = self.device.type == "cuda"
-            stage = torch.empty(n4 + 4, dtype=torch.int32, pin_memory=cuda)
-            stage[:n4] = params.reshape(-1).view(torch.int32)
-            stage[n4:] = order
-            d = stage.to(self.device, non_blocking=True)
-            ops.color_jiggle(ring, idx, d[:n4].view(torch.float32).view(params.shape), d[n4:], B, out)
-        elif isinstance(aug, augmentations.RandomConv):
-            weights = aug.draw_weights(B)
-            # (one pinned staging block, one asynchronous copy, as above)
-            stage = torch.empty(weights.shape, dtype=torch.float32, pin_memory=self.device.type == "cuda")
-            stage.copy_(weights)
-            ops.random_conv(ring, idx, stage.to(self.device, non_blocking=True), B, out)
-        elif isinstance(aug, augmentations.NoisyCover):
-            colors = aug.draw_colors()
-            noise = torch.randn((B, h, w, c), device=self.device) * aug.std
-            ops.noisy_cover(ring, idx, noise, colors, aug.top, aug.bottom, B, out)
-        else:
-            ops.gather_nhwc(ring, idx, B, out)
+        self.augmentor.launch(ring, idx, B, out, self._aug_args(dev, j) if self.staged_aug else None)
         return out
-
-    def _is_float_aug(self):
-        return isinstance(self.augmentor, (augmentations.ColorJiggle, augmentations.NoisyCover, augmentations.RandomConv))
 
     def block_layout(self):
         """Byte offsets inside a minibatch's block -- the ONE place that knows them.  Every block starts with
         idx int64 [2B] | crop offsets int32 [6][B] at ``offs`` .. ``offs_end`` (_fill_index_block).  ``staged_aug``
-        appends the parameters of the three tensors (obs, next_obs, pos), ``aug_stride`` bytes each:
-          ColorJiggle  params float [B k][4] (apply, contrast, saturation, hue) | order int32 [4]
-          NoisyCover   colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2]   (8-byte aligned)
+        appends the parameters of the three tensors (obs, next_obs, pos), ``aug_stride`` bytes each, laid out by
+        the augmentation (``staged_layout``):
+          ColorJiggle  params float [B k][4] (apply, contrast, saturation, hue) | order int32 [4]   (at ``aug_order``)
+          NoisyCover   colours float [3] | 4 bytes of padding | (seed, Philox counter) uint64 [2]   (at ``aug_rng`` = 16)
           RandomConv   weights float [B][81] | 4 bytes of padding when B is odd (``aug_weights`` = 324 B, the bytes of the
                        weights; a key only this layout has -- the stride keeps ``nbytes`` a multiple of 8)
-        A RandomCutout appends ``cut`` int32 [2][3B] at ``offs_end``: the packed box sizes of obs | next_obs | pos, then
-        their colour words -- contiguous runs for one launch of n = 3B.
+        An augmentation that draws four index words -- RandomCutout -- appends ``cut`` int32 [2][3B] behind them: the third
+        words of obs | next_obs | pos (its packed box sizes), then the fourth (its colour words) -- contiguous runs for
+        one launch of n = 3B.
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
         ``nbytes`` is what a rotating sample slot stages per minibatch; the block of a captured update graph carries
         GRAPH_TAIL more bytes of per-update control values behind it (at ``tail``; ``graph_nbytes`` in all)."""
@@ -720,15 +659,10 @@ class ReplayBuffer(object):
         n = 2 * B * 8 + 6 * B * 4
         lay = dict(idx=0, offs=2 * B * 8, offs_end=n, aug=None, aug_stride=0, aug_order=None, aug_rng=None)
         if self.staged_aug:
-            if isinstance(self.augmentor, augmentations.ColorJiggle):
-                n_par = 16 * B * (self.obs_shape[0] // 3)
-                lay.update(aug=n, aug_stride=n_par + 16, aug_order=n_par)
-            elif isinstance(self.augmentor, augmentations.RandomConv):
-                lay.update(aug=n, aug_stride=(324 * B + 7) // 8 * 8, aug_weights=324 * B)
-            else:
-                lay.update(aug=n, aug_stride=32, aug_rng=16)
-            n += 3 * lay["aug_stride"]
-        if self._is_cutout():
+            stride, fields = self.augmentor.staged_layout(B, self.obs_shape)
+            lay.update(aug=n, aug_stride=stride, **fields)
+            n += 3 * stride
+        if self._index_rows > 2:
             lay["cut"] = n
             n += 2 * 3 * B * 4
         assert n % 8 == 0
@@ -748,57 +682,26 @@ class ReplayBuffer(object):
 
     def draw_aug(self):
         """(staged_aug) The host draws of the three tensors' augmentations, obs then next_obs then pos -- what the
-        default path draws one tensor at a time (utils.py:173-182): ``ColorJiggle.draw_params`` from torch's CPU
-        generator (``RandomConv.draw_weights`` likewise), ``NoisyCover.draw_colors`` from NumPy.  NoisyCover also reserves the tensor's ceil(n / 4) Philox
-        counters by moving the device generator's offset on by 4 ceil(n / 4), as CurlSacAgent._noise does.  None when
-        nothing is staged."""
+        default path draws one tensor at a time (utils.py:173-182), by the augmentation's ``draw_staged``:
+        ``ColorJiggle.draw_params`` and ``RandomConv.draw_weights`` from torch's CPU generator, ``NoisyCover.draw_colors``
+        from NumPy; NoisyCover also reserves the tensor's Philox counters in the device generator (_noise_generator).
+        None when nothing is staged."""
         if not self.staged_aug:
             return None
-        B = self.batch_size
-        c, h, w = self.obs_shape
-        aug, out = self.augmentor, []
-        for _ in range(3):
-            if isinstance(aug, augmentations.ColorJiggle):
-                out.append(aug.draw_params(B * (c // 3)))
-            elif isinstance(aug, augmentations.RandomConv):
-                out.append(aug.draw_weights(B))
-            else:
-                colors = aug.draw_colors()
-                gen = self._noise_generator()
-                off, n = gen.get_offset(), B * c * h * w
-                gen.set_offset(off + 4 * ((n + 3) // 4))
-                out.append((colors, gen.initial_seed() & (2 ** 64 - 1), off // 4))
-        return out
+        return [self.augmentor.draw_staged(self.batch_size, self.obs_shape, self._noise_generator) for _ in range(3)]
 
     def _fill_aug(self, host, aug):
         """draw_aug()'s values into a pinned block (block_layout)."""
         lay = self._layout
-        for j, item in enumerate(aug):
-            a = lay["aug"] + j * lay["aug_stride"]
-            if lay["aug_order"] is not None:
-                params, order = item
-                host[a:a + lay["aug_order"]].view(torch.float32).copy_(params.reshape(-1))
-                host[a + lay["aug_order"]:a + lay["aug_stride"]].view(torch.int32).copy_(order)
-            elif lay.get("aug_weights") is not None:
-                host[a:a + lay["aug_weights"]].view(torch.float32).copy_(item.reshape(-1))
-            else:
-                colors, seed, ctr = item
-                host[a:a + 12].view(torch.float32).copy_(torch.tensor([float(v) for v in colors]))
-                host[a + lay["aug_rng"]:a + 32].view(torch.int64).copy_(
-                    torch.from_numpy(np.array([seed, ctr], dtype=np.uint64).view(np.int64)))
+        for j, drawn in enumerate(aug):
+            self.augmentor.fill_staged(host, lay["aug"] + j * lay["aug_stride"], drawn)
 
     def _aug_args(self, dev, j):
-        """What the augmentation kernel of tensor j reads from the device copy ``dev`` of a block: ColorJiggle
-        (params [B k, 4], order [4]) as tensors, RandomConv its weights [B, 81] as a tensor, NoisyCover (colours,
-        (seed, counter)) as device addresses."""
+        """What the augmentation kernel of tensor j reads from the device copy ``dev`` of a block (``staged_args``):
+        ColorJiggle (params [B k, 4], order [4]) as tensors, RandomConv its weights [B, 81] as a tensor, NoisyCover
+        (colours, (seed, counter)) as device addresses."""
         lay = self._layout
-        a = lay["aug"] + j * lay["aug_stride"]
-        if lay["aug_order"] is not None:
-            return (dev[a:a + lay["aug_order"]].view(torch.float32).view(-1, 4),
-                    dev[a + lay["aug_order"]:a + lay["aug_stride"]].view(torch.int32))
-        if lay.get("aug_weights") is not None:
-            return dev[a:a + lay["aug_weights"]].view(torch.float32).view(-1, 81)
-        return dev.data_ptr() + a, dev.data_ptr() + a + lay["aug_rng"]
+        return self.augmentor.staged_args(dev, lay["aug"] + j * lay["aug_stride"], self.batch_size, self.obs_shape)
 
     def _fill_index_block(self, host, idxs, offs):
         """A minibatch's indices and crop offsets in the layout the kernels read:
@@ -892,9 +795,9 @@ class ReplayBuffer(object):
           off      the six offset rows: off[2j] / off[2j+1] = h1 / w1 of tensor j
           both     the ring of obs frames then next_obs frames in which (obs | next_obs) is ONE run of 2B rows ``idx2``
                    (None: rows 0..2B-1) with offsets ``h2`` / ``w2``; None when the rings are two allocations
-          dy, dx   the h rows of obs, next_obs, pos as one int32 run of 3B, and the w rows (RandomShift's offsets,
-                   RandomCutout's y0 / x0, RandomTranslate's ty / tx)
-          size, rgb  the packed box sizes and the colour words of obs, next_obs, pos, 3B each (RandomCutout; else None)
+          words    the index words of obs, next_obs, pos as int32 runs of 3B each: the h rows, the w rows (RandomShift's
+                   (dy, dx), RandomTranslate's (ty, tx), RandomCutout's (y0, x0)) and, where four words are drawn, the
+                   two runs of ``cut`` (RandomCutout's packed box sizes and colour words)
         Plain storage reads the rings at the sampled rows.  The frame store first assembles the k frames of every
         sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor)."""
         B, lay, dev = self.batch_size, self._layout, slot["dev"]
@@ -912,34 +815,24 @@ class ReplayBuffer(object):
             rows = rows_n = None
         else:
             both, rings, idx2 = self._both, (self.obses, self.next_obses), d64
-        size = rgb = None
+        words = (d32[:3 * B], d32[3 * B:])
         if "cut" in lay:
             c32 = dev[lay["cut"]:lay["cut"] + 24 * B].view(torch.int32)
-            size, rgb = c32[:3 * B], c32[3 * B:]
+            words += (c32[:3 * B], c32[3 * B:])
         return _Sources(both, idx2, d32[:2 * B], d32[3 * B:5 * B], ((rings[0], rows), (rings[1], rows_n), (rings[0], rows)),
-                        off, d32[:3 * B], d32[3 * B:], size, rgb)
+                        off, words)
 
     def _scratch_aug(self, slot, src):
-        """RandomShift / RandomCutout / RandomTranslate: the frames of a minibatch (``src``: _sources), shifted by (dy, dx)
-        resp. with the boxes painted resp. placed at (ty, tx) on the canvas, into the slot's scratch as obs | next_obs |
-        pos; returns the [3B][Ho][Wo][C] view ((Ho, Wo) = output_shape: (H, W) but for a translate).  With ``both`` ONE
-        launch, pos reading the obs rows again (period 2B); with the rings in two allocations one launch per tensor."""
+        """A "scratch" augmentation: the frames of a minibatch (``src``: _sources) augmented by its ``scratch_launch`` --
+        shifted, boxes painted, placed on the canvas -- into the slot's scratch as obs | next_obs | pos; returns the
+        [3B][Ho][Wo][C] view ((Ho, Wo) = output_shape).  With ``both`` ONE launch, pos reading the obs rows again (period
+        2B); with the rings in two allocations one launch per tensor."""
         B = self.batch_size
-        c = self.obs_shape[0]
         oh, ow = self.augmentor.output_shape
-        out = slot["shift_u8"][:3 * B * self._scratch_frame()].view(3 * B, oh, ow, c)
-        if self._is_translate():
-            def launch(ring, rows, period, lo, hi):
-                ops.translate_u8(ring, rows, period, src.dy[lo:hi], src.dx[lo:hi], hi - lo, out[lo:hi])
-        elif self._is_shift():
-            pad = self.augmentor.pad
+        out = slot["shift_u8"][:3 * B * self._scratch_frame()].view(3 * B, oh, ow, self.obs_shape[0])
 
-            def launch(ring, rows, period, lo, hi):
-                ops.random_shift_u8(ring, rows, period, src.dy[lo:hi], src.dx[lo:hi], pad, hi - lo, out[lo:hi])
-        else:
-            def launch(ring, rows, period, lo, hi):
-                ops.cutout_u8(ring, rows, period, src.dy[lo:hi], src.dx[lo:hi], src.size[lo:hi], src.rgb[lo:hi], hi - lo,
-                              out[lo:hi])
+        def launch(ring, rows, period, lo, hi):
+            self.augmentor.scratch_launch(ring, rows, period, [w[lo:hi] for w in src.words], hi - lo, out[lo:hi])
         if src.both is not None:
             launch(src.both, src.idx2, 2 * B, 0, 3 * B)
         else:
@@ -948,7 +841,7 @@ class ReplayBuffer(object):
         return out
 
     def _shift_refs(self, shifted, guard):
-        """(obs, next_obs, pos) handles over a shifted / cut / translated minibatch: an ordinary uint8 ring of 3B rows of
+        """(obs, next_obs, pos) handles over the minibatch in a scratch: an ordinary uint8 ring of 3B rows of
         ``output_shape``, nothing left to crop; obs carries the (obs | next_obs) pair of 2B rows."""
         B = self.batch_size
         hw = tuple(self.augmentor.output_shape)
@@ -962,12 +855,12 @@ class ReplayBuffer(object):
         """The (obs, next_obs, pos) handles of the minibatch whose block and scalars are staged in ``slot`` -- a rotating
         slot (sample_cpc_refs; ``guard`` from _upload_indices) or a captured graph's (graph_refs; ``guard`` None), whose
         launches then write to fixed addresses: the
-        gathers of the frame store (_sources), then by augmentation ring handles (nothing is launched: the first conv
-        layer gathers and crops), the shift / cutout / translate launch(es), or the three jitter / cover / convolution launches."""
+        gathers of the frame store (_sources), then by the augmentation's kind ring handles (nothing is launched: the first
+        conv layer gathers and crops), the launch(es) into the scratch, or the three float launches."""
         B = self.batch_size
         src = self._sources(slot)
         both, idx2, tensors, off = src.both, src.idx2, src.tensors, src.off
-        if self._is_float_aug():
+        if self._kind == "float":
             # obs, next_obs and pos (= a copy of obs) are augmented independently (utils.py:173-182); obs and
             # next_obs are written into the two halves of one [2B] tensor (ObsRef.pair, see below)
             c, h, w = self.obs_shape
@@ -978,7 +871,7 @@ class ReplayBuffer(object):
             obses, next_obses, pos = (ops.ObsRef.from_nhwc(self._float_augmented(ring, rows, slot["dev"], j, outs[j]))
                                       for j, (ring, rows) in enumerate(tensors))
             obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
-        elif self._has_scratch():
+        elif self._kind == "scratch":
             obses, next_obses, pos = self._shift_refs(self._scratch_aug(slot, src), guard)
         else:
             crop = tuple(self.augmentor.output_shape)
@@ -1009,7 +902,7 @@ class ReplayBuffer(object):
         through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""
         if self.device.type != "cuda" or self._h_index_dev is None:
             return False
-        if self._is_float_aug():
+        if self._kind == "float":
             return self.staged_aug
         return self.dedup_frames or self._both is not None
 
@@ -1032,9 +925,9 @@ class ReplayBuffer(object):
             if self.dedup_frames:
                 (g["mb_u8"],) = self._guarded([2 * B * frame + 32], g["guards"])  # (+32: the loaders' slack, as a ring)
                 g["ar2"] = torch.arange(2 * B, device=self.device, dtype=torch.int64)
-            if self._has_scratch():  # the shifted / cut / translated (obs | next_obs | pos) frames, + the loaders' slack
+            if self._kind == "scratch":  # the augmented (obs | next_obs | pos) frames, + the loaders' slack
                 (g["shift_u8"],) = self._guarded([3 * B * self._scratch_frame() + 32], g["guards"])
-            if self._is_float_aug():
+            if self._kind == "float":
                 c, h, w = self.obs_shape
                 both, pos = self._guarded([4 * 2 * B * frame, 4 * B * frame], g["guards"])
                 g["both_f32"] = both.view(torch.float32).view(2 * B, h, w, c)
@@ -1107,14 +1000,14 @@ class ReplayBuffer(object):
         c = self.obs_shape[0]
         oh, ow = self.augmentor.output_shape
         src = self._sources(slot)
-        shifted = self._scratch_aug(slot, src) if self._has_scratch() else None
+        shifted = self._scratch_aug(slot, src) if self._kind == "scratch" else None
         outs = []
         for j, (ring, rows) in enumerate(src.tensors):
             t = torch.empty((B, c, oh, ow), dtype=torch.float32, device=self.device)
             if shifted is not None:  # the shifted frames as they are: rows j B .. of the scratch, zero offsets
                 z = self._shift_zero[:B]
                 ops.crop_nchw(shifted, self._shift_rows[j * B:(j + 1) * B], z, z, B, (oh, ow), out_f32=t)
-            elif self._is_float_aug():
+            elif self._kind == "float":
                 ops.nhwc_to_nchw(self._float_augmented(ring, rows, slot["dev"], j), t)
             else:
                 ops.crop_nchw(ring, rows, src.off[2 * j], src.off[2 * j + 1], B, (oh, ow), out_f32=t)

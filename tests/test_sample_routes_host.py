@@ -2,9 +2,12 @@
 
 ``sample_cpc_refs``, ``sample_cpc`` and ``graph_block`` + ``graph_write`` + ``graph_refs`` are run on CPU buffers under
 the launch-trace hook (nothing is computed) over storage x augmentation x n_step x staging, and every launch is compared,
-argument for argument, with ``tests/sample_route_launches.json``.  The table was written by ``record()`` (``python -m
-tests.test_sample_routes_host``) from the commit BEFORE the three routes were folded into one assembly function, so an
-equal trace says that the fold launches what the three hand-written copies launched.
+argument for argument, with a recorded table.  The table is two files, each written once and never regenerated:
+``tests/sample_route_launches.json`` (``OLD_AUGS``) from the commit BEFORE the three routes were folded into one assembly
+function, so an equal trace says that the fold launches what the three hand-written copies launched; and
+``tests/sample_route_launches_aug.json`` (``NEW_AUGS``: cutout, translate, RandomConv, which came later) by ``record()``
+(``python -m tests.test_sample_routes_host``) from the commit BEFORE the augmentation classes began to describe their own
+sampling path to the buffer, so an equal trace says that the protocol launches what the buffer's class tests launched.
 
 A pointer argument is recorded as (ordinal of its allocation by first appearance, byte offset inside it): ``a3+128``.
 The allocations are whatever tensors the buffer holds, found by walking its attributes through lists, tuples and dicts
@@ -16,7 +19,8 @@ offsets.
 
 The one difference the fold was allowed: on the copy route (``_h_index_dev = None``) with ``n_step = 1`` the launch
 ``curla_gather_transition_scalars`` moved from the end of sampling to directly behind the block copy, i.e. to the front
-of the call's launches (the copy is no launch); there the table's entry is compared after that move.
+of the call's launches (the copy is no launch); there the first table's entry is compared after that move (the second
+table was recorded behind the fold: the move leaves its entries as they are).
 """
 import contextlib
 import hashlib
@@ -32,10 +36,13 @@ from curla_amd import _lib, ops
 from curla_amd.utils import ReplayBuffer
 
 TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "sample_route_launches.json")
+TABLE_AUG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "sample_route_launches_aug.json")
 B = 4
 # c6: capacity * C * H * W is a multiple of 4 (both rings in one allocation); c3: 7 * 429 bytes is not (two allocations)
 GEOMS = {"c6": ((6, 12, 16), 16), "c3": ((3, 11, 13), 7)}
-AUGS = ("identity", "crop", "shift", "jiggle", "jiggle_staged", "cover", "cover_staged")
+OLD_AUGS = ("identity", "crop", "shift", "jiggle", "jiggle_staged", "cover", "cover_staged")  # TABLE
+NEW_AUGS = ("cutout", "cutout_color", "translate", "conv", "conv_staged")  # TABLE_AUG
+AUGS = OLD_AUGS + NEW_AUGS
 SLOT0, GRAPH_SLOT = 1 << 60, 100  # stand-in device addresses of the pinned slots: SLOT0 + 4096 k
 GATHER = "curla_gather_transition_scalars"
 
@@ -74,6 +81,12 @@ def _augmentor(name, hw):
         return curla_amd.RandomCrop(hw, (h - 2, w - 4))
     if name == "shift":
         return curla_amd.RandomShift(hw, pad=2)
+    if name.startswith("cutout"):
+        return curla_amd.RandomCutout(hw, 2, 5, color=name == "cutout_color")
+    if name == "translate":
+        return curla_amd.RandomTranslate(hw, (h + 3, w + 4))  # an odd and an even margin
+    if name.startswith("conv"):
+        return curla_amd.RandomConv(hw, 0.5)  # p < 1: both generator calls of draw_weights
     return (curla_amd.ColorJiggle if name.startswith("jiggle") else curla_amd.NoisyCover)(hw)
 
 
@@ -94,7 +107,7 @@ def _graphable(rb):
     """graph_supported() but for the device type: what it would say of this buffer on the HIP device."""
     if rb._h_index_dev is None:
         return False
-    if isinstance(rb.augmentor, (curla_amd.ColorJiggle, curla_amd.NoisyCover)):
+    if isinstance(rb.augmentor, (curla_amd.ColorJiggle, curla_amd.NoisyCover, curla_amd.RandomConv)):
         return rb.staged_aug
     return rb.dedup_frames or rb._both is not None
 
@@ -235,9 +248,9 @@ def _key(geom, dedup, aug, n_step, in_place, route):
 
 
 def record():
-    """Write the table -- from the commit whose launches are the yardstick."""
-    table = {_key(*cfg, route): run_route(*cfg, route) for cfg in CONFIGS for route in ROUTES}
-    with open(TABLE, "w") as f:
+    """Write the NEW_AUGS table -- from the commit whose launches are the yardstick.  (TABLE is never written again.)"""
+    table = {_key(*cfg, route): run_route(*cfg, route) for cfg in CONFIGS if cfg[2] in NEW_AUGS for route in ROUTES}
+    with open(TABLE_AUG, "w") as f:
         f.write("{\n" + ",\n".join("%s: %s" % (json.dumps(k), json.dumps(v, separators=(",", ":")))
                                    for k, v in table.items()) + "\n}\n")
     return table
@@ -245,12 +258,15 @@ def record():
 
 @pytest.fixture(scope="module")
 def table():
-    with open(TABLE) as f:
-        return json.load(f)
+    with open(TABLE) as f, open(TABLE_AUG) as f_aug:
+        old, new = json.load(f), json.load(f_aug)
+    assert {k.split("/")[2] for k in old} == set(OLD_AUGS) and {k.split("/")[2] for k in new} == set(NEW_AUGS)
+    return {**old, **new}
 
 
 def test_the_table_covers_the_matrix(table):
-    assert sorted(table) == sorted(_key(*cfg, route) for cfg in CONFIGS for route in ROUTES)
+    assert sorted(table) == sorted(_key(*cfg, route) for cfg in CONFIGS for route in ROUTES)  # both files, exactly
+    assert len(table) == 576
     assert {_key(*cfg, "x").split("/")[1] for cfg in CONFIGS} == {"rings", "store"}
     rings = {g: _buffer(g, False, "identity", 1, True)._both is not None for g in GEOMS}
     assert rings == {"c6": True, "c3": False}  # one allocation, two allocations
@@ -291,4 +307,4 @@ def test_every_route_launches_what_the_table_says(table, cfg):
 
 
 if __name__ == "__main__":
-    print("%d entries -> %s" % (len(record()), TABLE))
+    print("%d entries -> %s" % (len(record()), TABLE_AUG))

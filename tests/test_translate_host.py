@@ -296,7 +296,7 @@ def test_the_other_buffers_never_launch_a_translate(name):
     calls, _ = _traced(lambda: (rb.sample_cpc_refs(), rb.sample_cpc()))
     names = [n for n, _ in calls]
     assert "curla_sample_stage" in names and "curla_translate_u8" not in names
-    assert hasattr(rb, "_shift_store") == (name in ("random_shift", "cutout_color")) and not rb._is_translate()
+    assert hasattr(rb, "_shift_store") == (name in ("random_shift", "cutout_color")) and not isinstance(rb.augmentor, curla_amd.RandomTranslate)
     if hasattr(rb, "_shift_store"):  # the scratch of a shift / cutout keeps frames of the stored size
         assert rb._scratch_frame() == rb._frame
         assert rb._shift_store.shape[1] == (3 * B * rb._frame + 32 + 255) // 256 * 256
