@@ -6,6 +6,7 @@
 // Both kernels read the uint8 NHWC replay ring directly (gather by frame index fused in) and write the
 // float32 NHWC minibatch [B][H][W][C] in [0,255] that the first conv kernel consumes (src kind 2).
 #include "common.h"
+#include "u8_mover.h"  // RandomShift and RandomTranslate; U8_UNROLL and u32x4 for RandomCutout below
 
 namespace {
 
@@ -312,103 +313,6 @@ __global__ void gather_nhwc_kernel(const uint8_t* frames, const int64_t* idx, in
   }
 }
 
-// ---- RandomShift (beyond the reference: the pad-and-crop shift of DrQ / DrQ-v2) ----
-// out[s][y][x][c] = in[row(s)][clamp(y + dy[s] - pad, 0, H - 1)][clamp(x + dx[s] - pad, 0, W - 1)][c], uint8 NHWC in and
-// out: a frame padded by `pad` replicated edge pixels on every side, then an H x W window cut at (dy, dx).  A byte
-// mover (roof: HBM).  A thread owns 16 consecutive output bytes of a sample (one 16-byte store); grid row = sample, so
-// the only division is r / (W C) once per group.  The shift is the same for every channel, so in bytes it is
-// (dx - pad) C along a row and byte b of an output row comes from byte b + (dx - pad) C of the source row wherever
-// that lies inside the row: a group that sits in ONE output row and whose 16 source bytes need no x-clamp is one
-// unaligned 16-byte load (it cannot leave the source row, hence not the ring).  Row clamping only picks the source
-// row.  Groups that straddle two rows or touch the replicated left / right pixels walk their bytes ((y, x, c) are
-// stepped, not divided); so does every group when a frame is not a whole number of 16-byte groups or `out` is off
-// the 16-byte grid (vec == false: byte stores, the last group of a sample is short).
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-struct ShiftGeom {
-  int H, W, C, oy, ox;  // oy / ox = dy - pad / dx - pad of the sample
-  unsigned rb, frame;   // bytes of a row / of a frame
-};
-
-// one group, byte by byte: (y, x, c) of its first byte are stepped through the 16 bytes, each read at its clamped source
-__device__ __forceinline__ void shift_group_bytes(const uint8_t* src, uint8_t* dst, const ShiftGeom& q, unsigned r,
-                                                  bool vec) {
-  const unsigned cnt = min(16u, q.frame - r);
-  const unsigned y = r / q.rb;
-  const int xb = (int)(r - y * q.rb);
-  int yy = (int)y, x = xb / q.C, c = xb - x * q.C;
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (unsigned e = 0; e < 16; ++e) {
-    if (e < cnt) {
-      const int ys = min(max(yy + q.oy, 0), q.H - 1), xs = min(max(x + q.ox, 0), q.W - 1);
-      const uint8_t b = src[(size_t)ys * q.rb + (unsigned)(xs * q.C + c)];
-      if (vec)
-        w[e >> 2] |= (uint32_t)b << (8 * (e & 3));
-      else
-        dst[r + e] = b;
-      if (++c == q.C) {
-        c = 0;
-        if (++x == q.W) x = 0, ++yy;
-      }
-    }
-  }
-  if (vec) *reinterpret_cast<u32x4*>(dst + r) = u32x4{w[0], w[1], w[2], w[3]};
-}
-
-// A thread takes SHIFT_UNROLL groups per trip, a grid stride apart, and issues the loads of all its fast groups before
-// the first store: a wave has up to 4 KiB in flight.  Measured: what sets the time is not the
-// fast path but the byte-wise groups -- a wave that holds one runs the 16 byte loads for it, and at rows of 756 bytes
-// (84 x 84 x 9: 47.25 groups) every wave holds a row-straddling group.
-constexpr int SHIFT_UNROLL = 4;
-
-__global__ __launch_bounds__(256) void random_shift_u8_kernel(const uint8_t* frames, const int64_t* idx, int period,
-                                                                const int32_t* dy, const int32_t* dx, int pad, int n,
-                                                                int H, int W, int C, unsigned groups, bool vec,
-                                                                uint8_t* out) {
-  ShiftGeom q;
-  q.H = H, q.W = W, q.C = C, q.rb = (unsigned)W * C, q.frame = (unsigned)H * q.rb;
-  const unsigned stride = gridDim.x * 256;
-  for (int s = blockIdx.y; s < n; s += gridDim.y) {
-    const int p = s % period;
-    const int64_t row = idx ? idx[p] : (int64_t)p;
-    // (offsets outside [0, 2 pad] are clamped into it: whatever the block holds, every read stays inside the frame)
-    q.oy = min(max(dy[s], 0), 2 * pad) - pad, q.ox = min(max(dx[s], 0), 2 * pad) - pad;
-    const int sx = q.ox * C;
-    const uint8_t* src = frames + (size_t)row * q.frame;
-    uint8_t* dst = out + (size_t)s * q.frame;
-    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += SHIFT_UNROLL * stride) {
-      u32x4 v[SHIFT_UNROLL];
-      bool fast[SHIFT_UNROLL];
-#pragma unroll
-      for (int u = 0; u < SHIFT_UNROLL; ++u) {
-        const unsigned g = g0 + u * stride;
-        fast[u] = false;
-        if (vec && g < groups) {
-          const unsigned r = 16 * g;
-          const unsigned y = r / q.rb;
-          const int xb = (int)(r - y * q.rb);
-          if (xb + 16 <= (int)q.rb && xb + sx >= 0 && xb + sx + 16 <= (int)q.rb) {
-            const int ys = min(max((int)y + q.oy, 0), H - 1);
-            __builtin_memcpy(&v[u], src + (size_t)ys * q.rb + (xb + sx), 16);  // one unaligned global_load_dwordx4
-            fast[u] = true;
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < SHIFT_UNROLL; ++u) {
-        const unsigned g = g0 + u * stride;
-        if (g < groups) {
-          if (fast[u])
-            *reinterpret_cast<u32x4*>(dst + 16 * g) = v[u];
-          else
-            shift_group_bytes(src, dst, q, 16 * g, vec);
-        }
-      }
-    }
-  }
-}
-
 // ---- RandomCutout (beyond the reference: RAD's cutout / cutout-color) ----
 // out[s][y][x][c] = colour(s)[c % 3] inside the sample's box [y0, y0 + bh) x [x0, x0 + bw), frames[row(s)][y][x][c]
 // elsewhere; uint8 NHWC in and out, all frames of a stack share the box.  Like the shift a byte mover whose thread owns
@@ -420,6 +324,9 @@ __global__ __launch_bounds__(256) void random_shift_u8_kernel(const uint8_t* fra
 // (cut_blend) -- arithmetic only, no byte-wise memory access: in the shift kernel the byte loads of such groups set the
 // time.  Byte-wise loads and stores are left to frames that are no whole number of groups and to an
 // `out` off the 16-byte grid (vec == false), as there.
+// The frame of the kernel (sample loop, byte loop, U8_UNROLL groups per trip with their loads before the first store) is
+// u8_mover_kernel's written out once more: as an Op of that skeleton, with the same registers, LDS reads and occupancy
+// as here, the cutout ran 48.3 us where this kernel runs 45.1 us (84 x 84 x 9, n = 1536).
 struct CutGeom {
   unsigned rb, frame;  // bytes of a row / of a frame
   int C, y0, y1;       // box rows [y0, y1)
@@ -465,8 +372,6 @@ __device__ __forceinline__ void cut_group_bytes(const uint8_t* src, uint8_t* dst
   }
 }
 
-constexpr int CUT_UNROLL = 4;  // groups per thread and trip, their loads issued before the first store (as SHIFT_UNROLL)
-
 __global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, const int64_t* idx, int period,
                                                           const int32_t* y0, const int32_t* x0, const int32_t* size,
                                                           const int32_t* rgb, int n, int H, int W, int C,
@@ -498,12 +403,12 @@ __global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, c
       for (unsigned g = blockIdx.x * 256 + threadIdx.x; g < groups; g += stride) cut_group_bytes(src, dst, q, 16 * g);
       continue;
     }
-    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += CUT_UNROLL * stride) {
-      u32x4 v[CUT_UNROLL];
-      int kind[CUT_UNROLL];  // 0 outside the box, 1 inside, 2 both
-      unsigned gy[CUT_UNROLL], gxb[CUT_UNROLL];
+    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += U8_UNROLL * stride) {
+      u32x4 v[U8_UNROLL];
+      int kind[U8_UNROLL];  // 0 outside the box, 1 inside, 2 both
+      unsigned gy[U8_UNROLL], gxb[U8_UNROLL];
 #pragma unroll
-      for (int u = 0; u < CUT_UNROLL; ++u) {
+      for (int u = 0; u < U8_UNROLL; ++u) {
         const unsigned g = g0 + u * stride;
         kind[u] = 0, gy[u] = 0, gxb[u] = 0;
         v[u] = u32x4{0u, 0u, 0u, 0u};
@@ -531,7 +436,7 @@ __global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, c
         }
       }
 #pragma unroll
-      for (int u = 0; u < CUT_UNROLL; ++u) {
+      for (int u = 0; u < U8_UNROLL; ++u) {
         const unsigned g = g0 + u * stride;
         if (g < groups) {
           u32x4 o = v[u];
@@ -544,156 +449,6 @@ __global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, c
             o = cut_blend(q, o, gy[u], gxb[u]);
           }
           *reinterpret_cast<u32x4*>(dst + 16 * g) = o;
-        }
-      }
-    }
-  }
-}
-
-// ---- RandomTranslate (beyond the reference: RAD's translate) ----
-// out[s][y][x][c] = frames[row(s)][y - ty][x - tx][c] where 0 <= y - ty < H and 0 <= x - tx < W, 0 elsewhere: the H x W
-// frame placed at (ty, tx) on a black Ho x Wo canvas; uint8 NHWC in and out, all channels of a stack share the offset
-// (clamped into [0, Ho - H] x [0, Wo - W]).  The first of these byte movers whose output frame is larger than its source
-// frame: a thread owns 16 consecutive OUTPUT bytes of a sample (one 16-byte store), grid row = sample.  In output order
-// the bytes of an output row that lie inside the image are ONE run, bytes [tx C, tx C + W C) of the row, and along such a
-// run the source address steps with the output address.  So per output row that a group touches (two at most where rows
-// are no shorter than a group) there is at most one run [lo, hi) of the group's bytes, with group byte e = source-frame
-// byte base + e: ONE unaligned 16-byte load at base, masked to [lo, hi).  The three kinds of groups are then one code:
-//   margin  no run: a store of zeros, nothing is loaded;
-//   inside  one run [0, 16): the load is stored as it is;
-//   mixed   (crosses the image's left / right edge or straddles two output rows) one or two runs: the loads are masked
-//           and OR-ed in registers -- no byte-wise memory access (in the shift kernel the byte loads of such groups set
-//           the time).
-// `base` may lie up to 15 bytes in front of the source frame (the image's first row behind a left margin) or less than 16
-// bytes in front of its end: the load address is clamped into [0, frame - 16] and the 16 bytes are shifted by the
-// difference, so nothing outside the source frame is read -- ring row 0 has nothing in front of it, and the slack behind
-// a ring is not relied on.  Where the canvas is no wider than the frame (Wo == W) the runs of two rows are one run of the
-// source and take one load.  Groups that touch three or more rows (rows shorter than a group) walk their rows in a loop
-// with the same run arithmetic.  Byte-wise loads and stores are left to output frames of no whole number of groups, an
-// `out` off the 16-byte grid and source frames shorter than a group (vec == false), as in the shift and the cutout.
-typedef unsigned __int128 u128;
-
-struct TrGeom {
-  int H, ty, txb;           // image rows [ty, ty + H) of the canvas, image columns in bytes of an output row from txb on
-  int srb, orb;             // bytes of a source row / of an output row
-  unsigned sframe, oframe;  // bytes of a source frame / of an output frame
-};
-
-// The run of output row yy inside a group: `rel` = the group byte at which row yy starts (negative: the row started in
-// front of the group).  Group bytes [lo, hi) are the row's bytes inside the image, group byte e is source-frame byte
-// base + e.  False: row yy has no image byte in the group.
-__device__ __forceinline__ bool tr_run(const TrGeom& q, int yy, int rel, int& lo, int& hi, int& base) {
-  lo = max(rel + q.txb, 0), hi = min(rel + q.txb + q.srb, 16);
-  base = (yy - q.ty) * q.srb - rel - q.txb;
-  return yy >= q.ty && yy < q.ty + q.H && lo < hi;
-}
-
-// The 16-byte load of a run, at its address clamped into the source frame; returns lo | hi << 8 | (d + 16) << 16 (never 0:
-// hi >= 1), d = the bytes the load sits in front of (d > 0) or behind (d < 0) `base`.  Every byte of [lo, hi) is in the
-// load: base + e is a byte of the frame, and the clamp moves the address only as far as the frame's ends.
-__device__ __forceinline__ int tr_load(const uint8_t* src, const TrGeom& q, int lo, int hi, int base, u32x4& v) {
-  const int a = min(max(base, 0), (int)q.sframe - 16);
-  __builtin_memcpy(&v, src + a, 16);  // one unaligned global_load_dwordx4
-  return lo | (hi << 8) | ((base - a + 16) << 16);
-}
-
-// the loaded bytes moved to their places in the group (only the runs at the two ends of a frame are shifted), all
-// others zero
-__device__ __forceinline__ u128 tr_place(u32x4 v, int meta) {
-  const int lo = meta & 0xff, hi = (meta >> 8) & 0xff, d = (meta >> 16) - 16;
-  u128 x = __builtin_bit_cast(u128, v);
-  if (d > 0) x >>= 8 * d;
-  if (d < 0) x <<= -8 * d;
-  if (hi - lo < 16) x &= (~(u128)0 >> (8 * (16 - (hi - lo)))) << (8 * lo);
-  return x;
-}
-
-// a group that touches three or more output rows (rows shorter than a group): its rows one by one
-__device__ __forceinline__ u128 tr_group_rows(const uint8_t* src, const TrGeom& q, unsigned r) {
-  const unsigned y = r / (unsigned)q.orb;
-  u128 o = 0;
-  int yy = (int)y;
-  for (int rel = (int)(y * (unsigned)q.orb) - (int)r; rel < 16; rel += q.orb, ++yy) {
-    int lo, hi, base;
-    if (tr_run(q, yy, rel, lo, hi, base)) {
-      u32x4 v;
-      const int meta = tr_load(src, q, lo, hi, base, v);
-      o |= tr_place(v, meta);
-    }
-  }
-  return o;
-}
-
-// one (possibly short) group byte by byte: (row, byte in row) are stepped, not divided
-__device__ __forceinline__ void tr_group_bytes(const uint8_t* src, uint8_t* dst, const TrGeom& q, unsigned r) {
-  const unsigned cnt = min(16u, q.oframe - r);
-  const unsigned y = r / (unsigned)q.orb;
-  int yy = (int)y, xb = (int)(r - y * (unsigned)q.orb);
-  for (unsigned e = 0; e < cnt; ++e) {
-    const bool inside = yy >= q.ty && yy < q.ty + q.H && xb >= q.txb && xb < q.txb + q.srb;
-    dst[r + e] = inside ? src[(size_t)(yy - q.ty) * q.srb + (unsigned)(xb - q.txb)] : (uint8_t)0;
-    if (++xb == q.orb) xb = 0, ++yy;
-  }
-}
-
-constexpr int TR_UNROLL = 4;  // groups per thread and trip, their loads issued before the first store (as SHIFT_UNROLL)
-
-__global__ __launch_bounds__(256) void translate_u8_kernel(const uint8_t* frames, const int64_t* idx, int period,
-                                                             const int32_t* ty, const int32_t* tx, int n, int H, int W,
-                                                             int C, int Ho, int Wo, unsigned groups, bool vec,
-                                                             uint8_t* out) {
-  TrGeom q;
-  q.H = H, q.srb = W * C, q.orb = Wo * C, q.sframe = (unsigned)H * q.srb, q.oframe = (unsigned)Ho * q.orb;
-  const bool flat = q.srb == q.orb;  // no margin left or right: the image rows follow one another in the output too
-  const unsigned stride = gridDim.x * 256;
-  for (int s = blockIdx.y; s < n; s += gridDim.y) {
-    const int p = s % period;
-    const int64_t row = idx ? idx[p] : (int64_t)p;
-    // (offsets outside their ranges are clamped into them: whatever the block holds, the image lies on the canvas)
-    q.ty = min(max(ty[s], 0), Ho - H), q.txb = min(max(tx[s], 0), Wo - W) * C;
-    const uint8_t* src = frames + (size_t)row * q.sframe;
-    uint8_t* dst = out + (size_t)s * q.oframe;
-    if (!vec) {
-      for (unsigned g = blockIdx.x * 256 + threadIdx.x; g < groups; g += stride) tr_group_bytes(src, dst, q, 16 * g);
-      continue;
-    }
-    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += TR_UNROLL * stride) {
-      u32x4 v[TR_UNROLL][2];
-      int meta[TR_UNROLL][2];  // of the runs of the group's first and second row; 0: no run
-      bool rows3[TR_UNROLL];   // the group touches three or more rows
-#pragma unroll
-      for (int u = 0; u < TR_UNROLL; ++u) {
-        const unsigned g = g0 + u * stride;
-        meta[u][0] = meta[u][1] = 0, rows3[u] = false;
-        v[u][0] = v[u][1] = u32x4{0u, 0u, 0u, 0u};
-        if (g < groups) {
-          const unsigned r = 16 * g;
-          const unsigned y = r / (unsigned)q.orb;
-          const int xb = (int)(r - y * (unsigned)q.orb);
-          if (xb + 15 >= 2 * q.orb) {
-            rows3[u] = true;
-          } else {
-            int lo0, hi0, b0, lo1, hi1, b1;
-            const bool r0 = tr_run(q, (int)y, -xb, lo0, hi0, b0);
-            bool r1 = tr_run(q, (int)y + 1, q.orb - xb, lo1, hi1, b1);  // (a group inside one row: lo1 >= 16, no run)
-            if (flat && r0 && r1) hi0 = hi1, r1 = false;                // b1 == b0, lo1 == hi0: one run of the source
-            if (r0) meta[u][0] = tr_load(src, q, lo0, hi0, b0, v[u][0]);
-            if (r1) meta[u][1] = tr_load(src, q, lo1, hi1, b1, v[u][1]);
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < TR_UNROLL; ++u) {
-        const unsigned g = g0 + u * stride;
-        if (g < groups) {
-          u128 o = 0;
-          if (rows3[u]) {
-            o = tr_group_rows(src, q, 16 * g);
-          } else {
-            if (meta[u][0]) o = tr_place(v[u][0], meta[u][0]);
-            if (meta[u][1]) o |= tr_place(v[u][1], meta[u][1]);
-          }
-          *reinterpret_cast<u32x4*>(dst + 16 * g) = __builtin_bit_cast(u32x4, o);
         }
       }
     }
@@ -958,15 +713,9 @@ int curla_random_shift_u8(const uint8_t* frames, const int64_t* idx, int period,
   CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 3) == 0 &&
                 (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
   const long long frame = (long long)H * W * C;
-  // (bytes inside a frame and the byte shift (dx - pad) C are 32-bit quantities in the kernel)
-  if (frame >= (1LL << 31) - 16 || 2LL * pad * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;
-  const bool vec = frame % 16 == 0 && aligned16(out);
-  const unsigned groups = (unsigned)((frame + 15) / 16);
-  const unsigned gx = (groups + 1023) / 1024;  // (256 threads of SHIFT_UNROLL = 4 groups)
-  const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
-  hipLaunchKernelGGL(random_shift_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period,
-                     dy, dx, pad, n, H, W, C, groups, vec, out);
-  return curla_launch_status();
+  if (2LL * pad * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;  // (the byte shift (dx - pad) C is a 32-bit quantity in the kernel)
+  const ShiftOp op{dy, dx, pad, H, W, C, (unsigned)frame, (unsigned)frame};
+  return launch_u8_mover(op, frames, idx, period, n, frame, true, out, stream);
 }
 
 int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* y0, const int32_t* x0,
@@ -978,7 +727,7 @@ int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const
   if (frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;  // (bytes inside a frame are 32-bit quantities in the kernel)
   const bool vec = frame % 16 == 0 && aligned16(out);
   const unsigned groups = (unsigned)((frame + 15) / 16);
-  const unsigned per_block = vec ? 256 * CUT_UNROLL : 256;
+  const unsigned per_block = vec ? 256 * U8_UNROLL : 256;
   const unsigned gx = (groups + per_block - 1) / per_block;
   const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
   hipLaunchKernelGGL(cutout_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period, y0, x0,
@@ -992,17 +741,10 @@ int curla_translate_u8(const uint8_t* frames, const int64_t* idx, int period, co
   CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(ty) | reinterpret_cast<uintptr_t>(tx)) & 3) == 0 &&
                 (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
   const long long sframe = (long long)H * W * C, oframe = (long long)Ho * Wo * C;
-  // (bytes inside an output frame, hence inside a source frame and the byte offset tx C, are 32-bit quantities in the
-  // kernel, and so is twice an output row: the run arithmetic reaches 2 Wo C)
-  if (oframe >= (1LL << 31) - 16 || (long long)Wo * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;
-  const bool vec = oframe % 16 == 0 && aligned16(out) && sframe >= 16;  // (a load of 16 bytes must fit the source frame)
-  const unsigned groups = (unsigned)((oframe + 15) / 16);
-  const unsigned per_block = vec ? 256 * TR_UNROLL : 256;
-  const unsigned gx = (groups + per_block - 1) / per_block;
-  const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
-  hipLaunchKernelGGL(translate_u8_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period, ty,
-                     tx, n, H, W, C, Ho, Wo, groups, vec, out);
-  return curla_launch_status();
+  // (twice an output row is a 32-bit quantity in the kernel: the run arithmetic reaches 2 Wo C)
+  if ((long long)Wo * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;
+  const TrOp op{ty, tx, H, W, C, Ho, Wo, (unsigned)sframe, (unsigned)oframe};
+  return launch_u8_mover(op, frames, idx, period, n, oframe, sframe >= 16, out, stream);  // (a load of 16 bytes must fit the source frame)
 }
 
 int curla_random_conv(const uint8_t* frames, const int64_t* idx, const float* weights, int B, int C, int H, int W,

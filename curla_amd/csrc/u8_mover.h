@@ -1,0 +1,283 @@
+// The uint8 byte movers RandomShift and RandomTranslate of augment.hip: one kernel skeleton and one launch path, and one
+// `Op` per augmentation that says what a group of 16 output bytes loads and what becomes of it.  (RandomCutout is the same
+// frame written out once more in augment.hip: on this skeleton it was measured 7 % slower, see there and DESIGN.md.)
+//
+// A mover gathers a frame of the uint8 NHWC ring per sample (row(s) = idx ? idx[s % period] : s % period) and writes a
+// uint8 NHWC frame per sample (roof: HBM).  A thread owns 16 consecutive OUTPUT bytes of a sample, a "group" (one 16-byte
+// store); grid row = sample, so the only division is r / (row bytes) once per group.  A thread takes U8_UNROLL groups per
+// trip, a grid stride apart, and issues the loads of all of them before the first store: a wave has up to 4 KiB in
+// flight.  Byte-wise stores are left to output frames of no whole number of groups and to an `out` off the 16-byte grid
+// (vec == false; the last group of a sample is then short).
+//
+// An Op holds the entry point's pointers and geometry (it is a kernel argument and never written) and provides
+//   src_frame, out_frame              bytes of a source / an output frame;
+//   Geom sample(s)                    sample s's parameters, clamped so that whatever the parameter block holds nothing
+//                                     outside a frame is read or written; passed by value to the three below, so that it
+//                                     lives in registers (a mutated Op would live in private memory);
+//   load(q, src, r, held)             the loads of the group at output byte r (a multiple of 16), into a Held;
+//   u32x4 finish(q, src, r, held)     the group's 16 output bytes;
+//   group_bytes(q, src, dst, r)       the (possibly short) group byte by byte.
+#pragma once
+#include "common.h"
+
+namespace {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned __int128 u128;
+
+constexpr int U8_UNROLL = 4;  // groups per thread and trip
+
+template <class Op>
+__global__ __launch_bounds__(256) void u8_mover_kernel(const uint8_t* frames, const int64_t* idx, int period, int n,
+                                                         unsigned groups, bool vec, const Op op, uint8_t* out) {
+  const unsigned stride = gridDim.x * 256;
+  for (int s = blockIdx.y; s < n; s += gridDim.y) {
+    const int p = s % period;
+    const int64_t row = idx ? idx[p] : (int64_t)p;
+    const typename Op::Geom q = op.sample(s);
+    const uint8_t* src = frames + (size_t)row * op.src_frame;
+    uint8_t* dst = out + (size_t)s * op.out_frame;
+    if (!vec) {
+      for (unsigned g = blockIdx.x * 256 + threadIdx.x; g < groups; g += stride) Op::group_bytes(q, src, dst, 16 * g);
+      continue;
+    }
+    for (unsigned g0 = blockIdx.x * 256 + threadIdx.x; g0 < groups; g0 += U8_UNROLL * stride) {
+      typename Op::Held held[U8_UNROLL];
+#pragma unroll
+      for (int u = 0; u < U8_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        if (g < groups) Op::load(q, src, 16 * g, held[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < U8_UNROLL; ++u) {
+        const unsigned g = g0 + u * stride;
+        if (g < groups) *reinterpret_cast<u32x4*>(dst + 16 * g) = Op::finish(q, src, 16 * g, held[u]);
+      }
+    }
+  }
+}
+
+// `out_frame` in 64 bits: bytes inside an output frame (hence inside a source frame, which is never larger) are 32-bit
+// quantities in the kernel.  vec_extra: what the Op's 16-byte loads ask for beyond whole groups and an aligned `out`.
+template <class Op>
+int launch_u8_mover(const Op& op, const uint8_t* frames, const int64_t* idx, int period, int n, long long out_frame,
+                    bool vec_extra, uint8_t* out, void* stream) {
+  if (out_frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;
+  const bool vec = out_frame % 16 == 0 && aligned16(out) && vec_extra;
+  const unsigned groups = (unsigned)((out_frame + 15) / 16);
+  const unsigned per_block = vec ? 256 * U8_UNROLL : 256;
+  const unsigned gx = (groups + per_block - 1) / per_block;
+  const dim3 grid(gx < 64 ? gx : 64, n < 65535 ? n : 65535);
+  hipLaunchKernelGGL(u8_mover_kernel<Op>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, idx, period, n,
+                     groups, vec, op, out);
+  return curla_launch_status();
+}
+
+// ---- RandomShift (beyond the reference: the pad-and-crop shift of DrQ / DrQ-v2) ----
+// out[s][y][x][c] = in[row(s)][clamp(y + dy[s] - pad, 0, H - 1)][clamp(x + dx[s] - pad, 0, W - 1)][c]: a frame padded by
+// `pad` replicated edge pixels on every side, then an H x W window cut at (dy, dx).  The shift is the same for every
+// channel, so in bytes it is (dx - pad) C along a row and byte b of an output row comes from byte b + (dx - pad) C of the
+// source row wherever that lies inside the row: a group that sits in ONE output row and whose 16 source bytes need no
+// x-clamp is one unaligned 16-byte load (it cannot leave the source row, hence not the ring).  Row clamping only picks
+// the source row.  Groups that straddle two rows or touch the replicated left / right pixels walk their bytes ((y, x, c)
+// are stepped, not divided).  Measured: what sets the time is not the fast path but these byte-wise
+// groups -- a wave that holds one runs the 16 byte loads for it, and at rows of 756 bytes (84 x 84 x 9: 47.25 groups)
+// every wave holds a row-straddling group.
+struct ShiftGeom {
+  int H, W, C, oy, ox;  // oy / ox = dy - pad / dx - pad of the sample
+  unsigned rb, frame;   // bytes of a row / of a frame
+};
+
+struct ShiftOp {
+  using Geom = ShiftGeom;
+  const int32_t *dy, *dx;
+  int pad, H, W, C;
+  unsigned src_frame, out_frame;
+
+  struct Held {
+    u32x4 v;
+    bool fast = false;
+  };
+
+  __device__ __forceinline__ Geom sample(int s) const {
+    Geom q;
+    q.H = H, q.W = W, q.C = C, q.rb = (unsigned)W * C, q.frame = (unsigned)H * q.rb;
+    // (offsets outside [0, 2 pad] are clamped into it: whatever the block holds, every read stays inside the frame)
+    q.oy = min(max(dy[s], 0), 2 * pad) - pad, q.ox = min(max(dx[s], 0), 2 * pad) - pad;
+    return q;
+  }
+
+  // byte e of the group at byte r, read at its clamped source, for e < cnt: (y, x, c) of the first byte are stepped
+  template <class Put>
+  static __device__ __forceinline__ void walk(const Geom& q, const uint8_t* src, unsigned r, unsigned cnt, Put put) {
+    const unsigned y = r / q.rb;
+    const int xb = (int)(r - y * q.rb);
+    int yy = (int)y, x = xb / q.C, c = xb - x * q.C;
+#pragma unroll
+    for (unsigned e = 0; e < 16; ++e) {
+      if (e < cnt) {
+        const int ys = min(max(yy + q.oy, 0), q.H - 1), xs = min(max(x + q.ox, 0), q.W - 1);
+        put(e, src[(size_t)ys * q.rb + (unsigned)(xs * q.C + c)]);
+        if (++c == q.C) {
+          c = 0;
+          if (++x == q.W) x = 0, ++yy;
+        }
+      }
+    }
+  }
+
+  static __device__ __forceinline__ void load(const Geom& q, const uint8_t* src, unsigned r, Held& h) {
+    const int sx = q.ox * q.C;
+    const unsigned y = r / q.rb;
+    const int xb = (int)(r - y * q.rb);
+    if (xb + 16 <= (int)q.rb && xb + sx >= 0 && xb + sx + 16 <= (int)q.rb) {
+      const int ys = min(max((int)y + q.oy, 0), q.H - 1);
+      __builtin_memcpy(&h.v, src + (size_t)ys * q.rb + (xb + sx), 16);  // one unaligned global_load_dwordx4
+      h.fast = true;
+    }
+  }
+
+  static __device__ __forceinline__ u32x4 finish(const Geom& q, const uint8_t* src, unsigned r, const Held& h) {
+    if (h.fast) return h.v;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    walk(q, src, r, 16u, [&](unsigned e, uint8_t b) { w[e >> 2] |= (uint32_t)b << (8 * (e & 3)); });
+    return u32x4{w[0], w[1], w[2], w[3]};
+  }
+
+  static __device__ __forceinline__ void group_bytes(const Geom& q, const uint8_t* src, uint8_t* dst, unsigned r) {
+    walk(q, src, r, min(16u, q.frame - r), [&](unsigned e, uint8_t b) { dst[r + e] = b; });
+  }
+};
+
+// ---- RandomTranslate (beyond the reference: RAD's translate) ----
+// out[s][y][x][c] = frames[row(s)][y - ty][x - tx][c] where 0 <= y - ty < H and 0 <= x - tx < W, 0 elsewhere: the H x W
+// frame placed at (ty, tx) on a black Ho x Wo canvas; all channels of a stack share the offset (clamped into
+// [0, Ho - H] x [0, Wo - W]).  The one byte mover whose output frame is larger than its source frame.  In output order
+// the bytes of an output row that lie inside the image are ONE run, bytes [tx C, tx C + W C) of the row, and along such a
+// run the source address steps with the output address.  So per output row that a group touches (two at most where rows
+// are no shorter than a group) there is at most one run [lo, hi) of the group's bytes, with group byte e = source-frame
+// byte base + e: ONE unaligned 16-byte load at base, masked to [lo, hi).  The three kinds of groups are then one code:
+//   margin  no run: a store of zeros, nothing is loaded;
+//   inside  one run [0, 16): the load is stored as it is;
+//   mixed   (crosses the image's left / right edge or straddles two output rows) one or two runs: the loads are masked
+//           and OR-ed in registers -- no byte-wise memory access (in the shift the byte loads of such groups set the time,
+//           DESIGN.md section 4).
+// `base` may lie up to 15 bytes in front of the source frame (the image's first row behind a left margin) or less than 16
+// bytes in front of its end: the load address is clamped into [0, frame - 16] and the 16 bytes are shifted by the
+// difference, so nothing outside the source frame is read -- ring row 0 has nothing in front of it, and the slack behind
+// a ring is not relied on.  Where the canvas is no wider than the frame (Wo == W) the runs of two rows are one run of the
+// source and take one load.  Groups that touch three or more rows (rows shorter than a group) walk their rows in a loop
+// with the same run arithmetic.  Source frames shorter than a group go byte by byte as well (vec_extra).
+struct TrGeom {
+  int H, ty, txb;           // image rows [ty, ty + H) of the canvas, image columns in bytes of an output row from txb on
+  int srb, orb;             // bytes of a source row / of an output row
+  unsigned sframe, oframe;  // bytes of a source frame / of an output frame
+  bool flat;                // no margin left or right: the image rows follow one another in the output too
+};
+
+// The run of output row yy inside a group: `rel` = the group byte at which row yy starts (negative: the row started in
+// front of the group).  Group bytes [lo, hi) are the row's bytes inside the image, group byte e is source-frame byte
+// base + e.  False: row yy has no image byte in the group.
+__device__ __forceinline__ bool tr_run(const TrGeom& q, int yy, int rel, int& lo, int& hi, int& base) {
+  lo = max(rel + q.txb, 0), hi = min(rel + q.txb + q.srb, 16);
+  base = (yy - q.ty) * q.srb - rel - q.txb;
+  return yy >= q.ty && yy < q.ty + q.H && lo < hi;
+}
+
+// The 16-byte load of a run, at its address clamped into the source frame; returns lo | hi << 8 | (d + 16) << 16 (never
+// 0: hi >= 1), d = the bytes the load sits in front of (d > 0) or behind (d < 0) `base`.  Every byte of [lo, hi) is in
+// the load: base + e is a byte of the frame, and the clamp moves the address only as far as the frame's ends.
+__device__ __forceinline__ int tr_load(const uint8_t* src, const TrGeom& q, int lo, int hi, int base, u32x4& v) {
+  const int a = min(max(base, 0), (int)q.sframe - 16);
+  __builtin_memcpy(&v, src + a, 16);  // one unaligned global_load_dwordx4
+  return lo | (hi << 8) | ((base - a + 16) << 16);
+}
+
+// the loaded bytes moved to their places in the group (only the runs at the two ends of a frame are shifted), all
+// others zero
+__device__ __forceinline__ u128 tr_place(u32x4 v, int meta) {
+  const int lo = meta & 0xff, hi = (meta >> 8) & 0xff, d = (meta >> 16) - 16;
+  u128 x = __builtin_bit_cast(u128, v);
+  if (d > 0) x >>= 8 * d;
+  if (d < 0) x <<= -8 * d;
+  if (hi - lo < 16) x &= (~(u128)0 >> (8 * (16 - (hi - lo)))) << (8 * lo);
+  return x;
+}
+
+// a group that touches three or more output rows (rows shorter than a group): its rows one by one
+__device__ __forceinline__ u128 tr_group_rows(const uint8_t* src, const TrGeom& q, unsigned r) {
+  const unsigned y = r / (unsigned)q.orb;
+  u128 o = 0;
+  int yy = (int)y;
+  for (int rel = (int)(y * (unsigned)q.orb) - (int)r; rel < 16; rel += q.orb, ++yy) {
+    int lo, hi, base;
+    if (tr_run(q, yy, rel, lo, hi, base)) {
+      u32x4 v;
+      const int meta = tr_load(src, q, lo, hi, base, v);
+      o |= tr_place(v, meta);
+    }
+  }
+  return o;
+}
+
+struct TrOp {
+  using Geom = TrGeom;
+  const int32_t *ty, *tx;
+  int H, W, C, Ho, Wo;
+  unsigned src_frame, out_frame;
+
+  struct Held {
+    u32x4 v[2] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
+    int meta[2] = {0, 0};  // of the runs of the group's first and second row; 0: no run
+    bool rows3 = false;    // the group touches three or more rows
+  };
+
+  __device__ __forceinline__ Geom sample(int s) const {
+    Geom q;
+    q.H = H, q.srb = W * C, q.orb = Wo * C, q.sframe = src_frame, q.oframe = out_frame;
+    q.flat = q.srb == q.orb;
+    // (offsets outside their ranges are clamped into them: whatever the block holds, the image lies on the canvas)
+    q.ty = min(max(ty[s], 0), Ho - H), q.txb = min(max(tx[s], 0), Wo - W) * C;
+    return q;
+  }
+
+  static __device__ __forceinline__ void load(const Geom& q, const uint8_t* src, unsigned r, Held& h) {
+    const unsigned y = r / (unsigned)q.orb;
+    const int xb = (int)(r - y * (unsigned)q.orb);
+    if (xb + 15 >= 2 * q.orb) {
+      h.rows3 = true;
+    } else {
+      int lo0, hi0, b0, lo1, hi1, b1;
+      const bool r0 = tr_run(q, (int)y, -xb, lo0, hi0, b0);
+      bool r1 = tr_run(q, (int)y + 1, q.orb - xb, lo1, hi1, b1);  // (a group inside one row: lo1 >= 16, no run)
+      if (q.flat && r0 && r1) hi0 = hi1, r1 = false;           // b1 == b0, lo1 == hi0: one run of the source
+      if (r0) h.meta[0] = tr_load(src, q, lo0, hi0, b0, h.v[0]);
+      if (r1) h.meta[1] = tr_load(src, q, lo1, hi1, b1, h.v[1]);
+    }
+  }
+
+  static __device__ __forceinline__ u32x4 finish(const Geom& q, const uint8_t* src, unsigned r, const Held& h) {
+    u128 o = 0;
+    if (h.rows3) {
+      o = tr_group_rows(src, q, r);
+    } else {
+      if (h.meta[0]) o = tr_place(h.v[0], h.meta[0]);
+      if (h.meta[1]) o |= tr_place(h.v[1], h.meta[1]);
+    }
+    return __builtin_bit_cast(u32x4, o);
+  }
+
+  // (row, byte in row) are stepped, not divided
+  static __device__ __forceinline__ void group_bytes(const Geom& q, const uint8_t* src, uint8_t* dst, unsigned r) {
+    const unsigned cnt = min(16u, q.oframe - r);
+    const unsigned y = r / (unsigned)q.orb;
+    int yy = (int)y, xb = (int)(r - y * (unsigned)q.orb);
+    for (unsigned e = 0; e < cnt; ++e) {
+      const bool in = yy >= q.ty && yy < q.ty + q.H && xb >= q.txb && xb < q.txb + q.srb;
+      dst[r + e] = in ? src[(size_t)(yy - q.ty) * q.srb + (unsigned)(xb - q.txb)] : (uint8_t)0;
+      if (++xb == q.orb) xb = 0, ++yy;
+    }
+  }
+};
+
+}  // namespace
