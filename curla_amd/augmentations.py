@@ -53,8 +53,8 @@ class IdentityAugmentation:
     #              obs_shape, noise_generator)`` draws one tensor's, ``fill_staged(host, at, drawn)`` writes them at byte
     #              ``at`` of a host copy of the block and ``staged_args(dev, at, B, obs_shape)`` reads ``staged`` back
     #              from there in the device copy.
-    # Any kind may draw ``index_rows`` (0, 2 or 4) int32 words per sample and tensor on the host, ``draw_index_words(n)``:
-    # the first two travel as the block's offset rows, the other two behind them (block_layout: ``cut``).
+    # Any kind may draw ``index_rows`` (0, 2, 4 or 6) int32 words per sample and tensor on the host,
+    # ``draw_index_words(n)``: the first two travel as the block's offset rows, the others behind them (block_layout: ``cut``).
     index_rows = 0
 
     @property
@@ -293,6 +293,52 @@ class RandomTranslate(IdentityAugmentation):
         return out
 
 
+class Compose(IdentityAugmentation):
+    """Beyond the reference: a geometric uint8 augmentation followed by a cutout -- RAD's ``crop-cutout_color`` or
+    ``translate-cutout`` -- as ONE augmentation.  ``move`` is a RandomCrop, a RandomShift or a RandomTranslate, ``paint`` a
+    RandomCutout built for the move's ``output_shape``:
+        mid = move(in)                                               (Ho, Wo) = move.output_shape
+        out[c][y][x] = colour[c % 3]   if y0 <= y < y0 + bh and x0 <= x < x0 + bw,   mid[c][y][x] otherwise
+    with the box in coordinates of the OUTPUT frame; one draw of everything per sample, shared by the frames of a stack:
+    first the move's two words, then the paint's four (``RandomCutout.draw_boxes``).  ``input_shape`` / ``output_shape``
+    are the move's, and so is evaluation (the cutout's is the identity).  On the learner path the pixels are moved and
+    painted by one launch of ``curla_move_cutout_u8`` -- the ring is read once and the scratch written once -- and stay
+    uint8 (ReplayBuffer); under a RandomCrop mover the encoder is built for the cropped size, as for a RandomCrop alone."""
+
+    sample_kind, index_rows = "scratch", 6
+
+    def __init__(self, move, paint):
+        kinds = ((RandomCrop, ops.MOVE_CROP), (RandomShift, ops.MOVE_SHIFT), (RandomTranslate, ops.MOVE_TRANSLATE))
+        code = [c for cls, c in kinds if isinstance(move, cls)]
+        if not code:
+            raise ValueError("Compose: move must be a RandomCrop, RandomShift or RandomTranslate, got %r" % (move,))
+        if not isinstance(paint, RandomCutout):
+            raise ValueError("Compose: paint must be a RandomCutout, got %r" % (paint,))
+        if tuple(paint.input_shape) != tuple(move.output_shape):
+            raise ValueError("Compose: the paint is built for frames of %r, the move makes frames of %r"
+                             % (tuple(paint.input_shape), tuple(move.output_shape)))
+        self.move, self.paint = move, paint
+        self.input_shape, self.output_shape = tuple(move.input_shape), tuple(move.output_shape)
+        self._move_code = code[0]
+
+    def draw_index_words(self, n):
+        """The move's two words, then the paint's four, drawn in that order."""
+        return tuple(self.move.draw_index_words(n)) + tuple(self.paint.draw_index_words(n))
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        a, b, y0, x0, size, rgb = words
+        ops.move_cutout_u8(ring, rows, period, self._move_code, a, b, getattr(self.move, "pad", 0), (y0, x0, size, rgb),
+                           n, out)
+
+    def evaluation_augmentation(self, image):
+        return self.move.evaluation_augmentation(image)
+
+    def training_augmentation(self, image_batch):
+        """Host-side move, then cutout, of a (B, C, H, W) NumPy array, for callers outside the fused path (the draws in
+        the order of ``draw_index_words``)."""
+        return self.paint.training_augmentation(self.move.training_augmentation(np.asarray(image_batch)))
+
+
 class RandomConv(IdentityAugmentation):
     """Beyond the reference: the random convolution of RAD (``random_convolution``) and of Lee et al., "Network
     Randomization".  Every sample's RGB frames go through one freshly drawn 3x3, 3 -> 3 channel filter, shared by all
@@ -528,8 +574,17 @@ class NoisyCover(IdentityAugmentation):
 def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30, conv_p=1.0):
     """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding), 'cutout' / 'cutout_color' (``min_cut``,
     ``max_cut``: the range of a box side), 'random_conv' (``conv_p``: the probability that a sample is convolved) and
-    'translate' (``output_shape``: its canvas, None = 8 pixels more per side length) -- all five beyond the reference."""
+    'translate' (``output_shape``: its canvas, None = 8 pixels more per side length) -- all five beyond the reference --
+    and '<move>+<paint>' with <move> one of 'random_crop', 'random_shift', 'translate' and <paint> one of 'cutout',
+    'cutout_color': a ``Compose`` of the two, the paint built for the move's output_shape."""
     print(f'CHOSEN AUGMENTATION: {name}')
+    if '+' in name:
+        move, _, paint = name.partition('+')
+        if move not in ('random_crop', 'random_shift', 'translate') or paint not in ('cutout', 'cutout_color'):
+            raise ValueError('augmentation is not supported: %s' % name)
+        move = (RandomCrop(input_shape, output_shape) if move == 'random_crop' else
+                RandomShift(input_shape, pad) if move == 'random_shift' else RandomTranslate(input_shape, output_shape))
+        return Compose(move, RandomCutout(move.output_shape, min_cut, max_cut, color=paint == 'cutout_color'))
     if name == 'identity':
         return IdentityAugmentation(input_shape)
     if name == 'random_crop':

@@ -6,7 +6,7 @@
 // Both kernels read the uint8 NHWC replay ring directly (gather by frame index fused in) and write the
 // float32 NHWC minibatch [B][H][W][C] in [0,255] that the first conv kernel consumes (src kind 2).
 #include "common.h"
-#include "u8_mover.h"  // RandomShift and RandomTranslate; U8_UNROLL and u32x4 for RandomCutout below
+#include "u8_mover.h"  // RandomShift, RandomTranslate and the crop; U8_UNROLL and u32x4 for RandomCutout below
 
 namespace {
 
@@ -455,6 +455,176 @@ __global__ __launch_bounds__(256) void cutout_u8_kernel(const uint8_t* frames, c
   }
 }
 
+// ---- Compose(move, paint): a mover of u8_mover.h with the cutout's box painted over its output, in ONE launch ----
+// out[s] = the inner Op's output frame with colour(s)[c % 3] inside the sample's box, the box in coordinates of the OUTPUT
+// frame (Ho x Wo) and clamped into it exactly as cutout_u8_kernel clamps it.  A cutout is a pointwise repaint of what the
+// mover produces, and the skeleton has each group's 16 bytes in registers before the store: the ring is read once and
+// the scratch written once, where a mover launch followed by a cutout launch moves the minibatch through memory twice.
+// Per group, by cutout_u8_kernel's three kinds (paint_kind): outside the box the inner Op's load and finish as they are;
+// wholly inside nothing is loaded and the colour pattern is stored; across a box edge the inner Op's bytes are blended in
+// registers (paint_blend: cut_blend's arithmetic).  Byte-wise (group_bytes) the inner Op writes its group and the bytes
+// inside the box are painted over by the same thread.  The colours and pattern words are plain members selected BY VALUE
+// (sel3): cut_colour's select between elements of q.col is a select of addresses that keeps the whole per-sample struct
+// in memory -- LDS in cutout_u8_kernel, private memory for the larger struct here.
+struct PaintGeom {
+  unsigned rb, frame;       // bytes of a row / of a frame of the OUTPUT
+  int C, y0, y1;            // box rows [y0, y1)
+  unsigned xb0, xb1;        // box columns in bytes of a row [xb0, xb1)
+  uint32_t c0, c1, c2;      // the colours of channels 0, 1, 2 (mod 3)
+  uint32_t p0, p1, p2;      // pattern words: pm = colours m, m + 1, m + 2, m (indices mod 3), as in cutout_u8_kernel
+  bool empty, c3ok;         // no box; C % 3 == 0
+};
+
+__device__ __forceinline__ uint32_t sel3(unsigned k, uint32_t a, uint32_t b, uint32_t c) {  // (copies: selects of values)
+  return k == 0 ? a : k == 1 ? b : c;
+}
+
+__device__ __forceinline__ bool paint_inside(const PaintGeom& q, int yy, unsigned xb) {
+  return yy >= q.y0 && yy < q.y1 && xb >= q.xb0 && xb < q.xb1;
+}
+
+// 0: the group at byte r = y rb + xb lies outside the box, 1: inside, 2: both (cutout_u8_kernel's classification)
+__device__ __forceinline__ int paint_kind(const PaintGeom& q, unsigned r, unsigned y, unsigned xb) {
+  const unsigned last = xb + 15;  // the group's last byte, counted from the start of row y
+  if (q.empty) return 0;
+  if (last < q.rb) {  // one row
+    const bool in_rows = (int)y >= q.y0 && (int)y < q.y1;
+    if (!in_rows || last < q.xb0 || xb >= q.xb1) return 0;
+    return (xb >= q.xb0 && last < q.xb1) ? 1 : 2;
+  }
+  if (last < 2 * q.rb) {  // rows y and y + 1
+    const unsigned last2 = last - q.rb;
+    const bool in0 = (int)y >= q.y0 && (int)y < q.y1, in1 = (int)y + 1 >= q.y0 && (int)y + 1 < q.y1;
+    if ((!in0 || xb >= q.xb1) && (!in1 || last2 < q.xb0)) return 0;
+    return (in0 && in1 && q.xb0 == 0 && q.xb1 == q.rb) ? 1 : 2;
+  }
+  const unsigned ylast = (r + 15) / q.rb;  // rows shorter than a group
+  return ((int)ylast < q.y0 || (int)y >= q.y1) ? 0 : 2;
+}
+
+// cut_blend's arithmetic with the colours by value
+__device__ __forceinline__ u32x4 paint_blend(const PaintGeom& q, u32x4 v, unsigned y, unsigned xb) {
+  int yy = (int)y, c = (int)(xb % (unsigned)q.C), c3 = c % 3;
+  const uint32_t c0 = q.c0, c1 = q.c1, c2 = q.c2;
+  uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int sh = 8 * (e & 3);
+    if (paint_inside(q, yy, xb)) w[e >> 2] = (w[e >> 2] & ~(0xffu << sh)) | (sel3((unsigned)c3, c0, c1, c2) << sh);
+    if (++c3 == 3) c3 = 0;
+    if (++c == q.C) c = 0, c3 = 0;
+    if (++xb == q.rb) xb = 0, ++yy;  // (rb is a multiple of C: c is 0 here)
+  }
+  return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// group bytes [lo, hi) as a mask of whole bytes (0 where the run is empty)
+__device__ __forceinline__ u128 paint_run_mask(int lo, int hi) {
+  return hi > lo ? (~(u128)0 >> (8 * (16 - (hi - lo)))) << (8 * lo) : (u128)0;
+}
+
+// paint_blend for C % 3 == 0 and rows no shorter than a group, without a walk over the bytes: the bytes of the box in
+// the group are one run per row the group touches (two rows at most), and the colour of byte e is (xb + e) % 3 across
+// the row end too (a row is a multiple of 3 bytes) -- the pattern words under a mask of two runs.
+__device__ __forceinline__ u32x4 paint_blend_runs(const PaintGeom& q, u32x4 v, unsigned y, unsigned xb, u32x4 pattern) {
+  const int x = (int)xb, rel = (int)q.rb - x;  // the group byte at which row y + 1 starts
+  const int x0 = (int)q.xb0, x1 = (int)q.xb1;
+  u128 m = 0;
+  if ((int)y >= q.y0 && (int)y < q.y1) m = paint_run_mask(max(x0 - x, 0), min(min(x1 - x, rel), 16));
+  if ((int)y + 1 >= q.y0 && (int)y + 1 < q.y1) m |= paint_run_mask(min(rel + x0, 16), min(rel + x1, 16));
+  const u128 o = (__builtin_bit_cast(u128, v) & ~m) | (__builtin_bit_cast(u128, pattern) & m);
+  return __builtin_bit_cast(u32x4, o);
+}
+
+template <class Inner>
+struct PaintOp {
+  Inner in;
+  const int32_t *y0, *x0, *size, *rgb;
+  int Ho, Wo, C;
+  unsigned src_frame, out_frame;
+
+  struct Geom {
+    typename Inner::Geom g;
+    PaintGeom p;
+  };
+
+  struct Held {
+    typename Inner::Held h;
+    unsigned yk = 0, xb = 0;  // the group's row y and its kind (paint_kind) as y << 2 | kind; its byte in that row
+  };
+
+  __device__ __forceinline__ Geom sample(int s) const {
+    Geom q;
+    q.g = in.sample(s);
+    PaintGeom& b = q.p;
+    b.C = C, b.rb = Inner::out_row(q.g), b.frame = out_frame, b.c3ok = C % 3 == 0;  // (the inner Op's row: ONE division per group)
+    // whatever the block holds is clamped: the box lies inside the output frame (an empty one is a plain move)
+    const uint32_t sz = (uint32_t)size[s], colour = (uint32_t)rgb[s];
+    const int yc = min(max(y0[s], 0), Ho), xc = min(max(x0[s], 0), Wo);
+    const int bh = min((int)(sz & 0xffffu), Ho - yc), bw = min((int)(sz >> 16), Wo - xc);
+    b.empty = bh == 0 || bw == 0;
+    b.y0 = yc, b.y1 = b.empty ? yc : yc + bh;
+    b.xb0 = (unsigned)(xc * C), b.xb1 = (unsigned)((xc + bw) * C);
+    const uint32_t c0 = colour & 0xffu, c1 = (colour >> 8) & 0xffu, c2 = (colour >> 16) & 0xffu;
+    b.c0 = c0, b.c1 = c1, b.c2 = c2;
+    b.p0 = c0 | (c1 << 8) | (c2 << 16) | (c0 << 24);
+    b.p1 = c1 | (c2 << 8) | (c0 << 16) | (c1 << 24);
+    b.p2 = c2 | (c0 << 8) | (c1 << 16) | (c2 << 24);
+    return q;
+  }
+
+  static __device__ __forceinline__ void load(const Geom& q, const uint8_t* src, unsigned r, Held& h) {
+    const unsigned y = r / q.p.rb;  // (below 2^29: the entry point refuses taller frames)
+    h.xb = r - y * q.p.rb;
+    const int kind = paint_kind(q.p, r, y, h.xb);
+    h.yk = y << 2 | (unsigned)kind;
+    if (kind != 1) Inner::load(q.g, src, r, h.h);
+  }
+
+  static __device__ __forceinline__ u32x4 finish(const Geom& q, const uint8_t* src, unsigned r, const Held& h) {
+    const unsigned kind = h.yk & 3;
+    // C % 3 == 0: a byte's colour is (byte offset in row) % 3, and the pattern runs on across rows -- the group's words
+    // are patterns k, k + 1, k + 2, k (mod 3)
+    const unsigned k = h.xb % 3;
+    const uint32_t a = sel3(k, q.p.p0, q.p.p1, q.p.p2);
+    const u32x4 pattern = u32x4{a, sel3(k, q.p.p1, q.p.p2, q.p.p0), sel3(k, q.p.p2, q.p.p0, q.p.p1), a};
+    if (kind == 1 && q.p.c3ok) return pattern;
+    u32x4 o = u32x4{0u, 0u, 0u, 0u};
+    if (kind != 1) o = Inner::finish(q.g, src, r, h.h);
+    if (kind != 0) {
+      if (q.p.c3ok && q.p.rb >= 16) o = paint_blend_runs(q.p, o, h.yk >> 2, h.xb, pattern);  // (uniform over the launch)
+      else o = paint_blend(q.p, o, h.yk >> 2, h.xb);
+    }
+    return o;
+  }
+
+  static __device__ __forceinline__ void group_bytes(const Geom& q, const uint8_t* src, uint8_t* dst, unsigned r) {
+    Inner::group_bytes(q.g, src, dst, r);
+    const PaintGeom& b = q.p;
+    if (b.empty) return;
+    const unsigned cnt = min(16u, b.frame - r);
+    const unsigned y = r / b.rb;
+    unsigned xb = r - y * b.rb;
+    int yy = (int)y, c = (int)(xb % (unsigned)b.C), c3 = c % 3;
+    for (unsigned e = 0; e < cnt; ++e) {
+      if (paint_inside(b, yy, xb)) dst[r + e] = (uint8_t)sel3((unsigned)c3, b.c0, b.c1, b.c2);
+      if (++c3 == 3) c3 = 0;
+      if (++c == b.C) c = 0, c3 = 0;
+      if (++xb == b.rb) xb = 0, ++yy;
+    }
+  }
+};
+
+// the plain mover where there is no box (size == nullptr), the mover with the box painted in where there is one
+template <class Op>
+int launch_move_cutout(const Op& op, const int32_t* y0, const int32_t* x0, const int32_t* size, const int32_t* rgb, int Ho,
+                       int Wo, int C, const uint8_t* frames, const int64_t* idx, int period, int n, long long out_frame,
+                       bool vec_extra, uint8_t* out, void* stream) {
+  if (!size) return launch_u8_mover(op, frames, idx, period, n, out_frame, vec_extra, out, stream);
+  const PaintOp<Op> paint{op, y0, x0, size, rgb, Ho, Wo, C, op.src_frame, op.out_frame};
+  return launch_u8_mover(paint, frames, idx, period, n, out_frame, vec_extra, out, stream);
+}
+
 // ---- RandomConv (beyond the reference: the random convolution of RAD / "Network Randomization") ----
 // out[s][y][x][3 f + co] = sum over ci, ky, kx of w[s][co][ci][ky][kx] * in[row(s)][y + ky - 1][x + kx - 1][3 f + ci], `in`
 // zero outside the frame; one weight set per sample, shared by its frames; uint8 NHWC in, float NHWC out, not clamped.
@@ -745,6 +915,35 @@ int curla_translate_u8(const uint8_t* frames, const int64_t* idx, int period, co
   if ((long long)Wo * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;
   const TrOp op{ty, tx, H, W, C, Ho, Wo, (unsigned)sframe, (unsigned)oframe};
   return launch_u8_mover(op, frames, idx, period, n, oframe, sframe >= 16, out, stream);  // (a load of 16 bytes must fit the source frame)
+}
+
+int curla_move_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, int move, const int32_t* a,
+                         const int32_t* b, int pad, const int32_t* y0, const int32_t* x0, const int32_t* size,
+                         const int32_t* rgb, int n, int C, int H, int W, int Ho, int Wo, uint8_t* out, void* stream) {
+  CURLA_REQUIRE(frames && a && b && out && n > 0 && period > 0 && pad >= 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0);
+  CURLA_REQUIRE(move >= 0 && move <= 2 && (!size || (y0 && x0 && rgb)));
+  CURLA_REQUIRE(move == 0 ? (Ho <= H && Wo <= W) : move == 1 ? (Ho == H && Wo == W) : (Ho >= H && Wo >= W));
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3) == 0 &&
+                (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  if (size)
+    CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(y0) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(size) |
+                    reinterpret_cast<uintptr_t>(rgb)) & 3) == 0);
+  const long long sframe = (long long)H * W * C, oframe = (long long)Ho * Wo * C;
+  if (size && Ho >= (1 << 29)) return CURLA_ERR_UNSUPPORTED;  // (PaintOp holds a group's row and kind in one word)
+  if (move == 0) {
+    // (bytes inside the source frame, the larger one here, and twice an output row are 32-bit quantities in the kernel)
+    if (sframe >= (1LL << 31) - 16 || (long long)Wo * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;
+    const CropOp op{a, b, H, W, C, Ho, Wo, (unsigned)sframe, (unsigned)oframe};
+    return launch_move_cutout(op, y0, x0, size, rgb, Ho, Wo, C, frames, idx, period, n, oframe, true, out, stream);
+  }
+  if (move == 1) {
+    if (2LL * pad * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;  // (as curla_random_shift_u8)
+    const ShiftOp op{a, b, pad, H, W, C, (unsigned)sframe, (unsigned)sframe};
+    return launch_move_cutout(op, y0, x0, size, rgb, Ho, Wo, C, frames, idx, period, n, sframe, true, out, stream);
+  }
+  if ((long long)Wo * C >= (1LL << 30)) return CURLA_ERR_UNSUPPORTED;  // (as curla_translate_u8)
+  const TrOp op{a, b, H, W, C, Ho, Wo, (unsigned)sframe, (unsigned)oframe};
+  return launch_move_cutout(op, y0, x0, size, rgb, Ho, Wo, C, frames, idx, period, n, oframe, sframe >= 16, out, stream);
 }
 
 int curla_random_conv(const uint8_t* frames, const int64_t* idx, const float* weights, int B, int C, int H, int W,

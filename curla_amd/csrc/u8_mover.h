@@ -1,6 +1,7 @@
-// The uint8 byte movers RandomShift and RandomTranslate of augment.hip: one kernel skeleton and one launch path, and one
-// `Op` per augmentation that says what a group of 16 output bytes loads and what becomes of it.  (RandomCutout is the same
-// frame written out once more in augment.hip: on this skeleton it was measured 7 % slower, see there and DESIGN.md.)
+// The uint8 byte movers RandomShift, RandomTranslate and the crop of augment.hip: one kernel skeleton and one launch path,
+// and one `Op` per augmentation that says what a group of 16 output bytes loads and what becomes of it.  (RandomCutout is
+// the same frame written out once more in augment.hip: on this skeleton it was measured 7 % slower, see there and
+// DESIGN.md; PaintOp there wraps a mover Op and paints the cutout's box over its bytes before the store.)
 //
 // A mover gathers a frame of the uint8 NHWC ring per sample (row(s) = idx ? idx[s % period] : s % period) and writes a
 // uint8 NHWC frame per sample (roof: HBM).  A thread owns 16 consecutive OUTPUT bytes of a sample, a "group" (one 16-byte
@@ -17,6 +18,7 @@
 //   load(q, src, r, held)             the loads of the group at output byte r (a multiple of 16), into a Held;
 //   u32x4 finish(q, src, r, held)     the group's 16 output bytes;
 //   group_bytes(q, src, dst, r)       the (possibly short) group byte by byte.
+//   out_row(q)                        bytes of an output row (for PaintOp of augment.hip, which wraps an Op).
 #pragma once
 #include "common.h"
 
@@ -57,8 +59,8 @@ __global__ __launch_bounds__(256) void u8_mover_kernel(const uint8_t* frames, co
   }
 }
 
-// `out_frame` in 64 bits: bytes inside an output frame (hence inside a source frame, which is never larger) are 32-bit
-// quantities in the kernel.  vec_extra: what the Op's 16-byte loads ask for beyond whole groups and an aligned `out`.
+// `out_frame` in 64 bits: bytes inside an output frame (hence inside a source frame, which only the crop has larger: its
+// entry point checks that one) are 32-bit quantities in the kernel.  vec_extra: what the Op's 16-byte loads ask for beyond whole groups and an aligned `out`.
 template <class Op>
 int launch_u8_mover(const Op& op, const uint8_t* frames, const int64_t* idx, int period, int n, long long out_frame,
                     bool vec_extra, uint8_t* out, void* stream) {
@@ -106,6 +108,8 @@ struct ShiftOp {
     q.oy = min(max(dy[s], 0), 2 * pad) - pad, q.ox = min(max(dx[s], 0), 2 * pad) - pad;
     return q;
   }
+
+  static __device__ __forceinline__ unsigned out_row(const Geom& q) { return q.rb; }  // bytes of an output row (PaintOp)
 
   // byte e of the group at byte r, read at its clamped source, for e < cnt: (y, x, c) of the first byte are stepped
   template <class Put>
@@ -187,10 +191,14 @@ __device__ __forceinline__ bool tr_run(const TrGeom& q, int yy, int rel, int& lo
 // The 16-byte load of a run, at its address clamped into the source frame; returns lo | hi << 8 | (d + 16) << 16 (never
 // 0: hi >= 1), d = the bytes the load sits in front of (d > 0) or behind (d < 0) `base`.  Every byte of [lo, hi) is in
 // the load: base + e is a byte of the frame, and the clamp moves the address only as far as the frame's ends.
-__device__ __forceinline__ int tr_load(const uint8_t* src, const TrGeom& q, int lo, int hi, int base, u32x4& v) {
-  const int a = min(max(base, 0), (int)q.sframe - 16);
+__device__ __forceinline__ int u8_run_load(const uint8_t* src, int sframe, int lo, int hi, int base, u32x4& v) {
+  const int a = min(max(base, 0), sframe - 16);
   __builtin_memcpy(&v, src + a, 16);  // one unaligned global_load_dwordx4
   return lo | (hi << 8) | ((base - a + 16) << 16);
+}
+
+__device__ __forceinline__ int tr_load(const uint8_t* src, const TrGeom& q, int lo, int hi, int base, u32x4& v) {
+  return u8_run_load(src, (int)q.sframe, lo, hi, base, v);
 }
 
 // the loaded bytes moved to their places in the group (only the runs at the two ends of a frame are shifted), all
@@ -241,6 +249,8 @@ struct TrOp {
     return q;
   }
 
+  static __device__ __forceinline__ unsigned out_row(const Geom& q) { return (unsigned)q.orb; }  // (PaintOp)
+
   static __device__ __forceinline__ void load(const Geom& q, const uint8_t* src, unsigned r, Held& h) {
     const unsigned y = r / (unsigned)q.orb;
     const int xb = (int)(r - y * (unsigned)q.orb);
@@ -276,6 +286,102 @@ struct TrOp {
       const bool in = yy >= q.ty && yy < q.ty + q.H && xb >= q.txb && xb < q.txb + q.srb;
       dst[r + e] = in ? src[(size_t)(yy - q.ty) * q.srb + (unsigned)(xb - q.txb)] : (uint8_t)0;
       if (++xb == q.orb) xb = 0, ++yy;
+    }
+  }
+};
+
+// ---- the crop as a mover (Compose: RandomCrop + RandomCutout, curla_move_cutout_u8) ----
+// out[s][y][x][c] = frames[row(s)][y + h1][x + w1][c]: the Ho x Wo window at (h1, w1) of the H x W frame, all channels of a
+// stack sharing the offset (clamped into [0, H - Ho] x [0, W - Wo]).  The one byte mover whose output frame is SMALLER than
+// its source frame.  Every output byte has a source byte, and along an output row the source address steps with the output
+// address: per output row that a group touches there is one run [lo, hi) of the group's bytes with group byte e =
+// source-frame byte base + e -- the translate's runs without margins.  A group inside one output row is ONE unaligned
+// 16-byte load; a group that straddles two rows is two loads, masked and OR-ed in registers (tr_place): no byte-wise
+// memory access.  Where the window is as wide as the frame (Wo == W) the two runs are one run of the
+// source.  A load whose 16 bytes would end behind the source frame (the window's last row in the frame's last row) is
+// moved back into the frame and shifted, as tr_load does: nothing in the slack behind a ring is read; no base lies in
+// front of the frame.  Groups that touch three or more rows (rows shorter than a group) walk their rows in a loop.
+struct CropGeom {
+  int Ho, srb, orb;         // output rows; bytes of a source row / of an output row
+  unsigned base0;           // source-frame byte of the window's first byte: h1 srb + w1 C
+  unsigned sframe, oframe;  // bytes of a source frame / of an output frame
+  bool flat;                // the window is as wide as the frame: its rows follow one another in the source too
+};
+
+// The run of output row yy inside a group, `rel` as for tr_run: group bytes [lo, hi) are the row's, group byte e is
+// source-frame byte base + e (base >= 0: rel <= lo).  False: the group has no byte of row yy, or the frame no such row.
+__device__ __forceinline__ bool crop_run(const CropGeom& q, int yy, int rel, int& lo, int& hi, int& base) {
+  lo = max(rel, 0), hi = min(rel + q.orb, 16);
+  base = (int)q.base0 + yy * q.srb - rel;
+  return yy < q.Ho && lo < hi;
+}
+
+struct CropOp {
+  using Geom = CropGeom;
+  const int32_t *h1, *w1;
+  int H, W, C, Ho, Wo;
+  unsigned src_frame, out_frame;
+
+  using Held = TrOp::Held;  // the runs of the group's first and second row, or rows3
+
+  __device__ __forceinline__ Geom sample(int s) const {
+    Geom q;
+    q.Ho = Ho, q.srb = W * C, q.orb = Wo * C, q.sframe = src_frame, q.oframe = out_frame;
+    q.flat = q.srb == q.orb;
+    // (offsets outside their ranges are clamped into them: whatever the block holds, the window lies inside the frame)
+    q.base0 = (unsigned)(min(max(h1[s], 0), H - Ho) * q.srb + min(max(w1[s], 0), W - Wo) * C);
+    return q;
+  }
+
+  static __device__ __forceinline__ unsigned out_row(const Geom& q) { return (unsigned)q.orb; }  // (PaintOp)
+
+  static __device__ __forceinline__ int run_load(const uint8_t* src, const Geom& q, int lo, int hi, int base, u32x4& v) {
+    return u8_run_load(src, (int)q.sframe, lo, hi, base, v);
+  }
+
+  static __device__ __forceinline__ void load(const Geom& q, const uint8_t* src, unsigned r, Held& h) {
+    const unsigned y = r / (unsigned)q.orb;
+    const int xb = (int)(r - y * (unsigned)q.orb);
+    if (xb + 15 >= 2 * q.orb) {
+      h.rows3 = true;
+    } else {
+      int lo0, hi0, b0, lo1, hi1, b1;
+      const bool r0 = crop_run(q, (int)y, -xb, lo0, hi0, b0);  // (always a run: the group's first byte is row y's)
+      bool r1 = crop_run(q, (int)y + 1, q.orb - xb, lo1, hi1, b1);  // (a group inside one row: lo1 >= 16, no run)
+      if (q.flat && r1) hi0 = hi1, r1 = false;                      // b1 == b0, lo1 == hi0: one run of the source
+      if (r0) h.meta[0] = run_load(src, q, lo0, hi0, b0, h.v[0]);
+      if (r1) h.meta[1] = run_load(src, q, lo1, hi1, b1, h.v[1]);
+    }
+  }
+
+  static __device__ __forceinline__ u32x4 finish(const Geom& q, const uint8_t* src, unsigned r, const Held& h) {
+    u128 o = 0;
+    if (h.rows3) {  // rows shorter than a group: its rows one by one
+      const unsigned y = r / (unsigned)q.orb;
+      int yy = (int)y;
+      for (int rel = (int)(y * (unsigned)q.orb) - (int)r; rel < 16; rel += q.orb, ++yy) {
+        int lo, hi, base;
+        if (crop_run(q, yy, rel, lo, hi, base)) {
+          u32x4 v;
+          const int meta = run_load(src, q, lo, hi, base, v);
+          o |= tr_place(v, meta);
+        }
+      }
+    } else {
+      if (h.meta[0]) o = tr_place(h.v[0], h.meta[0]);
+      if (h.meta[1]) o |= tr_place(h.v[1], h.meta[1]);
+    }
+    return __builtin_bit_cast(u32x4, o);
+  }
+
+  // (row, byte in row) are stepped, not divided
+  static __device__ __forceinline__ void group_bytes(const Geom& q, const uint8_t* src, uint8_t* dst, unsigned r) {
+    const unsigned cnt = min(16u, q.oframe - r);
+    const unsigned y = r / (unsigned)q.orb;
+    unsigned xb = r - y * (unsigned)q.orb, at = q.base0 + y * (unsigned)q.srb;  // source byte of row y's first byte
+    for (unsigned e = 0; e < cnt; ++e) {
+      dst[r + e] = src[at + xb];
+      if (++xb == (unsigned)q.orb) xb = 0, at += (unsigned)q.srb;
     }
   }
 };

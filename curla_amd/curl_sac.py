@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import autograd, ops
-from .augmentations import RandomCrop, RandomTranslate
+from .augmentations import Compose, RandomCrop, RandomTranslate
 from .encoder import CNNEncoder
 from .ops import ObsRef
 from .optim import FlatAdam
@@ -771,10 +771,13 @@ class CurlSacAgent(object):
         whole frame) and, under a RandomCrop, the crop's input size (the centre window of
         RandomCrop.evaluation_augmentation, augmentations.py:26-45).  Under a RandomTranslate also the translate's input
         size, with None for an origin: such frames are no window of anything, they are centred on a black canvas as
-        RandomTranslate.evaluation_augmentation does (_act_centred), whatever the margins (0 and 1 included)."""
+        RandomTranslate.evaluation_augmentation does (_act_centred), whatever the margins (0 and 1 included).  A Compose
+        acts as its ``move`` does: the cutout's evaluation is the identity."""
         h, w = self.image_shape
         windows = {(h, w): (0, 0)}
         aug = self.augmentor
+        if isinstance(aug, Compose):
+            aug = aug.move
         if isinstance(aug, (RandomCrop, RandomTranslate)) and tuple(aug.output_shape) == (h, w):
             H, W = aug.input_shape
             windows.setdefault((H, W), ((H - h) // 2, (W - w) // 2) if isinstance(aug, RandomCrop) else None)

@@ -747,6 +747,28 @@ def translate_u8(frames, idx, period, ty, tx, n, out):
          int(out.shape[2]), ptr(out), stream())
 
 
+MOVE_CROP, MOVE_SHIFT, MOVE_TRANSLATE = 0, 1, 2  # curla_move_cutout_u8's `move`
+
+
+def move_cutout_u8(frames, idx, period, move, a, b, pad, box, n, out):
+    """Compose(move, paint) of n samples in one launch (curla_move_cutout_u8): frames u8 [rows, H, W, C]; sample s is row
+    idx[s % period] (idx None: s % period) moved by ``move`` -- MOVE_CROP with (a, b) = (h1, w1), MOVE_SHIFT with (dy, dx)
+    and ``pad``, MOVE_TRANSLATE with (ty, tx) -- and then painted with ``box`` = (y0, x0, size, rgb) as cutout_u8 takes
+    them, in coordinates of the output frame; ``box`` None: the plain move.  out u8 [n, Ho, Wo, C], no larger than the
+    frame for a crop, of its size for a shift, no smaller for a translate."""
+    _, H, W, C = frames.shape
+    fits = out.dim() == 4 and out.shape[0] == n and out.shape[3] == C and move in (MOVE_CROP, MOVE_SHIFT, MOVE_TRANSLATE)
+    if fits:
+        Ho, Wo = out.shape[1:3]
+        fits = ((Ho <= H and Wo <= W) if move == MOVE_CROP else (Ho == H and Wo == W) if move == MOVE_SHIFT
+                else (Ho >= H and Wo >= W))
+    box = tuple(box) if box is not None else ()
+    _check_scratch_u8("move_cutout_u8", frames, idx, period, (a, b) + box, n, out, fits and len(box) in (0, 4),
+                      ("offset and box words", " under move %r" % (move,)))
+    call("curla_move_cutout_u8", ptr(frames), ptr(idx), int(period), int(move), ptr(a), ptr(b), int(pad),
+         *(ptr(t) for t in (box or (None,) * 4)), int(n), C, H, W, int(out.shape[1]), int(out.shape[2]), ptr(out), stream())
+
+
 def nhwc_to_nchw(x, out):
     B, H, W, C = x.shape
     call("curla_nhwc_to_nchw", ptr(x), ptr(out), B, H, W, C, stream())

@@ -247,7 +247,7 @@ class ReplayBuffer(object):
         # (draw_indices raises).
         self._kind = getattr(augmentor, "sample_kind", None)
         self._index_rows = augmentor.index_rows if self._kind else 0
-        assert self._kind in ("ring", "scratch", "float", None) and self._index_rows in (0, 2, 4)
+        assert self._kind in ("ring", "scratch", "float", None) and self._index_rows in (0, 2, 4, 6)
         # float augmentations only: the parameters travel in the index block, NoisyCover's noise is drawn in the kernel
         self.staged_aug = bool(staged_aug) and self._kind == "float"
         if self.staged_aug:
@@ -607,7 +607,8 @@ class ReplayBuffer(object):
     # ------------------------------------------------------------------ sampling
     def _scratch_frame(self):
         """Bytes of a frame of the scratch: a MINIBATCH frame (C, Ho, Wo), (Ho, Wo) the augmentor's output_shape.  Only a
-        RandomTranslate makes it differ from a stored frame (``_frame``: the rings, add, save / load, the frame store)."""
+        RandomTranslate (larger) or a Compose over one or over a RandomCrop (smaller) makes it differ from a stored frame
+        (``_frame``: the rings, add, save / load, the frame store)."""
         oh, ow = self.augmentor.output_shape
         return self.obs_shape[0] * oh * ow
 
@@ -617,12 +618,13 @@ class ReplayBuffer(object):
         the augmentation draws for tensor j (``draw_index_words``: h1 / w1 of a RandomCrop, (dy, dx) / (ty, tx) of a
         RandomShift / RandomTranslate, (y0, x0) of a RandomCutout's boxes; zeros when it draws none).  An augmentation of
         four words -- RandomCutout -- returns int32 [12, B], rows 6 + 2j, 6 + 2j + 1 = the other two (its packed sizes
-        and colours)."""
+        and colours); one of six -- Compose -- int32 [18, B] by the same rule (word r of tensor j in row 6 (r // 2) + 2 j +
+        r % 2): the move's offsets, the box's (y0, x0), its sizes and colours."""
         B = self.batch_size
         idxs = np.random.randint(0, self.capacity if self.full else self.idx, size=B)
         if self._kind is None:
             raise NotImplementedError("unknown augmentation object: %r" % (self.augmentor,))
-        offs = np.zeros((12 if self._index_rows > 2 else 6, B), dtype=np.int32)
+        offs = np.zeros((6 * max(1, (self._index_rows + 1) // 2), B), dtype=np.int32)
         for j in range(3):
             for r, word in enumerate(self.augmentor.draw_index_words(B)):
                 offs[6 * (r // 2) + 2 * j + r % 2] = word
@@ -651,7 +653,8 @@ class ReplayBuffer(object):
                        weights; a key only this layout has -- the stride keeps ``nbytes`` a multiple of 8)
         An augmentation that draws four index words -- RandomCutout -- appends ``cut`` int32 [2][3B] behind them: the third
         words of obs | next_obs | pos (its packed box sizes), then the fourth (its colour words) -- contiguous runs for
-        one launch of n = 3B.
+        one launch of n = 3B.  One that draws six -- Compose -- appends ``cut`` int32 [4][3B]: the third to sixth words, the
+        box's y0 | x0 | sizes | colours.
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
         ``nbytes`` is what a rotating sample slot stages per minibatch; the block of a captured update graph carries
         GRAPH_TAIL more bytes of per-update control values behind it (at ``tail``; ``graph_nbytes`` in all)."""
@@ -664,7 +667,7 @@ class ReplayBuffer(object):
             n += 3 * stride
         if self._index_rows > 2:
             lay["cut"] = n
-            n += 2 * 3 * B * 4
+            n += (self._index_rows - 2) * 3 * B * 4
         assert n % 8 == 0
         if self.n_step > 1:  # next_row int64 [B]: the bootstrap rows without the double ring's offset (device-written)
             lay["next_row"] = n
@@ -714,12 +717,15 @@ class ReplayBuffer(object):
         i64[B:].copy_(i64[:B] + self.capacity)
         o32 = host[lay["offs"]:lay["offs_end"]].view(torch.int32).view(6, B)
         offs = np.ascontiguousarray(offs, dtype=np.int32)
-        if "cut" in lay and len(offs) != 12:
-            raise ValueError("a RandomCutout buffer's block takes offsets of 12 rows (draw_indices), got %d" % len(offs))
+        if "cut" in lay and len(offs) != 3 * self._index_rows:
+            raise ValueError("the block of an augmentor of %d index words takes offsets of %d rows (draw_indices), got %d"
+                             % (self._index_rows, 3 * self._index_rows, len(offs)))
         o32.copy_(torch.from_numpy(np.ascontiguousarray(offs[[0, 2, 4, 1, 3, 5]])))
-        if "cut" in lay:  # sizes of obs | next_obs | pos, then their colours
-            c32 = host[lay["cut"]:lay["cut"] + 24 * B].view(torch.int32).view(6, B)
-            c32.copy_(torch.from_numpy(np.ascontiguousarray(offs[[6, 8, 10, 7, 9, 11]])))
+        if "cut" in lay:  # per further word a run of obs | next_obs | pos: sizes, then colours (Compose: y0, x0 in front)
+            runs = self._index_rows - 2
+            c32 = host[lay["cut"]:lay["cut"] + 12 * runs * B].view(torch.int32).view(3 * runs, B)
+            c32.copy_(torch.from_numpy(np.ascontiguousarray(offs[[6 * (r // 2) + 2 * j + r % 2 for r in range(2, 2 + runs)
+                                                                  for j in range(3)]])))
 
     def _upload_indices(self, idxs, offs, aug=None):
         """A minibatch's indices and crop offsets (and, staged_aug, its augmentation parameters ``aug``) into the next
@@ -797,7 +803,7 @@ class ReplayBuffer(object):
                    (None: rows 0..2B-1) with offsets ``h2`` / ``w2``; None when the rings are two allocations
           words    the index words of obs, next_obs, pos as int32 runs of 3B each: the h rows, the w rows (RandomShift's
                    (dy, dx), RandomTranslate's (ty, tx), RandomCutout's (y0, x0)) and, where four words are drawn, the
-                   two runs of ``cut`` (RandomCutout's packed box sizes and colour words)
+                   runs of ``cut`` (RandomCutout's packed box sizes and colour words; Compose's y0, x0, sizes, colours)
         Plain storage reads the rings at the sampled rows.  The frame store first assembles the k frames of every
         sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor)."""
         B, lay, dev = self.batch_size, self._layout, slot["dev"]
@@ -817,8 +823,9 @@ class ReplayBuffer(object):
             both, rings, idx2 = self._both, (self.obses, self.next_obses), d64
         words = (d32[:3 * B], d32[3 * B:])
         if "cut" in lay:
-            c32 = dev[lay["cut"]:lay["cut"] + 24 * B].view(torch.int32)
-            words += (c32[:3 * B], c32[3 * B:])
+            runs = self._index_rows - 2
+            c32 = dev[lay["cut"]:lay["cut"] + 12 * runs * B].view(torch.int32)
+            words += tuple(c32[3 * B * k:3 * B * (k + 1)] for k in range(runs))
         return _Sources(both, idx2, d32[:2 * B], d32[3 * B:5 * B], ((rings[0], rows), (rings[1], rows_n), (rings[0], rows)),
                         off, words)
 

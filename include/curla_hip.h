@@ -609,6 +609,30 @@ int curla_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, const
  * CURLA_ABI_VERSION stays 8.  CURLA_ERR_UNSUPPORTED when Ho Wo C does not fit 31 bits or a row Wo C does not fit 30. */
 int curla_translate_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* ty, const int32_t* tx, int n,
                        int C, int H, int W, int Ho, int Wo, uint8_t* out, void* stream);
+/* Compose(move, paint): a geometric uint8 move with RandomCutout's box painted over its OUTPUT, in one launch -- the ring is
+ * read once and `out` written once, where a mover launch followed by curla_cutout_u8 moves the minibatch twice:
+ *   mid[s] = move(frames[row(s)])                          (Ho x Wo; the mover's own formula and clamps)
+ *   out[s][y][x][c] = colour(s)[c % 3]   if y0c <= y < y0c + bhc and x0c <= x < x0c + bwc,   mid[s][y][x][c] otherwise
+ * `move` selects the mover and what (a, b), int32 [n] each, mean:
+ *   0  crop       (a, b) = (h1, w1): mid[y][x][c] = frames[row(s)][y + h1c][x + w1c][c], h1c = clamp(h1, 0, H - Ho), w1c =
+ *                 clamp(w1, 0, W - Wo).  Needs Ho <= H and Wo <= W; `pad` is not used.
+ *   1  shift      (a, b) = (dy, dx) and `pad`, as curla_random_shift_u8.  Needs Ho == H and Wo == W.
+ *   2  translate  (a, b) = (ty, tx), as curla_translate_u8.  Needs Ho >= H and Wo >= W; `pad` is not used.
+ * uint8 NHWC in ([rows][H][W][C]) and out ([n][Ho][Wo][C], 32 bytes of slack behind it like a ring), row(s) = idx[s % period]
+ * (idx NULL: s % period) as for curla_random_shift_u8.  y0 / x0 / size / rgb: int32 [n] as for curla_cutout_u8, the box in
+ * coordinates of the OUTPUT frame and clamped into it in the kernel (y0c = clamp(y0, 0, Ho), bhc = clamp(bh, 0, Ho - y0c),
+ * likewise in x); an empty box is a plain move.  size NULL: no box -- y0, x0 and rgb are ignored and the launch is the
+ * plain mover (for move 1 and 2 the kernels of curla_random_shift_u8 / curla_translate_u8; for move 0 the crop on its
+ * own).  Nothing is read outside a source frame (neither in front of it nor in the slack behind a ring) and nothing is
+ * written outside `out`.  An output frame of a multiple of 16 bytes with `out` on a 16-byte boundary moves 16 bytes per
+ * lane: no load for a group wholly inside the box, the mover's loads for every other group, the box's bytes replaced in
+ * registers where a group crosses a box edge; every other case gives the same bytes one at a time.  Any C > 0.  Additive:
+ * CURLA_ABI_VERSION stays 8.  CURLA_ERR_ARG on an unknown move, a NULL required pointer, n < 1, C < 1, pad < 0 or sizes that
+ * do not fit the move; CURLA_ERR_UNSUPPORTED when H W C or Ho Wo C does not fit 31 bits, 2 pad C (move 1) or a row Wo C
+ * (move 0 and 2) does not fit 30, or, with a box, Ho does not fit 29. */
+int curla_move_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, int move, const int32_t* a, const int32_t* b,
+                         int pad, const int32_t* y0, const int32_t* x0, const int32_t* size, const int32_t* rgb, int n, int C,
+                         int H, int W, int Ho, int Wo, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

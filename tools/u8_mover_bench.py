@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """The uint8 movers (curla_random_shift_u8, curla_cutout_u8, curla_translate_u8; csrc/u8_mover.h, augment.hip) against
 one another and against a plain device-to-device copy, and whole updates with their augmentations:
-python tools/u8_mover_bench.py [--kernels shift,cutout,translate,copy] [--kinds] [--launches K]
+python tools/u8_mover_bench.py [--kernels shift,cutout,translate,copy] [--kinds] [--fused] [--launches K]
                                [--augs identity,random_shift,cutout_color,translate] [--no-updates]
 Kernels: one launch for a 3B minibatch (obs | next_obs | pos from a double ring, period 2B, as ReplayBuffer issues it),
 B = 512, so n = 1536, at 84 x 84 x 9 and 90 x 160 x 9: the shift (pad 4), the cutout (boxes drawn by RandomCutout's defaults,
 min_cut 10, max_cut 30, random colours), the translate onto a canvas 8 pixels larger per side length (-> 92 x 92 and
 98 x 168, offsets in [0, 8]^2) and ``copy_`` of a uint8 tensor of the frame's 3B * frame bytes.  ``--kinds`` adds the
 translate onto a canvas of the frame's own size (a plain gather: every group is an inside group, one load and one store),
-to tell what the margin and mixed groups cost.  The selected forms alternate; each sample is 10 back-to-back repetitions
+to tell what the margin and mixed groups cost.  ``--fused`` adds, for each of the three movers of curla_move_cutout_u8
+(the crop to 76 x 76 and 80 x 144 -- output frames of whole 16-byte groups --, the shift, the translate), three forms: the
+plain mover (``crop``; the shift and the translate are the kernels above), the fused launch with boxes drawn for the
+OUTPUT frame (``crop+cutout`` ...) and the two launches it replaces, the mover into a scratch and curla_cutout_u8 over that
+scratch (``crop,cutout`` ...); the ratios fused / plain and fused / two launches are printed.  The selected forms alternate; each sample is 10 back-to-back repetitions
 between two HIP events (launch gaps hidden behind the queue); medians of 15 samples (``--launches K``: K / 10) are printed
 with min - max and the rates of bytes WRITTEN and of bytes read + written, then the ratios of the times to the copy's and
 to the shift's, the latter also as bytes written per second.
@@ -17,7 +21,7 @@ u8_mover_kernel<ShiftOp>, u8_mover_kernel<TrOp> and cutout_u8_kernel from kernel
 there, the statistics go by kernel name:
 rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/u8_mover_bench.py --no-updates
 Updates (tools/host_overhead.py's loop): 60 updates back to back, three times, eager and replayed from update graphs,
-with each of ``--augs`` at the same geometries."""
+with each of ``--augs`` at the same geometries (names that begin with ``random_crop`` crop to 76 x 76 and 80 x 144)."""
 import argparse, os, statistics, sys, time
 import numpy as np
 import torch
@@ -29,6 +33,7 @@ from curla_amd import ops
 ap = argparse.ArgumentParser()
 ap.add_argument("--kernels", default="shift,cutout,translate,copy")
 ap.add_argument("--kinds", action="store_true")
+ap.add_argument("--fused", action="store_true")
 ap.add_argument("--launches", type=int, default=150)
 ap.add_argument("--augs", default="identity,random_shift,cutout_color,translate")
 ap.add_argument("--no-updates", action="store_true")
@@ -36,6 +41,7 @@ args = ap.parse_args()
 REP = 10
 SAMPLES = max(1, args.launches // REP)
 GEOMETRIES = ((84, 84, 9, 512), (90, 160, 9, 512))
+CROPS = {(84, 84): (76, 76), (90, 160): (80, 144)}
 PAD, CAP = 4, 4096
 dev = torch.device("cuda")
 
@@ -80,6 +86,33 @@ for (H, W, C, B) in GEOMETRIES:
         "copy": (lambda: dst.copy_(src), n * frame, "copy_"),
     }
     names = [k for k in args.kernels.split(",") if k] + (["gather"] if args.kinds else [])
+    if args.fused:
+        Hc, Wc = CROPS[(H, W)]
+        h1 = torch.randint(0, H - Hc + 1, (n,), device=dev, dtype=torch.int32)
+        w1 = torch.randint(0, W - Wc + 1, (n,), device=dev, dtype=torch.int32)
+        mid = torch.zeros(n * oframe + 32, dtype=torch.uint8, device=dev)  # the scratch between the two launches
+        movers = {"crop": (ops.MOVE_CROP, h1, w1, 0, (Hc, Wc)), "shift": (ops.MOVE_SHIFT, dy, dx, PAD, (H, W)),
+                  "translate": (ops.MOVE_TRANSLATE, ty, tx, 0, (Ho, Wo))}
+        for k, (code, a, b, pad, (h, w)) in movers.items():
+            np.random.seed(2)
+            y0, x0, bh, bw, rgb = curla_amd.RandomCutout((h, w), color=True).draw_boxes(n)
+            bx = [i32(y0), i32(x0), i32(bh | (bw << 16)), i32(rgb[:, 0] | (rgb[:, 1] << 8) | (rgb[:, 2] << 16))]
+            o_v, m_v = out[:n * h * w * C].view(n, h, w, C), mid[:n * h * w * C].view(n, h, w, C)
+            what = f"-> {h}x{w}, {100 * float((bh * bw).sum()) / (n * h * w):.1f} % of the bytes inside a box"
+
+            def plain(code=code, a=a, b=b, pad=pad, to=o_v):
+                ops.move_cutout_u8(ring, idx2, 2 * B, code, a, b, pad, None, n, to)
+
+            def fused(code=code, a=a, b=b, pad=pad, bx=bx, to=o_v):
+                ops.move_cutout_u8(ring, idx2, 2 * B, code, a, b, pad, bx, n, to)
+
+            def two(code=code, a=a, b=b, pad=pad, bx=bx, m_v=m_v, to=o_v):
+                ops.move_cutout_u8(ring, idx2, 2 * B, code, a, b, pad, None, n, m_v)
+                ops.cutout_u8(m_v, None, n, *bx, n, to)
+            forms.setdefault(k, (plain, n * h * w * C, f"-> {h}x{w}"))
+            forms[k + "+cutout"] = (fused, n * h * w * C, what + ", one launch")
+            forms[k + ",cutout"] = (two, n * h * w * C, what + ", two launches")
+            names += [x for x in (k, k + "+cutout", k + ",cutout") if x not in names]
     for _ in range(3):
         for k in names:
             forms[k][0]()
@@ -97,9 +130,14 @@ for (H, W, C, B) in GEOMETRIES:
     ratios = [f"{k} / copy {med[k] / med['copy']:.3f}" for k in names if k != "copy" and "copy" in med]
     ratios += [f"{k} / shift {med[k] / med['shift']:.3f} (bytes written per second: {rate[k] / rate['shift']:.3f})"
                for k in names if k not in ("copy", "shift") and "shift" in med]
+    if args.fused:
+        ratios += [f"{k}+cutout / {k} {med[k + '+cutout'] / med[k]:.3f}, {k}+cutout / {k},cutout "
+                   f"{med[k + '+cutout'] / med[k + ',cutout']:.3f}" for k in movers]
     if ratios:
         print(f"{H}x{W}x{C} n={n} ratios of the medians: " + ", ".join(ratios), flush=True)
     del store, ring, out, out_v, out_tv, src, dst, forms
+    if args.fused:
+        del mid, movers, plain, fused, two, o_v, m_v
 
 if args.no_updates:
     sys.exit(0)
@@ -114,7 +152,7 @@ for (H, W, C, B) in GEOMETRIES:
     for graphs in (False, True):
         for name in [a for a in args.augs.split(",") if a]:
             curla_amd.set_seed_everywhere(1)
-            aug = curla_amd.make_augmentor(name, (H, W))
+            aug = curla_amd.make_augmentor(name, (H, W), CROPS[(H, W)] if name.startswith("random_crop") else None)
             out_hw = getattr(aug, "output_shape", None) or (H, W)
             agent = curla_amd.CurlSacAgent((C,) + tuple(out_hw), (2,), dev, aug, hidden_dim=1024, log_interval=10 ** 9)
             rb = curla_amd.ReplayBuffer((C, H, W), (2,), 20000, B, dev, aug)
