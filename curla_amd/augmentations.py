@@ -293,6 +293,169 @@ class RandomTranslate(IdentityAugmentation):
         return out
 
 
+def _checked_hw_p(name, input_shape, p):
+    """(input_shape as a tuple of two ints, p as a float): what RandomFlip, RandomRotate and RandomGrayscale validate alike."""
+    if len(input_shape) != 2:
+        raise ValueError("%s: input_shape must be 2D, got %r" % (name, input_shape))
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in input_shape):
+        raise ValueError("%s: input_shape must hold ints, got %r" % (name, input_shape))
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
+        raise ValueError("%s: p must be a number in [0, 1], got %r" % (name, p))
+    return tuple(int(x) for x in input_shape), float(p)
+
+
+FLIP_X, FLIP_Y, TRANSPOSE = 1, 2, 4  # the bits of a dihedral code (curla_dihedral_u8)
+ROT90_CODES = (0, FLIP_X | TRANSPOSE, FLIP_X | FLIP_Y, FLIP_Y | TRANSPOSE)  # of np.rot90(k = 0, 1, 2, 3) over (H, W)
+
+
+def dihedral(image_batch, codes):
+    """The map of ``curla_dihedral_u8`` on a (B, C, H, W) array, on the host: with (a, b) = (x, y) if the TRANSPOSE bit of
+    codes[b] is set, else (y, x), out[c][y][x] = in[c][FLIP_Y ? H - 1 - a : a][FLIP_X ? W - 1 - b : b]."""
+    image_batch = np.asarray(image_batch)
+    out = np.empty_like(image_batch)
+    for b in range(image_batch.shape[0]):
+        img, code = image_batch[b], int(codes[b])
+        if code & FLIP_Y:
+            img = img[:, ::-1]
+        if code & FLIP_X:
+            img = img[:, :, ::-1]
+        out[b] = img.transpose(0, 2, 1) if code & TRANSPOSE else img
+    return out
+
+
+class RandomFlip(IdentityAugmentation):
+    """Beyond the reference: the flip of RAD.  A sample is mirrored left-right with probability ``p``, one draw per sample
+    shared by all frames of the stack:
+        out[c][y][x] = in[c][y][W - 1 - x]   if flipped,   in[c][y][x] otherwise
+    ``output_shape == input_shape``; evaluation is the identity.  A clean restatement of RAD's ``random_flip``, not a
+    port.  On the learner path the pixels are moved by ``curla_dihedral_u8`` (code 1 or 0) and stay uint8 (ReplayBuffer);
+    the flags are drawn on the host from NumPy's global stream, one ``np.random.rand(n) < p`` per tensor."""
+
+    def __init__(self, input_shape, p=0.5):
+        shape, self.p = _checked_hw_p("RandomFlip", input_shape, p)
+        super().__init__(shape)
+
+    def draw_flags(self, n):
+        """One RNG call: ``np.random.rand(n) < p``."""
+        return np.random.rand(n) < self.p
+
+    sample_kind, index_rows = "scratch", 2
+
+    def draw_index_words(self, n):
+        """(code, 0): 1 where the sample is flipped, 0 where it is not; the second word is not used."""
+        return self.draw_flags(n).astype(np.int32) * FLIP_X, 0
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        ops.dihedral_u8(ring, rows, period, words[0], n, out)
+
+    @staticmethod
+    def flip(image_batch, flags):
+        """A (B, C, H, W) array with the samples whose flag is set mirrored left-right, on the host."""
+        out = np.array(image_batch, copy=True)
+        for b in range(out.shape[0]):
+            if flags[b]:
+                out[b] = out[b, :, :, ::-1]
+        return out
+
+    def training_augmentation(self, image_batch):
+        """Host-side flip of a (B, C, H, W) NumPy array, for callers outside the fused path."""
+        image_batch = np.asarray(image_batch)
+        return self.flip(image_batch, self.draw_flags(image_batch.shape[0]))
+
+
+class RandomRotate(IdentityAugmentation):
+    """Beyond the reference: the rotate of RAD.  With probability ``p`` (RAD's default 0.3) a sample is turned by a random
+    multiple of 90 degrees, counter-clockwise as ``np.rot90`` over (H, W) turns, one draw per sample shared by all frames
+    of the stack; a frame that is not square is turned by 0 or 180 degrees only, which keep its size.
+    ``output_shape == input_shape``; evaluation is the identity.  A clean restatement of RAD's ``random_rotation``, not a
+    port.  On the learner path the pixels are moved by ``curla_dihedral_u8`` (codes 0, 5, 3, 6 for k = 0, 1, 2, 3) and stay
+    uint8 (ReplayBuffer); the turns are drawn on the host from NumPy's global stream."""
+
+    def __init__(self, input_shape, p=0.3):
+        shape, self.p = _checked_hw_p("RandomRotate", input_shape, p)
+        super().__init__(shape)
+
+    def draw_turns(self, n):
+        """Two RNG calls, always both and in this order: ``turns = np.random.randint(0, 4, n)`` on a square frame,
+        ``2 * np.random.randint(0, 2, n)`` on any other; then ``keep = np.random.rand(n) < p``.  Returns k = turns where
+        keep, else 0."""
+        if self.input_shape[0] == self.input_shape[1]:
+            turns = np.random.randint(0, 4, n)
+        else:
+            turns = 2 * np.random.randint(0, 2, n)
+        keep = np.random.rand(n) < self.p
+        return np.where(keep, turns, 0)
+
+    sample_kind, index_rows = "scratch", 2
+
+    def draw_index_words(self, n):
+        """(code, 0): the dihedral code of each sample's k; the second word is not used."""
+        return np.asarray(ROT90_CODES, dtype=np.int32)[self.draw_turns(n)], 0
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        ops.dihedral_u8(ring, rows, period, words[0], n, out)
+
+    @staticmethod
+    def rotate(image_batch, k):
+        """A (B, C, H, W) array with sample b turned k[b] times by 90 degrees counter-clockwise, on the host (odd k[b] on
+        square frames only)."""
+        return dihedral(image_batch, [ROT90_CODES[int(t) % 4] for t in k])
+
+    def training_augmentation(self, image_batch):
+        """Host-side rotation of a (B, C, H, W) NumPy array, for callers outside the fused path."""
+        image_batch = np.asarray(image_batch)
+        return self.rotate(image_batch, self.draw_turns(image_batch.shape[0]))
+
+
+class RandomGrayscale(IdentityAugmentation):
+    """Beyond the reference: the grayscale of RAD.  With probability ``p`` (RAD's default 0.3) every RGB frame of a sample
+    loses its colour, one draw per sample shared by all frames of the stack: each triplet (R, G, B) becomes (g, g, g),
+        g = (77 R + 150 G + 29 B + 128) >> 8
+    an integer mix within 1 of RAD's 0.2989 R + 0.587 G + 0.114 B whose weights sum to 256 -- a grey pixel stays what it
+    is, so the map is idempotent.  ``output_shape == input_shape``; evaluation is the identity.  A clean restatement of
+    RAD's ``random_grayscale``, not a port.  On the learner path the bytes are mixed by ``curla_grayscale_u8`` and stay
+    uint8 (ReplayBuffer); the flags are drawn on the host from NumPy's global stream, one ``np.random.rand(n) < p`` per
+    tensor.  The channel count is no part of ``input_shape``: one that is no multiple of 3 is refused where it is first
+    seen -- by ``grey`` on the host, by ``ops.grayscale_u8`` and by the kernel on the learner path, before any launch."""
+
+    def __init__(self, input_shape, p=0.3):
+        shape, self.p = _checked_hw_p("RandomGrayscale", input_shape, p)
+        super().__init__(shape)
+
+    def draw_flags(self, n):
+        """One RNG call: ``np.random.rand(n) < p``."""
+        return np.random.rand(n) < self.p
+
+    sample_kind, index_rows = "scratch", 2
+
+    def draw_index_words(self, n):
+        """(flag, 0): 1 where the sample is greyed, 0 where it is not; the second word is not used."""
+        return self.draw_flags(n).astype(np.int32), 0
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        ops.grayscale_u8(ring, rows, period, words[0], n, out)
+
+    @staticmethod
+    def grey(image_batch, flags):
+        """A (B, 3k, H, W) uint8 array with the samples whose flag is set greyed, on the host: the integer formula of the
+        class docstring."""
+        out = np.array(image_batch, copy=True)
+        B, C, H, W = out.shape
+        if C % 3:
+            raise ValueError("RandomGrayscale: the channels must be RGB triplets, got %d channels" % C)
+        x = out.reshape(B, C // 3, 3, H, W).astype(np.int64)
+        g = ((77 * x[:, :, 0] + 150 * x[:, :, 1] + 29 * x[:, :, 2] + 128) >> 8).astype(out.dtype)
+        for b in range(B):
+            if flags[b]:
+                out[b] = np.repeat(g[b], 3, axis=0)
+        return out
+
+    def training_augmentation(self, image_batch):
+        """Host-side greyscale of a (B, 3k, H, W) uint8 NumPy array, for callers outside the fused path."""
+        image_batch = np.asarray(image_batch)
+        return self.grey(image_batch, self.draw_flags(image_batch.shape[0]))
+
+
 class Compose(IdentityAugmentation):
     """Beyond the reference: a geometric uint8 augmentation followed by a cutout -- RAD's ``crop-cutout_color`` or
     ``translate-cutout`` -- as ONE augmentation.  ``move`` is a RandomCrop, a RandomShift or a RandomTranslate, ``paint`` a
@@ -571,10 +734,11 @@ class NoisyCover(IdentityAugmentation):
         return out
 
 
-def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30, conv_p=1.0):
+def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30, conv_p=1.0, p=None):
     """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding), 'cutout' / 'cutout_color' (``min_cut``,
-    ``max_cut``: the range of a box side), 'random_conv' (``conv_p``: the probability that a sample is convolved) and
-    'translate' (``output_shape``: its canvas, None = 8 pixels more per side length) -- all five beyond the reference --
+    ``max_cut``: the range of a box side), 'random_conv' (``conv_p``: the probability that a sample is convolved),
+    'translate' (``output_shape``: its canvas, None = 8 pixels more per side length) and 'flip' / 'rotate' / 'grayscale'
+    (``p``: the probability that a sample is transformed, None = the class's default) -- all eight beyond the reference --
     and '<move>+<paint>' with <move> one of 'random_crop', 'random_shift', 'translate' and <paint> one of 'cutout',
     'cutout_color': a ``Compose`` of the two, the paint built for the move's output_shape."""
     print(f'CHOSEN AUGMENTATION: {name}')
@@ -601,4 +765,7 @@ def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, m
         return RandomConv(input_shape, conv_p)
     if name == 'translate':
         return RandomTranslate(input_shape, output_shape)
+    if name in ('flip', 'rotate', 'grayscale'):
+        cls = RandomFlip if name == 'flip' else RandomRotate if name == 'rotate' else RandomGrayscale
+        return cls(input_shape) if p is None else cls(input_shape, p)
     raise ValueError('augmentation is not supported: %s' % name)

@@ -946,6 +946,26 @@ int curla_move_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, 
   return launch_move_cutout(op, y0, x0, size, rgb, Ho, Wo, C, frames, idx, period, n, oframe, sframe >= 16, out, stream);
 }
 
+int curla_dihedral_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* code, int n, int C, int H,
+                      int W, uint8_t* out, void* stream) {
+  CURLA_REQUIRE(frames && code && out && n > 0 && period > 0 && C > 0 && H > 0 && W > 0);
+  CURLA_REQUIRE((reinterpret_cast<uintptr_t>(code) & 3) == 0 && (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  const long long frame = (long long)H * W * C;
+  if (frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;  // (bytes inside a frame are 32-bit quantities in the kernel)
+  const FlipOp op{code, H, W, C, (unsigned)frame, (unsigned)frame};
+  return launch_dihedral_u8(op, frames, idx, period, n, frame, out, stream);
+}
+
+int curla_grayscale_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* grey, int n, int C, int H,
+                       int W, uint8_t* out, void* stream) {
+  CURLA_REQUIRE(frames && grey && out && n > 0 && period > 0 && C > 0 && C % 3 == 0 && H > 0 && W > 0);
+  CURLA_REQUIRE((reinterpret_cast<uintptr_t>(grey) & 3) == 0 && (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  const long long frame = (long long)H * W * C;
+  if (frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;  // (as curla_dihedral_u8)
+  const GreyOp op{grey, (unsigned)frame, (unsigned)frame};
+  return launch_u8_mover(op, frames, idx, period, n, frame, true, out, stream);
+}
+
 int curla_random_conv(const uint8_t* frames, const int64_t* idx, const float* weights, int B, int C, int H, int W,
                       float* out, void* stream) {
   CURLA_REQUIRE(frames && weights && out && B > 0 && C > 0 && C % 3 == 0 && H > 0 && W > 0);

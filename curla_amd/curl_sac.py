@@ -1393,7 +1393,7 @@ class CurlSacAgent(object):
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
             raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
                              "(covered: RandomCrop, RandomShift, RandomCutout, RandomTranslate or identity, plain storage with both rings in one "
-                             "allocation or dedup_frames storage; ColorJiggle / NoisyCover / RandomConv "
+                             "allocation or dedup_frames storage -- RandomFlip, RandomRotate and RandomGrayscale like them; ColorJiggle / NoisyCover / RandomConv "
                              "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
                              "CURLA_STAGE_COPY=1)")
         opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer)

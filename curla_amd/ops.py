@@ -769,6 +769,25 @@ def move_cutout_u8(frames, idx, period, move, a, b, pad, box, n, out):
          *(ptr(t) for t in (box or (None,) * 4)), int(n), C, H, W, int(out.shape[1]), int(out.shape[2]), ptr(out), stream())
 
 
+def dihedral_u8(frames, idx, period, code, n, out):
+    """RandomFlip / RandomRotate of n samples (curla_dihedral_u8): frames u8 [rows, H, W, C]; sample s is row
+    idx[s % period] (idx None: s % period) mapped by code[s] (int32 [n]: FX = 1, FY = 2, T = 4; taken & 7, and & 3 where
+    H != W, by the kernel); out u8 [n, H, W, C]."""
+    _, H, W, C = frames.shape
+    _check_scratch_u8("dihedral_u8", frames, idx, period, (code,), n, out, tuple(out.shape) == (n, H, W, C), ("codes", ""))
+    call("curla_dihedral_u8", ptr(frames), ptr(idx), int(period), ptr(code), int(n), C, H, W, ptr(out), stream())
+
+
+def grayscale_u8(frames, idx, period, grey, n, out):
+    """RandomGrayscale of n samples (curla_grayscale_u8): frames u8 [rows, H, W, C] with C a multiple of 3; sample s is row
+    idx[s % period] (idx None: s % period), every RGB triplet replaced by its grey value where grey[s] != 0 (int32 [n]);
+    out u8 [n, H, W, C]."""
+    _, H, W, C = frames.shape
+    _check_scratch_u8("grayscale_u8", frames, idx, period, (grey,), n, out, tuple(out.shape) == (n, H, W, C) and C % 3 == 0,
+                      ("flags", " of RGB triplets"))
+    call("curla_grayscale_u8", ptr(frames), ptr(idx), int(period), ptr(grey), int(n), C, H, W, ptr(out), stream())
+
+
 def nhwc_to_nchw(x, out):
     B, H, W, C = x.shape
     call("curla_nhwc_to_nchw", ptr(x), ptr(out), B, H, W, C, stream())

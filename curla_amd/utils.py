@@ -903,7 +903,7 @@ class ReplayBuffer(object):
     # control values (RNG stream positions, Adam step factors) that the graph's kernels read from the device copy.
     def graph_supported(self):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
-        ones (RandomCrop / RandomShift / RandomCutout / RandomTranslate / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
+        ones (RandomCrop / RandomShift / RandomCutout / RandomTranslate / RandomFlip / RandomRotate / RandomGrayscale / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
         are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover / RandomConv constructed with
         ``staged_aug=True`` (either storage).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
         through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""

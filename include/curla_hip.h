@@ -633,6 +633,35 @@ int curla_translate_u8(const uint8_t* frames, const int64_t* idx, int period, co
 int curla_move_cutout_u8(const uint8_t* frames, const int64_t* idx, int period, int move, const int32_t* a, const int32_t* b,
                          int pad, const int32_t* y0, const int32_t* x0, const int32_t* size, const int32_t* rgb, int n, int C,
                          int H, int W, int Ho, int Wo, uint8_t* out, void* stream);
+/* RandomFlip / RandomRotate, the flip and rotate of RAD (beyond the reference: its augmentations.py has neither): one of
+ * the eight maps of the dihedral group per sample, shared by all channels of a stack.  code: int32 [n], three bits
+ * FX = 1, FY = 2, T = 4; with (a, b) = (x, y) if T is set, else (y, x):
+ *   out[s][y][x][c] = frames[row(s)][FY ? H - 1 - a : a][FX ? W - 1 - b : b][c],  0 <= s < n
+ * (1 mirrors left-right, 2 upside down; 5, 3, 6 turn by 90, 180, 270 degrees counter-clockwise, as np.rot90 over (H, W)).
+ * uint8 NHWC in ([rows][H][W][C]) and out ([n][H][W][C], 32 bytes of slack behind it like a ring), row(s) = idx[s % period]
+ * (idx NULL: s % period) as for curla_random_shift_u8.  The effective code is code[s] & 7, and additionally & 3 where
+ * H != W (only a square frame can be transposed in place): whatever the words hold, every output byte is written exactly
+ * once, nothing is read outside the source frame and nothing is written outside `out`.  One launch, mixed codes in it:
+ * codes 0..3 move 16 bytes per lane from unaligned 16-byte loads combined in registers (a frame of a multiple of 16 bytes
+ * with `out` on a 16-byte boundary; every other case gives the same bytes one at a time); codes 4..7 stage the source
+ * columns of a band of output rows in LDS (gathered from global memory directly where H segments do not fit 64 KiB).
+ * Any C > 0.  Additive: CURLA_ABI_VERSION stays 8.  CURLA_ERR_ARG on a NULL pointer, `code` off 4 bytes, `idx` off 8, or
+ * n, period, C, H or W < 1; CURLA_ERR_UNSUPPORTED when H W C does not fit 31 bits; both before any launch. */
+int curla_dihedral_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* code, int n, int C, int H,
+                      int W, uint8_t* out, void* stream);
+/* RandomGrayscale, the grayscale of RAD (beyond the reference: its augmentations.py has no such class).  Where grey[s] != 0
+ * every RGB triplet of the sample, in all frames of the stack, becomes (g, g, g):
+ *   g = (77 R + 150 G + 29 B + 128) >> 8        (weights that sum to 256: (v, v, v) stays (v, v, v), the map is idempotent)
+ * and where grey[s] == 0 the frame is copied.  uint8 NHWC in ([rows][H][W][C]) and out ([n][H][W][C], 32 bytes of slack
+ * behind it like a ring), row(s) = idx[s % period] (idx NULL: s % period) as for curla_random_shift_u8.  grey: int32 [n].
+ * C must be a multiple of 3.  No address depends on the words: nothing is read outside the source frame and nothing is
+ * written outside `out`.  A frame of a multiple of 16 bytes with `out` on a 16-byte boundary moves 16 bytes per lane (the
+ * triplets that straddle a group's ends come from the dword in front of and behind it); every other case gives the same
+ * bytes one at a time.  Additive: CURLA_ABI_VERSION stays 8.  CURLA_ERR_ARG on a NULL pointer, `grey` off 4 bytes, `idx`
+ * off 8, n, period, C, H or W < 1 or C % 3 != 0; CURLA_ERR_UNSUPPORTED when H W C does not fit 31 bits; both before any
+ * launch. */
+int curla_grayscale_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* grey, int n, int C, int H,
+                       int W, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
