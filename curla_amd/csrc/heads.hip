@@ -1382,6 +1382,7 @@ __global__ void gather_stacks_kernel(const uint8_t* store, const int32_t* fid, i
   }
 }
 
+#include "per.h"    // prioritized replay: per_set's three phases, per_sample_kernel, per_td_kernel
 #include "stage.h"  // stage_frames_kernel: N planar frames into N ring slots, crop fused (batched acting)
 
 // NHWC float activation -> NCHW (for callers that read encoder.outputs)
@@ -2063,6 +2064,42 @@ int curla_sample_stage_nstep(const void* host_block, void* device_block, long lo
                      static_cast<hipStream_t>(stream), static_cast<const unsigned long long*>(host_block),
                      static_cast<unsigned long long*>(device_block), nwords, (int)(next_row_offset / 8), scalars, cont,
                      capacity, n, discount, B, A, action, reward, not_done);
+  return curla_launch_status();
+}
+
+int curla_per_set(float* s, double* sums, float* vmax, long long capacity, const int64_t* rows, long long first_row,
+                  const float* values, int n, void* stream) {
+  CURLA_REQUIRE(s && sums && vmax && n >= 1 && capacity >= 1);
+  CURLA_REQUIRE((((uintptr_t)s | (uintptr_t)vmax | (uintptr_t)values) & 3) == 0 && (((uintptr_t)sums | (uintptr_t)rows) & 7) == 0);
+  CURLA_REQUIRE(rows || (first_row >= 0 && first_row < capacity));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((n + 255) / 256), block(256);
+  if (values) hipLaunchKernelGGL(per_clear_kernel, grid, block, 0, st, s, rows, first_row, capacity, n);
+  hipLaunchKernelGGL(per_write_kernel, grid, block, 0, st, s, vmax, rows, first_row, capacity, values, n);
+  hipLaunchKernelGGL(per_resum_kernel, dim3((n + 3) / 4), block, 0, st, s, sums, rows, first_row, capacity, n);
+  return curla_launch_status();
+}
+
+int curla_per_sample(const float* s, const double* sums, long long capacity, void* device_block, long long u_offset,
+                     long long prob_offset, int B, void* stream) {
+  CURLA_REQUIRE(s && sums && device_block && B >= 1 && capacity >= 1);
+  CURLA_REQUIRE(((uintptr_t)s & 3) == 0 && (((uintptr_t)sums | (uintptr_t)device_block) & 7) == 0);
+  CURLA_REQUIRE(u_offset % 8 == 0 && prob_offset % 4 == 0 && u_offset >= 16LL * B && prob_offset >= 16LL * B);
+  CURLA_REQUIRE(u_offset < (1LL << 30) && prob_offset < (1LL << 30));
+  CURLA_REQUIRE(u_offset + 8LL * B <= prob_offset || prob_offset + 4LL * B <= u_offset);
+  hipLaunchKernelGGL(per_sample_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), s, sums, capacity,
+                     static_cast<unsigned long long*>(device_block), (int)(u_offset / 8), (int)(prob_offset / 4), B);
+  return curla_launch_status();
+}
+
+int curla_per_td(const float* q, long long twin_stride, const float* target_q, const float* prob, float beta, float eps,
+                 float alpha, int B, float* dq, float* loss, float* w, float* value, void* stream) {
+  CURLA_REQUIRE(q && target_q && prob && dq && loss && w && value && B >= 1 && twin_stride >= B);
+  CURLA_REQUIRE((((uintptr_t)q | (uintptr_t)target_q | (uintptr_t)prob | (uintptr_t)dq | (uintptr_t)loss | (uintptr_t)w |
+                  (uintptr_t)value) & 3) == 0);
+  CURLA_REQUIRE(beta >= 0.f && beta <= 1.f && eps > 0.f && alpha >= 0.f);
+  hipLaunchKernelGGL(per_td_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), q, twin_stride, target_q,
+                     prob, beta, eps, alpha, B, dq, loss, w, value);
   return curla_launch_status();
 }
 

@@ -333,6 +333,7 @@ class _Workspace:
         self.dxa = f(2, B, F + A)
         self.q_dh1, self.q_dh2 = f(2, B, H), f(2, B, H)
         self.dq, self.target_q = f(2, B, 1), f(B, 1)
+        self.per_w = self.per_value = None  # importance weights / new stored values [B]: a prioritized buffer's updates only
         # scalars: [0] critic loss, [1..4] actor_loss/alpha_loss/entropy/alpha, [5] curl loss, [6] batch reward
         self.scalars = torch.zeros(8, device=dev, dtype=torch.float32)
         # CURL
@@ -1067,6 +1068,16 @@ class CurlSacAgent(object):
                    scalars=ws.scalars[0:1], dq=ws.dq),
               lambda: ops.critic_td_loss(ws.q, ws.tq, B, ws.log_pi, reward, not_done, self.log_alpha, self.discount, B,
                                          ws.target_q, ws.scalars[0:1], ws.dq))
+        per = getattr(obs, "per", None)
+        if per is not None:
+            # a prioritized minibatch (ReplayBuffer(prioritized=True)): the loss launch on its own, then the importance
+            # weights scale dq and the loss in place and the drawn rows get their new priorities -- all on the device --,
+            # and the backward pass runs on the weighted dq
+            if ws.per_w is None:
+                ws.per_w, ws.per_value = (torch.empty(B, device=ws.dq.device, dtype=torch.float32) for _ in range(2))
+            td[1]()
+            per.td_update(ws.q, B, ws.target_q, ws.dq, ws.scalars[0:1], ws.per_w, ws.per_value)
+            td = None
         _mlp_bwd(ws.xa, 0, self.critic.twin(), self.critic.twin(grads=True), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.dq,
                  ws.q_dh2, ws.q_dh1, ws.dxa, loss=td)
         if step % self.log_interval == 0:
@@ -1395,7 +1406,8 @@ class CurlSacAgent(object):
                              "(covered: RandomCrop, RandomShift, RandomCutout, RandomTranslate or identity, plain storage with both rings in one "
                              "allocation or dedup_frames storage -- RandomFlip, RandomRotate and RandomGrayscale like them; ColorJiggle / NoisyCover / RandomConv "
                              "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
-                             "CURLA_STAGE_COPY=1)")
+                             "CURLA_STAGE_COPY=1; not a prioritized=True buffer, whose draw and priority update are not "
+                             "nodes of the graphs)")
         opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer)
         if not all(isinstance(o, FlatAdam) and "step" not in vars(o) for o in opts) or \
                 type(self.log_alpha_optimizer) is not torch.optim.Adam or self._noise_launch:

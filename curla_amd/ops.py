@@ -27,13 +27,15 @@ class ObsRef:
     a float NCHW tensor in [0,255] (is_u8 = 0: the reference's tensor contract) or
     a float NHWC tensor (is_u8 = 2: output of the float augmentations)."""
 
-    __slots__ = ("src", "is_u8", "idx", "h1", "w1", "B", "C", "Hs", "Ws", "Hc", "Wc", "guard", "pair")
+    __slots__ = ("src", "is_u8", "idx", "h1", "w1", "B", "C", "Hs", "Ws", "Hc", "Wc", "guard", "pair", "per")
 
     def __init__(self):
         self.guard = None
         # (merged handle, second handle): this minibatch followed by ``second``'s as ONE handle of 2B observations
         # (set by ReplayBuffer.sample_cpc_refs on obs for (obs | next_obs))
         self.pair = None
+        # the priority side of a minibatch drawn from a prioritized ReplayBuffer (utils.PerHandle; set on obs)
+        self.per = None
 
     @staticmethod
     def from_ring(frames, idx, h1, w1, B, crop_hw, guard=None):
@@ -667,6 +669,49 @@ def sample_stage_nstep(host_dev_ptr, dev_block, nbytes, next_row_off, sc, cont, 
     """sample_stage with the n-step composition in the same launch."""
     call("curla_sample_stage_nstep", host_dev_ptr, ptr(dev_block), nbytes, int(next_row_off), ptr(sc), ptr(cont),
          int(capacity), int(n), float(discount), B, A, ptr(act), ptr(rew), ptr(nd), stream())
+
+
+# ---- prioritized replay (curla_hip.h: curla_per_set / curla_per_sample / curla_per_td) ----
+PER_CHUNK = 256  # CURLA_PER_CHUNK: rows per float64 chunk sum
+
+
+def per_chunks(capacity):
+    """Chunk sums a ring of ``capacity`` rows needs."""
+    return (int(capacity) + PER_CHUNK - 1) // PER_CHUNK
+
+
+def per_set(s, sums, vmax, n, rows=None, first_row=0, values=None):
+    """Store the values of n rows: ``rows`` (int64 device tensor) or the run first_row, first_row + 1, ... modulo the
+    capacity; ``values`` (float32 device tensor) or, None, the maximum scalar ``vmax``.  Duplicates take their maximum,
+    ``vmax`` is raised, the touched chunk sums are rebuilt."""
+    _dev(s), _dev(sums, torch.float64), _dev(vmax)
+    cap = s.numel()
+    if sums.numel() != per_chunks(cap) or vmax.numel() != 1 or n < 1:
+        raise _lib.CurlaHipError(f"per_set: {sums.numel()} chunk sums / {vmax.numel()} maxima for {cap} rows, n = {n}")
+    if rows is not None and (_dev(rows, torch.int64).numel() < n):
+        raise _lib.CurlaHipError(f"per_set: {rows.numel()} rows for n = {n}")
+    if values is not None and (_dev(values).numel() < n):
+        raise _lib.CurlaHipError(f"per_set: {values.numel()} values for n = {n}")
+    call("curla_per_set", ptr(s), ptr(sums), ptr(vmax), cap, ptr(rows), int(first_row), ptr(values), int(n), stream())
+
+
+def per_sample(s, sums, dev_block, u_off, prob_off, B):
+    """Draw the B rows of a minibatch whose targets u (float64 [B] at byte ``u_off`` of the device block) are staged:
+    writes the block's int64 [2B] index run and the probabilities (float32 [B] at ``prob_off``)."""
+    _dev(s), _dev(sums, torch.float64), _dev(dev_block, torch.uint8)
+    if max(u_off + 8 * B, prob_off + 4 * B) > dev_block.numel() or sums.numel() != per_chunks(s.numel()):
+        raise _lib.CurlaHipError("per_sample: the u / prob fields do not fit the block, or the chunk sums the ring")
+    call("curla_per_sample", ptr(s), ptr(sums), s.numel(), ptr(dev_block), int(u_off), int(prob_off), B, stream())
+
+
+def per_td(q, twin_stride, target_q, prob, beta, eps, alpha, B, dq, loss, w, value):
+    """Importance weights ``w``, ``dq`` scaled by them in place, the weighted critic loss and the candidate stored
+    values of a prioritized minibatch (behind critic_td_loss)."""
+    for t, n in ((q, twin_stride + B), (target_q, B), (prob, B), (dq, twin_stride + B), (loss, 1), (w, B), (value, B)):
+        if _dev(t).numel() < n:
+            raise _lib.CurlaHipError(f"per_td: a tensor of {t.numel()} elements where {n} are needed")
+    call("curla_per_td", ptr(q), twin_stride, ptr(target_q), ptr(prob), float(beta), float(eps), float(alpha), B, ptr(dq),
+         ptr(loss), ptr(w), ptr(value), stream())
 
 
 def crop_nchw(frames, idx, h1, w1, B, crop_hw, out_f32=None, out_u8=None):

@@ -199,6 +199,50 @@ class _FrameStore:
                     del self.recent[h]
 
 
+def _checked_per(alpha, beta, eps):
+    """(per_alpha, per_beta, per_eps) of a prioritized ReplayBuffer as floats; ValueError unless 0 <= alpha,
+    0 <= beta <= 1 and eps > 0."""
+    vals = []
+    for name, v in (("per_alpha", alpha), ("per_beta", beta), ("per_eps", eps)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+        vals.append(float(v))
+    a, b, e = vals
+    if not (0.0 <= a < float("inf") and 0.0 <= b <= 1.0 and 0.0 < e < float("inf")):
+        raise ValueError("prioritized replay needs 0 <= per_alpha, 0 <= per_beta <= 1 and per_eps > 0, got %r, %r, %r"
+                         % (alpha, beta, eps))
+    return a, b, e
+
+
+class PerHandle:
+    """What a prioritized minibatch hands the learner (``obs.per``, the way ``ObsRef.pair`` rides on the obs handle):
+    ``rows`` int64 [B] and ``prob`` float32 [B], views of the minibatch's device block -- the drawn ring rows and their
+    sampling probabilities --, and ``td_update``, the priority half of a critic update.  Valid as long as the
+    minibatch's pixel handles are."""
+
+    __slots__ = ("buffer", "rows", "prob", "guard")
+
+    def __init__(self, buffer, rows, prob, guard):
+        self.buffer, self.rows, self.prob, self.guard = buffer, rows, prob, guard
+
+    def td_update(self, q, twin_stride, target_q, dq, loss, w, value):
+        """Behind the critic's TD loss launch (``q``, ``target_q`` and the unweighted ``dq`` are there): the importance
+        weights into ``w``, ``dq`` scaled by them in place, the weighted loss into ``loss``, and the rows' new stored
+        values ``(0.5 (|q1 - t| + |q2 - t|) + per_eps) ** per_alpha`` into ``value`` and from there into the buffer (a row
+        drawn twice keeps the larger one).  Two entry points: curla_per_td, curla_per_set.
+        The rows are those of the DRAW: call this before any ``add`` that may overwrite one of them (``agent.update()``
+        does).  An add between the draw and this call that lands on a drawn row would see its fresh transition's
+        maximum priority replaced by the old transition's TD error; the guard only notices a recycled sample slot."""
+        g = self.guard
+        if g is not None and g[0][g[1]] != g[2]:
+            raise RuntimeError("stale minibatch: the replay buffer has recycled this sample's device block")
+        rb = self.buffer
+        alpha, beta, eps = _checked_per(rb.per_alpha, rb.per_beta, rb.per_eps)
+        B = rb.batch_size
+        ops.per_td(q, twin_stride, target_q, self.prob, beta, eps, alpha, B, dq, loss, w, value)
+        ops.per_set(rb._per_s, rb._per_sums, rb._per_max, B, rows=self.rows, values=value)
+
+
 # what ReplayBuffer._sources returns
 _Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off words")
 
@@ -215,7 +259,21 @@ class ReplayBuffer(object):
     that was the very next add, ``done`` was false and row i's ``next_obs`` equals row i + 1's ``obs`` byte for byte --
     a time-limit truncation or a reset breaks the chain without a change to ``add``'s signature.  A caller that
     interleaves several environments into one buffer therefore gets a break at every switch, i.e. 1-step targets.
-    ``n_step=1`` (default) is the reference's buffer: nothing is allocated, launched or laid out differently."""
+    ``n_step=1`` (default) is the reference's buffer: nothing is allocated, launched or laid out differently.
+
+    ``prioritized=True`` (beyond the reference; Schaul et al. 2016, the proportional variant) draws row i with
+    probability ``s_i / sum_j s_j``, ``s_i = p_i ** per_alpha`` being the value stored for the row in HBM.  A transition
+    written by ``add``, ``add_batch`` or ``load`` (a ring wrap included) gets the largest value stored so far (1.0 at
+    first); rows never written hold 0 and are never drawn.  The draw is stratified -- the host draws
+    ``np.random.random_sample(B)`` where it draws ``randint`` otherwise, sample k looks for ``(k + r_k) / B`` of the total
+    -- and happens in a kernel that writes the rows into the minibatch's device block, so ``draw_indices`` returns
+    ``(u, offs)`` in this mode and the host never learns the rows.  The obs handle of a sample carries ``per`` (a
+    ``PerHandle``): ``CurlSacAgent.update_critic`` weights its loss by ``(min_j P_j / P_k) ** per_beta`` and stores
+    ``(0.5 (|q1 - t| + |q2 - t|) + per_eps) ** per_alpha`` for the drawn rows; ``update_priorities`` does the same for user
+    code.  ``per_alpha``, ``per_beta`` and ``per_eps`` are plain attributes read at every sample or update (anneal
+    ``per_beta`` by assigning it).  Priorities are not part of the reference's ``save`` payload and are NOT persisted:
+    ``load`` gives every loaded row the maximum.  Such a buffer is not graph-replayable (``graph_supported``).
+    ``prioritized=False`` (default): nothing is allocated, launched or laid out differently."""
 
     N_SAMPLE_SLOTS = 2  # minibatches whose references may be alive at once (the current one + one drawn ahead)
     EVENT_EVERY = 8     # index uploads per recorded event (16 pinned slots)
@@ -225,11 +283,16 @@ class ReplayBuffer(object):
     GUARD, GUARD_BYTE = 256, 0xA5  # around a graph slot's minibatch buffers (_guarded)
 
     def __init__(self, obs_shape, action_shape, capacity, batch_size, device, augmentor, transform=None,
-                 dedup_frames=False, frame_capacity=None, staged_aug=False, n_step=1, discount=None):
+                 dedup_frames=False, frame_capacity=None, staged_aug=False, n_step=1, discount=None,
+                 prioritized=False, per_alpha=0.6, per_beta=0.4, per_eps=1e-6):
         if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or n_step < 1:
             raise ValueError("n_step must be an int >= 1, got %r" % (n_step,))
         self.n_step = int(n_step)
         self.discount = _checked_discount(discount) if self.n_step > 1 else discount
+        self.prioritized = bool(prioritized)
+        if self.prioritized:
+            _checked_per(per_alpha, per_beta, per_eps)
+        self.per_alpha, self.per_beta, self.per_eps = per_alpha, per_beta, per_eps
         self.capacity = capacity
         self.batch_size = batch_size
         self.device = torch.device(device)
@@ -267,6 +330,8 @@ class ReplayBuffer(object):
             total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * self._scratch_frame() + 32)
         if self.n_step > 1:  # the continuity flags
             total_bytes += capacity
+        if self.prioritized:  # the stored values and their chunk sums
+            total_bytes += 4 * capacity + 8 * ops.per_chunks(capacity)
         if self.device.type == "cuda":
             free, _ = torch.cuda.mem_get_info(self.device)
             if total_bytes > free:
@@ -307,6 +372,11 @@ class ReplayBuffer(object):
         self.actions = self._sc[:, :A].unflatten(1, tuple(action_shape)) if len(action_shape) != 1 else self._sc[:, :A]
         self.rewards = self._sc[:, A:A + 1]
         self.not_dones = self._sc[:, A + 1:A + 2]
+        if self.prioritized:
+            # stored values p^alpha, one float64 sum per chunk of ops.PER_CHUNK rows, the largest value given so far
+            self._per_s = torch.zeros(capacity, dtype=torch.float32, device=dev)
+            self._per_sums = torch.zeros(ops.per_chunks(capacity), dtype=torch.float64, device=dev)
+            self._per_max = torch.ones(1, dtype=torch.float32, device=dev)
         self.idx = 0
         self.last_save = 0
         self.full = False
@@ -350,8 +420,9 @@ class ReplayBuffer(object):
         self._h_index = torch.empty((self._n_slots, nbytes), dtype=torch.uint8, pin_memory=pin)
         self._slot_events = {}
         # pinned slots are read by the GPU in place (ops.sample_stage): no copy-engine transfer in front of an update
+        # (a prioritized block goes by the copy: the draw is a kernel of its own between the block and the gathers)
         self._h_index_dev = ([ops.host_device_pointer(self._h_index[k]) for k in range(self._n_slots)]
-                             if pin and os.environ.get("CURLA_STAGE_COPY", "0") != "1" else None)
+                             if pin and os.environ.get("CURLA_STAGE_COPY", "0") != "1" and not self.prioritized else None)
         # every minibatch gets its own device index block (and, de-duplicated, its own assembled stacks), so the
         # references of one sample stay valid while the next one is drawn (N_SAMPLE_SLOTS alive at a time)
         self._d_index = torch.empty((self.N_SAMPLE_SLOTS, nbytes), dtype=torch.uint8, device=dev)
@@ -471,6 +542,8 @@ class ReplayBuffer(object):
             self._sc[i].copy_(self._d_add_sc)
             if self.n_step > 1:
                 self._store_cont(i, prev)
+            if self.prioritized:
+                self._per_new_rows(i, 1)
         else:  # host-side bookkeeping only (index logic tests); pixels are still stored, HWC
             h, w = self.obs_shape[1:]
             n = self._d_add_frames[0].numel()
@@ -482,7 +555,14 @@ class ReplayBuffer(object):
             if self.n_step > 1:
                 for r in (i,) if prev is None else (prev, i):
                     self._cont[r] = int(self._cont_h[r])
+            if self.prioritized and _lib_tracing():
+                self._per_new_rows(i, 1)
         self._advance(1)
+
+    def _per_new_rows(self, first, n):
+        """Rows first, first + 1, ... (n of them, modulo capacity) hold new transitions: they get the maximum stored
+        value.  One curla_per_set, stream-ordered behind the rows' writes."""
+        ops.per_set(self._per_s, self._per_sums, self._per_max, n, first_row=first)
 
     def _advance(self, n):
         new_idx = self.idx + n
@@ -598,6 +678,8 @@ class ReplayBuffer(object):
             self.not_dones[slots_d] = torch.as_tensor(nd, device=self.device)
             if self.n_step > 1:
                 self._cont_rows(self.idx, obses[s:e], next_obses[s:e], nd)
+            if self.prioritized and (self.device.type == "cuda" or _lib_tracing()):
+                self._per_new_rows(self.idx, m)
             self._advance(m)
 
     def frames_in_use(self):
@@ -619,9 +701,18 @@ class ReplayBuffer(object):
         RandomShift / RandomTranslate, (y0, x0) of a RandomCutout's boxes; zeros when it draws none).  An augmentation of
         four words -- RandomCutout -- returns int32 [12, B], rows 6 + 2j, 6 + 2j + 1 = the other two (its packed sizes
         and colours); one of six -- Compose -- int32 [18, B] by the same rule (word r of tensor j in row 6 (r // 2) + 2 j +
-        r % 2): the move's offsets, the box's (y0, x0), its sizes and colours."""
+        r % 2): the move's offsets, the box's (y0, x0), its sizes and colours.
+        ``prioritized``: returns (u, offsets), u float64 [B] the stratified targets (k + r_k) / B with
+        r = np.random.random_sample(B) drawn where the rows are drawn otherwise -- the rows themselves are drawn by
+        curla_per_sample from u."""
         B = self.batch_size
-        idxs = np.random.randint(0, self.capacity if self.full else self.idx, size=B)
+        if self.prioritized:
+            # the stratified targets instead of the rows: u_k = (k + r_k) / B; the rows are drawn on the device
+            if not self.full and self.idx == 0:
+                raise ValueError("cannot sample an empty prioritized buffer")
+            idxs = (np.arange(B) + np.random.random_sample(B)) / B
+        else:
+            idxs = np.random.randint(0, self.capacity if self.full else self.idx, size=B)
         if self._kind is None:
             raise NotImplementedError("unknown augmentation object: %r" % (self.augmentor,))
         offs = np.zeros((6 * max(1, (self._index_rows + 1) // 2), B), dtype=np.int32)
@@ -656,6 +747,9 @@ class ReplayBuffer(object):
         one launch of n = 3B.  One that draws six -- Compose -- appends ``cut`` int32 [4][3B]: the third to sixth words, the
         box's y0 | x0 | sizes | colours.
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
+        ``prioritized`` appends ``u`` float64 [B], the targets of the draw (written by the host), and ``prob`` float32 [B]
+        (+ 4 bytes of padding when B is odd), the drawn rows' probabilities (written by curla_per_sample, which also
+        writes the idx run: the host leaves zeros there).
         ``nbytes`` is what a rotating sample slot stages per minibatch; the block of a captured update graph carries
         GRAPH_TAIL more bytes of per-update control values behind it (at ``tail``; ``graph_nbytes`` in all)."""
         B = self.batch_size
@@ -672,6 +766,11 @@ class ReplayBuffer(object):
         if self.n_step > 1:  # next_row int64 [B]: the bootstrap rows without the double ring's offset (device-written)
             lay["next_row"] = n
             n += 8 * B
+        if self.prioritized:  # u float64 [B]: the draw's targets (host-written) | prob float32 [B] (device-written)
+            lay["u"] = n
+            n += 8 * B
+            lay["prob"] = n
+            n += (4 * B + 7) // 8 * 8
         lay.update(nbytes=n, tail=n, graph_nbytes=n + self.GRAPH_TAIL)
         return lay
 
@@ -713,8 +812,16 @@ class ReplayBuffer(object):
         offsets and 2B column offsets."""
         B, lay = self.batch_size, self._layout
         i64 = host[lay["idx"]:lay["offs"]].view(torch.int64)
-        i64[:B].copy_(torch.from_numpy(np.ascontiguousarray(idxs, dtype=np.int64)))
-        i64[B:].copy_(i64[:B] + self.capacity)
+        if self.prioritized:  # ``idxs`` are the targets u: the rows are the draw kernel's to write
+            u = np.ascontiguousarray(idxs, dtype=np.float64).reshape(-1)
+            if np.asarray(idxs).dtype.kind != "f" or u.shape != (B,) or not ((u >= 0.0) & (u < 1.0)).all():
+                raise ValueError("a prioritized buffer takes indices=(u, offs) with u float64 [B] in [0, 1) (draw_indices)")
+            i64.zero_()
+            host[lay["u"]:lay["u"] + 8 * B].view(torch.float64).copy_(torch.from_numpy(u))
+            host[lay["prob"]:lay["nbytes"]].zero_()
+        else:
+            i64[:B].copy_(torch.from_numpy(np.ascontiguousarray(idxs, dtype=np.int64)))
+            i64[B:].copy_(i64[:B] + self.capacity)
         o32 = host[lay["offs"]:lay["offs_end"]].view(torch.int32).view(6, B)
         offs = np.ascontiguousarray(offs, dtype=np.int32)
         if "cut" in lay and len(offs) != 3 * self._index_rows:
@@ -756,6 +863,8 @@ class ReplayBuffer(object):
             if self.device.type == "cuda" or _lib_tracing():
                 B, A, lay = self.batch_size, self._n_act, self._layout
                 out = slot["scalars"]
+                if self.prioritized:  # the draw: rows into the block's idx run, their probabilities into ``prob``
+                    ops.per_sample(self._per_s, self._per_sums, dst, lay["u"], lay["prob"], B)
                 ops.gather_transition_scalars(self._sc, dst[lay["idx"]:lay["idx"] + 8 * B].view(torch.int64), B, A, *out)
                 if self.n_step > 1:  # the bootstrap rows must be in the block before anything reads pixels
                     ops.nstep_compose(dst, lay["next_row"], self._sc, self._cont, self.capacity, self.n_step,
@@ -905,9 +1014,10 @@ class ReplayBuffer(object):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
         ones (RandomCrop / RandomShift / RandomCutout / RandomTranslate / RandomFlip / RandomRotate / RandomGrayscale / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
         are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover / RandomConv constructed with
-        ``staged_aug=True`` (either storage).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
+        ``staged_aug=True`` (either storage).  A ``prioritized`` buffer is not covered (its draw and its priority update are
+        not nodes of the captured graphs).  A float augmentation WITHOUT staged_aug draws and uploads its parameters
         through a pinned block of its own per call and stays eager.  Pinned index slots read in place are required."""
-        if self.device.type != "cuda" or self._h_index_dev is None:
+        if self.device.type != "cuda" or self._h_index_dev is None or self.prioritized:
             return False
         if self._kind == "float":
             return self.staged_aug
@@ -993,6 +1103,8 @@ class ReplayBuffer(object):
         idxs, offs = indices if indices is not None else self.draw_indices()
         slot, guard = self._upload_indices(idxs, offs, self.draw_aug())
         obses, next_obses, pos = self._assemble(slot, guard)
+        if self.prioritized:
+            obses.per = self._per_handle(slot, guard)
         actions, rewards, not_dones = slot["scalars"]  # (valid as long as the pixel handles are)
         cpc_kwargs = dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
         return obses, actions, rewards, next_obses, not_dones, cpc_kwargs
@@ -1002,7 +1114,7 @@ class ReplayBuffer(object):
         in [0,255] on the device (materialised by one crop kernel per tensor)."""
         self._require_cuda()
         idxs, offs = indices if indices is not None else self.draw_indices()
-        slot, _ = self._upload_indices(idxs, offs, self.draw_aug())
+        slot, guard = self._upload_indices(idxs, offs, self.draw_aug())
         B = self.batch_size
         c = self.obs_shape[0]
         oh, ow = self.augmentor.output_shape
@@ -1020,10 +1132,48 @@ class ReplayBuffer(object):
                 ops.crop_nchw(ring, rows, src.off[2 * j], src.off[2 * j + 1], B, (oh, ow), out_f32=t)
             outs.append(t)
         obses, next_obses, pos = outs
+        if self.prioritized:  # (the tensor is fresh, the handle is not: valid until the slot is drawn again)
+            obses.per = self._per_handle(slot, guard)
         # fresh tensors, like the reference's
         actions, rewards, not_dones = (t.clone() for t in slot["scalars"])
         cpc_kwargs = dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
         return obses, actions, rewards, next_obses, not_dones, cpc_kwargs
+
+    # ------------------------------------------------------------------ priorities
+    def _per_handle(self, slot, guard):
+        B, lay, dev = self.batch_size, self._layout, slot["dev"]
+        return PerHandle(self, dev[lay["idx"]:lay["idx"] + 8 * B].view(torch.int64),
+                         dev[lay["prob"]:lay["prob"] + 4 * B].view(torch.float32), guard)
+
+    def _require_prioritized(self):
+        if not self.prioritized:
+            raise RuntimeError("this ReplayBuffer was constructed with prioritized=False")
+
+    def update_priorities(self, rows, values):
+        """Store ``values`` (float32 device tensor [n], the stored values themselves, i.e. ``p ** per_alpha``; >= 0) for
+        ring rows ``rows`` (int64 device tensor [n]) -- the rule of the critic update: a row named several times takes
+        its largest value, and the maximum that new transitions get is raised, never lowered.
+        Preconditions, not checked on the device (a check would read the tensors back): every row lies in [0, len_valid)
+        -- ``capacity`` once the ring is full, ``idx`` before; a row beyond holds no transition and a positive value would
+        make it drawable, one outside [0, capacity) is written out of bounds -- and at least one row of the buffer keeps
+        a positive value (a draw from a ring without any mass returns row 0 with probability 0, which the critic update
+        gives weight 0).  Values are stored finite and non-negative: a negative one, -0 or a NaN becomes 0 (the row is
+        then never drawn), +inf the largest float."""
+        self._require_prioritized()
+        if not (isinstance(rows, torch.Tensor) and isinstance(values, torch.Tensor) and rows.dtype == torch.int64
+                and values.dtype == torch.float32 and rows.dim() == 1 and rows.shape == values.shape and rows.numel()):
+            raise ValueError("update_priorities takes an int64 and a float32 device tensor of one shape [n], n >= 1")
+        if rows.device != self._per_s.device or values.device != self._per_s.device:
+            raise ValueError("update_priorities takes tensors on the buffer's device %s, got %s and %s"
+                             % (self._per_s.device, rows.device, values.device))
+        ops.per_set(self._per_s, self._per_sums, self._per_max, rows.numel(), rows=rows.contiguous(),
+                    values=values.contiguous())
+
+    def priorities(self):
+        """The stored values ``p ** per_alpha`` of rows [0, len_valid) -- ``capacity`` once the ring is full, ``idx``
+        before -- as a NumPy float32 array (a device-to-host copy: inspection, not the training loop)."""
+        self._require_prioritized()
+        return self._per_s[:self.capacity if self.full else self.idx].cpu().numpy()
 
     # ------------------------------------------------------------------ persistence
     def stacks(self, lo, hi, which=0):
@@ -1066,7 +1216,7 @@ class ReplayBuffer(object):
             if lo != self.idx:
                 raise AssertionError("chunk %s does not continue the buffer at index %d" % (name, self.idx))
             obs, nxt, act, rew, nd = torch.load(os.path.join(save_dir, name), weights_only=False)
-            if self.dedup_frames:
+            if self.dedup_frames:  # (prioritized: every add of the loop gives its row the maximum)
                 self.add_batch(obs, act, rew, nxt, 1.0 - np.asarray(nd))
                 self.idx = hi  # (the reference's load does not wrap either)
                 continue
@@ -1077,6 +1227,8 @@ class ReplayBuffer(object):
                 dst[lo:hi] = torch.as_tensor(src).to(self.device)
             if self.n_step > 1:  # the flags are rebuilt from the payload, never stored
                 self._cont_rows(lo, obs, nxt, nd)
+            if self.prioritized and hi > lo and (self.device.type == "cuda" or _lib_tracing()):
+                self._per_new_rows(lo, hi - lo)  # priorities are not in the payload: the loaded rows get the maximum
             self.idx = hi
 
     def __len__(self):

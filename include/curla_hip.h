@@ -542,6 +542,49 @@ int curla_nstep_compose(void* device_block, long long next_row_offset, const flo
 int curla_sample_stage_nstep(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
                              const float* scalars, const uint8_t* cont, long long capacity, int n, float discount, int B,
                              int A, float* action, float* reward, float* not_done, void* stream);
+/* Proportional prioritized replay (beyond the reference: ReplayBuffer(prioritized=True); Schaul et al. 2016).
+ * Storage, all on the device: `s` float [capacity], the stored value p_i^alpha of every ring row (0 = never written:
+ * never drawn) | `sums` double [ceil(capacity / CURLA_PER_CHUNK)], one sum per chunk of CURLA_PER_CHUNK consecutive
+ * rows | `vmax` float [1], the largest value ever given (the caller initialises it, to 1), which new transitions take.
+ *
+ * curla_per_set writes the values of n rows -- rows[i] (int64, device), or with rows == NULL the run first_row,
+ * first_row + 1, ... modulo capacity -- to values[i], or with values == NULL to *vmax.  A row that occurs several
+ * times takes the maximum of its values; values are finite and non-negative (a negative one, -0 or a NaN stores +0,
+ * +inf stores FLT_MAX, so the sign bit is clear and every sum stays finite); *vmax is raised
+ * to the largest given value, never lowered.  Afterwards the sum of every chunk that holds a row of the call is the
+ * float64 sum of that chunk's current values in one fixed order (lane l of a wave adds rows l, l + 64, l + 128,
+ * l + 192, then an xor tree 32 .. 1 over the lanes).  Up to three stream-ordered launches (clear, write, re-sum): no
+ * chunk is summed before every row of the call is written.  CURLA_ERR_ARG before any launch on: s, sums or vmax NULL;
+ * s, vmax or values off 4 bytes; sums or rows off 8; n < 1; capacity < 1; rows == NULL and first_row outside
+ * [0, capacity).  rows[i] are not range-checked (as for the gathers above).
+ *
+ * curla_per_sample draws B rows: for sample k, with u = the float64 at byte u_offset + 8 k of `device_block`
+ * (0 <= u < 1) and total = the sum of `sums`, the smallest row i whose cumulative sum of s exceeds u total -- strictly --,
+ * cumulative sums in float64.  Found in three levels (64 runs of chunk sums, the chunks of one run, the rows of one
+ * chunk), each a sequential prefix sum; the levels associate their sums differently and may round differently, and where
+ * a level's walk would pass its end the last entry with a positive value is taken, so a row with s == 0 is never drawn;
+ * sums that are exact in float64 (integers, say) give the rows of a sequential cumulative sum exactly.  One workgroup per sample reads ceil(capacity / CURLA_PER_CHUNK) * 8 +
+ * CURLA_PER_CHUNK * 4 bytes.  Writes int64 [k] = i and [B + k] = capacity + i at the start of the block (the index run
+ * every loader reads) and the float s[i] / total at byte prob_offset + 4 k.  With total == 0: row 0, probability 0.
+ * CURLA_ERR_ARG before the launch on: a NULL pointer; s off 4 bytes; sums or device_block off 8; B < 1; capacity < 1;
+ * u_offset not a multiple of 8 or prob_offset of 4; either inside the 16 B index bytes, not below 2^30, or the two
+ * fields overlapping.
+ *
+ * curla_per_td, behind the critic's TD loss (q, target_q and dq as curla_critic_td_loss leaves them; prob from
+ * curla_per_sample), in one launch of one workgroup:
+ *   w[k] = (min_j prob[j] / prob[k])^beta;  dq[k] *= w[k], dq[twin_stride + k] *= w[k]  (beta == 0: dq keeps its bits;
+ *          prob[k] == 0, which only a draw from a ring without any mass gives: w[k] = 0)
+ *   loss[0] = (1/B) sum_k w[k] ((q[k] - t[k])^2 + (q[twin_stride + k] - t[k])^2)
+ *   value[k] = (0.5 (|q[k] - t[k]| + |q[twin_stride + k] - t[k]|) + eps)^alpha   -- what curla_per_set then stores.
+ * CURLA_ERR_ARG before the launch on: a NULL pointer or one off 4 bytes; B < 1; twin_stride < B; beta outside [0, 1];
+ * eps <= 0; alpha < 0.  All three are additive: CURLA_ABI_VERSION stays 8. */
+#define CURLA_PER_CHUNK 256
+int curla_per_set(float* s, double* sums, float* vmax, long long capacity, const int64_t* rows, long long first_row,
+                  const float* values, int n, void* stream);
+int curla_per_sample(const float* s, const double* sums, long long capacity, void* device_block, long long u_offset,
+                     long long prob_offset, int B, void* stream);
+int curla_per_td(const float* q, long long twin_stride, const float* target_q, const float* prob, float beta, float eps,
+                 float alpha, int B, float* dq, float* loss, float* w, float* value, void* stream);
 /* device-visible address of a pinned (hipHostMalloc'd / registered) host pointer; CURLA_ERR_ARG if it is not */
 int curla_host_device_pointer(void* host, void** device);
 /* ReplayBuffer.add: one CHW uint8 observation into ring slot `slot` (utils.py:120-128) */
