@@ -80,6 +80,9 @@ SIGNATURES = {
     "curla_sample_stage": [vp, vp, c_ll, vp, c_int, c_int, vp, vp, vp, vp],
     "curla_nstep_compose": [vp, c_ll, vp, vp, c_ll, c_int, c_float, c_int, c_int, vp, vp, vp, vp],
     "curla_sample_stage_nstep": [vp, vp, c_ll, c_ll, vp, vp, c_ll, c_int, c_float, c_int, c_int, vp, vp, vp, vp],
+    "curla_pos_walk": [vp, c_ll, c_ll, c_ll, vp, c_ll, c_int, c_int, c_int, vp],
+    "curla_sample_stage_pos": [vp, vp, c_ll, c_ll, c_ll, c_ll, vp, vp, c_ll, c_int, c_float, c_int, c_int, c_int, vp, vp, vp,
+                               vp],
     "curla_per_set": [vp, vp, vp, c_ll, vp, c_ll, vp, c_int, vp],
     "curla_per_sample": [vp, vp, c_ll, vp, c_ll, c_ll, c_int, vp],
     "curla_per_td": [vp, c_ll, vp, vp, c_float, c_float, c_float, c_int, vp, vp, vp, vp, vp],

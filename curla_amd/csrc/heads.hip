@@ -1306,6 +1306,70 @@ __global__ void sample_stage_nstep_kernel(const unsigned long long* host, unsign
     nstep_compose_one(sc, cont, capacity, n, gamma, A, r0, b, B, dev, dev + nr_word, rew, nd);
 }
 
+// Ring row r0 advanced along the continuity flags at most `steps` times (steps == 0 reads no flag): the row walk of
+// nstep_compose_one without its arithmetic.
+__device__ __forceinline__ long long chain_walk(const uint8_t* cont, long long capacity, long long r0, int steps) {
+  long long r = r0;
+  for (int m = 0; m < steps && cont[r]; ++m) r = r + 1 == capacity ? 0 : r + 1;
+  return r;
+}
+
+// Temporal positive of sample b, which starts at ring row r0 (beyond the reference; the positive selection of ATC,
+// Stooke et al. 2021): the positive is next_obs of row r = r0 walked k - 1 links, i.e. the observation min(k, steps the
+// chain still has) steps after obs[r0].  Written twice into pos[0 .. 2B): r in word b, capacity + r (the double ring's
+// next_obs half) in word B + b.  `run` (or NULL): int64 [3B] = obs | next_obs | pos rows of the double ring for ONE
+// launch of a scratch augmentation -- r0, capacity + (r0 walked n - 1 links: the n-step bootstrap row, walked again
+// here so that no word of the block is read that another thread of the launch writes), capacity + r.
+__device__ __forceinline__ void temporal_pos_one(const uint8_t* cont, long long capacity, int k, int n, long long r0, int b,
+                                                 int B, unsigned long long* pos, unsigned long long* run) {
+  const long long r = chain_walk(cont, capacity, r0, k - 1);
+  pos[b] = (unsigned long long)r;
+  pos[B + b] = (unsigned long long)(capacity + r);
+  if (run) {
+    run[b] = (unsigned long long)r0;
+    run[B + b] = (unsigned long long)(capacity + chain_walk(cont, capacity, r0, n - 1));
+    run[2 * B + b] = (unsigned long long)(capacity + r);
+  }
+}
+
+// The walk on a block that is already on the device (idx = its first B words): one thread per sample.
+__global__ void pos_walk_kernel(unsigned long long* dev, int pos_word, int run_word, const uint8_t* cont,
+                                long long capacity, int k, int n, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  temporal_pos_one(cont, capacity, k, n, (long long)dev[b], b, B, dev + pos_word, run_word >= 0 ? dev + run_word : nullptr);
+}
+
+// sample_stage_kernel (nr_word < 0) or sample_stage_nstep_kernel (nr_word >= 0) with the positive's walk in the same
+// launch, by the same discipline: the copy leaves out the words a walk writes (with the composition B .. 2B - 1 and
+// next_row; the 2B words of pos; the 3B of run), each of them has exactly one writer -- sample b's reward thread for the
+// composition's, its not_done thread for the positive's --, and a walking thread reads its start row from the pinned
+// block with the same system-scope load as the copy.  The two walks are independent: k and n are unrelated.
+__global__ void sample_stage_pos_kernel(const unsigned long long* host, unsigned long long* dev, int nwords, int nr_word,
+                                        int pos_word, int run_word, const float* sc, const uint8_t* cont,
+                                        long long capacity, int n, float gamma, int k, int B, int A, float* act,
+                                        float* rew, float* nd) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool walked = (nr_word >= 0 && ((i >= B && i < 2 * B) || (i >= nr_word && i < nr_word + B))) ||
+                      (i >= pos_word && i < pos_word + 2 * B) || (run_word >= 0 && i >= run_word && i < run_word + 3 * B);
+  if (i < nwords && !walked) dev[i] = __hip_atomic_load(host + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (i >= B * (A + 2)) return;
+  const int b = i / (A + 2), c = i - b * (A + 2);
+  const long long r0 = (long long)__hip_atomic_load(host + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  const size_t ld = (size_t)A + 2;
+  if (c < A) {
+    act[(size_t)b * A + c] = sc[(size_t)r0 * ld + c];
+  } else if (c == A) {
+    if (nr_word >= 0)
+      nstep_compose_one(sc, cont, capacity, n, gamma, A, r0, b, B, dev, dev + nr_word, rew, nd);
+    else
+      rew[b] = sc[(size_t)r0 * ld + A];
+  } else {
+    if (nr_word < 0) nd[b] = sc[(size_t)r0 * ld + A + 1];
+    temporal_pos_one(cont, capacity, k, n, r0, b, B, dev + pos_word, run_word >= 0 ? dev + run_word : nullptr);
+  }
+}
+
 // out[b][c][i][j] = (float) frames[idx[b]][h1[b]+i][w1[b]+j][c]          (augmentations.py:47-75 + utils.py:161)
 __global__ void crop_nchw_kernel(const uint8_t* frames, const int64_t* idx, const int32_t* h1, const int32_t* w1,
                                  int B, int C, int Hs, int Ws, int Hc, int Wc, float* out_f32, uint8_t* out_u8) {
@@ -2064,6 +2128,60 @@ int curla_sample_stage_nstep(const void* host_block, void* device_block, long lo
                      static_cast<hipStream_t>(stream), static_cast<const unsigned long long*>(host_block),
                      static_cast<unsigned long long*>(device_block), nwords, (int)(next_row_offset / 8), scalars, cont,
                      capacity, n, discount, B, A, action, reward, not_done);
+  return curla_launch_status();
+}
+
+// [a, a + na) and [b, b + nb) share no byte
+static inline bool curla_disjoint(long long a, long long na, long long b, long long nb) { return a + na <= b || b + nb <= a; }
+
+// The offsets of the positive's walk inside a block of `limit` bytes: pos (2B words) and, unless -1, run (3B words) and
+// next_row (B words) -- 8-byte aligned, behind the 2B index words, inside the block, none overlapping another.
+static bool curla_pos_offsets_ok(long long pos_offset, long long run_offset, long long next_row_offset, int B,
+                                 long long limit) {
+  const long long idx_end = 16LL * B, npos = 16LL * B, nrun = 24LL * B, nnr = 8LL * B;
+  if (pos_offset % 8 != 0 || pos_offset < idx_end || pos_offset + npos > limit) return false;
+  if (run_offset != -1) {
+    if (run_offset % 8 != 0 || run_offset < idx_end || run_offset + nrun > limit) return false;
+    if (!curla_disjoint(run_offset, nrun, pos_offset, npos)) return false;
+  }
+  if (next_row_offset != -1) {
+    if (next_row_offset % 8 != 0 || next_row_offset < idx_end || next_row_offset + nnr > limit) return false;
+    if (!curla_disjoint(next_row_offset, nnr, pos_offset, npos)) return false;
+    if (run_offset != -1 && !curla_disjoint(next_row_offset, nnr, run_offset, nrun)) return false;
+  }
+  return true;
+}
+
+int curla_pos_walk(void* device_block, long long pos_offset, long long run_offset, long long next_row_offset,
+                   const uint8_t* cont, long long capacity, int k, int n, int B, void* stream) {
+  CURLA_REQUIRE(device_block && B > 0 && k >= 1 && n >= 1 && capacity >= 1 && (uintptr_t)device_block % 8 == 0);
+  CURLA_REQUIRE(cont || (k == 1 && (n == 1 || run_offset == -1)));
+  CURLA_REQUIRE(curla_pos_offsets_ok(pos_offset, run_offset, next_row_offset, B, 1LL << 30));
+  hipLaunchKernelGGL(pos_walk_kernel, dim3((B + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned long long*>(device_block), (int)(pos_offset / 8),
+                     run_offset == -1 ? -1 : (int)(run_offset / 8), cont, capacity, k, n, B);
+  return curla_launch_status();
+}
+
+int curla_sample_stage_pos(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
+                           long long pos_offset, long long run_offset, const float* scalars, const uint8_t* cont,
+                           long long capacity, int n, float discount, int k, int B, int A, float* action, float* reward,
+                           float* not_done, void* stream) {
+  CURLA_REQUIRE(host_block && device_block && scalars && action && reward && not_done && B > 0 && A > 0);
+  CURLA_REQUIRE(k >= 1 && n >= 1 && capacity >= 1);
+  CURLA_REQUIRE(next_row_offset != -1 || n == 1);  // without a next_row region there is no composition
+  CURLA_REQUIRE(cont || (k == 1 && n == 1));
+  CURLA_REQUIRE(nbytes % 8 == 0 && nbytes >= 0 && nbytes < (1LL << 30));
+  CURLA_REQUIRE(curla_pos_offsets_ok(pos_offset, run_offset, next_row_offset, B, nbytes));
+  CURLA_REQUIRE(((uintptr_t)host_block | (uintptr_t)device_block) % 8 == 0);
+  const int nwords = (int)(nbytes / 8);
+  const int nthreads = nwords > B * (A + 2) ? nwords : B * (A + 2);
+  hipLaunchKernelGGL(sample_stage_pos_kernel, dim3((nthreads + 255) / 256), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned long long*>(host_block),
+                     static_cast<unsigned long long*>(device_block), nwords,
+                     next_row_offset == -1 ? -1 : (int)(next_row_offset / 8), (int)(pos_offset / 8),
+                     run_offset == -1 ? -1 : (int)(run_offset / 8), scalars, cont, capacity, n, discount, k, B, A, action,
+                     reward, not_done);
   return curla_launch_status();
 }
 

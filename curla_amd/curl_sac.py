@@ -1455,10 +1455,10 @@ class CurlSacAgent(object):
                 hyper, self._graph_rb_key())
 
     def _graph_rb_key(self):
-        """(n_step, discount) of the graphs' replay buffer: its staging launch holds both by value."""
+        """(n_step, discount, pos_offset) of the graphs' replay buffer: its staging launch holds them by value."""
         rb = getattr(self, "_graph_rb", None)
         n = getattr(rb, "n_step", 1)
-        return (n, float(rb.discount)) if n > 1 else (1, None)
+        return ((n, float(rb.discount)) if n > 1 else (1, None)) + (getattr(rb, "pos_offset", 0),)
 
     def _graph_tail(self, kind, B):
         """The 80 control bytes of one graphed update (ReplayBuffer.GRAPH_TAIL) -- and the host-side bookkeeping of

@@ -671,6 +671,26 @@ def sample_stage_nstep(host_dev_ptr, dev_block, nbytes, next_row_off, sc, cont, 
          int(capacity), int(n), float(discount), B, A, ptr(act), ptr(rew), ptr(nd), stream())
 
 
+def _off(o):
+    """A block offset as the library takes it: None (the block has no such region) travels as -1."""
+    return -1 if o is None else int(o)
+
+
+def pos_walk(dev_block, pos_off, run_off, next_row_off, cont, capacity, k, n, B):
+    """The temporal positive's rows of a minibatch whose index block is already on the device (curla_hip.h:
+    curla_pos_walk): r and capacity + r at ``pos_off``, the 3B run of a scratch augmentation at ``run_off`` (None: no
+    run); ``next_row_off`` (None: the block has none) is only checked against."""
+    call("curla_pos_walk", ptr(dev_block), int(pos_off), _off(run_off), _off(next_row_off), ptr(cont), int(capacity),
+         int(k), int(n), B, stream())
+
+
+def sample_stage_pos(host_dev_ptr, dev_block, nbytes, next_row_off, pos_off, run_off, sc, cont, capacity, n, discount, k,
+                     B, A, act, rew, nd):
+    """sample_stage (``next_row_off`` None) or sample_stage_nstep with the temporal positive's walk in the same launch."""
+    call("curla_sample_stage_pos", host_dev_ptr, ptr(dev_block), nbytes, _off(next_row_off), int(pos_off), _off(run_off),
+         ptr(sc), ptr(cont), int(capacity), int(n), float(discount), int(k), B, A, ptr(act), ptr(rew), ptr(nd), stream())
+
+
 # ---- prioritized replay (curla_hip.h: curla_per_set / curla_per_sample / curla_per_td) ----
 PER_CHUNK = 256  # CURLA_PER_CHUNK: rows per float64 chunk sum
 

@@ -244,7 +244,7 @@ class PerHandle:
 
 
 # what ReplayBuffer._sources returns
-_Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off words")
+_Sources = collections.namedtuple("_Sources", "both idx2 h2 w2 tensors off words pos2 run period")
 
 
 class ReplayBuffer(object):
@@ -273,7 +273,22 @@ class ReplayBuffer(object):
     code.  ``per_alpha``, ``per_beta`` and ``per_eps`` are plain attributes read at every sample or update (anneal
     ``per_beta`` by assigning it).  Priorities are not part of the reference's ``save`` payload and are NOT persisted:
     ``load`` gives every loaded row the maximum.  Such a buffer is not graph-replayable (``graph_supported``).
-    ``prioritized=False`` (default): nothing is allocated, launched or laid out differently."""
+    ``prioritized=False`` (default): nothing is allocated, launched or laid out differently.
+
+    ``pos_offset=k >= 1`` (beyond the reference; the temporal contrast of ATC, Stooke et al. 2021) makes the CURL positive
+    of a sampled row t an augmentation of the observation up to k steps LATER in the same episode instead of a second
+    augmentation of ``obs[t]``: the positive is ``next_obs[r]``, r being t advanced along the continuity flags ``cont``
+    (the rule above) at most k - 1 times -- ``r = t; repeat k - 1 times: if not cont[r]: stop; r = (r + 1) % capacity``
+    -- i.e. the observation ``min(k, steps the chain still has from t)`` steps after ``obs[t]``.  It never crosses an
+    episode end, a truncation, a reset, the write head or an overwritten row; interleaved environments break the chain
+    at every switch (the positive is then ``next_obs[t]``).  ``k = 1`` gives ``next_obs[t]`` and needs no flag: the flags
+    are kept when ``n_step > 1`` or ``pos_offset > 1``.  The walk happens on the device, in the staging launch of the
+    minibatch (curla_sample_stage_pos; curla_pos_walk where the block travels by copy), so the host draws exactly what
+    it draws with ``pos_offset=0``: a seeded run samples the same transitions with the same three augmentation draws,
+    only the positive's pixels differ, and ``cpc_kwargs`` keeps ``time_anchor=None, time_pos=None``.  This is ATC's
+    positive SELECTION behind CURL's own bilinear head and momentum encoder -- not ATC's residual predictor.  Read-only
+    after construction (it decides the block layout).  ``pos_offset=0`` (default): nothing is allocated, launched or laid
+    out differently."""
 
     N_SAMPLE_SLOTS = 2  # minibatches whose references may be alive at once (the current one + one drawn ahead)
     EVENT_EVERY = 8     # index uploads per recorded event (16 pinned slots)
@@ -284,11 +299,16 @@ class ReplayBuffer(object):
 
     def __init__(self, obs_shape, action_shape, capacity, batch_size, device, augmentor, transform=None,
                  dedup_frames=False, frame_capacity=None, staged_aug=False, n_step=1, discount=None,
-                 prioritized=False, per_alpha=0.6, per_beta=0.4, per_eps=1e-6):
+                 prioritized=False, per_alpha=0.6, per_beta=0.4, per_eps=1e-6, pos_offset=0):
+        if isinstance(pos_offset, bool) or not isinstance(pos_offset, (int, np.integer)) or pos_offset < 0:
+            raise ValueError("pos_offset must be an int >= 0, got %r" % (pos_offset,))
+        self._pos_offset = int(pos_offset)
         if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or n_step < 1:
             raise ValueError("n_step must be an int >= 1, got %r" % (n_step,))
         self.n_step = int(n_step)
         self.discount = _checked_discount(discount) if self.n_step > 1 else discount
+        # the continuity flags serve both chain walks: the n-step composition and a positive more than one step ahead
+        self._keep_cont = self.n_step > 1 or self._pos_offset > 1
         self.prioritized = bool(prioritized)
         if self.prioritized:
             _checked_per(per_alpha, per_beta, per_eps)
@@ -323,12 +343,12 @@ class ReplayBuffer(object):
                 frame_capacity = capacity + capacity // 16 + 4 * self._k + 8
             self.frame_capacity = int(frame_capacity)
             total_bytes = self.frame_capacity * 3 * h * w + capacity * (8 * self._k + 4 * A + 8) \
-                + self.N_SAMPLE_SLOTS * 2 * batch_size * frame
+                + self.N_SAMPLE_SLOTS * (3 if self._pos_offset else 2) * batch_size * frame
         else:
             total_bytes = 2 * capacity * frame + capacity * (4 * A + 8)
         if self._kind == "scratch":  # the augmented minibatches (obs | next_obs | pos) of the sample slots
             total_bytes += self.N_SAMPLE_SLOTS * (3 * batch_size * self._scratch_frame() + 32)
-        if self.n_step > 1:  # the continuity flags
+        if self._keep_cont:  # the continuity flags
             total_bytes += capacity
         if self.prioritized:  # the stored values and their chunk sums
             total_bytes += 4 * capacity + 8 * ops.per_chunks(capacity)
@@ -389,7 +409,7 @@ class ReplayBuffer(object):
         self._sc_off = (n_stage + 15) & ~15
         self._hdr = 4 * (2 * self._k) if self.dedup_frames else 0  # frame-id row in front of the scalars
         blk = self._sc_off + self._hdr + 4 * (A + 2)
-        if self.n_step > 1:
+        if self._keep_cont:
             # cont[i] = 1: row (i + 1) % capacity continues row i's episode (class docstring).  The flags of the previous
             # row and of the new one (always 0) ride behind the scalars of the add block; the host keeps a mirror and
             # what it needs of the previous add to evaluate the rule.
@@ -431,7 +451,9 @@ class ReplayBuffer(object):
         self._sample_slot = -1
         if self.dedup_frames:
             # (obs stacks | next_obs stacks) of a minibatch, contiguous: also one [2B] ring for ObsRef.pair
-            self._mb_store = torch.zeros((self.N_SAMPLE_SLOTS, 2 * B * frame + 32), dtype=torch.uint8, device=dev)
+            # (pos_offset > 0: | the positives' stacks, [3B])
+            self._mb_store = torch.zeros((self.N_SAMPLE_SLOTS, (3 if self._pos_offset else 2) * B * frame + 32),
+                                         dtype=torch.uint8, device=dev)
         if self._kind == "scratch":
             # The scratch of a "scratch" augmentation: a minibatch's augmented frames, uint8 [3B][Ho][Wo][C] = (obs |
             # next_obs | pos) -- (Ho, Wo) = the augmentor's output_shape -- + 32 B of slack like a ring, per sample slot
@@ -443,10 +465,12 @@ class ReplayBuffer(object):
             self._shift_zero = torch.zeros(3 * B, dtype=torch.int32, device=dev)
         # A slot = the buffers ONE minibatch is assembled in (_assemble): ``dev`` the device block, ``scal`` the
         # transitions' scalars and ``scalars`` its (actions, rewards, not_dones) views, ``mb_u8`` the gathered stacks +
-        # ``ar2`` = rows 0..2B-1 (frame store), ``shift_u8`` the frames of a "scratch" augmentation, ``both_f32`` / ``pos_f32``
+        # ``ar2`` = rows 0..2B-1 (frame store; pos_offset > 0: 0..3B-1), ``shift_u8`` the frames of a "scratch" augmentation,
+        # ``both_f32`` / ``pos_f32``
         # the float tensors (absent here: allocated per call).  The rotating slots are views of the stores above; a
         # captured update graph has slots of its own with the same keys (graph_block).
-        ar2 = torch.arange(2 * B, dtype=torch.int64, device=dev) if self.dedup_frames else None
+        ar2 = (torch.arange((3 if self._pos_offset else 2) * B, dtype=torch.int64, device=dev)
+               if self.dedup_frames else None)
         self._sample_slots = []
         for s in range(self.N_SAMPLE_SLOTS):
             slot = dict(dev=self._d_index[s], scal=self._d_scal[s], scalars=self._scalar_views(self._d_scal[s]))
@@ -456,6 +480,11 @@ class ReplayBuffer(object):
                 slot["shift_u8"] = self._shift_store[s]
             self._sample_slots.append(slot)
         self._graph_blocks = {}
+
+    @property
+    def pos_offset(self):
+        """k of the temporal positive (class docstring); fixed at construction: it decides the block layout."""
+        return self._pos_offset
 
     # ------------------------------------------------------------------ writing
     def _stage_scalars(self, row, action, reward, done):
@@ -516,7 +545,7 @@ class ReplayBuffer(object):
         row[fr:2 * fr] = np.asarray(next_obs, dtype=np.uint8).reshape(-1)
         sc = self._stage_scalars(row, action, reward, done)
         prev = None
-        if self.n_step > 1:  # one comparison of a frame on the host, against the copy kept of the previous next_obs
+        if self._keep_cont:  # one comparison of a frame on the host, against the copy kept of the previous next_obs
             same = self._last_next is not None and np.array_equal(row[:fr], self._last_next)
             prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0)
             if self._last_next is None:
@@ -540,7 +569,7 @@ class ReplayBuffer(object):
             if self.dedup_frames:
                 self._fid[i].view(-1).copy_(self._d_add[self._sc_off:self._sc_off + self._hdr].view(torch.int32))
             self._sc[i].copy_(self._d_add_sc)
-            if self.n_step > 1:
+            if self._keep_cont:
                 self._store_cont(i, prev)
             if self.prioritized:
                 self._per_new_rows(i, 1)
@@ -552,7 +581,7 @@ class ReplayBuffer(object):
             if self.dedup_frames:
                 self._fid[i] = torch.from_numpy(self._fid_h[i].copy())
             self._sc[i] = torch.from_numpy(sc.copy())
-            if self.n_step > 1:
+            if self._keep_cont:
                 for r in (i,) if prev is None else (prev, i):
                     self._cont[r] = int(self._cont_h[r])
             if self.prioritized and _lib_tracing():
@@ -614,13 +643,13 @@ class ReplayBuffer(object):
                     new.append(fid)
                 st.refs[fid] += 1
             ids[j] = fid
-        if self.n_step > 1:  # equal bytes have equal frame ids: the new obs row against the previous next_obs row
+        if self._keep_cont:  # equal bytes have equal frame ids: the new obs row against the previous next_obs row
             p = self._last_row
             same = p is not None and p != i and np.array_equal(ids[:K], self._fid_h[p, 1])
         self._fid_h[i] = ids.reshape(2, K)
         row[self._sc_off:self._sc_off + self._hdr].view(np.int32)[:] = ids
         sc = self._stage_scalars(row, action, reward, done)
-        prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0) if self.n_step > 1 else None
+        prev = self._stage_cont(row, i, same, sc[self._n_act + 1] == 1.0) if self._keep_cont else None
         # two partial copies: the new frames (if any), then frame ids | scalars | flags
         n = len(new) * f3
         copies = [(self._d_add[:n], self._h_add[slot, :n])] if n else []
@@ -676,7 +705,7 @@ class ReplayBuffer(object):
                                                     device=self.device)
             nd = 1.0 - np.asarray(dones[s:e], dtype=np.float32).reshape(m, 1)
             self.not_dones[slots_d] = torch.as_tensor(nd, device=self.device)
-            if self.n_step > 1:
+            if self._keep_cont:
                 self._cont_rows(self.idx, obses[s:e], next_obses[s:e], nd)
             if self.prioritized and (self.device.type == "cuda" or _lib_tracing()):
                 self._per_new_rows(self.idx, m)
@@ -747,6 +776,9 @@ class ReplayBuffer(object):
         one launch of n = 3B.  One that draws six -- Compose -- appends ``cut`` int32 [4][3B]: the third to sixth words, the
         box's y0 | x0 | sizes | colours.
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
+        ``pos_offset > 0`` appends ``pos_row`` int64 [2][B] behind them, written by the positive's walk: the rows r whose
+        next_obs is the positive, then capacity + r (the same rows in the double ring) -- and for a "scratch" augmentation
+        ``pos_run`` int64 [3B], the double-ring rows of obs | next_obs | pos as one run for its single launch.
         ``prioritized`` appends ``u`` float64 [B], the targets of the draw (written by the host), and ``prob`` float32 [B]
         (+ 4 bytes of padding when B is odd), the drawn rows' probabilities (written by curla_per_sample, which also
         writes the idx run: the host leaves zeros there).
@@ -766,6 +798,12 @@ class ReplayBuffer(object):
         if self.n_step > 1:  # next_row int64 [B]: the bootstrap rows without the double ring's offset (device-written)
             lay["next_row"] = n
             n += 8 * B
+        if self._pos_offset:  # pos_row int64 [2][B] (| pos_run int64 [3B], scratch): the positive's walk writes them
+            lay["pos_row"] = n
+            n += 16 * B
+            if self._kind == "scratch":
+                lay["pos_run"] = n
+                n += 24 * B
         if self.prioritized:  # u float64 [B]: the draw's targets (host-written) | prob float32 [B] (device-written)
             lay["u"] = n
             n += 8 * B
@@ -869,6 +907,9 @@ class ReplayBuffer(object):
                 if self.n_step > 1:  # the bootstrap rows must be in the block before anything reads pixels
                     ops.nstep_compose(dst, lay["next_row"], self._sc, self._cont, self.capacity, self.n_step,
                                       self._nstep_discount(), B, A, *out)
+                if self._pos_offset:  # ... and so must the positive's rows (behind the draw, which writes the idx run)
+                    ops.pos_walk(dst, lay["pos_row"], lay.get("pos_run"), lay.get("next_row"),
+                                 self._cont if self._keep_cont else None, self.capacity, self._pos_offset, self.n_step, B)
         if self.device.type == "cuda" and u % every == every - 1:
             ev = torch.cuda.Event()
             ev.record()
@@ -888,9 +929,15 @@ class ReplayBuffer(object):
 
     def _stage(self, host_dev, dev, nbytes, out):
         """The staging launch of a minibatch: pinned block -> device block + the transitions' scalars into ``out``
-        (_scalar_views); with n_step > 1 the n-step composition happens in the same launch."""
+        (_scalar_views); with n_step > 1 the n-step composition, with pos_offset > 0 the positive's walk happens in the same
+        launch."""
         B, A = self.batch_size, self._n_act
-        if self.n_step > 1:
+        if self._pos_offset:  # still ONE launch: the positive's walk beside the copy and, n_step > 1, the composition
+            lay = self._layout
+            ops.sample_stage_pos(host_dev, dev, nbytes, lay.get("next_row"), lay["pos_row"], lay.get("pos_run"), self._sc,
+                                 self._cont if self._keep_cont else None, self.capacity, self.n_step,
+                                 self._nstep_discount() if self.n_step > 1 else 1.0, self._pos_offset, B, A, *out)
+        elif self.n_step > 1:
             ops.sample_stage_nstep(host_dev, dev, nbytes, self._layout["next_row"], self._sc, self._cont, self.capacity,
                                    self.n_step, self._nstep_discount(), B, A, *out)
         else:
@@ -906,43 +953,57 @@ class ReplayBuffer(object):
         here and nowhere else.  Returns a _Sources:
           tensors  (ring, rows) of obs, next_obs, pos: ONE ring each, ``rows`` int64 [B] or None for rows 0..B-1;
                    next_obs at the sampled rows, or with n_step > 1 at the bootstrap rows that the composition wrote into
-                   the block (block_layout: next_row)
+                   the block (block_layout: next_row); pos the obs ring at the sampled rows, or with pos_offset > 0 the
+                   next_obs ring at the rows the positive's walk wrote (block_layout: pos_row)
           off      the six offset rows: off[2j] / off[2j+1] = h1 / w1 of tensor j
           both     the ring of obs frames then next_obs frames in which (obs | next_obs) is ONE run of 2B rows ``idx2``
                    (None: rows 0..2B-1) with offsets ``h2`` / ``w2``; None when the rings are two allocations
+          pos2     the positive's rows in ``both`` (None with ``idx2``: rows 0..B-1, pos_offset > 0: 2B..3B-1)
+          run      in ``both``, the rows that ONE launch over obs | next_obs | pos reads, sample s row run[s % period]
+                   (None: s % period): ``idx2`` with period 2B, with pos_offset > 0 the block's pos_run with period 3B
           words    the index words of obs, next_obs, pos as int32 runs of 3B each: the h rows, the w rows (RandomShift's
                    (dy, dx), RandomTranslate's (ty, tx), RandomCutout's (y0, x0)) and, where four words are drawn, the
                    runs of ``cut`` (RandomCutout's packed box sizes and colour words; Compose's y0, x0, sizes, colours)
         Plain storage reads the rings at the sampled rows.  The frame store first assembles the k frames of every
-        sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor)."""
+        sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor; with pos_offset > 0 a third
+        one, the next_obs stacks of the positive's rows, into a buffer of [3B])."""
         B, lay, dev = self.batch_size, self._layout, slot["dev"]
         d64 = dev[lay["idx"]:lay["offs"]].view(torch.int64)
         d32 = dev[lay["offs"]:lay["offs_end"]].view(torch.int32)
         off = [d32[(j // 2 + 3 * (j % 2)) * B:(j // 2 + 3 * (j % 2) + 1) * B] for j in range(6)]
         rows = d64[:B]
         rows_n = rows if self.n_step == 1 else dev[lay["next_row"]:lay["next_row"] + 8 * B].view(torch.int64)
+        kp = self._pos_offset
+        # the positive: an augmentation of obs again, or with pos_offset > 0 of next_obs at the rows its walk wrote
+        p64 = dev[lay["pos_row"]:lay["pos_row"] + 16 * B].view(torch.int64) if kp else None
+        rows_p, period = (p64[:B] if kp else rows), (3 if kp else 2) * B
         if self.dedup_frames:
             c, h, w = self.obs_shape
-            both = slot["mb_u8"][:2 * B * self._frame].view(2 * B, h, w, c)
-            rings, idx2 = (both[:B], both[B:]), None
-            for j, r in enumerate((rows, rows_n)):
-                ops.gather_stacks(self.frames, self._fid[:, j, :], r, B, rings[j])
-            rows = rows_n = None
+            nt = 3 if kp else 2
+            both = slot["mb_u8"][:nt * B * self._frame].view(nt * B, h, w, c)
+            rings, idx2 = tuple(both[j * B:(j + 1) * B] for j in range(nt)), None
+            for j, r in enumerate((rows, rows_n, rows_p)[:nt]):
+                ops.gather_stacks(self.frames, self._fid[:, min(j, 1), :], r, B, rings[j])
+            rows = rows_n = rows_p = None
+            pos, pos2, run = (rings[2 if kp else 0], None), None, None
         else:
             both, rings, idx2 = self._both, (self.obses, self.next_obses), d64
+            pos = (rings[1 if kp else 0], rows_p)
+            pos2 = p64[B:] if kp else rows  # (the double ring's next_obs half: capacity + r)
+            run = dev[lay["pos_run"]:lay["pos_run"] + 24 * B].view(torch.int64) if "pos_run" in lay else d64
         words = (d32[:3 * B], d32[3 * B:])
         if "cut" in lay:
             runs = self._index_rows - 2
             c32 = dev[lay["cut"]:lay["cut"] + 12 * runs * B].view(torch.int32)
             words += tuple(c32[3 * B * k:3 * B * (k + 1)] for k in range(runs))
-        return _Sources(both, idx2, d32[:2 * B], d32[3 * B:5 * B], ((rings[0], rows), (rings[1], rows_n), (rings[0], rows)),
-                        off, words)
+        return _Sources(both, idx2, d32[:2 * B], d32[3 * B:5 * B], ((rings[0], rows), (rings[1], rows_n), pos), off, words,
+                        pos2, run, period)
 
     def _scratch_aug(self, slot, src):
         """A "scratch" augmentation: the frames of a minibatch (``src``: _sources) augmented by its ``scratch_launch`` --
         shifted, boxes painted, placed on the canvas -- into the slot's scratch as obs | next_obs | pos; returns the
         [3B][Ho][Wo][C] view ((Ho, Wo) = output_shape).  With ``both`` ONE launch, pos reading the obs rows again (period
-        2B); with the rings in two allocations one launch per tensor."""
+        2B) or, pos_offset > 0, its own rows (period 3B); with the rings in two allocations one launch per tensor."""
         B = self.batch_size
         oh, ow = self.augmentor.output_shape
         out = slot["shift_u8"][:3 * B * self._scratch_frame()].view(3 * B, oh, ow, self.obs_shape[0])
@@ -950,7 +1011,7 @@ class ReplayBuffer(object):
         def launch(ring, rows, period, lo, hi):
             self.augmentor.scratch_launch(ring, rows, period, [w[lo:hi] for w in src.words], hi - lo, out[lo:hi])
         if src.both is not None:
-            launch(src.both, src.idx2, 2 * B, 0, 3 * B)
+            launch(src.both, src.run, src.period, 0, 3 * B)
         else:
             for j, (ring, rows) in enumerate(src.tensors):
                 launch(ring, rows, B, j * B, (j + 1) * B)
@@ -996,9 +1057,11 @@ class ReplayBuffer(object):
                 # them can share a first-layer launch (ops.conv1_fwd2), and (obs | next_obs) is itself a handle of
                 # 2B frames: the critic phase runs both through the online convs in one launch per layer
                 # (curl_sac.py:350-358)
+                pos2 = src.pos2
                 if idx2 is None:
-                    idx2 = slot["ar2"]
-                tensors = (both, idx2[:B]), (both, idx2[B:]), (both, idx2[:B])
+                    ar = slot["ar2"]
+                    idx2, pos2 = ar[:2 * B], (ar[2 * B:] if self._pos_offset else ar[:B])
+                tensors = (both, idx2[:B]), (both, idx2[B:]), (both, pos2)
             # (else rings in two allocations -- the second half would not start on a dword: no pair)
             obses, next_obses, pos = (ops.ObsRef.from_ring(ring, rows, off[2 * j], off[2 * j + 1], B, crop, guard)
                                       for j, (ring, rows) in enumerate(tensors))
@@ -1040,8 +1103,9 @@ class ReplayBuffer(object):
             # augmentation.  Each sits between guard bytes (tests/test_gpu_graph_aug.py).
             frame = self._frame
             if self.dedup_frames:
-                (g["mb_u8"],) = self._guarded([2 * B * frame + 32], g["guards"])  # (+32: the loaders' slack, as a ring)
-                g["ar2"] = torch.arange(2 * B, device=self.device, dtype=torch.int64)
+                nt = 3 if self._pos_offset else 2  # (+32: the loaders' slack, as a ring)
+                (g["mb_u8"],) = self._guarded([nt * B * frame + 32], g["guards"])
+                g["ar2"] = torch.arange(nt * B, device=self.device, dtype=torch.int64)
             if self._kind == "scratch":  # the augmented (obs | next_obs | pos) frames, + the loaders' slack
                 (g["shift_u8"],) = self._guarded([3 * B * self._scratch_frame() + 32], g["guards"])
             if self._kind == "float":
@@ -1082,13 +1146,15 @@ class ReplayBuffer(object):
     def graph_refs(self, slot):
         """Device side, called while the graph is being captured: the staging launch (pinned block -> device block +
         the transitions' scalars), for the de-duplicated store the two gather_stacks launches (they read ``_fid`` when
-        the graph is replayed), for RandomShift / RandomCutout / RandomTranslate the shift / cutout / translate launch (it
+        the graph is replayed; three with pos_offset > 0), for RandomShift / RandomCutout / RandomTranslate the shift /
+        cutout / translate launch (it
         reads its offsets, boxes and colours from the device block), for a
         staged float augmentation the three jitter / cover / convolution launches (they read their
         parameters from the device block), and the sample_cpc 6-tuple with handles into the slot's buffers.  Nothing
         here draws a random number."""
         g = self.graph_block(slot)
-        self._stage(g["host_dev"], g["dev"], g["host"].numel(), g["scalars"])  # (n_step: reads ``cont`` when the graph runs)
+        # (n_step, pos_offset: the launch reads ``cont`` when the graph runs)
+        self._stage(g["host_dev"], g["dev"], g["host"].numel(), g["scalars"])
         obses, next_obses, pos = self._assemble(g, None)
         act, rew, nd = g["scalars"]
         return obses, act, rew, next_obses, nd, dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
@@ -1225,7 +1291,7 @@ class ReplayBuffer(object):
             self.next_obses[lo:hi] = to_ring(nxt)
             for dst, src in ((self.actions, act), (self.rewards, rew), (self.not_dones, nd)):
                 dst[lo:hi] = torch.as_tensor(src).to(self.device)
-            if self.n_step > 1:  # the flags are rebuilt from the payload, never stored
+            if self._keep_cont:  # the flags are rebuilt from the payload, never stored
                 self._cont_rows(lo, obs, nxt, nd)
             if self.prioritized and hi > lo and (self.device.type == "cuda" or _lib_tracing()):
                 self._per_new_rows(lo, hi - lo)  # priorities are not in the payload: the loaded rows get the maximum

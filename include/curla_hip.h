@@ -542,6 +542,33 @@ int curla_nstep_compose(void* device_block, long long next_row_offset, const flo
 int curla_sample_stage_nstep(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
                              const float* scalars, const uint8_t* cont, long long capacity, int n, float discount, int B,
                              int A, float* action, float* reward, float* not_done, void* stream);
+/* Temporal positives for the CURL head (beyond the reference: ReplayBuffer(pos_offset=k); the positive selection of
+ * ATC, Stooke et al. 2021).  For sample b, starting at ring row r0 = idx[b] (the block's first B int64), with `cont` as
+ * above:
+ *   r = r0;  repeat k - 1 times: if not cont[r]: stop;  r = (r + 1) % capacity
+ *   block int64 [pos_offset / 8 + b]     = r              (the positive is next_obs of row r)
+ *   block int64 [pos_offset / 8 + B + b] = capacity + r   (the same row in the double ring's next_obs half)
+ * and, unless run_offset is -1, one run of 3 B double-ring rows obs | next_obs | pos for a single gather of 3 B frames:
+ *   block int64 [run_offset / 8 + b]         = r0
+ *   block int64 [run_offset / 8 + B + b]     = capacity + (r0 walked n - 1 links the same way: the n-step bootstrap row)
+ *   block int64 [run_offset / 8 + 2 B + b]   = capacity + r
+ * k = 1 gives r = r0 and reads no flag.  curla_pos_walk works on a `device_block` that has been staged already (behind
+ * curla_nstep_compose and curla_per_sample where they run; it reads the B idx words and writes the pos and run words,
+ * nothing else); `next_row_offset` (-1: the block has none) only takes part in the checks.  curla_sample_stage_pos is
+ * curla_sample_stage (next_row_offset == -1, then n must be 1) or curla_sample_stage_nstep (next_row_offset >= 0) with
+ * the walk in the same launch: the copy leaves out every word a walk writes, each such word has one writer, and the
+ * start rows are read from the pinned block.  k and n are unrelated.
+ * CURLA_ERR_ARG before any launch on: a NULL pointer (`cont` may be NULL only when nothing reads it: k == 1 and, where n
+ * is used, n == 1); k < 1, n < 1, capacity < 1; an offset (-1 aside, where allowed) that is not a multiple of 8, lies
+ * inside the 2 B index words, does not leave room for its words (2 B, 3 B, B) inside nbytes (stand-alone form: inside
+ * 1 GiB; the caller's block must hold them), or overlaps another of the three regions.  Rows are not range-checked.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_pos_walk(void* device_block, long long pos_offset, long long run_offset, long long next_row_offset,
+                   const uint8_t* cont, long long capacity, int k, int n, int B, void* stream);
+int curla_sample_stage_pos(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
+                           long long pos_offset, long long run_offset, const float* scalars, const uint8_t* cont,
+                           long long capacity, int n, float discount, int k, int B, int A, float* action, float* reward,
+                           float* not_done, void* stream);
 /* Proportional prioritized replay (beyond the reference: ReplayBuffer(prioritized=True); Schaul et al. 2016).
  * Storage, all on the device: `s` float [capacity], the stored value p_i^alpha of every ring row (0 = never written:
  * never drawn) | `sums` double [ceil(capacity / CURLA_PER_CHUNK)], one sum per chunk of CURLA_PER_CHUNK consecutive
