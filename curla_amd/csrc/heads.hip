@@ -1207,168 +1207,7 @@ __global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, 
   }
 }
 
-// out_act[b][:] = sc[idx[b]][0:A], out_rew[b] = sc[idx[b]][A], out_nd[b] = sc[idx[b]][A+1]: the action / reward /
-// not_done of the sampled transitions (utils.py:159-166) from the ring's [capacity][A+2] scalar rows, one launch
-__global__ void gather_transition_scalars_kernel(const float* sc, const int64_t* idx, int B, int A, float* act,
-                                                 float* rew, float* nd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * (A + 2)) return;
-  const int b = i / (A + 2), c = i - b * (A + 2);
-  const float v = sc[(size_t)idx[b] * (A + 2) + c];
-  if (c < A)
-    act[(size_t)b * A + c] = v;
-  else if (c == A)
-    rew[b] = v;
-  else
-    nd[b] = v;
-}
-
-// The same gather with the minibatch's index block taken straight from pinned host memory: the block (indices, crop
-// offsets; ~20 KB) is read over PCIe with system-scope loads and written to its device slot by this kernel, the
-// scalar rows are gathered with the indices as they arrive -- no copy-engine transfer (and its queue hand-over, ~15 us
-// of idle stream) in front of every update.  host / dev: the block as 8-byte words, idx = its first B words.
-__global__ void sample_stage_kernel(const unsigned long long* host, unsigned long long* dev, int nwords, const float* sc,
-                                    int B, int A, float* act, float* rew, float* nd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nwords) dev[i] = __hip_atomic_load(host + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (i >= B * (A + 2)) return;
-  const int b = i / (A + 2), c = i - b * (A + 2);
-  const long long row = (long long)__hip_atomic_load(host + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  const float v = sc[(size_t)row * (A + 2) + c];
-  if (c < A)
-    act[(size_t)b * A + c] = v;
-  else if (c == A)
-    rew[b] = v;
-  else
-    nd[b] = v;
-}
-
-// n-step return of sample b, which starts at ring row r0 (beyond the reference; DrQ-v2's multi-step TD target): walk
-// forward while the continuity flag of the current row is set, at most n - 1 times,
-//   R = reward[r0]; g = 1;  per step: r = (r + 1) % capacity; g = g * gamma; R = R + g * reward[r]
-// in fp32 with every product and sum rounded on its own (contraction is switched off for this function -- hipcc's
-// default would fuse g * reward into the sum, and HIP's __fmul_rn / __fadd_rn are plain operators that fuse as well:
-// the NumPy restatement of the tests gives the same bits).  Hands the TD kernels reward = R and
-// not_done = not_done[r_last] * g, and the bootstrap row r_last twice: as capacity + r_last in word B + b of the block
-// (the double ring's next_obs half) and as r_last in next_row[b].
-__device__ __forceinline__ void nstep_compose_one(const float* sc, const uint8_t* cont, long long capacity, int n,
-                                                  float gamma, int A, long long r0, int b, int B,
-                                                  unsigned long long* dev, unsigned long long* next_row, float* rew,
-                                                  float* nd) {
-#pragma clang fp contract(off)
-  const size_t ld = (size_t)A + 2;
-  float R = sc[(size_t)r0 * ld + A], g = 1.f;
-  long long r = r0;
-  for (int m = 1; m < n && cont[r]; ++m) {
-    r = r + 1 == capacity ? 0 : r + 1;
-    g = g * gamma;
-    const float term = g * sc[(size_t)r * ld + A];
-    R = R + term;
-  }
-  rew[b] = R;
-  nd[b] = sc[(size_t)r * ld + A + 1] * g;
-  dev[B + b] = (unsigned long long)(capacity + r);
-  next_row[b] = (unsigned long long)r;
-}
-
-// The composition on a block that is already on the device (idx = its first B words): one thread per scalar of a
-// sample as in gather_transition_scalars_kernel -- the action's threads copy action[r0], the reward's thread walks.
-__global__ void nstep_compose_kernel(unsigned long long* dev, int nr_word, const float* sc, const uint8_t* cont,
-                                     long long capacity, int n, float gamma, int B, int A, float* act, float* rew,
-                                     float* nd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * (A + 2)) return;
-  const int b = i / (A + 2), c = i - b * (A + 2);
-  const long long r0 = (long long)dev[b];
-  if (c < A)
-    act[(size_t)b * A + c] = sc[(size_t)r0 * (A + 2) + c];
-  else if (c == A)
-    nstep_compose_one(sc, cont, capacity, n, gamma, A, r0, b, B, dev, dev + nr_word, rew, nd);
-}
-
-// sample_stage_kernel + the composition in one launch.  The copy leaves out the words the composition writes
-// (B .. 2B - 1 and the B words of next_row): each of them has exactly one writer, sample b's reward thread, which
-// reads its row index from the pinned block with the same system-scope load as the copy -- nothing in the launch
-// reads a word that another thread of it writes.
-__global__ void sample_stage_nstep_kernel(const unsigned long long* host, unsigned long long* dev, int nwords,
-                                          int nr_word, const float* sc, const uint8_t* cont, long long capacity, int n,
-                                          float gamma, int B, int A, float* act, float* rew, float* nd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nwords && !(i >= B && i < 2 * B) && !(i >= nr_word && i < nr_word + B))
-    dev[i] = __hip_atomic_load(host + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (i >= B * (A + 2)) return;
-  const int b = i / (A + 2), c = i - b * (A + 2);
-  if (c > A) return;
-  const long long r0 = (long long)__hip_atomic_load(host + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (c < A)
-    act[(size_t)b * A + c] = sc[(size_t)r0 * (A + 2) + c];
-  else
-    nstep_compose_one(sc, cont, capacity, n, gamma, A, r0, b, B, dev, dev + nr_word, rew, nd);
-}
-
-// Ring row r0 advanced along the continuity flags at most `steps` times (steps == 0 reads no flag): the row walk of
-// nstep_compose_one without its arithmetic.
-__device__ __forceinline__ long long chain_walk(const uint8_t* cont, long long capacity, long long r0, int steps) {
-  long long r = r0;
-  for (int m = 0; m < steps && cont[r]; ++m) r = r + 1 == capacity ? 0 : r + 1;
-  return r;
-}
-
-// Temporal positive of sample b, which starts at ring row r0 (beyond the reference; the positive selection of ATC,
-// Stooke et al. 2021): the positive is next_obs of row r = r0 walked k - 1 links, i.e. the observation min(k, steps the
-// chain still has) steps after obs[r0].  Written twice into pos[0 .. 2B): r in word b, capacity + r (the double ring's
-// next_obs half) in word B + b.  `run` (or NULL): int64 [3B] = obs | next_obs | pos rows of the double ring for ONE
-// launch of a scratch augmentation -- r0, capacity + (r0 walked n - 1 links: the n-step bootstrap row, walked again
-// here so that no word of the block is read that another thread of the launch writes), capacity + r.
-__device__ __forceinline__ void temporal_pos_one(const uint8_t* cont, long long capacity, int k, int n, long long r0, int b,
-                                                 int B, unsigned long long* pos, unsigned long long* run) {
-  const long long r = chain_walk(cont, capacity, r0, k - 1);
-  pos[b] = (unsigned long long)r;
-  pos[B + b] = (unsigned long long)(capacity + r);
-  if (run) {
-    run[b] = (unsigned long long)r0;
-    run[B + b] = (unsigned long long)(capacity + chain_walk(cont, capacity, r0, n - 1));
-    run[2 * B + b] = (unsigned long long)(capacity + r);
-  }
-}
-
-// The walk on a block that is already on the device (idx = its first B words): one thread per sample.
-__global__ void pos_walk_kernel(unsigned long long* dev, int pos_word, int run_word, const uint8_t* cont,
-                                long long capacity, int k, int n, int B) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  temporal_pos_one(cont, capacity, k, n, (long long)dev[b], b, B, dev + pos_word, run_word >= 0 ? dev + run_word : nullptr);
-}
-
-// sample_stage_kernel (nr_word < 0) or sample_stage_nstep_kernel (nr_word >= 0) with the positive's walk in the same
-// launch, by the same discipline: the copy leaves out the words a walk writes (with the composition B .. 2B - 1 and
-// next_row; the 2B words of pos; the 3B of run), each of them has exactly one writer -- sample b's reward thread for the
-// composition's, its not_done thread for the positive's --, and a walking thread reads its start row from the pinned
-// block with the same system-scope load as the copy.  The two walks are independent: k and n are unrelated.
-__global__ void sample_stage_pos_kernel(const unsigned long long* host, unsigned long long* dev, int nwords, int nr_word,
-                                        int pos_word, int run_word, const float* sc, const uint8_t* cont,
-                                        long long capacity, int n, float gamma, int k, int B, int A, float* act,
-                                        float* rew, float* nd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool walked = (nr_word >= 0 && ((i >= B && i < 2 * B) || (i >= nr_word && i < nr_word + B))) ||
-                      (i >= pos_word && i < pos_word + 2 * B) || (run_word >= 0 && i >= run_word && i < run_word + 3 * B);
-  if (i < nwords && !walked) dev[i] = __hip_atomic_load(host + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (i >= B * (A + 2)) return;
-  const int b = i / (A + 2), c = i - b * (A + 2);
-  const long long r0 = (long long)__hip_atomic_load(host + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  const size_t ld = (size_t)A + 2;
-  if (c < A) {
-    act[(size_t)b * A + c] = sc[(size_t)r0 * ld + c];
-  } else if (c == A) {
-    if (nr_word >= 0)
-      nstep_compose_one(sc, cont, capacity, n, gamma, A, r0, b, B, dev, dev + nr_word, rew, nd);
-    else
-      rew[b] = sc[(size_t)r0 * ld + A];
-  } else {
-    if (nr_word < 0) nd[b] = sc[(size_t)r0 * ld + A + 1];
-    temporal_pos_one(cont, capacity, k, n, r0, b, B, dev + pos_word, run_word >= 0 ? dev + run_word : nullptr);
-  }
-}
+#include "sample_stage.h"  // a minibatch's index block and scalars: sample_stage_kernel<HOST, NSTEP, POS>, pos_walk_kernel
 
 // out[b][c][i][j] = (float) frames[idx[b]][h1[b]+i][w1[b]+j][c]          (augmentations.py:47-75 + utils.py:161)
 __global__ void crop_nchw_kernel(const uint8_t* frames, const int64_t* idx, const int32_t* h1, const int32_t* w1,
@@ -2070,14 +1909,6 @@ int curla_adam_step2(float* param, const float* grad, float* exp_avg1, float* ex
   return curla_launch_status();
 }
 
-int curla_gather_transition_scalars(const float* scalars, const int64_t* idx, int B, int A, float* action, float* reward,
-                                    float* not_done, void* stream) {
-  CURLA_REQUIRE(scalars && idx && action && reward && not_done && B > 0 && A > 0);
-  hipLaunchKernelGGL(gather_transition_scalars_kernel, dim3((B * (A + 2) + 255) / 256), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), scalars, idx, B, A, action, reward, not_done);
-  return curla_launch_status();
-}
-
 int curla_host_device_pointer(void* host, void** device) {
   CURLA_REQUIRE(host && device);
   void* d = nullptr;
@@ -2089,77 +1920,99 @@ int curla_host_device_pointer(void* host, void** device) {
   return CURLA_OK;
 }
 
+// [a, a + na) and [b, b + nb) share no byte
+static inline bool curla_disjoint(long long a, long long na, long long b, long long nb) { return a + na <= b || b + nb <= a; }
+
+// The geometry of a minibatch's block of `limit` bytes at `host` (NULL: it is on the device already, and `limit` bounds
+// its regions) and `dev`: 8-byte aligned, a pinned block shorter than 1 GiB, and the regions a walk writes -- next_row
+// (B words), pos_row (2B), pos_run (3B); -1: the block has none -- 8-byte aligned, behind the 2B index words, inside the
+// block, none overlapping another (sample_stage.h: walk_owns_word).
+static bool sample_block_ok(const void* host, const void* dev, long long limit, int B, long long next_row_offset,
+                            long long pos_offset, long long run_offset) {
+  if (((uintptr_t)host | (uintptr_t)dev) % 8 != 0) return false;
+  if (limit % 8 != 0 || limit < 8LL * B || (host && limit >= (1LL << 30))) return false;
+  const long long off[3] = {next_row_offset, pos_offset, run_offset}, len[3] = {8LL * B, 16LL * B, 24LL * B};
+  for (int i = 0; i < 3; ++i) {
+    if (off[i] == -1) continue;
+    if (off[i] % 8 != 0 || off[i] < 16LL * B || off[i] + len[i] > limit) return false;
+    for (int j = 0; j < i; ++j)
+      if (off[j] != -1 && !curla_disjoint(off[i], len[i], off[j], len[j])) return false;
+  }
+  return true;
+}
+
+// One thread per word of the pinned block and per scalar of the minibatch, whichever are more.
+static int sample_stage_launch(void (*kernel)(SampleStageArgs), const SampleStageArgs& a, void* stream) {
+  const int nthreads = a.nwords > a.B * (a.A + 2) ? a.nwords : a.B * (a.A + 2);
+  hipLaunchKernelGGL(kernel, dim3((nthreads + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return curla_launch_status();
+}
+
+// A block offset in bytes as the kernels take it, in words (-1, the block has no such region, stays)
+static inline int block_word(long long offset) { return offset == -1 ? -1 : (int)(offset / 8); }
+
+// The arguments every instantiation takes; a block that is on the device already (host_block NULL) has no pinned words
+// to copy.  The entry points with a walk add theirs.
+static SampleStageArgs sample_stage_args(const void* host_block, void* device_block, long long nbytes,
+                                         const float* scalars, int B, int A, float* action, float* reward,
+                                         float* not_done) {
+  SampleStageArgs a;
+  a.host = static_cast<const unsigned long long*>(host_block), a.dev = static_cast<unsigned long long*>(device_block);
+  a.nwords = host_block ? (int)(nbytes / 8) : 0;
+  a.sc = scalars, a.B = B, a.A = A, a.act = action, a.rew = reward, a.nd = not_done;
+  return a;
+}
+
+// `idx` need not be the start of a block (nor 8-byte aligned): it is the device block's word 0, which is all this
+// instantiation reads, so there is no geometry to check.
+int curla_gather_transition_scalars(const float* scalars, const int64_t* idx, int B, int A, float* action, float* reward,
+                                    float* not_done, void* stream) {
+  CURLA_REQUIRE(scalars && idx && action && reward && not_done && B > 0 && A > 0);
+  return sample_stage_launch(
+      sample_stage_kernel<false, false, false>,
+      sample_stage_args(nullptr, const_cast<int64_t*>(idx), 0, scalars, B, A, action, reward, not_done), stream);
+}
+
 int curla_sample_stage(const void* host_block, void* device_block, long long nbytes, const float* scalars, int B, int A,
                        float* action, float* reward, float* not_done, void* stream) {
   CURLA_REQUIRE(host_block && device_block && scalars && action && reward && not_done && B > 0 && A > 0);
-  CURLA_REQUIRE(nbytes >= (long long)B * 8 && nbytes % 8 == 0 && nbytes < (1LL << 30));
-  CURLA_REQUIRE(((uintptr_t)host_block | (uintptr_t)device_block) % 8 == 0);
-  const int nwords = (int)(nbytes / 8);
-  const int n = nwords > B * (A + 2) ? nwords : B * (A + 2);
-  hipLaunchKernelGGL(sample_stage_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const unsigned long long*>(host_block), static_cast<unsigned long long*>(device_block),
-                     nwords, scalars, B, A, action, reward, not_done);
-  return curla_launch_status();
+  CURLA_REQUIRE(sample_block_ok(host_block, device_block, nbytes, B, -1, -1, -1));
+  return sample_stage_launch(
+      sample_stage_kernel<true, false, false>,
+      sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done), stream);
 }
 
 int curla_nstep_compose(void* device_block, long long next_row_offset, const float* scalars, const uint8_t* cont,
                         long long capacity, int n, float discount, int B, int A, float* action, float* reward,
                         float* not_done, void* stream) {
   CURLA_REQUIRE(device_block && scalars && cont && action && reward && not_done && B > 0 && A > 0);
-  CURLA_REQUIRE(n >= 1 && capacity >= 1 && (uintptr_t)device_block % 8 == 0);
-  CURLA_REQUIRE(next_row_offset % 8 == 0 && next_row_offset >= 2LL * B * 8 && next_row_offset < (1LL << 30));
-  hipLaunchKernelGGL(nstep_compose_kernel, dim3((B * (A + 2) + 255) / 256), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<unsigned long long*>(device_block),
-                     (int)(next_row_offset / 8), scalars, cont, capacity, n, discount, B, A, action, reward, not_done);
-  return curla_launch_status();
+  CURLA_REQUIRE(n >= 1 && capacity >= 1 && next_row_offset != -1);
+  // this entry point holds the START of next_row below 1 GiB, the others the end of every region
+  CURLA_REQUIRE(sample_block_ok(nullptr, device_block, (1LL << 30) - 8 + 8LL * B, B, next_row_offset, -1, -1));
+  SampleStageArgs a = sample_stage_args(nullptr, device_block, 0, scalars, B, A, action, reward, not_done);
+  a.nr_word = block_word(next_row_offset), a.cont = cont, a.capacity = capacity, a.n = n, a.gamma = discount;
+  return sample_stage_launch(sample_stage_kernel<false, true, false>, a, stream);
 }
 
 int curla_sample_stage_nstep(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
                              const float* scalars, const uint8_t* cont, long long capacity, int n, float discount, int B,
                              int A, float* action, float* reward, float* not_done, void* stream) {
   CURLA_REQUIRE(host_block && device_block && scalars && cont && action && reward && not_done && B > 0 && A > 0);
-  CURLA_REQUIRE(n >= 1 && capacity >= 1);
-  CURLA_REQUIRE(nbytes % 8 == 0 && nbytes < (1LL << 30));
-  CURLA_REQUIRE(next_row_offset % 8 == 0 && next_row_offset >= 2LL * B * 8 && next_row_offset + 8LL * B <= nbytes);
-  CURLA_REQUIRE(((uintptr_t)host_block | (uintptr_t)device_block) % 8 == 0);
-  const int nwords = (int)(nbytes / 8);
-  const int nthreads = nwords > B * (A + 2) ? nwords : B * (A + 2);
-  hipLaunchKernelGGL(sample_stage_nstep_kernel, dim3((nthreads + 255) / 256), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const unsigned long long*>(host_block),
-                     static_cast<unsigned long long*>(device_block), nwords, (int)(next_row_offset / 8), scalars, cont,
-                     capacity, n, discount, B, A, action, reward, not_done);
-  return curla_launch_status();
-}
-
-// [a, a + na) and [b, b + nb) share no byte
-static inline bool curla_disjoint(long long a, long long na, long long b, long long nb) { return a + na <= b || b + nb <= a; }
-
-// The offsets of the positive's walk inside a block of `limit` bytes: pos (2B words) and, unless -1, run (3B words) and
-// next_row (B words) -- 8-byte aligned, behind the 2B index words, inside the block, none overlapping another.
-static bool curla_pos_offsets_ok(long long pos_offset, long long run_offset, long long next_row_offset, int B,
-                                 long long limit) {
-  const long long idx_end = 16LL * B, npos = 16LL * B, nrun = 24LL * B, nnr = 8LL * B;
-  if (pos_offset % 8 != 0 || pos_offset < idx_end || pos_offset + npos > limit) return false;
-  if (run_offset != -1) {
-    if (run_offset % 8 != 0 || run_offset < idx_end || run_offset + nrun > limit) return false;
-    if (!curla_disjoint(run_offset, nrun, pos_offset, npos)) return false;
-  }
-  if (next_row_offset != -1) {
-    if (next_row_offset % 8 != 0 || next_row_offset < idx_end || next_row_offset + nnr > limit) return false;
-    if (!curla_disjoint(next_row_offset, nnr, pos_offset, npos)) return false;
-    if (run_offset != -1 && !curla_disjoint(next_row_offset, nnr, run_offset, nrun)) return false;
-  }
-  return true;
+  CURLA_REQUIRE(n >= 1 && capacity >= 1 && next_row_offset != -1);
+  CURLA_REQUIRE(sample_block_ok(host_block, device_block, nbytes, B, next_row_offset, -1, -1));
+  SampleStageArgs a = sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done);
+  a.nr_word = block_word(next_row_offset), a.cont = cont, a.capacity = capacity, a.n = n, a.gamma = discount;
+  return sample_stage_launch(sample_stage_kernel<true, true, false>, a, stream);
 }
 
 int curla_pos_walk(void* device_block, long long pos_offset, long long run_offset, long long next_row_offset,
                    const uint8_t* cont, long long capacity, int k, int n, int B, void* stream) {
-  CURLA_REQUIRE(device_block && B > 0 && k >= 1 && n >= 1 && capacity >= 1 && (uintptr_t)device_block % 8 == 0);
+  CURLA_REQUIRE(device_block && B > 0 && k >= 1 && n >= 1 && capacity >= 1 && pos_offset != -1);
   CURLA_REQUIRE(cont || (k == 1 && (n == 1 || run_offset == -1)));
-  CURLA_REQUIRE(curla_pos_offsets_ok(pos_offset, run_offset, next_row_offset, B, 1LL << 30));
+  CURLA_REQUIRE(sample_block_ok(nullptr, device_block, 1LL << 30, B, next_row_offset, pos_offset, run_offset));
   hipLaunchKernelGGL(pos_walk_kernel, dim3((B + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<unsigned long long*>(device_block), (int)(pos_offset / 8),
-                     run_offset == -1 ? -1 : (int)(run_offset / 8), cont, capacity, k, n, B);
+                     static_cast<unsigned long long*>(device_block), block_word(pos_offset), block_word(run_offset), cont,
+                     capacity, k, n, B);
   return curla_launch_status();
 }
 
@@ -2168,21 +2021,15 @@ int curla_sample_stage_pos(const void* host_block, void* device_block, long long
                            long long capacity, int n, float discount, int k, int B, int A, float* action, float* reward,
                            float* not_done, void* stream) {
   CURLA_REQUIRE(host_block && device_block && scalars && action && reward && not_done && B > 0 && A > 0);
-  CURLA_REQUIRE(k >= 1 && n >= 1 && capacity >= 1);
+  CURLA_REQUIRE(k >= 1 && n >= 1 && capacity >= 1 && pos_offset != -1);
   CURLA_REQUIRE(next_row_offset != -1 || n == 1);  // without a next_row region there is no composition
   CURLA_REQUIRE(cont || (k == 1 && n == 1));
-  CURLA_REQUIRE(nbytes % 8 == 0 && nbytes >= 0 && nbytes < (1LL << 30));
-  CURLA_REQUIRE(curla_pos_offsets_ok(pos_offset, run_offset, next_row_offset, B, nbytes));
-  CURLA_REQUIRE(((uintptr_t)host_block | (uintptr_t)device_block) % 8 == 0);
-  const int nwords = (int)(nbytes / 8);
-  const int nthreads = nwords > B * (A + 2) ? nwords : B * (A + 2);
-  hipLaunchKernelGGL(sample_stage_pos_kernel, dim3((nthreads + 255) / 256), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const unsigned long long*>(host_block),
-                     static_cast<unsigned long long*>(device_block), nwords,
-                     next_row_offset == -1 ? -1 : (int)(next_row_offset / 8), (int)(pos_offset / 8),
-                     run_offset == -1 ? -1 : (int)(run_offset / 8), scalars, cont, capacity, n, discount, k, B, A, action,
-                     reward, not_done);
-  return curla_launch_status();
+  CURLA_REQUIRE(sample_block_ok(host_block, device_block, nbytes, B, next_row_offset, pos_offset, run_offset));
+  SampleStageArgs a = sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done);
+  a.nr_word = block_word(next_row_offset), a.pos_word = block_word(pos_offset), a.run_word = block_word(run_offset);
+  a.cont = cont, a.capacity = capacity, a.n = n, a.gamma = discount, a.k = k;
+  return sample_stage_launch(
+      next_row_offset == -1 ? sample_stage_kernel<true, false, true> : sample_stage_kernel<true, true, true>, a, stream);
 }
 
 int curla_per_set(float* s, double* sums, float* vmax, long long capacity, const int64_t* rows, long long first_row,

@@ -894,22 +894,12 @@ class ReplayBuffer(object):
         self._sample_gen[s] += 1
         slot = self._sample_slots[s]
         dst = slot["dev"]
-        if self._h_index_dev is not None:  # block and scalars in one launch, the block read from the pinned slot
+        if self._h_index_dev is not None:  # the block is read from the pinned slot by the staging launch
             self._stage(self._h_index_dev[k], dst, host.numel(), slot["scalars"])
         else:
             dst.copy_(host, non_blocking=True)
             if self.device.type == "cuda" or _lib_tracing():
-                B, A, lay = self.batch_size, self._n_act, self._layout
-                out = slot["scalars"]
-                if self.prioritized:  # the draw: rows into the block's idx run, their probabilities into ``prob``
-                    ops.per_sample(self._per_s, self._per_sums, dst, lay["u"], lay["prob"], B)
-                ops.gather_transition_scalars(self._sc, dst[lay["idx"]:lay["idx"] + 8 * B].view(torch.int64), B, A, *out)
-                if self.n_step > 1:  # the bootstrap rows must be in the block before anything reads pixels
-                    ops.nstep_compose(dst, lay["next_row"], self._sc, self._cont, self.capacity, self.n_step,
-                                      self._nstep_discount(), B, A, *out)
-                if self._pos_offset:  # ... and so must the positive's rows (behind the draw, which writes the idx run)
-                    ops.pos_walk(dst, lay["pos_row"], lay.get("pos_run"), lay.get("next_row"),
-                                 self._cont if self._keep_cont else None, self.capacity, self._pos_offset, self.n_step, B)
+                self._stage(None, dst, host.numel(), slot["scalars"], copied=True)
         if self.device.type == "cuda" and u % every == every - 1:
             ev = torch.cuda.Event()
             ev.record()
@@ -927,19 +917,29 @@ class ReplayBuffer(object):
         return (scal[:B * A].view((B,) + tuple(self.actions.shape[1:])), scal[B * A:B * A + B].view(B, 1),
                 scal[B * A + B:].view(B, 1))
 
-    def _stage(self, host_dev, dev, nbytes, out):
-        """The staging launch of a minibatch: pinned block -> device block + the transitions' scalars into ``out``
-        (_scalar_views); with n_step > 1 the n-step composition, with pos_offset > 0 the positive's walk happens in the same
-        launch."""
-        B, A = self.batch_size, self._n_act
-        if self._pos_offset:  # still ONE launch: the positive's walk beside the copy and, n_step > 1, the composition
-            lay = self._layout
+    def _stage(self, host_dev, dev, nbytes, out, copied=False):
+        """Staging a minibatch: the transitions' scalars into ``out`` (_scalar_views; n_step > 1: composed) and, with
+        pos_offset > 0, the positive's rows into the block.  ``host_dev``, the pinned block's device address: ONE launch,
+        which also brings the block to ``dev``.  ``copied``, the block is in ``dev`` already: a launch each."""
+        B, A, lay = self.batch_size, self._n_act, self._layout
+        cont = self._cont if self._keep_cont else None
+        if copied:
+            if self.prioritized:  # the draw: rows into the block's idx run, their probabilities into ``prob``
+                ops.per_sample(self._per_s, self._per_sums, dev, lay["u"], lay["prob"], B)
+            ops.gather_transition_scalars(self._sc, dev[lay["idx"]:lay["idx"] + 8 * B].view(torch.int64), B, A, *out)
+            if self.n_step > 1:  # the bootstrap rows must be in the block before anything reads pixels
+                ops.nstep_compose(dev, lay["next_row"], self._sc, cont, self.capacity, self.n_step,
+                                  self._nstep_discount(), B, A, *out)
+            if self._pos_offset:  # ... and so must the positive's rows (behind the draw, which writes the idx run)
+                ops.pos_walk(dev, lay["pos_row"], lay.get("pos_run"), lay.get("next_row"), cont, self.capacity,
+                             self._pos_offset, self.n_step, B)
+        elif self._pos_offset:
             ops.sample_stage_pos(host_dev, dev, nbytes, lay.get("next_row"), lay["pos_row"], lay.get("pos_run"), self._sc,
-                                 self._cont if self._keep_cont else None, self.capacity, self.n_step,
-                                 self._nstep_discount() if self.n_step > 1 else 1.0, self._pos_offset, B, A, *out)
+                                 cont, self.capacity, self.n_step, self._nstep_discount() if self.n_step > 1 else 1.0,
+                                 self._pos_offset, B, A, *out)
         elif self.n_step > 1:
-            ops.sample_stage_nstep(host_dev, dev, nbytes, self._layout["next_row"], self._sc, self._cont, self.capacity,
-                                   self.n_step, self._nstep_discount(), B, A, *out)
+            ops.sample_stage_nstep(host_dev, dev, nbytes, lay["next_row"], self._sc, cont, self.capacity, self.n_step,
+                                   self._nstep_discount(), B, A, *out)
         else:
             ops.sample_stage(host_dev, dev, nbytes, self._sc, B, A, *out)
 
