@@ -3,6 +3,8 @@ PyTorch fp32 (CPU) statement of the same op, through the C ABI.  Integer work
 (crop, frame store) bit-exact; floating point within 1e-4 per tensor
 (tests/_util.RTOL).  Shapes include ragged tiles, rectangular images and the
 BASELINE geometries (84->76, 37/35/33 feature maps, 83-wide maps of config 5)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -279,6 +281,53 @@ def test_gemm_bf16x3_128x64_tile(ops, M, N, K, nb, tile, ak, bk):
     check(f"gemm 128x64 mask {M}x{N}x{K} ak{ak} bk{bk} nb{nb}", C2.cpu(), (ref * (mask > 0)).float(), 2e-5)
     check(f"gemm f32 mask {M}x{N}x{K} ak{ak} bk{bk} nb{nb}", C3.cpu(), (ref * (mask > 0)).float(), 2e-5)
     assert not torch.equal(C2, C3)  # (two arithmetics: the tile was really taken)
+
+
+_TILED_VARIANTS = {"slow": (70, 45, 50, "auto"),   # K unaligned and below 256: neither interior + aligned nor small-output
+                   "fast": (128, 128, 64, "auto"),  # whole tiles of every shape, aligned: the f32 form without bounds tests
+                   "b3": (128, 128, 64, "b3")}      # ... and its bf16x3 form
+
+
+@functools.lru_cache(maxsize=None)
+def _tiled_problem(M, N, K, nb):
+    A, Bm = rnd(nb, M, K, seed=61), rnd(nb, N, K, seed=62)
+    bias, mask = rnd(nb, N, seed=63), rnd(nb, M, N, seed=64)
+    ref = torch.einsum("zmk,znk->zmn", A.double(), Bm.double())
+    return A, Bm, bias, mask, torch.relu(0.5 * ref + bias.double()[:, None, :]).float(), (ref * (mask > 0)).float()
+
+
+@pytest.mark.parametrize("ak,bk", [(0, 0), (0, 1), (1, 0), (1, 1)])
+@pytest.mark.parametrize("tile", ["6464", "6432", "3232"])
+@pytest.mark.parametrize("variant", list(_TILED_VARIANTS))
+def test_gemm_every_tiled_instantiation(ops, variant, tile, ak, bk):
+    """Each of the 36 gemm_kernel instantiations on 256 threads by name -- operand layout x tile shape x {bounds-checked,
+    interior + aligned, bf16x3} -- with two batch items, the bias + ReLU and the mask epilogues, against float64.  The
+    bf16x3 form must also differ from the f32 form on the same tiles: it was really taken."""
+    from curla_amd import _lib
+    nb = 2
+    M, N, K, mfma = _TILED_VARIANTS[variant]
+    A, Bm, bias, mask, ref_relu, ref_mask = _tiled_problem(M, N, K, nb)
+    Ad = dev(A.transpose(1, 2)) if ak else dev(A)
+    Bd = dev(Bm.transpose(1, 2)) if bk else dev(Bm)
+    lda, ldb = (M if ak else K), (N if bk else K)
+
+    def run(**epilogue):
+        C = torch.full((nb, M, N), float("nan"), device="cuda")
+        ops.gemm(Ad, ak, lda, M * K, Bd, bk, ldb, N * K, C, N, M * N, M, N, K, nb, **epilogue)
+        return C
+    with _lib.option("gemm_tile", tile):
+        with _lib.option("gemm_mfma", mfma):
+            C = run(alpha=0.5, bias=dev(bias), sBias=N, relu=1)
+            C2 = run(mask=dev(mask), ldmask=N, sMask=M * N)
+        if variant == "b3":
+            with _lib.option("gemm_mfma", "f32"):
+                C3 = run(mask=dev(mask), ldmask=N, sMask=M * N)
+    name = f"{variant} {tile} ak{ak} bk{bk}"
+    check(f"tiled gemm bias+relu {name}", C.cpu(), ref_relu, 2e-5)
+    check(f"tiled gemm mask {name}", C2.cpu(), ref_mask, 2e-5)
+    if variant == "b3":
+        check(f"tiled gemm mask {name} f32", C3.cpu(), ref_mask, 2e-5)
+        assert not torch.equal(C2, C3)  # (two arithmetics)
 
 
 @pytest.mark.parametrize("ak,bk", [(0, 0), (0, 1), (1, 0), (1, 1)])
