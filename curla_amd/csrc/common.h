@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/curla_hip.h"
 
@@ -103,6 +104,15 @@ static inline int curla_set_dyn_lds(const void* fn, size_t bytes) {
   } while (0)
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// f(std::integral_constant<int, V>) for the run-time `value` out of an explicit list: the list names the template
+// instances a call site compiles; a value that is not in it is CURLA_ERR_UNSUPPORTED
+template <int... Vs, typename F>
+int dispatch_int(int value, F&& f) {
+  int rc = CURLA_ERR_UNSUPPORTED;
+  (void)(... || (value == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false));
+  return rc;
+}
 
 // ---- counter-based normal draws (policy head, heads.hip; NoisyCover, augment.hip): ONE definition, so that both
 // translation units number and round the stream alike ----

@@ -306,14 +306,8 @@ int launch(void (*kernel)(Params...), int grid, int threads, size_t lds, hipStre
   return curla_launch_status();
 }
 
-// f(std::integral_constant<int, C>) for the run-time channel count C out of an explicit list: the list names the template
-// instances a call site compiles (the bf16 first-layer forms exist for 3 C <= 32 only)
-template <int... Cs, typename F>
-int dispatch_c(int C, F&& f) {
-  int rc = CURLA_ERR_UNSUPPORTED;
-  (void)(... || (C == Cs ? (rc = f(std::integral_constant<int, Cs>{}), true) : false));
-  return rc;
-}
+// (the run-time channel count C -> template instance: dispatch_int<Cs...>, common.h -- the list at a call site names the
+// instances it compiles; the bf16 first-layer forms exist for 3 C <= 32 only)
 
 // the C ABI's src_kind of the first layer's input, and f(the kernels' SRC_* of it)
 enum { kSrcF32Nchw = 0, kSrcU8Ring = 1, kSrcF32Nhwc = 2 };
@@ -729,8 +723,8 @@ static int launch_conv1_u8_rw(Conv1U8Form form, const Conv1Args& a, hipStream_t 
   const int want = (int)((pool + share - 1) / share);
   const int grid = want < cap ? (want < 1 ? 1 : want) : cap;
   if (b16)
-    return dispatch_c<9, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_rwb_fwd_kernel<cc()>, grid, threads, 0, st, ra); });
-  return dispatch_c<9, 12, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_rw_fwd_kernel<cc()>, grid, threads, 0, st, ra); });
+    return dispatch_int<9, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_rwb_fwd_kernel<cc()>, grid, threads, 0, st, ra); });
+  return dispatch_int<9, 12, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_rw_fwd_kernel<cc()>, grid, threads, 0, st, ra); });
 }
 
 // uint8 ring, crop staged as bytes in LDS: Conv1U8Form::Hybrid / Band
@@ -741,9 +735,9 @@ static int launch_conv1_u8_band(Conv1U8Form form, Conv1Args& a, hipStream_t st) 
     rw::Geom G;
     G.Hi = a.Hc, G.Wi = a.Wc, G.Ho = a.Ho, G.Wo = a.Wo;
     rw::plan_units(G, a.Ho, a.Wo, 16);
-    return dispatch_c<9, 12, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_walk_kernel<cc()>, grid, 512, lds, st, a, G); });
+    return dispatch_int<9, 12, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_walk_kernel<cc()>, grid, 512, lds, st, a, G); });
   }
-  return dispatch_c<9, 12, 6, 3>(a.C, [&](auto cc) { return launch(conv1_fwd_u8_kernel<cc()>, grid, 512, lds, st, a); });
+  return dispatch_int<9, 12, 6, 3>(a.C, [&](auto cc) { return launch(conv1_fwd_u8_kernel<cc()>, grid, 512, lds, st, a); });
 }
 
 // float NHWC minibatch, row walk with nothing staged (conv1_rw.h): Conv1F32Form::Rw
@@ -754,7 +748,7 @@ static int launch_conv1_rw(const Conv1Args& a, hipStream_t st) {
   ra.g.Hi = a.Hc, ra.g.Wi = a.Wc, ra.g.Ho = a.Ho, ra.g.Wo = a.Wo;
   rw::plan_units(ra.g, a.Ho, a.Wo, 16);
   const int grid = std::min(a.B, curla_cu_count());
-  return dispatch_c<12, 9, 6, 3>(a.C, [&](auto cc) { return launch(conv1_rw_fwd_kernel<cc()>, grid, 512, 0, st, ra); });
+  return dispatch_int<12, 9, 6, 3>(a.C, [&](auto cc) { return launch(conv1_rw_fwd_kernel<cc()>, grid, 512, 0, st, ra); });
 }
 
 // any source, band staged as floats in LDS (Conv1F32Form::Band): two workgroups per CU so one stages while the other
@@ -765,7 +759,7 @@ static int launch_conv1_band(int src_kind, Conv1Args& a, hipStream_t st) {
   const size_t lds = std::max<size_t>(((size_t)(2 * a.th + 1) * f32_row_floats(a.Wc, a.C) + 8) * sizeof(float),
                               (size_t)32 * a.C * 9 * sizeof(float));
   const int grid = std::min(a.B * a.nbands, 2 * curla_cu_count());
-  return dispatch_c<9, 12, 6, 3>(a.C, [&](auto cc) {
+  return dispatch_int<9, 12, 6, 3>(a.C, [&](auto cc) {
     return dispatch_src(src_kind, [&](auto src) { return launch(conv1_fwd_kernel<src(), cc()>, grid, 512, lds, st, a); });
   });
 }
@@ -934,11 +928,11 @@ static int launch_wgrad1(const void* src, int src_kind, const int64_t* idx, cons
     grid = std::min(B * a.nbands, (form == Wgrad1U8Form::F32FourWave ? 4 : 2) * curla_cu_count());
     switch (form) {
       case Wgrad1U8Form::B16:
-        return dispatch_c<9, 6, 3>(C, [&](auto cc) { return launch(wgrad1_u8b_kernel<cc(), 8>, grid, 512, lds, st, a); });
+        return dispatch_int<9, 6, 3>(C, [&](auto cc) { return launch(wgrad1_u8b_kernel<cc(), 8>, grid, 512, lds, st, a); });
       case Wgrad1U8Form::F32FourWave:
-        return dispatch_c<9, 12, 6, 3>(C, [&](auto cc) { return launch(wgrad1_u8_kernel<cc(), 4>, grid, 256, lds, st, a); });
+        return dispatch_int<9, 12, 6, 3>(C, [&](auto cc) { return launch(wgrad1_u8_kernel<cc(), 4>, grid, 256, lds, st, a); });
       default:
-        return dispatch_c<9, 12, 6, 3>(C, [&](auto cc) { return launch(wgrad1_u8_kernel<cc(), 8>, grid, 512, lds, st, a); });
+        return dispatch_int<9, 12, 6, 3>(C, [&](auto cc) { return launch(wgrad1_u8_kernel<cc(), 8>, grid, 512, lds, st, a); });
     }
   }
   if (src_kind != kSrcU8Ring && select_conv1_f32_form(src_kind, C, Hc, Wc) == Conv1F32Form::Rw) {
@@ -949,14 +943,14 @@ static int launch_wgrad1(const void* src, int src_kind, const int64_t* idx, cons
     ra.gg.Hi = Hc, ra.gg.Wi = Wc, ra.gg.Ho = a.Ho, ra.gg.Wo = a.Wo;
     rw::plan_units(ra.gg, a.Ho, a.Wo, 4);
     grid = std::min(B, curla_cu_count());
-    return dispatch_c<12, 9, 6, 3>(C, [&](auto cc) { return launch(wgrad1_rw_kernel<cc()>, grid, 512, slab_bytes, st, ra); });
+    return dispatch_int<12, 9, 6, 3>(C, [&](auto cc) { return launch(wgrad1_rw_kernel<cc()>, grid, 512, slab_bytes, st, ra); });
   }
   // any source, band staged as floats in LDS: input rows only, one workgroup per CU
   a.th = plan_band_conv1(a.Ho, a.Wo, Wc, C, 0, 150 * 1024);
   a.nbands = (a.Ho + a.th - 1) / a.th;
   const size_t lds = std::max<size_t>(((size_t)(2 * a.th + 1) * f32_row_floats(Wc, C) + 8) * sizeof(float), slab_bytes);
   grid = std::min(B * a.nbands, curla_cu_count());
-  return dispatch_c<9, 12, 6, 3>(C, [&](auto cc) {
+  return dispatch_int<9, 12, 6, 3>(C, [&](auto cc) {
     return dispatch_src(src_kind, [&](auto s) { return launch(wgrad1_kernel<s(), cc()>, grid, 512, lds, st, a); });
   });
 }

@@ -1,0 +1,178 @@
+// The optimiser step over the flat parameter buffers: the target networks' soft update (soft_update_kernel,
+// soft_update2_kernel) and Adam, one step or two back to back, with the float64 scalar and the target lerp that can
+// ride along (adam_step_kernel, adam_step2_kernel).  Included by heads.hip inside its anonymous namespace.
+#pragma once
+
+// target <- tau*p + (1-tau)*target                                     (utils.py:37-41)
+__global__ void soft_update_kernel(const float* p, float* tgt, size_t n, float tau, float omt) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  // two roundings of the products and one of the sum, as `tau * p + (1 - tau) * t` evaluates in torch (no fused
+  // multiply-add), so the targets match the reference's bit for bit given the same inputs
+  for (; i < n; i += stride) {
+#pragma clang fp contract(off)
+    tgt[i] = tau * p[i] + omt * tgt[i];
+  }
+}
+
+// the same over one flat block whose first `split` elements take (tau_a, 1-tau_a) and the rest (tau_b, 1-tau_b):
+// the encoder and the Q functions of the critic are adjacent in the flat layout and have their own rates
+__global__ void soft_update2_kernel(const float* p, float* tgt, size_t n, size_t split, float tau_a, float omt_a,
+                                    float tau_b, float omt_b) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+#pragma clang fp contract(off)
+    const bool a = i < split;
+    tgt[i] = (a ? tau_a : tau_b) * p[i] + (a ? omt_a : omt_b) * tgt[i];
+  }
+}
+
+// One Adam step over a flat run of parameters (torch.optim.Adam, weight_decay 0, no amsgrad; curl_sac.py:299-313):
+//   m += (1-b1)(g-m);  v = b2 v + (1-b2) g g;  p -= step_size * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+// with step_size = lr/(1-b1^t) and the two bias corrections evaluated on the host in double, as torch's
+// single-tensor Adam does.  Seven fp32 streams (4 read, 3 written), 16-byte accesses when the run is 16-byte
+// aligned: HBM-bound (28 B per parameter).
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float w1, float b2, float w2,
+                                         float step_size, float bc2_sqrt, float eps) {
+  // (no fused multiply-adds: every product and sum rounds on its own, as torch's element-wise Adam does, and the
+  // one-step and two-step kernels then agree bit for bit whatever the compiler would have contracted in each)
+#pragma clang fp contract(off)
+  m = (w1 < 0.5f) ? m + w1 * (g - m) : g - (g - m) * (1.0f - w1);
+  v = v * b2 + (w2 * g) * g;
+  const float denom = sqrtf(v) / bc2_sqrt + eps;
+  p = p - (step_size * m) / denom;
+}
+
+// A float64 scalar parameter stepped by the same launch (log_alpha beside the actor's parameters: the reference steps
+// actor_optimizer and log_alpha_optimizer back to back, curl_sac.py:393-404); p == nullptr: none.
+struct AdamScalar64 {
+  double *p, *m, *v;
+  const double* g;
+  double w1, b2, w2, step_size, bc2_sqrt, eps;
+  const double* dyn;  // != nullptr: step_size = dyn[0], bc2_sqrt = dyn[1], read when the kernel runs
+};
+
+// The target network's soft update in the same pass: target <- tau p + (1 - tau) target with the parameter this launch
+// has just stepped (utils.py:37-41 right after critic_optimizer.step(), curl_sac.py:367,442-445); elements [0, split)
+// take (tau_a, omt_a), the rest (tau_b, omt_b).  tgt == nullptr: none.
+struct AdamLerp {
+  float* tgt;
+  size_t split;
+  float tau_a, omt_a, tau_b, omt_b;
+};
+__device__ __forceinline__ float lerp_one(float p, float t, float tau, float omt) {
+#pragma clang fp contract(off)
+  return tau * p + omt * t;  // two roundings of the products and one of the sum, as soft_update_kernel
+}
+
+__global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, size_t n,
+                                                        int vec, float w1, float b2, float w2, float step_size,
+                                                        float bc2_sqrt, float eps, AdamScalar64 sc, AdamLerp lp,
+                                                        const float* __restrict__ dyn) {
+  // dyn != nullptr: the two step-dependent factors lr / (1 - b1^t) and sqrt(1 - b2^t) come from device memory, written
+  // there (by the host, through the update's pinned control block) before the kernel runs: a captured graph is
+  // replayed with new step counts.  The same two floats the host would have passed by value.
+  if (dyn) step_size = dyn[0], bc2_sqrt = dyn[1];
+  if (sc.p && blockIdx.x == 0 && threadIdx.x == 0) {  // torch's single-tensor Adam, in double
+#pragma clang fp contract(off)
+    if (sc.dyn) sc.step_size = sc.dyn[0], sc.bc2_sqrt = sc.dyn[1];
+    const double gs = *sc.g;
+    double ms = *sc.m, vs = *sc.v;
+    ms = (sc.w1 < 0.5) ? ms + sc.w1 * (gs - ms) : gs - (gs - ms) * (1.0 - sc.w1);
+    vs = vs * sc.b2 + (sc.w2 * gs) * gs;
+    *sc.m = ms, *sc.v = vs;
+    *sc.p = *sc.p - sc.step_size * (ms / (sqrt(vs) / sc.bc2_sqrt + sc.eps));
+  }
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (vec) {
+    const size_t n4 = n >> 2;
+    for (size_t i = tid; i < n4; i += stride) {
+      f32x4 pp = reinterpret_cast<f32x4*>(p)[i], mm = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+      const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        adam_one(pe, gg[e], me, ve, w1, b2, w2, step_size, bc2_sqrt, eps);
+        pp[e] = pe, mm[e] = me, vv[e] = ve;
+      }
+      reinterpret_cast<f32x4*>(p)[i] = pp;
+      reinterpret_cast<f32x4*>(m)[i] = mm;
+      reinterpret_cast<f32x4*>(v)[i] = vv;
+      if (lp.tgt) {  // (vec implies target and split are 16-byte granular too: a float4 lies on one side of split)
+        f32x4 tt = reinterpret_cast<f32x4*>(lp.tgt)[i];
+        const bool a = 4 * i < lp.split;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tt[e] = lerp_one(pp[e], tt[e], a ? lp.tau_a : lp.tau_b, a ? lp.omt_a : lp.omt_b);
+        reinterpret_cast<f32x4*>(lp.tgt)[i] = tt;
+      }
+    }
+    done = n4 << 2;
+  }
+  for (size_t i = done + tid; i < n; i += stride) {
+    adam_one(p[i], g[i], m[i], v[i], w1, b2, w2, step_size, bc2_sqrt, eps);
+    if (lp.tgt) lp.tgt[i] = lerp_one(p[i], lp.tgt[i], i < lp.split ? lp.tau_a : lp.tau_b, i < lp.split ? lp.omt_a : lp.omt_b);
+  }
+}
+
+// Two Adam steps of two optimizers on the SAME parameters with the same gradient, back to back, in one pass (the
+// reference steps the encoder with encoder_optimizer and then again with cpc_optimizer, curl_sac.py:418-423): elements
+// [0, n_pre) belong to the second optimizer only (CURL.W in front of the encoder in the flat buffer), the rest take
+// step 1 then step 2 exactly as the two launches would (the same per-element operation order).
+struct AdamHyper {
+  float w1, b2, w2, step_size, bc2_sqrt, eps;
+};
+
+__global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m1, float* __restrict__ v1,
+                                                         float* __restrict__ m2, float* __restrict__ v2, size_t n,
+                                                         size_t n_pre, int vec, AdamHyper h1, AdamHyper h2,
+                                                         const float* __restrict__ dyn) {
+  if (dyn) h1.step_size = dyn[0], h1.bc2_sqrt = dyn[1], h2.step_size = dyn[2], h2.bc2_sqrt = dyn[3];  // (adam_step_kernel)
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (vec) {  // everything 16-byte aligned and n_pre a multiple of 4: a float4 lies on one side of n_pre
+    const size_t n4 = n >> 2, pre4 = n_pre >> 2;
+    for (size_t i = tid; i < n4; i += stride) {
+      f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+      const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+      if (i >= pre4) {
+        f32x4 mm = reinterpret_cast<f32x4*>(m1)[i - pre4], vv = reinterpret_cast<f32x4*>(v1)[i - pre4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float pe = pp[e], me = mm[e], ve = vv[e];
+          adam_one(pe, gg[e], me, ve, h1.w1, h1.b2, h1.w2, h1.step_size, h1.bc2_sqrt, h1.eps);
+          pp[e] = pe, mm[e] = me, vv[e] = ve;
+        }
+        reinterpret_cast<f32x4*>(m1)[i - pre4] = mm;
+        reinterpret_cast<f32x4*>(v1)[i - pre4] = vv;
+      }
+      f32x4 mm = reinterpret_cast<f32x4*>(m2)[i], vv = reinterpret_cast<f32x4*>(v2)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        adam_one(pe, gg[e], me, ve, h2.w1, h2.b2, h2.w2, h2.step_size, h2.bc2_sqrt, h2.eps);
+        pp[e] = pe, mm[e] = me, vv[e] = ve;
+      }
+      reinterpret_cast<f32x4*>(m2)[i] = mm;
+      reinterpret_cast<f32x4*>(v2)[i] = vv;
+      reinterpret_cast<f32x4*>(p)[i] = pp;
+    }
+    done = n4 << 2;
+  }
+  for (size_t i = done + tid; i < n; i += stride) {
+    float pi = p[i];
+    const float gi = g[i];
+    if (i >= n_pre) {
+      float m = m1[i - n_pre], v = v1[i - n_pre];
+      adam_one(pi, gi, m, v, h1.w1, h1.b2, h1.w2, h1.step_size, h1.bc2_sqrt, h1.eps);
+      m1[i - n_pre] = m, v1[i - n_pre] = v;
+    }
+    float m = m2[i], v = v2[i];
+    adam_one(pi, gi, m, v, h2.w1, h2.b2, h2.w2, h2.step_size, h2.bc2_sqrt, h2.eps);
+    m2[i] = m, v2[i] = v;
+    p[i] = pi;
+  }
+}

@@ -1,5 +1,5 @@
 // Proportional prioritized replay (Schaul et al. 2016) on the HBM-resident ring: ReplayBuffer(prioritized=True).
-// Included by heads.hip inside its anonymous namespace (wave_sum / block_sum_256 are in scope).
+// Included by heads.hip inside its anonymous namespace, behind reduce.h (wave_sum / block_sum_256).
 //
 // Storage: s float [capacity], the stored value p_i^alpha of every ring row (0: never written, never drawn) |
 // sums double [ceil(capacity / kPerChunk)], sums[c] = the sum of chunk c's current values in the fixed order of

@@ -1,6 +1,6 @@
 // Staging a minibatch: its index block to the device and the sampled transitions' scalars out of the ring, with the
 // n-step composition and the temporal positive's walk beside them.  Included by heads.hip inside its anonymous
-// namespace, beside the other replay / ring kernels.
+// namespace, in front of the other replay / ring kernels (ring.h, per.h, stage.h).
 //
 // One kernel template, sample_stage_kernel<HOST, NSTEP, POS>, behind six entry points (curla_hip.h):
 //   <0,0,0> curla_gather_transition_scalars     <1,0,0> curla_sample_stage

@@ -1,5 +1,6 @@
 // curla_stage_frames_u8: the front of the batched acting path (CurlSacAgent.select_actions / sample_actions).
-// Included by heads.hip inside its anonymous namespace, beside the other replay / ring kernels.
+// Included by heads.hip inside its anonymous namespace, behind ring.h and per.h; the launches are in heads.hip
+// (curla_stage_frames_u8).
 //
 // N planar uint8 observations [N][C][Hs][Ws] (what a vector of environments hands over) go into N consecutive NHWC
 // slots, out[n][y][x][c] = nchw[n][c][top + y][left + x]: the CHW -> HWC transpose of ReplayBuffer.add for N frames
@@ -106,13 +107,4 @@ __global__ void stage_frames_bytes_kernel(const uint8_t* nchw, uint8_t* out, siz
     const size_t n = t / Hd;
     out[i] = nchw[(n * C + c) * plane + (size_t)(top + y) * Ws + left + x];
   }
-}
-
-template <int C>
-inline void stage_frames_launch(const uint8_t* nchw, size_t src_bytes, uint8_t* out, uint32_t npix, int Hs, int Ws,
-                                int top, int left, int Hd, int Wd, hipStream_t st) {
-  const uint32_t groups = (npix + 3) / 4;
-  const uint32_t blocks = (groups + 255) / 256;
-  hipLaunchKernelGGL(stage_frames_kernel<C>, dim3(blocks < 8192u ? blocks : 8192u), dim3(256), 0, st, nchw, src_bytes,
-                     out, npix, Hs, Ws, top, left, Hd, Wd);
 }

@@ -472,6 +472,61 @@ def test_gemm_splitk_and_fc_ln(ops, B, Fd, K):
     check("splitk_reduce", red.cpu(), fc.detach())
 
 
+@pytest.mark.parametrize("B", [3, 5])  # fewer than a block's four rows; a second, partly filled block
+@pytest.mark.parametrize("Fd", [100, 300, 512, 513, 1024])
+def test_layernorm_every_width(ops, B, Fd):
+    """The LayerNorm kernels at the widths the other cases leave out -- a lane holds NF = 2 (F = 100), 8 (300: lanes past
+    the end; 512: exactly full) or 16 (513: one feature in the ninth slot; 1024: full) features -- forward from split-K
+    partials with and without the [y | action] rows, backward plain, from the twin halves and with the parameter
+    gradients left as per-block partial sums, against F.layer_norm and autograd in float64."""
+    A, ns = 3, 2
+    part, bias = rnd(ns, B, Fd, seed=61), rnd(Fd, seed=62)
+    gamma, beta = 1 + 0.1 * rnd(Fd, seed=63), 0.1 * rnd(Fd, seed=64)
+    act, dy = rnd(B, A, seed=65), rnd(B, Fd, seed=66)
+    fc = (part.double().sum(0) + bias.double()).requires_grad_(True)
+    g64, b64 = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    y_ref = F.layer_norm(fc, (Fd,), g64, b64, 1e-5)
+    y_ref.backward(dy.double())
+    fcd = fc.detach()
+    rstd_ref = (fcd.var(1, unbiased=False) + 1e-5).rsqrt()
+    xhat_ref = (fcd - fcd.mean(1, keepdim=True)) * rstd_ref[:, None]
+    f = lambda *sh: torch.full(sh, float("nan"), device="cuda")  # noqa: E731
+    tag = f"B{B} F{Fd}"
+    # ---- forward
+    y, fco, xhat, rstd = f(B, Fd), f(B, Fd), f(B, Fd), f(B)
+    ops.fc_ln_fwd(dev(part), ns, B * Fd, Fd, dev(bias), dev(gamma), dev(beta), B, Fd, y, fc_out=fco, xhat=xhat, rstd=rstd)
+    check(f"ln widths fc {tag}", fco.cpu(), fcd)
+    check(f"ln widths y {tag}", y.cpu(), y_ref.detach())
+    check(f"ln widths xhat {tag}", xhat.cpu(), xhat_ref)
+    check(f"ln widths rstd {tag}", rstd.cpu(), rstd_ref)
+    y2, xa = f(B, Fd), f(B, Fd + A)
+    ops.fc_ln_fwd(dev(part), ns, B * Fd, Fd, dev(bias), dev(gamma), dev(beta), B, Fd, y2, xa=xa, act=dev(act))
+    assert torch.equal(y2, y) and torch.equal(xa.cpu(), torch.cat([y.cpu(), act], 1))
+    # ---- backward, plain
+    refs = (("dx", fc.grad), ("dgamma", g64.grad), ("dbeta", b64.grad), ("fc dbias", fc.grad.sum(0)))
+    dx, dg, db_, dbin = f(B, Fd), f(Fd), f(Fd), f(Fd)
+    ops.ln_bwd(dev(dy), xhat, rstd, dev(gamma), B, Fd, dx, dgamma=dg, dbeta=db_, dbias_in=dbin)
+    for (n, r), got in zip(refs, (dx, dg, db_, dbin)):
+        check(f"ln widths {n} {tag}", got.cpu(), r)
+    # ---- the incoming gradient as the sum of two strided row blocks
+    half = rnd(2, B, Fd + A, seed=67)
+    half[1, :, :Fd] = dy - half[0, :, :Fd]
+    twin = dev(half)
+    dx2, dg2, db2, dbin2 = f(B, Fd), f(Fd), f(Fd), f(Fd)
+    ops.ln_bwd(twin[0], xhat, rstd, dev(gamma), B, Fd, dx2, dgamma=dg2, dbeta=db2, dbias_in=dbin2, dy2=twin[1], ld=Fd + A)
+    for (n, r), got in zip(refs, (dx2, dg2, db2, dbin2)):
+        check(f"ln widths twin {n} {tag}", got.cpu(), r, 2e-5)
+    # ---- the parameter gradients left as partial sums [ceil(B / 4)][3][F]: a block's rows of dy xhat (dgamma), dy
+    # (dbeta) and dx (the fc bias gradient), finished here on the host
+    dx3, buf = f(B, Fd), f(ops.ln_partial_floats(B, Fd))
+    tok = ops.ln_bwd(dev(dy), xhat, rstd, dev(gamma), B, Fd, dx3, dgamma=dg, dbeta=db_, dbias_in=dbin, defer=buf)
+    assert tok is not None and tok[1] == (B + 3) // 4
+    sums = buf.view(tok[1], 3, Fd).cpu().double().sum(0)
+    check(f"ln widths partial dx {tag}", dx3.cpu(), fc.grad, 2e-5)
+    for i, (n, r) in enumerate(refs[1:]):
+        check(f"ln widths partial {n} {tag}", sums[i], r, 2e-5)
+
+
 def _head_ref(out2a, noise, lo, hi):
     A = noise.shape[1]
     mu, ls = out2a.chunk(2, dim=-1)
@@ -484,8 +539,11 @@ def _head_ref(out2a, noise, lo, hi):
     return mu_t, pi_t, log_pi, log_std
 
 
-@pytest.mark.parametrize("B,A", [(8, 2), (300, 2), (17, 3)])
-def test_actor_head(ops, B, A):
+# (K = 1024 with A = 8: the 2A x K weights are 64 KB, past what the fused launch stages in LDS -- the head without LDS
+# weights, and the plain last layer's form that reads them from memory with N >= 2)
+@pytest.mark.parametrize("B,A,K", [pytest.param(8, 2, 64, id="8-2"), pytest.param(300, 2, 64, id="300-2"),
+                                   pytest.param(17, 3, 64, id="17-3"), pytest.param(5, 8, 1024, id="5-8-1024")])
+def test_actor_head(ops, B, A, K):
     lo, hi = -10.0, 2.0
     out = rnd(B, 2 * A, seed=41).requires_grad_(True)
     noise = rnd(B, A, seed=42)
@@ -516,7 +574,6 @@ def test_actor_head(ops, B, A):
     check(f"actor_head_fwd mu-only B{B}", mu2.cpu(), mu_r.detach())
     # the head inside the trunk's last-layer launch (curla_mlp_out_head_fwd): same trunk output as the plain layer, same
     # head outputs as the head kernel fed with it, pi also written into the action columns of the Q input rows
-    K = 64
     h, W, b = torch.relu(rnd(B, K, seed=45)).cuda(), (rnd(2 * A, K, seed=46) * 0.2).cuda(), rnd(2 * A, seed=47).cuda()
     o1 = torch.empty(B, 2 * A, device="cuda")
     ops.mlp_out_fwd(h, 0, W, 0, b, 0, o1, 0, B, 2 * A, K)
@@ -836,7 +893,8 @@ def test_colsum3(ops):
         assert torch.isnan(outs[i][:, n:]).all()  # nothing written past N
 
 
-@pytest.mark.parametrize("M,N,K,nb", [(512, 1, 1024, 2), (512, 4, 1024, 1), (37, 3, 100, 2), (5, 16, 64, 1), (130, 6, 96, 3)])
+@pytest.mark.parametrize("M,N,K,nb", [(512, 1, 1024, 2), (512, 4, 1024, 1), (37, 3, 100, 2), (5, 16, 64, 1), (130, 6, 96, 3),
+                                      (5, 16, 1024, 1)])  # (the last: 64 KB of weights, read from memory, not staged in LDS)
 def test_mlp_out_layer(ops, M, N, K, nb):
     """Last layer of the trunks (hidden -> 1 or 2|A| outputs) as row dot products / one fused backward pass,
     batched over twin networks with a parameter stride, against plain matmuls."""
