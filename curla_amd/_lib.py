@@ -74,6 +74,16 @@ SIGNATURES = {
                                  c_double, c_double, c_double, c_double, c_ll, vp, vp],
     "curla_adam_step2": [vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_double, c_double, c_double, c_double, c_ll, c_double,
                          c_double, c_double, c_double, c_ll, vp, vp],
+    # clipping by the global gradient norm: the namesakes' arguments, then (partials, n_partials, max_norm, stats), stream
+    "curla_grad_sqsum": [vp, c_size_t, vp, c_int, vp],
+    "curla_adam_step_clip": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int,
+                             c_double, vp, vp],
+    "curla_adam_step_lerp_clip": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_size_t,
+                                  c_float, c_float, c_float, c_float, vp, c_int, c_double, vp, vp],
+    "curla_adam_step_scalar64_clip": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_ll, vp, vp, vp,
+                                      vp, vp, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int, c_double, vp, vp],
+    "curla_adam_step2_clip": [vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_double, c_double, c_double, c_double, c_ll,
+                              c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int, c_double, vp, vp],
     "curla_f64_pack": [vp, vp, vp],
     "curla_f64_unpack": [vp, c_double, c_double, vp, vp],
     "curla_gather_transition_scalars": [vp, vp, c_int, c_int, vp, vp, vp, vp],

@@ -16,12 +16,12 @@
 
 namespace {
 
-#include "reduce.h"        // wave_sum, wave_max, block_sum_256; colsum_kernel, colsum3_kernel, mean_kernel
+#include "reduce.h"        // wave_sum, wave_max, block_sum_256; colsum, colsum3, mean and grad_sqsum kernels
 #include "layernorm.h"     // fc_ln_fwd_kernel<NF>, ln_bwd_kernel<NF>, ln_param_grad_kernel
 #include "mlp_out.h"       // mlp_out_fwd_kernel<HEAD, R, LDSW>, mlp_out_bwd_kernel<GEN>, the policy head's three kernels
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
 #include "curl_head.h"     // curl_head_kernel<NTILE>
-#include "optim.h"         // soft_update_kernel, soft_update2_kernel, adam_step_kernel, adam_step2_kernel
+#include "optim.h"         // soft_update_kernel, soft_update2_kernel, adam_step_kernel<CLIP>, adam_step2_kernel<CLIP>
 #include "sample_stage.h"  // a minibatch's index block and scalars: sample_stage_kernel<HOST, NSTEP, POS>, pos_walk_kernel
 #include "ring.h"          // crop_nchw_kernel, store_frame_kernel, gather_stacks_kernel<FAST>, nhwc_to_nchw_kernel
 #include "per.h"           // prioritized replay: per_set's three phases, per_sample_kernel, per_td_kernel
@@ -121,16 +121,53 @@ AdamHyper adam_hyper(double lr, double beta1, double beta2, double eps, long lon
   return h;
 }
 
-int adam_step_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+template <typename... P>
+bool float_pointers(const P*... p) {  // none NULL, none off 4 bytes
+  return (... && (p != nullptr && (reinterpret_cast<uintptr_t>(p) & 3) == 0));
+}
+
+// The clip argument of the curla_adam_step*_clip entry points (optim.h AdamClip), checked: the partials of
+// curla_grad_sqsum (doubles, 1 .. CURLA_CLIP_MAX_PARTIALS of them), a positive max_norm (inf allowed), the stats slot.
+int clip_args(const double* partials, int n_partials, double max_norm, float* stats, AdamClip* clip) {
+  CURLA_REQUIRE(partials && stats && (reinterpret_cast<uintptr_t>(partials) & 7) == 0 &&
+                (reinterpret_cast<uintptr_t>(stats) & 3) == 0 && n_partials >= 1 && n_partials <= CURLA_CLIP_MAX_PARTIALS &&
+                max_norm > 0.);  // (false for a NaN)
+  clip->partials = partials, clip->count = n_partials, clip->max_norm = max_norm, clip->stats = stats;
+  return CURLA_OK;
+}
+
+// `grad` is written only by a clipping launch (clip.partials != nullptr): the plain entry points hand in their const
+// gradient and an empty clip.
+int adam_step_launch(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                      double beta2, double eps, long long step, const float* dyn, const AdamScalar64& sc, void* stream,
-                     const AdamLerp& lp = AdamLerp{}) {
+                     const AdamLerp& lp = AdamLerp{}, const AdamClip& clip = AdamClip{}) {
   CURLA_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1 && beta1 >= 0. && beta1 < 1. &&
                 beta2 >= 0. && beta2 < 1. && (reinterpret_cast<uintptr_t>(dyn) & 3) == 0);
   const AdamHyper hy = adam_hyper(lr, beta1, beta2, eps, step);
   const int vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) &&
                   (!lp.tgt || (aligned16(lp.tgt) && lp.split % 4 == 0));
-  return launch(adam_step_kernel, dim3(nblocks((n + 3) / 4, 256, 8192)), 256, 0, static_cast<hipStream_t>(stream), param,
-                grad, exp_avg, exp_avg_sq, n, vec, hy.w1, hy.b2, hy.w2, hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn);
+  const dim3 grid(nblocks((n + 3) / 4, 256, 8192));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (clip.partials)
+    return launch(adam_step_kernel<true>, grid, 256, 0, st, param, grad, exp_avg, exp_avg_sq, n, vec, hy.w1, hy.b2, hy.w2,
+                  hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip);
+  return launch(adam_step_kernel<false>, grid, 256, 0, st, param, static_cast<const float*>(grad), exp_avg, exp_avg_sq, n,
+                vec, hy.w1, hy.b2, hy.w2, hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip);
+}
+
+// curla_adam_step2 and curla_adam_step2_clip
+int adam_step2_launch(float* param, float* grad, float* exp_avg1, float* exp_avg_sq1, float* exp_avg2, float* exp_avg_sq2,
+                      size_t n, size_t n_pre, const AdamHyper& h1, const AdamHyper& h2, const float* dyn, void* stream,
+                      const AdamClip& clip = AdamClip{}) {
+  const int vec = (n_pre % 4 == 0) && aligned16(param) && aligned16(grad) && aligned16(exp_avg1) &&
+                  aligned16(exp_avg_sq1) && aligned16(exp_avg2) && aligned16(exp_avg_sq2);
+  const dim3 grid(nblocks((n + 3) / 4, 256, 8192));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (clip.partials)
+    return launch(adam_step2_kernel<true>, grid, 256, 0, st, param, grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2, n,
+                  n_pre, vec, h1, h2, dyn, clip);
+  return launch(adam_step2_kernel<false>, grid, 256, 0, st, param, static_cast<const float*>(grad), exp_avg1, exp_avg_sq1,
+                exp_avg2, exp_avg_sq2, n, n_pre, vec, h1, h2, dyn, clip);
 }
 
 // [a, a + na) and [b, b + nb) share no byte
@@ -498,27 +535,90 @@ int curla_adam_step_lerp(float* param, const float* grad, float* exp_avg, float*
   CURLA_REQUIRE(target && split <= n);
   AdamScalar64 none = {};
   AdamLerp lp{target, split, tau_a, one_minus_tau_a, tau_b, one_minus_tau_b};
-  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none, stream, lp);
+  return adam_step_launch(param, const_cast<float*>(grad), exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none,
+                          stream, lp);
+}
+
+int curla_adam_step_lerp_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                              double beta1, double beta2, double eps, long long step, const float* dyn, float* target,
+                              size_t split, float tau_a, float one_minus_tau_a, float tau_b, float one_minus_tau_b,
+                              const double* partials, int n_partials, double max_norm, float* stats, void* stream) {
+  AdamClip clip;
+  const int rc = clip_args(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(float_pointers(param, grad, exp_avg, exp_avg_sq, target) && split <= n);
+  AdamScalar64 none = {};
+  AdamLerp lp{target, split, tau_a, one_minus_tau_a, tau_b, one_minus_tau_b};
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none, stream, lp, clip);
+}
+
+int curla_grad_sqsum(const float* grad, size_t n, double* partials, int n_partials, void* stream) {
+  CURLA_REQUIRE(float_pointers(grad) && partials && (reinterpret_cast<uintptr_t>(partials) & 7) == 0 && n > 0 &&
+                n_partials >= 1 && n_partials <= CURLA_CLIP_MAX_PARTIALS);
+  return launch(grad_sqsum_kernel, dim3(n_partials), 256, 0, static_cast<hipStream_t>(stream), grad, n,
+                (int)aligned16(grad), partials);
+}
+
+int curla_adam_step_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                         double beta2, double eps, long long step, const float* dyn, const double* partials,
+                         int n_partials, double max_norm, float* stats, void* stream) {
+  AdamClip clip;
+  const int rc = clip_args(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(float_pointers(param, grad, exp_avg, exp_avg_sq));
+  AdamScalar64 none = {};
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none, stream, AdamLerp{},
+                          clip);
 }
 
 int curla_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
                     double beta1, double beta2, double eps, long long step, const float* dyn, void* stream) {
   AdamScalar64 none = {};
-  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none, stream);
+  return adam_step_launch(param, const_cast<float*>(grad), exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none,
+                          stream);
+}
+
+// the float64 rider of curla_adam_step_scalar64 and curla_adam_step_scalar64_clip, checked
+int scalar64_args(double* param64, const double* grad64, double* exp_avg64, double* exp_avg_sq64, double lr64,
+                  double beta1_64, double beta2_64, double eps64, long long step64, const double* dyn64, AdamScalar64* sc) {
+  CURLA_REQUIRE(param64 && grad64 && exp_avg64 && exp_avg_sq64 && step64 >= 1 && beta1_64 >= 0. && beta1_64 < 1. &&
+                beta2_64 >= 0. && beta2_64 < 1. && (reinterpret_cast<uintptr_t>(dyn64) & 7) == 0);
+  sc->p = param64, sc->g = grad64, sc->m = exp_avg64, sc->v = exp_avg_sq64;
+  sc->w1 = 1.0 - beta1_64, sc->b2 = beta2_64, sc->w2 = 1.0 - beta2_64;
+  sc->step_size = lr64 / (1.0 - pow(beta1_64, (double)step64));
+  sc->bc2_sqrt = sqrt(1.0 - pow(beta2_64, (double)step64)), sc->eps = eps64, sc->dyn = dyn64;
+  return CURLA_OK;
 }
 
 int curla_adam_step_scalar64(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
                              double beta1, double beta2, double eps, long long step, const float* dyn, double* param64,
                              const double* grad64, double* exp_avg64, double* exp_avg_sq64, double lr64, double beta1_64,
                              double beta2_64, double eps64, long long step64, const double* dyn64, void* stream) {
-  CURLA_REQUIRE(param64 && grad64 && exp_avg64 && exp_avg_sq64 && step64 >= 1 && beta1_64 >= 0. && beta1_64 < 1. &&
-                beta2_64 >= 0. && beta2_64 < 1. && (reinterpret_cast<uintptr_t>(dyn64) & 7) == 0);
   AdamScalar64 sc;
-  sc.p = param64, sc.g = grad64, sc.m = exp_avg64, sc.v = exp_avg_sq64;
-  sc.w1 = 1.0 - beta1_64, sc.b2 = beta2_64, sc.w2 = 1.0 - beta2_64;
-  sc.step_size = lr64 / (1.0 - pow(beta1_64, (double)step64));
-  sc.bc2_sqrt = sqrt(1.0 - pow(beta2_64, (double)step64)), sc.eps = eps64, sc.dyn = dyn64;
-  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, sc, stream);
+  const int rc =
+      scalar64_args(param64, grad64, exp_avg64, exp_avg_sq64, lr64, beta1_64, beta2_64, eps64, step64, dyn64, &sc);
+  if (rc != CURLA_OK) return rc;
+  return adam_step_launch(param, const_cast<float*>(grad), exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, sc,
+                          stream);
+}
+
+int curla_adam_step_scalar64_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                                  double beta1, double beta2, double eps, long long step, const float* dyn,
+                                  double* param64, const double* grad64, double* exp_avg64, double* exp_avg_sq64,
+                                  double lr64, double beta1_64, double beta2_64, double eps64, long long step64,
+                                  const double* dyn64, const double* partials, int n_partials, double max_norm,
+                                  float* stats, void* stream) {
+  AdamClip clip;
+  int rc = clip_args(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(float_pointers(param, grad, exp_avg, exp_avg_sq) &&
+                ((reinterpret_cast<uintptr_t>(param64) | reinterpret_cast<uintptr_t>(grad64) |
+                  reinterpret_cast<uintptr_t>(exp_avg64) | reinterpret_cast<uintptr_t>(exp_avg_sq64)) & 7) == 0);
+  AdamScalar64 sc;
+  rc = scalar64_args(param64, grad64, exp_avg64, exp_avg_sq64, lr64, beta1_64, beta2_64, eps64, step64, dyn64, &sc);
+  if (rc != CURLA_OK) return rc;
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, sc, stream, AdamLerp{},
+                          clip);
 }
 
 int curla_adam_step2(float* param, const float* grad, float* exp_avg1, float* exp_avg_sq1, float* exp_avg2,
@@ -529,11 +629,26 @@ int curla_adam_step2(float* param, const float* grad, float* exp_avg1, float* ex
                 step1 >= 1 && step2 >= 1 && (reinterpret_cast<uintptr_t>(dyn) & 3) == 0);
   CURLA_REQUIRE(beta1_1 >= 0. && beta1_1 < 1. && beta2_1 >= 0. && beta2_1 < 1. && beta1_2 >= 0. && beta1_2 < 1. &&
                 beta2_2 >= 0. && beta2_2 < 1.);
-  const int vec = (n_pre % 4 == 0) && aligned16(param) && aligned16(grad) && aligned16(exp_avg1) &&
-                  aligned16(exp_avg_sq1) && aligned16(exp_avg2) && aligned16(exp_avg_sq2);
-  return launch(adam_step2_kernel, dim3(nblocks((n + 3) / 4, 256, 8192)), 256, 0, static_cast<hipStream_t>(stream), param,
-                grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2, n, n_pre, vec,
-                adam_hyper(lr1, beta1_1, beta2_1, eps1, step1), adam_hyper(lr2, beta1_2, beta2_2, eps2, step2), dyn);
+  return adam_step2_launch(param, const_cast<float*>(grad), exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2, n, n_pre,
+                           adam_hyper(lr1, beta1_1, beta2_1, eps1, step1), adam_hyper(lr2, beta1_2, beta2_2, eps2, step2),
+                           dyn, stream);
+}
+
+int curla_adam_step2_clip(float* param, float* grad, float* exp_avg1, float* exp_avg_sq1, float* exp_avg2,
+                          float* exp_avg_sq2, size_t n, size_t n_pre, double lr1, double beta1_1, double beta2_1,
+                          double eps1, long long step1, double lr2, double beta1_2, double beta2_2, double eps2,
+                          long long step2, const float* dyn, const double* partials, int n_partials, double max_norm,
+                          float* stats, void* stream) {
+  AdamClip clip;
+  const int rc = clip_args(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(float_pointers(param, grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2) && n > 0 && n_pre <= n &&
+                step1 >= 1 && step2 >= 1 && (reinterpret_cast<uintptr_t>(dyn) & 3) == 0);
+  CURLA_REQUIRE(beta1_1 >= 0. && beta1_1 < 1. && beta2_1 >= 0. && beta2_1 < 1. && beta1_2 >= 0. && beta1_2 < 1. &&
+                beta2_2 >= 0. && beta2_2 < 1.);
+  return adam_step2_launch(param, grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2, n, n_pre,
+                           adam_hyper(lr1, beta1_1, beta2_1, eps1, step1), adam_hyper(lr2, beta1_2, beta2_2, eps2, step2),
+                           dyn, stream, clip);
 }
 
 int curla_host_device_pointer(void* host, void** device) {

@@ -1,6 +1,7 @@
 // The optimiser step over the flat parameter buffers: the target networks' soft update (soft_update_kernel,
 // soft_update2_kernel) and Adam, one step or two back to back, with the float64 scalar and the target lerp that can
-// ride along (adam_step_kernel, adam_step2_kernel).  Included by heads.hip inside its anonymous namespace.
+// ride along (adam_step_kernel, adam_step2_kernel), clipping by the global gradient norm included (AdamClip).
+// Included by heads.hip inside its anonymous namespace.
 #pragma once
 
 // target <- tau*p + (1-tau)*target                                     (utils.py:37-41)
@@ -66,11 +67,49 @@ __device__ __forceinline__ float lerp_one(float p, float t, float tau, float omt
   return tau * p + omt * t;  // two roundings of the products and one of the sum, as soft_update_kernel
 }
 
-__global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, const float* __restrict__ g,
+// Clipping by the global gradient norm inside the step (torch.nn.utils.clip_grad_norm_, norm_type 2, right in front of
+// the optimizer's step).  `partials` are the `count` (1 .. 256) double sums of squares grad_sqsum_kernel left for ALL the
+// runs of this step; every block adds them up in the same fixed order, so every block of every launch of the step holds
+// the same norm = sqrt(sum) and coef = min(1, max_norm / (norm + 1e-6)), formed in double and rounded to float once.
+// coef != 1: the gradient is scaled (one rounding per element), written back -- .grad afterwards is what Adam consumed,
+// as with torch -- and stepped on; coef == 1: nothing is written and the step is the unclipped one.  A NaN norm gives a
+// NaN coefficient (torch's clamp(max=1) lets it through too).  Block 0 leaves (norm, coef) in stats[0 .. 1].
+// The kernels are templates on whether they clip: without (partials == nullptr) they are the ones they were.
+struct AdamClip {
+  const double* partials;
+  int count;
+  double max_norm;
+  float* stats;
+};
+__device__ __forceinline__ float clip_coef(const AdamClip& c) {
+  __shared__ double sm[4];
+  const double total = block_sum_256((int)threadIdx.x < c.count ? c.partials[threadIdx.x] : 0.0, sm);
+  const double norm = sqrt(total);
+  double cd = c.max_norm / (norm + 1e-6);
+  if (cd > 1.0) cd = 1.0;  // (a NaN stays)
+  const float coef = (float)cd;
+  if (blockIdx.x == 0 && threadIdx.x == 0) c.stats[0] = (float)norm, c.stats[1] = coef;
+  return coef;
+}
+__device__ __forceinline__ float clip_one(float g, float coef) {
+#pragma clang fp contract(off)
+  return coef * g;
+}
+
+// CLIP false is the kernel without clipping, instruction for instruction what it was (the gradient const, no LDS);
+// CLIP true writes the gradient, and only where the coefficient is not 1: each element by the thread that read it.
+template <bool CLIP>
+using AdamGrad = std::conditional_t<CLIP, float, const float>;
+
+template <bool CLIP>
+__global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, AdamGrad<CLIP>* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, size_t n,
                                                         int vec, float w1, float b2, float w2, float step_size,
                                                         float bc2_sqrt, float eps, AdamScalar64 sc, AdamLerp lp,
-                                                        const float* __restrict__ dyn) {
+                                                        const float* __restrict__ dyn, AdamClip clip) {
+  float coef = 1.0f;
+  if constexpr (CLIP) coef = clip_coef(clip);
+  const bool scale = CLIP && coef != 1.0f;
   // dyn != nullptr: the two step-dependent factors lr / (1 - b1^t) and sqrt(1 - b2^t) come from device memory, written
   // there (by the host, through the update's pinned control block) before the kernel runs: a captured graph is
   // replayed with new step counts.  The same two floats the host would have passed by value.
@@ -91,7 +130,14 @@ __global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, c
     const size_t n4 = n >> 2;
     for (size_t i = tid; i < n4; i += stride) {
       f32x4 pp = reinterpret_cast<f32x4*>(p)[i], mm = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
-      const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+      f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+      if constexpr (CLIP) {
+        if (scale) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) gg[e] = clip_one(gg[e], coef);
+          reinterpret_cast<f32x4*>(g)[i] = gg;
+        }
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pp[e], me = mm[e], ve = vv[e];
@@ -112,7 +158,11 @@ __global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, c
     done = n4 << 2;
   }
   for (size_t i = done + tid; i < n; i += stride) {
-    adam_one(p[i], g[i], m[i], v[i], w1, b2, w2, step_size, bc2_sqrt, eps);
+    float gi = g[i];
+    if constexpr (CLIP) {
+      if (scale) g[i] = gi = clip_one(gi, coef);
+    }
+    adam_one(p[i], gi, m[i], v[i], w1, b2, w2, step_size, bc2_sqrt, eps);
     if (lp.tgt) lp.tgt[i] = lerp_one(p[i], lp.tgt[i], i < lp.split ? lp.tau_a : lp.tau_b, i < lp.split ? lp.omt_a : lp.omt_b);
   }
 }
@@ -125,11 +175,16 @@ struct AdamHyper {
   float w1, b2, w2, step_size, bc2_sqrt, eps;
 };
 
-__global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, const float* __restrict__ g,
+template <bool CLIP>
+__global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, AdamGrad<CLIP>* __restrict__ g,
                                                          float* __restrict__ m1, float* __restrict__ v1,
                                                          float* __restrict__ m2, float* __restrict__ v2, size_t n,
                                                          size_t n_pre, int vec, AdamHyper h1, AdamHyper h2,
-                                                         const float* __restrict__ dyn) {
+                                                         const float* __restrict__ dyn, AdamClip clip) {
+  // (adam_step_kernel: the gradient is clipped ONCE, over the whole run, and both steps consume the clipped value)
+  float coef = 1.0f;
+  if constexpr (CLIP) coef = clip_coef(clip);
+  const bool scale = CLIP && coef != 1.0f;
   if (dyn) h1.step_size = dyn[0], h1.bc2_sqrt = dyn[1], h2.step_size = dyn[2], h2.bc2_sqrt = dyn[3];  // (adam_step_kernel)
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
   size_t done = 0;
@@ -137,7 +192,14 @@ __global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, 
     const size_t n4 = n >> 2, pre4 = n_pre >> 2;
     for (size_t i = tid; i < n4; i += stride) {
       f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
-      const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+      f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+      if constexpr (CLIP) {
+        if (scale) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) gg[e] = clip_one(gg[e], coef);
+          reinterpret_cast<f32x4*>(g)[i] = gg;
+        }
+      }
       if (i >= pre4) {
         f32x4 mm = reinterpret_cast<f32x4*>(m1)[i - pre4], vv = reinterpret_cast<f32x4*>(v1)[i - pre4];
 #pragma unroll
@@ -164,7 +226,10 @@ __global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, 
   }
   for (size_t i = done + tid; i < n; i += stride) {
     float pi = p[i];
-    const float gi = g[i];
+    float gi = g[i];
+    if constexpr (CLIP) {
+      if (scale) g[i] = gi = clip_one(gi, coef);
+    }
     if (i >= n_pre) {
       float m = m1[i - n_pre], v = v1[i - n_pre];
       adam_one(pi, gi, m, v, h1.w1, h1.b2, h1.w2, h1.step_size, h1.bc2_sqrt, h1.eps);

@@ -30,7 +30,7 @@ from . import autograd, ops
 from .augmentations import Compose, RandomCrop, RandomTranslate
 from .encoder import CNNEncoder
 from .ops import ObsRef
-from .optim import FlatAdam
+from .optim import FlatAdam, check_max_grad_norm
 
 LOG_FREQ = 25_000
 
@@ -1102,6 +1102,7 @@ class CurlSacAgent(object):
             saved = [(p, p.grad) for m in enc.convs for p in (m.weight, m.bias)]
             for p, _ in saved:
                 p.grad = None
+            self._clip_torch(0, self.critic_optimizer)
             self.critic_optimizer.step()
             for p, g in saved:
                 p.grad = g
@@ -1115,7 +1116,10 @@ class CurlSacAgent(object):
                                                 self.encoder_tau, self.critic_tau)
                 self._soft_update_done = fused
             if not fused:
+                self._clip_torch(0, self.critic_optimizer)
                 self.critic_optimizer.step()
+        if self._max_grad_norm is not None and step % self.log_interval == 0:
+            L.log('train_critic/grad_norm', self.grad_clip_stats[0, 0], step)
         if self.log_param_hist_imgs:
             self.critic.log(L, step)
 
@@ -1204,6 +1208,8 @@ class CurlSacAgent(object):
                 self._allreduce_wait()
         else:
             self._allreduce(self._actor_gbucket, f64_rider=rider)
+        # (the norm is logged once the step that takes it has been enqueued: a deferred step is not, yet)
+        self._actor_norm_log = (L, step) if self._max_grad_norm is not None and step % self.log_interval == 0 else None
         if not self._actor_step_pending:
             self._actor_steps()
         if self.log_param_hist_imgs:
@@ -1214,15 +1220,21 @@ class CurlSacAgent(object):
 
     _defer_actor_step = False    # set by update(): the CURL phase follows the actor phase (overlapped data parallel)
     _actor_step_pending = False  # the actor phase has left its optimizer steps to _finish_actor_step()
+    _actor_norm_log = None       # (logger, step) of a logging step while clipping is on, until the actor's step is taken
 
     def _actor_steps(self):
         # actor_optimizer.step() ... log_alpha_optimizer.step() (curl_sac.py:393-404): nothing in between reads
         # log_alpha (the logged alpha is the loss kernel's), so the two steps share a launch
+        # (clipping: the actor's own parameters; log_alpha has its own optimizer and loss scale and is not clipped)
         if isinstance(self.actor_optimizer, FlatAdam):
             FlatAdam.step_with_scalar(self.actor_optimizer, self.log_alpha_optimizer)
         else:
+            self._clip_torch(1, self.actor_optimizer)
             self.actor_optimizer.step()
             self.log_alpha_optimizer.step()
+        if self._actor_norm_log is not None:
+            (L, step), self._actor_norm_log = self._actor_norm_log, None
+            L.log('train_actor/grad_norm', self.grad_clip_stats[1, 0], step)
 
     def _finish_actor_step(self):
         if self._actor_step_pending:
@@ -1287,10 +1299,54 @@ class CurlSacAgent(object):
         if isinstance(self.encoder_optimizer, FlatAdam):
             FlatAdam.step_pair(self.encoder_optimizer, self.cpc_optimizer)  # both steps in one pass over the encoder
         else:
+            self._clip_torch(2, self.cpc_optimizer)  # [W | encoder], once: both steps consume the clipped gradient
             self.encoder_optimizer.step()
             self.cpc_optimizer.step()
         if step % self.log_interval == 0:
             L.log('train/curl_loss', ws.scalars[5], step)
+            if self._max_grad_norm is not None:
+                L.log('train/curl_grad_norm', self.grad_clip_stats[2, 0], step)
+
+    # ---------------------------------------------------------------- clipping by the global gradient norm
+    _max_grad_norm = None
+    grad_clip_stats = None
+
+    @property
+    def max_grad_norm(self):
+        """The threshold set by ``set_max_grad_norm`` (None: no clipping)."""
+        return self._max_grad_norm
+
+    def set_max_grad_norm(self, value):
+        """Clip every phase's gradient by its global norm right in front of the phase's optimizer steps:
+        ``torch.nn.utils.clip_grad_norm_(parameters with a gradient, value)`` where one would put it in the reference
+        -- in front of curl_sac.py:367 over ``critic.parameters()`` (without the convs under ``detach_encoder``), in
+        front of :393-404 over the actor's own parameters (``log_alpha`` is not clipped), in front of :418-423 over
+        [CURL.W | encoder], once for both optimizers; data parallel: after the gradient's all-reduce.  ``value``: None
+        (off, the default: the launches are the unclipped ones) or a positive number shared by the three phases.
+        With the flat optimizers the norm never leaves the device: one square-sum launch per phase, the coefficient
+        applied inside the Adam launch (optim.py).  ``grad_clip_stats`` (float32 device tensor [3, 2]; rows critic /
+        actor / cpc, columns norm before clipping / coefficient applied) holds each phase's last figures.
+        A hyper-parameter, not state: checkpoints do not carry it, a resumed run calls this again."""
+        value = check_max_grad_norm(value)
+        if value is not None and self.grad_clip_stats is None:
+            self.grad_clip_stats = torch.zeros(3, 2, device=self.device, dtype=torch.float32)
+        rows = ((self.critic_optimizer, 0), (self.actor_optimizer, 1), (self.encoder_optimizer, 2), (self.cpc_optimizer, 2))
+        for opt, row in rows:
+            if isinstance(opt, FlatAdam):
+                if value is not None:
+                    opt.clip_stats = self.grad_clip_stats[row]
+                opt.max_grad_norm = value
+        self._max_grad_norm = value  # (captured update graphs hold it by value: _graph_key)
+
+    def _clip_torch(self, row, opt):
+        """The clipping step of a phase whose optimizer is torch's own (CURLA_TORCH_ADAM=1, a CPU agent): FlatAdam
+        clips inside its launches."""
+        if self._max_grad_norm is None or isinstance(opt, FlatAdam):
+            return
+        params = [p for g in opt.param_groups for p in g["params"] if p.grad is not None]
+        norm = torch.nn.utils.clip_grad_norm_(params, self._max_grad_norm)
+        self.grad_clip_stats[row, 0] = norm
+        self.grad_clip_stats[row, 1] = torch.clamp(self._max_grad_norm / (norm + 1e-6), max=1.0)
 
     def soft_update_targets(self):
         """utils.soft_update_params x3 (curl_sac.py:442-445) as one flat lerp with two rates."""
@@ -1395,9 +1451,9 @@ class CurlSacAgent(object):
         pinned block and a copy of their own per call).  Data-parallel updates over RCCL
         ARE captured, collectives included (round 5; the replica check stays on the host, in front of the replay).
         Values the graphs hold as kernel arguments (discount, taus, betas / eps, detach_encoder, the update
-        frequencies, the data-parallel group and schedule, ``n_step`` and ``discount`` of an n-step replay buffer) are
-        fingerprinted at capture: editing one of them drops the graphs and they are captured again; so does
-        ``load_checkpoint``.  A capture that raises leaves the agent's
+        frequencies, the data-parallel group and schedule, ``max_grad_norm``, ``n_step`` and ``discount`` of an n-step
+        replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
+        so does ``load_checkpoint``.  A capture that raises leaves the agent's
         state untouched and that update runs eagerly."""
         if self.device.type != "cuda":
             raise RuntimeError("update graphs need the HIP device")
@@ -1452,7 +1508,7 @@ class CurlSacAgent(object):
                 bool(self.pixel_sac), float(self.target_entropy), float(self.actor.log_std_min),
                 float(self.actor.log_std_max), self.actor_update_freq, self.critic_target_update_freq,
                 self.cpc_update_freq, self._dp_active, self._dp_overlap, id(self._dp_group) if self._dp_active else 0,
-                hyper, self._graph_rb_key())
+                hyper, self._graph_rb_key(), self._max_grad_norm)
 
     def _graph_rb_key(self):
         """(n_step, discount, pos_offset) of the graphs' replay buffer: its staging launch holds them by value."""

@@ -9,16 +9,39 @@ workgroups on a 256-CU chip (45 us for 6 MB of parameters; the flat kernel
 streams the same 7 arrays at HBM rate).  The moments live in two flat mirror
 buffers; ``state[p]['exp_avg']`` / ``['exp_avg_sq']`` are views into them, so a
 checkpoint written from ``state_dict()`` is what torch's Adam would write.
+
+``max_grad_norm`` (off by default) clips the gradient of a step by its global norm inside those launches:
+``torch.nn.utils.clip_grad_norm_(live parameters, max_grad_norm)`` right in front of ``step()``, as one square-sum launch
+per run (``curla_grad_sqsum``: float64 partial sums in a buffer this optimizer owns) and the coefficient formed and
+applied by the Adam launch that follows (``curla_adam_step*_clip``).  No host read, no allocation in the step.
 """
+import math
+import numbers
+
 import torch
 
 from ._lib import call, stream
 
 
+def check_max_grad_norm(value):
+    """``value`` as a clipping threshold: None (off) or a positive number (inf allowed: the coefficient is then always
+    1) as a float; ValueError for a bool, a non-number, NaN or a value <= 0."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or math.isnan(value) or not value > 0:
+        raise ValueError("max_grad_norm must be None or a positive number (inf allowed), got %r" % (value,))
+    return float(value)
+
+
 class FlatAdam(torch.optim.Adam):
-    def __init__(self, params, flat, gflat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    CLIP_MAX_PARTIALS = 256  # include/curla_hip.h: one Adam workgroup sums a step's partials with one load per thread
+    SQSUM_BLOCK = 1024       # elements a square-sum workgroup takes per trip of its grid-stride loop (256 x 16 bytes)
+
+    def __init__(self, params, flat, gflat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, max_grad_norm=None):
         """``params``: Parameters whose ``.data`` are views into ``flat`` and whose ``.grad`` (when not None) are the
-        views at the same offsets of ``gflat``."""
+        views at the same offsets of ``gflat``.  ``max_grad_norm``: None, or the threshold every step clips its live
+        gradient's global norm to (a hyper-parameter, not state: it is neither in ``param_groups`` nor in
+        ``state_dict()``)."""
         super().__init__(params, lr=lr, betas=betas, eps=eps)
         self._flat, self._gflat = flat, gflat
         self._plist = [p for g in self.param_groups for p in g["params"]]
@@ -40,6 +63,29 @@ class FlatAdam(torch.optim.Adam):
         # when it runs, and the step counts are NOT advanced by the launching code (the graph manager advances them
         # once per replay: advance()).
         self._dyn = None
+        # Clipping: the partial sums of squares of one step (float64, device) and where its (norm, coefficient) go --
+        # ``clip_stats`` may be pointed at any two-float device tensor (CurlSacAgent: a row of grad_clip_stats).
+        self._max_grad_norm = None
+        self._clip_partials = None
+        self.clip_stats = None
+        self._shared_clip = None  # step_pair's two separate steps: (the pair's clip arguments, runs already scaled)
+        self._touched = ()        # the runs [lo, hi) the last step() launched over
+        self.max_grad_norm = max_grad_norm
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        value = check_max_grad_norm(value)
+        if value is not None:
+            if self._clip_partials is None:  # (here, not in the step: a captured step allocates nothing)
+                dev = self._flat.device
+                self._clip_partials = torch.zeros(self.CLIP_MAX_PARTIALS, device=dev, dtype=torch.float64)
+                if self.clip_stats is None:
+                    self.clip_stats = torch.zeros(2, device=dev, dtype=torch.float32)
+        self._max_grad_norm = value
 
     # -- state kept in torch's format ------------------------------------------------------------------------
     def _views(self, i):
@@ -125,12 +171,9 @@ class FlatAdam(torch.optim.Adam):
                 runs.append([a, b, [i]])
         return runs
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _segments(self, commit):
+        """The flat runs [lo, hi) a step launches over, each with its group and the step count its parameters share:
+        [(group, lo, hi, t)].  ``commit``: do the step's bookkeeping (state, step counts) as well."""
         live = tuple(p.grad is not None for p in self._plist)
         plans = self._plans.get(live)
         if plans is None:
@@ -139,11 +182,10 @@ class FlatAdam(torch.optim.Adam):
                 if live[i] and (p.grad.data_ptr() - base) // 4 != self._span[i][0]:
                     raise ValueError("FlatAdam: a gradient is not the flat gradient buffer's view of its parameter")
             plans = self._plans[live] = [self._plan(gi, g, live) for gi, g in enumerate(self.param_groups)]
-        s = stream()
+        segs = []
         for group, runs in zip(self.param_groups, plans):
             if group.get("weight_decay", 0) != 0 or group.get("amsgrad", False) or group.get("maximize", False):
                 raise NotImplementedError("FlatAdam implements the options the learner uses: plain Adam")
-            lr, (b1, b2), eps = group["lr"], group["betas"], group["eps"]
             for a, b, members in runs:
                 # parameters of one run normally share their step count; split the run where they do not
                 k = 0
@@ -154,18 +196,66 @@ class FlatAdam(torch.optim.Adam):
                         e += 1
                     lo = a if k == 0 else self._span[members[k]][0]
                     hi = b if e == len(members) - 1 else self._span[members[e]][1]
-                    if self._dyn is None:
+                    if not commit:
+                        pass
+                    elif self._dyn is None:
                         for i in members[k:e + 1]:
                             self._ensure_state(i)
                             self._steps[i] = t + 1
                     elif len(plans) != 1 or len(runs) != 1 or e != len(members) - 1 or k != 0:
                         raise RuntimeError("FlatAdam: a captured step must be ONE run with one step count")
-                    call("curla_adam_step", self._flat.data_ptr() + 4 * lo, self._gflat.data_ptr() + 4 * lo,
-                         self._m.data_ptr() + 4 * (lo - self._lo), self._v.data_ptr() + 4 * (lo - self._lo), hi - lo,
-                         float(lr), float(b1), float(b2), float(eps), t + 1, self._dyn, s)
+                    segs.append((group, lo, hi, t))
                     k = e + 1
-        return loss
+        return segs
 
+    def _sqsum(self, runs, s):
+        """One square-sum launch per run [lo, hi) of the flat gradient, into disjoint slots of the partials buffer;
+        returns the clip arguments of the Adam launches of the step: (partials, their total count, max_norm, stats).
+        A run's workgroup count is a function of its length alone, capped so that the step's partials stay within
+        CLIP_MAX_PARTIALS: the norm depends only on the gradient's bytes and the layout of the runs."""
+        if len(runs) > self.CLIP_MAX_PARTIALS:
+            raise NotImplementedError("FlatAdam: a clipped step over more than %d runs" % self.CLIP_MAX_PARTIALS)
+        cap = self.CLIP_MAX_PARTIALS // len(runs)
+        base, count = self._clip_partials.data_ptr(), 0
+        for lo, hi in runs:
+            nb = max(1, min(cap, -(-(hi - lo) // self.SQSUM_BLOCK)))
+            call("curla_grad_sqsum", self._gflat.data_ptr() + 4 * lo, hi - lo, base + 8 * count, nb, s)
+            count += nb
+        return base, count, self._max_grad_norm, self.clip_stats.data_ptr()
+
+    def _adam_args(self, lo, hi, t, g):
+        return (self._flat.data_ptr() + 4 * lo, self._gflat.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * (lo - self._lo),
+                self._v.data_ptr() + 4 * (lo - self._lo), hi - lo, float(g["lr"]), float(g["betas"][0]),
+                float(g["betas"][1]), float(g["eps"]), t + 1, self._dyn)
+
+    @staticmethod
+    def _pieces(lo, hi, done):
+        """[lo, hi) cut at the borders of the runs in ``done``: (a, b, inside one of them?) in order."""
+        cuts = sorted({lo, hi} | {x for r in done for x in r if lo < x < hi})
+        return [(a, b, any(c <= a and b <= d for c, d in done)) for a, b in zip(cuts[:-1], cuts[1:])]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        segs = self._segments(commit=True)
+        self._touched = tuple((lo, hi) for _, lo, hi, _ in segs)
+        s = stream()
+        clip, done = None, ()
+        if self._max_grad_norm is not None and segs:
+            if self._shared_clip is not None:  # step_pair's separate steps: ONE norm for both, each element scaled once
+                clip, done = self._shared_clip
+            else:
+                clip = self._sqsum(self._touched, s)  # one norm over all the runs of the step
+        for group, lo, hi, t in segs:
+            for a, b, scaled in self._pieces(lo, hi, done):
+                if clip is None or scaled:
+                    call("curla_adam_step", *self._adam_args(a, b, t, group), s)
+                else:
+                    call("curla_adam_step_clip", *self._adam_args(a, b, t, group), *clip, s)
+        return loss
 
     # -- two optimizers, one pass ------------------------------------------------------------------------------
     def _single_run(self):
@@ -190,14 +280,16 @@ class FlatAdam(torch.optim.Adam):
     def step_pair(first, second):
         """``first.step(); second.step()`` for two FlatAdams over the same flat buffer where first's parameters are the
         tail of second's (the encoder inside [CURL.W | encoder]): one launch that applies both steps per element in
-        that order.  Anything else (partial gradients, unequal step counts, other layouts) takes the two steps."""
+        that order.  Anything else (partial gradients, unequal step counts, other layouts) takes the two steps.
+        With ``max_grad_norm`` set (both must carry the same value) the gradient is clipped ONCE, by its norm over the
+        second optimizer's run, and both steps consume the clipped gradient -- in the two separate steps as well
+        (_two_steps)."""
         plain = isinstance(first, FlatAdam) and isinstance(second, FlatAdam) and first._flat is second._flat and \
             first._gflat is second._gflat and "step" not in vars(first) and "step" not in vars(second)  # (a step
         # replaced on the instance -- tests do that to look at gradients before they are consumed -- is respected)
         ra, rb = (first._single_run(), second._single_run()) if plain else (None, None)
-        if ra is None or rb is None or ra[1] != rb[1] or ra[0] < rb[0]:
-            first.step()
-            second.step()
+        if ra is None or rb is None or ra[1] != rb[1] or ra[0] < rb[0] or first.max_grad_norm != second.max_grad_norm:
+            FlatAdam._two_steps(first, second)
             return
         (a0, a1, ta, ga), (b0, b1, tb, gb) = ra, rb
         if first._dyn is None:
@@ -208,12 +300,42 @@ class FlatAdam(torch.optim.Adam):
         elif second._dyn != first._dyn + 8:
             raise RuntimeError("FlatAdam.step_pair: the second optimizer's captured factors must follow the first's")
         flat, gflat = first._flat, first._gflat
-        call("curla_adam_step2", flat.data_ptr() + 4 * b0, gflat.data_ptr() + 4 * b0,
-             first._m.data_ptr() + 4 * (a0 - first._lo), first._v.data_ptr() + 4 * (a0 - first._lo),
-             second._m.data_ptr() + 4 * (b0 - second._lo), second._v.data_ptr() + 4 * (b0 - second._lo), b1 - b0, a0 - b0,
-             float(ga["lr"]), float(ga["betas"][0]), float(ga["betas"][1]), float(ga["eps"]), ta + 1,
-             float(gb["lr"]), float(gb["betas"][0]), float(gb["betas"][1]), float(gb["eps"]), tb + 1, first._dyn, stream())
+        args = (flat.data_ptr() + 4 * b0, gflat.data_ptr() + 4 * b0,
+                first._m.data_ptr() + 4 * (a0 - first._lo), first._v.data_ptr() + 4 * (a0 - first._lo),
+                second._m.data_ptr() + 4 * (b0 - second._lo), second._v.data_ptr() + 4 * (b0 - second._lo), b1 - b0, a0 - b0,
+                float(ga["lr"]), float(ga["betas"][0]), float(ga["betas"][1]), float(ga["eps"]), ta + 1,
+                float(gb["lr"]), float(gb["betas"][0]), float(gb["betas"][1]), float(gb["eps"]), tb + 1, first._dyn)
+        if second.max_grad_norm is None:
+            call("curla_adam_step2", *args, stream())
+        else:
+            s = stream()
+            call("curla_adam_step2_clip", *args, *second._sqsum([(b0, b1)], s), s)
 
+    @staticmethod
+    def _two_steps(first, second):
+        """``first.step(); second.step()``.  When both are FlatAdams over one gradient buffer that clip to the same
+        ``max_grad_norm`` and every run first steps over lies inside a run of second's, the two steps are ONE clipped
+        step, as the fused launch is: one norm, over second's runs; first's step scales its runs by the coefficient
+        (and writes them back); second's step scales only what first has not -- its launches over first's runs are
+        the unclipped ones, so no element is scaled twice.  Otherwise each step clips (or not) on its own."""
+        shared = isinstance(first, FlatAdam) and isinstance(second, FlatAdam) and first._gflat is second._gflat and \
+            first.max_grad_norm is not None and first.max_grad_norm == second.max_grad_norm
+        if shared:
+            runs1 = [(lo, hi) for _, lo, hi, _ in first._segments(commit=False)]
+            runs2 = [(lo, hi) for _, lo, hi, _ in second._segments(commit=False)]
+            shared = bool(runs1) and all(any(c <= a and b <= d for c, d in runs2) for a, b in runs1)
+        if not shared:
+            first.step()
+            second.step()
+            return
+        clip = second._sqsum(runs2, stream())
+        try:
+            first._shared_clip = (clip, ())
+            first.step()
+            second._shared_clip = (clip, first._touched)
+            second.step()
+        finally:
+            first._shared_clip = second._shared_clip = None
 
     # -- this optimizer's step and the target copy's soft update, one launch ---------------------------------------
     @staticmethod
@@ -235,11 +357,13 @@ class FlatAdam(torch.optim.Adam):
             for i in range(len(opt._plist)):
                 opt._ensure_state(i)
                 opt._steps[i] = t + 1
-        call("curla_adam_step_lerp", opt._flat.data_ptr() + 4 * lo, opt._gflat.data_ptr() + 4 * lo,
-             opt._m.data_ptr() + 4 * (lo - opt._lo), opt._v.data_ptr() + 4 * (lo - opt._lo), hi - lo, float(g["lr"]),
-             float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), t + 1, opt._dyn, target_flat.data_ptr() + 4 * lo,
-             split,
-             float(tau_a), float(1.0 - tau_a), float(tau_b), float(1.0 - tau_b), stream())
+        args = opt._adam_args(lo, hi, t, g) + (target_flat.data_ptr() + 4 * lo, split, float(tau_a), float(1.0 - tau_a),
+                                               float(tau_b), float(1.0 - tau_b))
+        s = stream()
+        if opt.max_grad_norm is None:
+            call("curla_adam_step_lerp", *args, s)
+        else:
+            call("curla_adam_step_lerp_clip", *args, *opt._sqsum([(lo, hi)], s), s)
         return True
 
     # -- this optimizer and a float64 scalar's, one launch -----------------------------------------------------------
@@ -275,14 +399,16 @@ class FlatAdam(torch.optim.Adam):
             for i in range(len(first._plist)):
                 first._ensure_state(i)
                 first._steps[i] = t + 1
-        call("curla_adam_step_scalar64", first._flat.data_ptr() + 4 * lo, first._gflat.data_ptr() + 4 * lo,
-             first._m.data_ptr() + 4 * (lo - first._lo), first._v.data_ptr() + 4 * (lo - first._lo), hi - lo,
-             float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), t + 1, first._dyn,
-             p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), float(g["lr"]),
-             float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), t64, getattr(scalar_opt, "_curla_dyn64", None),
-             stream())
+        args = first._adam_args(lo, hi, t, grp) + (
+            p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), float(g["lr"]),
+            float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), t64, getattr(scalar_opt, "_curla_dyn64", None))
+        s = stream()
+        if first.max_grad_norm is None:
+            call("curla_adam_step_scalar64", *args, s)
+        else:  # (the norm is the flat run's: the scalar is not clipped)
+            call("curla_adam_step_scalar64_clip", *args, *first._sqsum([(lo, hi)], s), s)
         if not frozen:
             st["step"] = torch.tensor(float(t64), dtype=torch.float32)
 
 
-__all__ = ["FlatAdam"]
+__all__ = ["FlatAdam", "check_max_grad_norm"]

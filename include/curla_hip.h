@@ -453,6 +453,42 @@ int curla_adam_step2(float* param, const float* grad, float* exp_avg1, float* ex
                      float* exp_avg_sq2, size_t n, size_t n_pre, double lr1, double beta1_1, double beta2_1, double eps1,
                      long long step1, double lr2, double beta1_2, double beta2_2, double eps2, long long step2,
                      const float* dyn, void* stream);
+/* Clipping by the global gradient norm inside the Adam launches: torch.nn.utils.clip_grad_norm_(params, max_norm,
+ * norm_type=2.0, error_if_nonfinite=False) right in front of the optimizer's step, without a host read.
+ * curla_grad_sqsum writes n_partials (1 .. CURLA_CLIP_MAX_PARTIALS) float64 partial sums of squares of one flat gradient
+ * run, one per workgroup: partials[b] = sum of grad[i]^2 over workgroup b's grid-stride share, accumulated in double in a
+ * fixed order (no atomics: the partials are a function of the gradient's bytes, n, n_partials and whether `grad` is
+ * 16-byte aligned).  A step over several runs calls it once per run, with disjoint slots of ONE partials buffer.
+ * The four curla_adam_step*_clip entry points are their namesakes with four more arguments in front of `stream`: the
+ * partials of ALL the runs of the step and their total count, max_norm (> 0; inf allowed) and a two-float stats slot.
+ * Every workgroup sums the partials in the same fixed order, in double: norm = sqrt(sum), coef = min(1, max_norm /
+ * (norm + 1e-6)) rounded to float once.  coef != 1: grad[i] <- coef * grad[i] (one rounding; written back, so the
+ * gradient buffer afterwards holds what Adam consumed, as with torch) and the step runs on the result -- in
+ * curla_adam_step2_clip both steps; coef == 1: nothing is written to `grad` and the step is the unclipped one, bit for
+ * bit.  A non-finite norm propagates as in torch.  stats[0] = (float)norm (before clipping), stats[1] = coef.
+ * CURLA_ERR_ARG before any launch on: a NULL pointer (dyn / dyn64 may be NULL), a float pointer off 4 bytes, a double
+ * pointer off 8, n == 0, n_partials outside 1 .. CURLA_CLIP_MAX_PARTIALS, max_norm <= 0 or NaN, and whatever the
+ * unclipped namesake refuses.  Additive: CURLA_ABI_VERSION stays 8. */
+#define CURLA_CLIP_MAX_PARTIALS 256
+int curla_grad_sqsum(const float* grad, size_t n, double* partials, int n_partials, void* stream);
+int curla_adam_step_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                         double beta2, double eps, long long step, const float* dyn, const double* partials,
+                         int n_partials, double max_norm, float* stats, void* stream);
+int curla_adam_step_lerp_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                              double beta1, double beta2, double eps, long long step, const float* dyn, float* target,
+                              size_t split, float tau_a, float one_minus_tau_a, float tau_b, float one_minus_tau_b,
+                              const double* partials, int n_partials, double max_norm, float* stats, void* stream);
+int curla_adam_step_scalar64_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                                  double beta1, double beta2, double eps, long long step, const float* dyn,
+                                  double* param64, const double* grad64, double* exp_avg64, double* exp_avg_sq64,
+                                  double lr64, double beta1_64, double beta2_64, double eps64, long long step64,
+                                  const double* dyn64, const double* partials, int n_partials, double max_norm,
+                                  float* stats, void* stream);
+int curla_adam_step2_clip(float* param, float* grad, float* exp_avg1, float* exp_avg_sq1, float* exp_avg2,
+                          float* exp_avg_sq2, size_t n, size_t n_pre, double lr1, double beta1_1, double beta2_1,
+                          double eps1, long long step1, double lr2, double beta1_2, double beta2_2, double eps2,
+                          long long step2, const float* dyn, const double* partials, int n_partials, double max_norm,
+                          float* stats, void* stream);
 
 /* ---- augmentations that produce float observations (augmentations.py:78-205; kornia arithmetic is not
  * vendored by the reference: PARITY UNPINNED, the algorithm is this build's statement of kornia's documented
