@@ -432,7 +432,7 @@ int curla_concat(const float* z, const float* act, int B, int F, int A, float* x
 
 int curla_split_sum(const float* dxa, long long twin_stride, int B, int F, int A, float* dz, float* dact,
                     void* stream) {
-  CURLA_REQUIRE(dxa && B > 0 && F > 0 && A > 0 && (dz || dact));
+  CURLA_REQUIRE(dxa && B > 0 && F > 0 && A > 0 && (dz || dact) && twin_stride >= (long long)B * (F + A));
   return launch(split_sum_kernel, dim3((B * (F + A) + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), dxa,
                 twin_stride, B, F, A, dz, dact);
 }
@@ -440,14 +440,14 @@ int curla_split_sum(const float* dxa, long long twin_stride, int B, int F, int A
 int curla_td_target(const float* tq, long long twin_stride, const float* log_pi, const float* reward,
                     const float* not_done, const double* log_alpha, float discount, int B, float* target_q,
                     void* stream) {
-  CURLA_REQUIRE(tq && log_pi && reward && not_done && log_alpha && target_q && B > 0);
+  CURLA_REQUIRE(tq && log_pi && reward && not_done && log_alpha && target_q && B > 0 && twin_stride >= B);
   return launch(td_target_kernel, dim3((B + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), tq, twin_stride, log_pi,
                 reward, not_done, log_alpha, discount, B, target_q);
 }
 
 int curla_critic_loss(const float* q, long long twin_stride, const float* target_q, int B, float* loss, float* dq,
                       void* stream) {
-  CURLA_REQUIRE(q && target_q && loss && dq && B > 0);
+  CURLA_REQUIRE(q && target_q && loss && dq && B > 0 && twin_stride >= B);
   return launch(critic_loss_kernel, dim3(1), 256, 0, static_cast<hipStream_t>(stream), q, twin_stride, target_q, B, loss,
                 dq);
 }
@@ -455,7 +455,8 @@ int curla_critic_loss(const float* q, long long twin_stride, const float* target
 int curla_critic_td_loss(const float* q, const float* tq, long long twin_stride, const float* log_pi,
                          const float* reward, const float* not_done, const double* log_alpha, float discount, int B,
                          float* target_q, float* loss, float* dq, void* stream) {
-  CURLA_REQUIRE(q && tq && log_pi && reward && not_done && log_alpha && target_q && loss && dq && B > 0);
+  CURLA_REQUIRE(q && tq && log_pi && reward && not_done && log_alpha && target_q && loss && dq && B > 0 &&
+                twin_stride >= B);
   return launch(critic_td_loss_kernel, dim3(1), 256, 0, static_cast<hipStream_t>(stream), q, tq, twin_stride, log_pi,
                 reward, not_done, log_alpha, discount, B, target_q, loss, dq);
 }
@@ -463,7 +464,7 @@ int curla_critic_td_loss(const float* q, const float* tq, long long twin_stride,
 int curla_actor_loss(const float* q, long long twin_stride, const float* log_pi, const float* log_std, int A,
                      const double* log_alpha, float target_entropy, int B, float* scalars4, float* dq,
                      double* dlog_alpha, void* stream) {
-  CURLA_REQUIRE(q && log_pi && log_std && log_alpha && scalars4 && dq && B > 0 && A > 0);
+  CURLA_REQUIRE(q && log_pi && log_std && log_alpha && scalars4 && dq && B > 0 && A > 0 && twin_stride >= B);
   return launch(actor_loss_kernel, dim3(1), 256, 0, static_cast<hipStream_t>(stream), q, twin_stride, log_pi, log_std, A,
                 log_alpha, target_entropy, B, scalars4, dq, dlog_alpha);
 }

@@ -16,6 +16,8 @@
  *   dense weights      float32 [out][in] row-major (nn.Linear layout); the encoder
  *                      fc weight has its input columns in (y,x,c) order
  *   twin-Q tensors     two equally shaped blocks separated by a `twin_stride`
+ *                      (floats; at least one block's length, else CURLA_ERR_ARG
+ *                      before any launch)
  */
 #ifndef CURLA_HIP_H
 #define CURLA_HIP_H
