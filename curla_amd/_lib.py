@@ -93,6 +93,12 @@ SIGNATURES = {
     "curla_pos_walk": [vp, c_ll, c_ll, c_ll, vp, c_ll, c_int, c_int, c_int, vp],
     "curla_sample_stage_pos": [vp, vp, c_ll, c_ll, c_ll, c_ll, vp, vp, c_ll, c_int, c_float, c_int, c_int, c_int, vp, vp, vp,
                                vp],
+    "curla_nstep_compose_strided": [vp, c_ll, vp, vp, c_ll, c_ll, c_int, c_float, c_int, c_int, vp, vp, vp, vp],
+    "curla_sample_stage_nstep_strided": [vp, vp, c_ll, c_ll, vp, vp, c_ll, c_ll, c_int, c_float, c_int, c_int, vp, vp, vp,
+                                         vp],
+    "curla_pos_walk_strided": [vp, c_ll, c_ll, c_ll, vp, c_ll, c_ll, c_int, c_int, c_int, vp],
+    "curla_sample_stage_pos_strided": [vp, vp, c_ll, c_ll, c_ll, c_ll, vp, vp, c_ll, c_ll, c_int, c_float, c_int, c_int,
+                                       c_int, vp, vp, vp, vp],
     "curla_per_set": [vp, vp, vp, c_ll, vp, c_ll, vp, c_int, vp],
     "curla_per_sample": [vp, vp, c_ll, vp, c_ll, c_ll, c_int, vp],
     "curla_per_td": [vp, c_ll, vp, vp, c_float, c_float, c_float, c_int, vp, vp, vp, vp, vp],
@@ -121,6 +127,7 @@ SIGNATURES = {
     "curla_crop_nchw": [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp],
     "curla_store_frame": [vp, vp, c_ll, c_int, c_int, c_int, vp],
     "curla_stage_frames_u8": [vp, vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp],
+    "curla_add_vec": [vp, vp, vp, vp, vp, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, vp],
     "curla_gather_stacks": [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_nhwc_to_nchw": [vp, vp, c_int, c_int, c_int, c_int, vp],
     "curla_color_jiggle": [vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp],

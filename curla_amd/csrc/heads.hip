@@ -26,6 +26,7 @@ namespace {
 #include "ring.h"          // crop_nchw_kernel, store_frame_kernel, gather_stacks_kernel<FAST>, nhwc_to_nchw_kernel
 #include "per.h"           // prioritized replay: per_set's three phases, per_sample_kernel, per_td_kernel
 #include "stage.h"         // stage_frames_kernel<C>: N planar frames into N ring slots, crop fused (batched acting)
+#include "add_vec.h"       // add_vec_kernel<C>: a vector step of N environments into the ring (ReplayBuffer.add_vec)
 
 // ------------------------------ host side ------------------------------
 // Every launch of this file: launch, report the launch status.  A kernel's dynamic-LDS limit is NOT touched here: the
@@ -199,6 +200,11 @@ int sample_stage_launch(void (*kernel)(SampleStageArgs), const SampleStageArgs& 
 
 // A block offset in bytes as the kernels take it, in words (-1, the block has no such region, stays)
 inline int block_word(long long offset) { return offset == -1 ? -1 : (int)(offset / 8); }
+
+// A chain walk's step (the _strided entry points): at least 1, and the lanes tile the ring
+inline bool stride_ok(long long capacity, long long stride) {
+  return stride >= 1 && capacity >= 1 && capacity % stride == 0;
+}
 
 // The arguments every instantiation takes; a block that is on the device already (host_block NULL) has no pinned words
 // to copy.  The entry points with a walk add theirs.
@@ -682,53 +688,83 @@ int curla_sample_stage(const void* host_block, void* device_block, long long nby
       sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done), stream);
 }
 
-int curla_nstep_compose(void* device_block, long long next_row_offset, const float* scalars, const uint8_t* cont,
-                        long long capacity, int n, float discount, int B, int A, float* action, float* reward,
-                        float* not_done, void* stream) {
+int curla_nstep_compose_strided(void* device_block, long long next_row_offset, const float* scalars, const uint8_t* cont,
+                                long long capacity, long long stride, int n, float discount, int B, int A, float* action,
+                                float* reward, float* not_done, void* stream) {
   CURLA_REQUIRE(device_block && scalars && cont && action && reward && not_done && B > 0 && A > 0);
-  CURLA_REQUIRE(n >= 1 && capacity >= 1 && next_row_offset != -1);
+  CURLA_REQUIRE(n >= 1 && stride_ok(capacity, stride) && next_row_offset != -1);
   // this entry point holds the START of next_row below 1 GiB, the others the end of every region
   CURLA_REQUIRE(sample_block_ok(nullptr, device_block, (1LL << 30) - 8 + 8LL * B, B, next_row_offset, -1, -1));
   SampleStageArgs a = sample_stage_args(nullptr, device_block, 0, scalars, B, A, action, reward, not_done);
-  a.nr_word = block_word(next_row_offset), a.cont = cont, a.capacity = capacity, a.n = n, a.gamma = discount;
+  a.nr_word = block_word(next_row_offset), a.cont = cont, a.capacity = capacity, a.stride = stride, a.n = n;
+  a.gamma = discount;
   return sample_stage_launch(sample_stage_kernel<false, true, false>, a, stream);
+}
+
+int curla_nstep_compose(void* device_block, long long next_row_offset, const float* scalars, const uint8_t* cont,
+                        long long capacity, int n, float discount, int B, int A, float* action, float* reward,
+                        float* not_done, void* stream) {
+  return curla_nstep_compose_strided(device_block, next_row_offset, scalars, cont, capacity, 1, n, discount, B, A, action,
+                                     reward, not_done, stream);
+}
+
+int curla_sample_stage_nstep_strided(const void* host_block, void* device_block, long long nbytes,
+                                     long long next_row_offset, const float* scalars, const uint8_t* cont,
+                                     long long capacity, long long stride, int n, float discount, int B, int A,
+                                     float* action, float* reward, float* not_done, void* stream) {
+  CURLA_REQUIRE(host_block && device_block && scalars && cont && action && reward && not_done && B > 0 && A > 0);
+  CURLA_REQUIRE(n >= 1 && stride_ok(capacity, stride) && next_row_offset != -1);
+  CURLA_REQUIRE(sample_block_ok(host_block, device_block, nbytes, B, next_row_offset, -1, -1));
+  SampleStageArgs a = sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done);
+  a.nr_word = block_word(next_row_offset), a.cont = cont, a.capacity = capacity, a.stride = stride, a.n = n;
+  a.gamma = discount;
+  return sample_stage_launch(sample_stage_kernel<true, true, false>, a, stream);
 }
 
 int curla_sample_stage_nstep(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
                              const float* scalars, const uint8_t* cont, long long capacity, int n, float discount, int B,
                              int A, float* action, float* reward, float* not_done, void* stream) {
-  CURLA_REQUIRE(host_block && device_block && scalars && cont && action && reward && not_done && B > 0 && A > 0);
-  CURLA_REQUIRE(n >= 1 && capacity >= 1 && next_row_offset != -1);
-  CURLA_REQUIRE(sample_block_ok(host_block, device_block, nbytes, B, next_row_offset, -1, -1));
-  SampleStageArgs a = sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done);
-  a.nr_word = block_word(next_row_offset), a.cont = cont, a.capacity = capacity, a.n = n, a.gamma = discount;
-  return sample_stage_launch(sample_stage_kernel<true, true, false>, a, stream);
+  return curla_sample_stage_nstep_strided(host_block, device_block, nbytes, next_row_offset, scalars, cont, capacity, 1, n,
+                                          discount, B, A, action, reward, not_done, stream);
 }
 
-int curla_pos_walk(void* device_block, long long pos_offset, long long run_offset, long long next_row_offset,
-                   const uint8_t* cont, long long capacity, int k, int n, int B, void* stream) {
-  CURLA_REQUIRE(device_block && B > 0 && k >= 1 && n >= 1 && capacity >= 1 && pos_offset != -1);
+int curla_pos_walk_strided(void* device_block, long long pos_offset, long long run_offset, long long next_row_offset,
+                           const uint8_t* cont, long long capacity, long long stride, int k, int n, int B, void* stream) {
+  CURLA_REQUIRE(device_block && B > 0 && k >= 1 && n >= 1 && stride_ok(capacity, stride) && pos_offset != -1);
   CURLA_REQUIRE(cont || (k == 1 && (n == 1 || run_offset == -1)));
   CURLA_REQUIRE(sample_block_ok(nullptr, device_block, 1LL << 30, B, next_row_offset, pos_offset, run_offset));
   return launch(pos_walk_kernel, dim3((B + 255) / 256), 256, 0, static_cast<hipStream_t>(stream),
                 static_cast<unsigned long long*>(device_block), block_word(pos_offset), block_word(run_offset), cont,
-                capacity, k, n, B);
+                capacity, stride, k, n, B);
+}
+
+int curla_pos_walk(void* device_block, long long pos_offset, long long run_offset, long long next_row_offset,
+                   const uint8_t* cont, long long capacity, int k, int n, int B, void* stream) {
+  return curla_pos_walk_strided(device_block, pos_offset, run_offset, next_row_offset, cont, capacity, 1, k, n, B, stream);
+}
+
+int curla_sample_stage_pos_strided(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
+                                   long long pos_offset, long long run_offset, const float* scalars, const uint8_t* cont,
+                                   long long capacity, long long stride, int n, float discount, int k, int B, int A,
+                                   float* action, float* reward, float* not_done, void* stream) {
+  CURLA_REQUIRE(host_block && device_block && scalars && action && reward && not_done && B > 0 && A > 0);
+  CURLA_REQUIRE(k >= 1 && n >= 1 && stride_ok(capacity, stride) && pos_offset != -1);
+  CURLA_REQUIRE(next_row_offset != -1 || n == 1);  // without a next_row region there is no composition
+  CURLA_REQUIRE(cont || (k == 1 && n == 1));
+  CURLA_REQUIRE(sample_block_ok(host_block, device_block, nbytes, B, next_row_offset, pos_offset, run_offset));
+  SampleStageArgs a = sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done);
+  a.nr_word = block_word(next_row_offset), a.pos_word = block_word(pos_offset), a.run_word = block_word(run_offset);
+  a.cont = cont, a.capacity = capacity, a.stride = stride, a.n = n, a.gamma = discount, a.k = k;
+  return sample_stage_launch(
+      next_row_offset == -1 ? sample_stage_kernel<true, false, true> : sample_stage_kernel<true, true, true>, a, stream);
 }
 
 int curla_sample_stage_pos(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
                            long long pos_offset, long long run_offset, const float* scalars, const uint8_t* cont,
                            long long capacity, int n, float discount, int k, int B, int A, float* action, float* reward,
                            float* not_done, void* stream) {
-  CURLA_REQUIRE(host_block && device_block && scalars && action && reward && not_done && B > 0 && A > 0);
-  CURLA_REQUIRE(k >= 1 && n >= 1 && capacity >= 1 && pos_offset != -1);
-  CURLA_REQUIRE(next_row_offset != -1 || n == 1);  // without a next_row region there is no composition
-  CURLA_REQUIRE(cont || (k == 1 && n == 1));
-  CURLA_REQUIRE(sample_block_ok(host_block, device_block, nbytes, B, next_row_offset, pos_offset, run_offset));
-  SampleStageArgs a = sample_stage_args(host_block, device_block, nbytes, scalars, B, A, action, reward, not_done);
-  a.nr_word = block_word(next_row_offset), a.pos_word = block_word(pos_offset), a.run_word = block_word(run_offset);
-  a.cont = cont, a.capacity = capacity, a.n = n, a.gamma = discount, a.k = k;
-  return sample_stage_launch(
-      next_row_offset == -1 ? sample_stage_kernel<true, false, true> : sample_stage_kernel<true, true, true>, a, stream);
+  return curla_sample_stage_pos_strided(host_block, device_block, nbytes, next_row_offset, pos_offset, run_offset, scalars,
+                                        cont, capacity, 1, n, discount, k, B, A, action, reward, not_done, stream);
 }
 
 int curla_per_set(float* s, double* sums, float* vmax, long long capacity, const int64_t* rows, long long first_row,
@@ -796,6 +832,32 @@ int curla_stage_frames_u8(const uint8_t* nchw, uint8_t* frames, long long first_
   // other channel counts, pointers off a dword boundary: the same bytes one by one
   return launch(stage_frames_bytes_kernel, dim3(nblocks(npix * C, 256, 8192)), 256, 0, st, nchw, out, npix * C, C, Hs, Ws,
                 top, left, Hd, Wd);
+}
+
+int curla_add_vec(const uint8_t* block, uint8_t* obs_ring, uint8_t* next_ring, float* scalars, uint8_t* cont,
+                  long long capacity, long long first, int has_prev, int N, int C, int H, int W, int A, void* stream) {
+  CURLA_REQUIRE(block && obs_ring && next_ring && scalars && N >= 1 && C >= 1 && H > 0 && W > 0 && A > 0);
+  CURLA_REQUIRE(capacity >= 1 && capacity % N == 0 && first >= 0 && first % N == 0 && first + N <= capacity);
+  CURLA_REQUIRE(!has_prev || (cont && capacity > N));  // (capacity == N: the previous run IS the new one)
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(block) | reinterpret_cast<uintptr_t>(scalars)) & 3) == 0);
+  const size_t HW = (size_t)H * W;
+  CURLA_REQUIRE(2 * (size_t)N * HW < (1ull << 31));  // (the groups number the staged pixels in 32 bits)
+  AddVecArgs a = {};
+  a.block = block, a.obs = obs_ring, a.next = next_ring, a.sc = scalars, a.cont = cont, a.first = first;
+  a.prev = !has_prev ? -1 : first >= N ? first - N : capacity - N;
+  a.N = N, a.C = C, a.H = H, a.W = W, a.A = A;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t tail = (size_t)N * (A + 2) + 2 * (size_t)N;
+  // whole 4-pixel groups per frame and dword-aligned rows on both rings: the transpose in registers
+  const bool words = HW % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(obs_ring) | reinterpret_cast<uintptr_t>(next_ring)) & 3) == 0;
+  const dim3 grid(nblocks((words ? 2 * N * HW / 4 : 2 * N * HW * C) + tail, 256, 8192));
+  if (words && C == 3) return launch(add_vec_kernel<3>, grid, 256, 0, st, a);
+  if (words && C == 6) return launch(add_vec_kernel<6>, grid, 256, 0, st, a);
+  if (words && C == 9) return launch(add_vec_kernel<9>, grid, 256, 0, st, a);
+  if (words && C == 12) return launch(add_vec_kernel<12>, grid, 256, 0, st, a);
+  // other channel counts, frames that are no whole number of groups, rings off a dword boundary: byte by byte
+  return launch(add_vec_kernel<ADD_VEC_BYTES>, grid, 256, 0, st, a);
 }
 
 int curla_gather_stacks(const uint8_t* store, const int32_t* fid, int fid_stride, const int64_t* idx, int B, int K,

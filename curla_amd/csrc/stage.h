@@ -36,75 +36,86 @@ __device__ __forceinline__ uint32_t stage_load_u8x4(const uint8_t* base, size_t 
   return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * s));
 }
 
+// One group: the np (1..4) output pixels p0 .. p0 + np - 1 of the straight-through numbering, read from the planar frames
+// and written as np * C bytes at `o8` (np == 4: C dwords, `o8` on a dword).  Shared by stage_frames_kernel and
+// add_vec_kernel (add_vec.h), which differ only in where a group's bytes go.
+template <int C>
+__device__ __forceinline__ void stage_group(const uint8_t* nchw, size_t src_bytes, uint8_t* o8, uint32_t p0, int np, int Hs,
+                                            int Ws, int top, int left, int Hd, int Wd) {
+  const uint32_t HWd = (uint32_t)Hd * Wd;
+  const size_t plane = (size_t)Hs * Ws;
+  const uint32_t n = p0 / HWd, r = p0 - n * HWd;
+  const uint32_t y = r / Wd, x = r - y * Wd;
+  uint32_t ob[C];
+#pragma unroll
+  for (int w = 0; w < C; ++w) ob[w] = 0;
+  if (np == 4 && x + 4 <= (uint32_t)Wd) {  // the 4 pixels sit side by side in one source row
+    const size_t o = (size_t)n * C * plane + (size_t)(top + y) * Ws + left + x;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const uint32_t s = stage_load_u8x4(nchw, o + c * plane, src_bytes);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int db = p * C + c;  // byte of the 4 * C output bytes
+        ob[db >> 2] |= ((s >> (8 * p)) & 0xffu) << (8 * (db & 3));
+      }
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      if (p < np) {
+        const uint32_t q = p0 + p;
+        const uint32_t qn = q / HWd, qr = q - qn * HWd;
+        const uint32_t qy = qr / Wd, qx = qr - qy * Wd;
+        const size_t o = (size_t)qn * C * plane + (size_t)(top + qy) * Ws + left + qx;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const int db = p * C + c;
+          ob[db >> 2] |= (uint32_t)nchw[o + c * plane] << (8 * (db & 3));
+        }
+      }
+    }
+  }
+  if (np == 4) {
+    uint32_t* o4 = reinterpret_cast<uint32_t*>(o8);
+#pragma unroll
+    for (int w = 0; w < C; ++w) o4[w] = ob[w];  // 4 pixels x C bytes = C dwords
+  } else {
+#pragma unroll
+    for (int b = 0; b < 3 * C; ++b)
+      if (b < np * C) o8[b] = (uint8_t)(ob[b >> 2] >> (8 * (b & 3)));
+  }
+}
+
 template <int C>
 __global__ void stage_frames_kernel(const uint8_t* nchw, size_t src_bytes, uint8_t* out, uint32_t npix, int Hs, int Ws,
                                     int top, int left, int Hd, int Wd) {
   const uint32_t groups = (npix + 3) >> 2;
-  const uint32_t HWd = (uint32_t)Hd * Wd;
-  const size_t plane = (size_t)Hs * Ws;
   uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t stride = gridDim.x * blockDim.x;
   for (; g < groups; g += stride) {
     const uint32_t p0 = 4 * g;
-    const uint32_t n = p0 / HWd, r = p0 - n * HWd;
-    const uint32_t y = r / Wd, x = r - y * Wd;
-    const int np = (int)min(4u, npix - p0);
-    uint32_t ob[C];
-#pragma unroll
-    for (int w = 0; w < C; ++w) ob[w] = 0;
-    if (np == 4 && x + 4 <= (uint32_t)Wd) {  // the 4 pixels sit side by side in one source row
-      const size_t o = (size_t)n * C * plane + (size_t)(top + y) * Ws + left + x;
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const uint32_t s = stage_load_u8x4(nchw, o + c * plane, src_bytes);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int db = p * C + c;  // byte of the 4 * C output bytes
-          ob[db >> 2] |= ((s >> (8 * p)) & 0xffu) << (8 * (db & 3));
-        }
-      }
-    } else {
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        if (p < np) {
-          const uint32_t q = p0 + p;
-          const uint32_t qn = q / HWd, qr = q - qn * HWd;
-          const uint32_t qy = qr / Wd, qx = qr - qy * Wd;
-          const size_t o = (size_t)qn * C * plane + (size_t)(top + qy) * Ws + left + qx;
-#pragma unroll
-          for (int c = 0; c < C; ++c) {
-            const int db = p * C + c;
-            ob[db >> 2] |= (uint32_t)nchw[o + c * plane] << (8 * (db & 3));
-          }
-        }
-      }
-    }
-    uint8_t* o8 = out + (size_t)p0 * C;
-    if (np == 4) {
-      uint32_t* o4 = reinterpret_cast<uint32_t*>(o8);
-#pragma unroll
-      for (int w = 0; w < C; ++w) o4[w] = ob[w];  // 4 pixels x C bytes = C dwords
-    } else {
-#pragma unroll
-      for (int b = 0; b < 3 * C; ++b)
-        if (b < np * C) o8[b] = (uint8_t)(ob[b >> 2] >> (8 * (b & 3)));
-    }
+    stage_group<C>(nchw, src_bytes, out + (size_t)p0 * C, p0, (int)min(4u, npix - p0), Hs, Ws, top, left, Hd, Wd);
   }
+}
+
+// Output byte i of the straight-through NHWC numbering, from the planar frames: the byte-wise form of stage_group.
+__device__ __forceinline__ uint8_t stage_byte(const uint8_t* nchw, size_t i, int C, int Hs, int Ws, int top, int left,
+                                              int Hd, int Wd) {
+  const size_t plane = (size_t)Hs * Ws;
+  const int c = i % C;
+  size_t t = i / C;
+  const int x = t % Wd;
+  t /= Wd;
+  const int y = t % Hd;
+  const size_t n = t / Hd;
+  return nchw[(n * C + c) * plane + (size_t)(top + y) * Ws + left + x];
 }
 
 // the same bytes one at a time: any channel count, any pointer alignment
 __global__ void stage_frames_bytes_kernel(const uint8_t* nchw, uint8_t* out, size_t nout, int C, int Hs, int Ws, int top,
                                           int left, int Hd, int Wd) {
-  const size_t plane = (size_t)Hs * Ws;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < nout; i += stride) {
-    const int c = i % C;
-    size_t t = i / C;
-    const int x = t % Wd;
-    t /= Wd;
-    const int y = t % Hd;
-    const size_t n = t / Hd;
-    out[i] = nchw[(n * C + c) * plane + (size_t)(top + y) * Ws + left + x];
-  }
+  for (; i < nout; i += stride) out[i] = stage_byte(nchw, i, C, Hs, Ws, top, left, Hd, Wd);
 }

@@ -1511,10 +1511,11 @@ class CurlSacAgent(object):
                 hyper, self._graph_rb_key(), self._max_grad_norm)
 
     def _graph_rb_key(self):
-        """(n_step, discount, pos_offset) of the graphs' replay buffer: its staging launch holds them by value."""
+        """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value
+        (n_envs as the stride of the chain walks)."""
         rb = getattr(self, "_graph_rb", None)
         n = getattr(rb, "n_step", 1)
-        return ((n, float(rb.discount)) if n > 1 else (1, None)) + (getattr(rb, "pos_offset", 0),)
+        return ((n, float(rb.discount)) if n > 1 else (1, None)) + (getattr(rb, "pos_offset", 0), getattr(rb, "n_envs", 1))
 
     def _graph_tail(self, kind, B):
         """The 80 control bytes of one graphed update (ReplayBuffer.GRAPH_TAIL) -- and the host-side bookkeeping of

@@ -658,17 +658,26 @@ def sample_stage(host_dev_ptr, dev_block, nbytes, sc, B, A, act, rew, nd):
     call("curla_sample_stage", host_dev_ptr, ptr(dev_block), nbytes, ptr(sc), B, A, ptr(act), ptr(rew), ptr(nd), stream())
 
 
-def nstep_compose(dev_block, next_row_off, sc, cont, capacity, n, discount, B, A, act, rew, nd):
+def _strided(name, stride):
+    """The entry point ``name`` and the arguments behind ``capacity``: the namesake itself for stride 1 (the
+    single-environment ring), its ``_strided`` form with the stride otherwise (ReplayBuffer(n_envs > 1))."""
+    return (name, ()) if stride == 1 else (name + "_strided", (int(stride),))
+
+
+def nstep_compose(dev_block, next_row_off, sc, cont, capacity, n, discount, B, A, act, rew, nd, stride=1):
     """n-step reward / not_done / bootstrap rows of a minibatch whose index block is already on the device
-    (curla_hip.h: curla_nstep_compose)."""
-    call("curla_nstep_compose", ptr(dev_block), int(next_row_off), ptr(sc), ptr(cont), int(capacity), int(n),
+    (curla_hip.h: curla_nstep_compose; ``stride``: rows between two steps of one environment)."""
+    name, st = _strided("curla_nstep_compose", stride)
+    call(name, ptr(dev_block), int(next_row_off), ptr(sc), ptr(cont), int(capacity), *st, int(n),
          float(discount), B, A, ptr(act), ptr(rew), ptr(nd), stream())
 
 
-def sample_stage_nstep(host_dev_ptr, dev_block, nbytes, next_row_off, sc, cont, capacity, n, discount, B, A, act, rew, nd):
+def sample_stage_nstep(host_dev_ptr, dev_block, nbytes, next_row_off, sc, cont, capacity, n, discount, B, A, act, rew, nd,
+                       stride=1):
     """sample_stage with the n-step composition in the same launch."""
-    call("curla_sample_stage_nstep", host_dev_ptr, ptr(dev_block), nbytes, int(next_row_off), ptr(sc), ptr(cont),
-         int(capacity), int(n), float(discount), B, A, ptr(act), ptr(rew), ptr(nd), stream())
+    name, st = _strided("curla_sample_stage_nstep", stride)
+    call(name, host_dev_ptr, ptr(dev_block), nbytes, int(next_row_off), ptr(sc), ptr(cont),
+         int(capacity), *st, int(n), float(discount), B, A, ptr(act), ptr(rew), ptr(nd), stream())
 
 
 def _off(o):
@@ -676,19 +685,22 @@ def _off(o):
     return -1 if o is None else int(o)
 
 
-def pos_walk(dev_block, pos_off, run_off, next_row_off, cont, capacity, k, n, B):
+def pos_walk(dev_block, pos_off, run_off, next_row_off, cont, capacity, k, n, B, stride=1):
     """The temporal positive's rows of a minibatch whose index block is already on the device (curla_hip.h:
     curla_pos_walk): r and capacity + r at ``pos_off``, the 3B run of a scratch augmentation at ``run_off`` (None: no
     run); ``next_row_off`` (None: the block has none) is only checked against."""
-    call("curla_pos_walk", ptr(dev_block), int(pos_off), _off(run_off), _off(next_row_off), ptr(cont), int(capacity),
+    name, st = _strided("curla_pos_walk", stride)
+    call(name, ptr(dev_block), int(pos_off), _off(run_off), _off(next_row_off), ptr(cont), int(capacity), *st,
          int(k), int(n), B, stream())
 
 
 def sample_stage_pos(host_dev_ptr, dev_block, nbytes, next_row_off, pos_off, run_off, sc, cont, capacity, n, discount, k,
-                     B, A, act, rew, nd):
+                     B, A, act, rew, nd, stride=1):
     """sample_stage (``next_row_off`` None) or sample_stage_nstep with the temporal positive's walk in the same launch."""
-    call("curla_sample_stage_pos", host_dev_ptr, ptr(dev_block), nbytes, _off(next_row_off), int(pos_off), _off(run_off),
-         ptr(sc), ptr(cont), int(capacity), int(n), float(discount), int(k), B, A, ptr(act), ptr(rew), ptr(nd), stream())
+    name, st = _strided("curla_sample_stage_pos", stride)
+    call(name, host_dev_ptr, ptr(dev_block), nbytes, _off(next_row_off), int(pos_off), _off(run_off),
+         ptr(sc), ptr(cont), int(capacity), *st, int(n), float(discount), int(k), B, A, ptr(act), ptr(rew), ptr(nd),
+         stream())
 
 
 # ---- prioritized replay (curla_hip.h: curla_per_set / curla_per_sample / curla_per_td) ----
@@ -758,6 +770,23 @@ def stage_frames(nchw_u8, frames, first_slot=0, top=0, left=0):
                                  f"{slots} slots of {Cf} channels")
     call("curla_stage_frames_u8", ptr(nchw_u8), ptr(frames), int(first_slot), N, C, Hs, Ws, int(top), int(left), Hd, Wd,
          stream())
+
+
+def add_vec(block, obs_ring, next_ring, sc, cont, first, has_prev, N):
+    """One vector step of N environments from the staged add block into ring rows first .. first + N - 1 in one launch
+    (curla_hip.h: curla_add_vec).  block u8: [N obs | N next_obs] planar | pad to 16 | f32 [N, A + 2] | 2N flag bytes;
+    obs_ring / next_ring u8 [capacity, H, W, C]; sc f32 [capacity, A + 2]; cont u8 [capacity] or None (no flags kept)."""
+    cap, H, W, C = obs_ring.shape
+    A = sc.shape[1] - 2
+    _dev(block, torch.uint8), _dev(obs_ring, torch.uint8), _dev(next_ring, torch.uint8), _dev(sc)
+    need = ((2 * N * C * H * W + 15) & ~15) + 4 * N * (A + 2) + (2 * N if cont is not None else 0)
+    if (next_ring.shape != obs_ring.shape or sc.shape[0] != cap or block.numel() < need
+            or (cont is not None and _dev(cont, torch.uint8).numel() != cap) or first < 0 or first + N > cap):
+        raise _lib.CurlaHipError(f"add_vec: a block of {block.numel()} bytes ({need} needed) for rows {first} .. "
+                                 f"{first + N - 1} of rings {tuple(obs_ring.shape)} / {tuple(next_ring.shape)}, "
+                                 f"{sc.shape[0]} scalar rows")
+    call("curla_add_vec", ptr(block), ptr(obs_ring), ptr(next_ring), ptr(sc), ptr(cont), cap, int(first),
+         int(bool(has_prev)), int(N), C, H, W, A, stream())
 
 
 def gather_stacks(store, fid, idx, B, out):

@@ -258,7 +258,8 @@ class ReplayBuffer(object):
     which is detected from the data handed to ``add`` (a per-row flag ``cont``): row i continues into row i + 1 when
     that was the very next add, ``done`` was false and row i's ``next_obs`` equals row i + 1's ``obs`` byte for byte --
     a time-limit truncation or a reset breaks the chain without a change to ``add``'s signature.  A caller that
-    interleaves several environments into one buffer therefore gets a break at every switch, i.e. 1-step targets.
+    interleaves several environments into one ``n_envs=1`` buffer through ``add`` gets a break at every switch, i.e.
+    1-step targets: several environments belong in an ``n_envs=N`` buffer (below), whose chains run per environment.
     ``n_step=1`` (default) is the reference's buffer: nothing is allocated, launched or laid out differently.
 
     ``prioritized=True`` (beyond the reference; Schaul et al. 2016, the proportional variant) draws row i with
@@ -280,15 +281,29 @@ class ReplayBuffer(object):
     augmentation of ``obs[t]``: the positive is ``next_obs[r]``, r being t advanced along the continuity flags ``cont``
     (the rule above) at most k - 1 times -- ``r = t; repeat k - 1 times: if not cont[r]: stop; r = (r + 1) % capacity``
     -- i.e. the observation ``min(k, steps the chain still has from t)`` steps after ``obs[t]``.  It never crosses an
-    episode end, a truncation, a reset, the write head or an overwritten row; interleaved environments break the chain
-    at every switch (the positive is then ``next_obs[t]``).  ``k = 1`` gives ``next_obs[t]`` and needs no flag: the flags
-    are kept when ``n_step > 1`` or ``pos_offset > 1``.  The walk happens on the device, in the staging launch of the
-    minibatch (curla_sample_stage_pos; curla_pos_walk where the block travels by copy), so the host draws exactly what
+    episode end, a truncation, a reset, the write head or an overwritten row; environments interleaved through ``add``
+    break the chain at every switch (the positive is then ``next_obs[t]``; ``n_envs=N`` keeps a chain per environment).
+    ``k = 1`` gives ``next_obs[t]`` and needs no flag: the flags are kept when ``n_step > 1`` or ``pos_offset > 1``.
+    The walk happens on the device, in the staging launch of the minibatch (curla_sample_stage_pos; curla_pos_walk where the block travels by copy), so the host draws exactly what
     it draws with ``pos_offset=0``: a seeded run samples the same transitions with the same three augmentation draws,
     only the positive's pixels differ, and ``cpc_kwargs`` keeps ``time_anchor=None, time_pos=None``.  This is ATC's
     positive SELECTION behind CURL's own bilinear head and momentum encoder -- not ATC's residual predictor.  Read-only
     after construction (it decides the block layout).  ``pos_offset=0`` (default): nothing is allocated, launched or laid
-    out differently."""
+    out differently.
+
+    ``n_envs=N > 1`` (beyond the reference) stores the steps of N environments that act side by side: ``add_vec`` takes one
+    step of all of them -- N observations, actions, rewards, next observations and dones -- and writes it in one launch.
+    Environment e at vector step t owns ring row ``(t * N + e) % capacity``, so each environment is a lane of stride N,
+    ``capacity`` must be a multiple of N and ``idx`` always is one (a vector step never straddles the ring's end).
+    ``cont[r] == 1`` then means that row ``(r + N) % capacity`` continues row r's episode, and the n-step composition and
+    the positive's walk advance by N rows: ``n_step`` and ``pos_offset`` work per environment.  The rule stays derived
+    from the data, per lane: lane e continues when the previous write was the vector step directly before, that step's
+    stored ``not_done[e]`` is 1 and its ``next_obs[e]`` equals the new ``obs[e]`` byte for byte -- an auto-resetting
+    vector environment hands back a reset stack and so breaks the chain by itself, as a time-limit truncation does.  The
+    newest N rows always carry flag 0.  ``add`` refuses such a buffer; ``add_batch`` and ``load`` take whole vector steps
+    in row order (step-major, environment-minor).  Not combined with ``dedup_frames`` (its match of recent frames is
+    per stream).  Read-only after construction.  ``n_envs=1`` (default): nothing is allocated, launched or laid out
+    differently."""
 
     N_SAMPLE_SLOTS = 2  # minibatches whose references may be alive at once (the current one + one drawn ahead)
     EVENT_EVERY = 8     # index uploads per recorded event (16 pinned slots)
@@ -299,7 +314,15 @@ class ReplayBuffer(object):
 
     def __init__(self, obs_shape, action_shape, capacity, batch_size, device, augmentor, transform=None,
                  dedup_frames=False, frame_capacity=None, staged_aug=False, n_step=1, discount=None,
-                 prioritized=False, per_alpha=0.6, per_beta=0.4, per_eps=1e-6, pos_offset=0):
+                 prioritized=False, per_alpha=0.6, per_beta=0.4, per_eps=1e-6, pos_offset=0, n_envs=1):
+        if isinstance(n_envs, bool) or not isinstance(n_envs, (int, np.integer)) or n_envs < 1:
+            raise ValueError("n_envs must be an int >= 1, got %r" % (n_envs,))
+        if capacity % n_envs != 0:
+            raise ValueError("capacity = %d is not a multiple of n_envs = %d" % (capacity, n_envs))
+        if n_envs > 1 and dedup_frames:
+            raise ValueError("n_envs > 1 is not combined with dedup_frames=True (the frame store matches recent frames "
+                             "per stream)")
+        self._n_envs = N = int(n_envs)
         if isinstance(pos_offset, bool) or not isinstance(pos_offset, (int, np.integer)) or pos_offset < 0:
             raise ValueError("pos_offset must be an int >= 0, got %r" % (pos_offset,))
         self._pos_offset = int(pos_offset)
@@ -405,20 +428,22 @@ class ReplayBuffer(object):
         # add(): one pinned block per slot = [frames | pad | frame ids, action, reward, not_done], a few slots
         # guarded by events so that add() never waits for the GPU; one device block receives the copy
         self._frame = frame
-        n_stage = 2 * frame  # plain: the two stacks; dedup: up to 2k new RGB frames = the same bytes
+        # (n_envs = N > 1, add_vec(): [N obs | N next_obs | pad | N scalar rows | 2N flags], curla_add_vec's block)
+        n_stage = 2 * N * frame  # plain: the two stacks; dedup: up to 2k new RGB frames = the same bytes
         self._sc_off = (n_stage + 15) & ~15
         self._hdr = 4 * (2 * self._k) if self.dedup_frames else 0  # frame-id row in front of the scalars
-        blk = self._sc_off + self._hdr + 4 * (A + 2)
+        blk = self._sc_off + self._hdr + 4 * N * (A + 2)
         if self._keep_cont:
             # cont[i] = 1: row (i + 1) % capacity continues row i's episode (class docstring).  The flags of the previous
             # row and of the new one (always 0) ride behind the scalars of the add block; the host keeps a mirror and
             # what it needs of the previous add to evaluate the rule.
             self._cont = torch.zeros(capacity, dtype=torch.uint8, device=dev)
             self._cont_h = np.zeros(capacity, dtype=np.uint8)
+            # (n_envs = N > 1: row (i + N) % capacity, and N flags each for the previous vector step and the new one)
             self._cont_off = blk
-            blk += 4
-            self._last_row = None   # the row the latest add wrote
-            self._last_nd = False   # ... its stored not_done == 1
+            blk += (2 * N + 3) & ~3
+            self._last_row = None   # the row the latest add wrote (n_envs > 1: the first row of the latest vector step)
+            self._last_nd = False   # ... its stored not_done == 1 (bulk writes and add_vec: a bool per lane)
             self._last_next = None  # ... its next_obs bytes (plain ring; the frame store compares frame ids)
         self._n_add, self._add_slot = 4, 0
         self._h_add = torch.empty((self._n_add, blk), dtype=torch.uint8, pin_memory=pin)
@@ -486,6 +511,11 @@ class ReplayBuffer(object):
         """k of the temporal positive (class docstring); fixed at construction: it decides the block layout."""
         return self._pos_offset
 
+    @property
+    def n_envs(self):
+        """Environments that share the ring (class docstring); fixed at construction: it decides the row layout."""
+        return self._n_envs
+
     # ------------------------------------------------------------------ writing
     def _stage_scalars(self, row, action, reward, done):
         A = self._n_act
@@ -505,7 +535,7 @@ class ReplayBuffer(object):
             p = None
         flag = 0
         if p is not None:
-            flag = int(bool(continues) and self._last_nd)
+            flag = int(bool(continues) and bool(self._last_nd))
             self._cont_h[p] = flag
         self._cont_h[i] = 0
         row[self._cont_off], row[self._cont_off + 1] = flag, 0
@@ -535,6 +565,9 @@ class ReplayBuffer(object):
         """utils.py:120-128: store one transition at ``idx``.  The two frames and the scalars travel in one
         pinned block and one async copy; two kernels turn CHW into the ring's HWC, one row copy stores the
         scalars.  Nothing here waits for the GPU (a slot is reused only after its copy has executed)."""
+        if self._n_envs > 1:
+            raise ValueError("add() stores one transition; a buffer of n_envs = %d takes a whole vector step: add_vec()"
+                             % self._n_envs)
         if self.dedup_frames:
             return self._add_dedup(obs, action, reward, next_obs, done)
         i = self.idx
@@ -587,6 +620,72 @@ class ReplayBuffer(object):
             if self.prioritized and _lib_tracing():
                 self._per_new_rows(i, 1)
         self._advance(1)
+
+    def _vec_args(self, obs, action, reward, next_obs, done):
+        """The five arguments of add_vec as NumPy arrays (N, C H W) uint8 twice, (N, A) float32, (N,) float32 and
+        (N,) bool; ValueError when a leading size is not n_envs or a shape does not fit."""
+        N, A = self._n_envs, self._n_act
+        got = [np.asarray(obs), np.asarray(action), np.asarray(reward), np.asarray(next_obs), np.asarray(done)]
+        want = [(N,) + self.obs_shape, (N, A), (N,), (N,) + self.obs_shape, (N,)]
+        if not all(g.ndim >= 1 and g.shape[0] == N and g.size == int(np.prod(w)) for g, w in zip(got, want)):
+            raise ValueError("add_vec of an n_envs = %d buffer takes obs and next_obs %r uint8, action %r (or (%d,) + "
+                             "action_shape), reward and done %r; got %s"
+                             % (N, want[0], want[1], N, want[2], ", ".join(str(g.shape) for g in got)))
+        o, a, r, n, d = got
+        return (np.asarray(o, dtype=np.uint8).reshape(N, -1), np.asarray(a, dtype=np.float32).reshape(N, A),
+                np.asarray(r, dtype=np.float32).reshape(N), np.asarray(n, dtype=np.uint8).reshape(N, -1),
+                d.reshape(N) != 0)
+
+    def add_vec(self, obs, action, reward, next_obs, done):
+        """One step of the buffer's ``n_envs = N`` environments: ``obs`` / ``next_obs`` (N, C, H, W) uint8, ``action``
+        (N, A) or (N,) + action_shape, ``reward`` and ``done`` (N,).  Environment e goes to ring row ``idx + e``; the
+        continuity flags of the previous vector step are set per lane by the rule of the class docstring.  The 2N
+        frames, the N scalar rows and the 2N flag bytes travel in one pinned block and one async copy, and ONE launch
+        (curla_add_vec) stores them all; nothing here waits for the GPU (the rotating pinned slots and events of
+        ``add``).  On an ``n_envs=1`` buffer this is ``add`` of the one transition."""
+        obs, action, reward, next_obs, done = self._vec_args(obs, action, reward, next_obs, done)
+        N, A = self._n_envs, self._n_act
+        if N == 1:
+            return self.add(obs[0].reshape(self.obs_shape), action[0], reward[0], next_obs[0].reshape(self.obs_shape),
+                            done[0])
+        i, fr, cap = self.idx, self._frame, self.capacity
+        k = self._next_add_slot()
+        row = self._h_add_np[k]
+        row[:N * fr] = obs.reshape(-1)
+        row[N * fr:2 * N * fr] = next_obs.reshape(-1)
+        sc = row[self._sc_off:self._sc_off + 4 * N * (A + 2)].view(np.float32).reshape(N, A + 2)
+        sc[:, :A], sc[:, A], sc[:, A + 1] = action, reward, ~done
+        prev = None
+        if self._keep_cont:  # N frame comparisons on the host, against the copy kept of the previous step's next_obs
+            prev = self._last_row
+            if prev is None or (prev + N) % cap != i or prev == i:
+                prev = None
+            flags = row[self._cont_off:self._cont_off + 2 * N]
+            flags[:] = 0
+            if prev is not None:
+                flags[:N] = (self._last_next.reshape(N, fr) == obs).all(axis=1) & np.reshape(self._last_nd, N)
+                self._cont_h[prev:prev + N] = flags[:N]
+            self._cont_h[i:i + N] = 0
+            self._last_row, self._last_nd, self._last_next = i, sc[:, A + 1] == 1.0, next_obs.reshape(-1).copy()
+        if self.device.type == "cuda":
+            self._d_add.copy_(self._h_add[k], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._add_events[k] = ev
+        else:  # host-side bookkeeping only (index logic tests); pixels are still stored, HWC
+            c, h, w = self.obs_shape
+            for ring, frames in ((self.obses, obs), (self.next_obses, next_obs)):
+                ring[i:i + N] = torch.from_numpy(frames.reshape(N, c, h, w)).permute(0, 2, 3, 1)
+            self._sc[i:i + N] = torch.from_numpy(sc.copy())
+            if self._keep_cont:
+                for r in (i,) if prev is None else (prev, i):
+                    self._cont[r:r + N] = torch.from_numpy(self._cont_h[r:r + N].copy())
+        if self.device.type == "cuda" or _lib_tracing():
+            ops.add_vec(self._d_add, self.obses, self.next_obses, self._sc, self._cont if self._keep_cont else None, i,
+                        prev is not None, N)
+            if self.prioritized:
+                self._per_new_rows(i, N)
+        self._advance(N)
 
     def _per_new_rows(self, first, n):
         """Rows first, first + 1, ... (n of them, modulo capacity) hold new transitions: they get the maximum stored
@@ -659,7 +758,10 @@ class ReplayBuffer(object):
     def _cont_rows(self, first, obs, nxt, not_done):
         """n-step bookkeeping of a bulk write (add_batch, load): transitions ``obs`` / ``nxt`` ((m, C, H, W) uint8 host
         arrays) with ``not_done`` (m values) go to rows first, first + 1, ... (mod capacity), in this order -- the rule
-        of add() applied to the arrays, the pair (previous add, first element) included."""
+        of add() applied to the arrays, the pair (previous add, first element) included.  With ``n_envs = N`` the rows
+        are whole vector steps (m and first multiples of N): element j continues into element j + N, its lane's next
+        step, and the pair (previous write, first step of the batch) is evaluated per lane."""
+        N = self._n_envs
         m = len(obs)
         if m == 0:
             return
@@ -669,30 +771,37 @@ class ReplayBuffer(object):
         cap = self.capacity
         rows = (first + np.arange(m)) % cap
         flags = np.zeros(m, dtype=np.uint8)
-        flags[:-1] = (nxt[:-1] == obs[1:]).all(axis=1) & nd[:-1]
+        flags[:-N] = (nxt[:-N] == obs[N:]).all(axis=1) & nd[:-N]
         touched = rows
         p = self._last_row
-        if p is not None and (p + 1) % cap == rows[0] and m < cap:  # (m >= cap: the batch overwrites row p itself)
-            self._cont_h[p] = int(self._last_nd and self._last_next is not None
-                                  and np.array_equal(self._last_next, obs[0]))
-            touched = np.concatenate([[p], rows])
+        if p is not None and (p + N) % cap == rows[0] and m < cap:  # (m >= cap: the batch overwrites row p itself)
+            prev = p + np.arange(N)
+            self._cont_h[prev] = 0
+            if self._last_next is not None:
+                self._cont_h[prev] = (self._last_next.reshape(N, -1) == obs[:N]).all(axis=1) & np.reshape(self._last_nd, N)
+            touched = np.concatenate([prev, rows])
         self._cont_h[rows] = flags  # (a row written twice keeps its last flag)
-        self._last_row, self._last_nd = int(rows[-1]), bool(nd[-1])
-        self._last_next = nxt[-1].copy()
+        self._last_row, self._last_nd = int(rows[-N]), nd[-N:].copy()
+        self._last_next = nxt[-N:].reshape(-1).copy()
         touched = np.unique(touched)
         self._cont[torch.from_numpy(touched).to(self.device)] = torch.from_numpy(self._cont_h[touched]).to(self.device)
 
     def add_batch(self, obses, actions, rewards, next_obses, dones):
         """Bulk fill (benchmarks / buffer load): N transitions, observations as
-        (N, C, H, W) uint8 arrays.  Same ring semantics as N add() calls."""
+        (N, C, H, W) uint8 arrays.  Same ring semantics as N add() calls -- with ``n_envs > 1`` as len / n_envs
+        add_vec() calls: whole vector steps in row order (step-major, environment-minor)."""
         n = len(obses)
+        if n % self._n_envs != 0:
+            raise ValueError("add_batch of an n_envs = %d buffer takes whole vector steps, got %d transitions"
+                             % (self._n_envs, n))
+        chunk = 1024 // self._n_envs * self._n_envs  # whole vector steps per chunk
         if self.dedup_frames:
             for j in range(n):
                 self.add(obses[j], actions[j], float(np.asarray(rewards[j]).reshape(-1)[0]), next_obses[j],
                          bool(np.asarray(dones[j]).reshape(-1)[0]))
             return
-        for s in range(0, n, 1024):
-            e = min(n, s + 1024)
+        for s in range(0, n, chunk):
+            e = min(n, s + chunk)
             m = e - s
             o = torch.from_numpy(np.ascontiguousarray(obses[s:e])).to(self.device).permute(0, 2, 3, 1)
             nx = torch.from_numpy(np.ascontiguousarray(next_obses[s:e])).to(self.device).permute(0, 2, 3, 1)
@@ -923,23 +1032,24 @@ class ReplayBuffer(object):
         which also brings the block to ``dev``.  ``copied``, the block is in ``dev`` already: a launch each."""
         B, A, lay = self.batch_size, self._n_act, self._layout
         cont = self._cont if self._keep_cont else None
+        lane = dict(stride=self._n_envs) if self._n_envs > 1 else {}  # the walks' step (the _strided entry points)
         if copied:
             if self.prioritized:  # the draw: rows into the block's idx run, their probabilities into ``prob``
                 ops.per_sample(self._per_s, self._per_sums, dev, lay["u"], lay["prob"], B)
             ops.gather_transition_scalars(self._sc, dev[lay["idx"]:lay["idx"] + 8 * B].view(torch.int64), B, A, *out)
             if self.n_step > 1:  # the bootstrap rows must be in the block before anything reads pixels
                 ops.nstep_compose(dev, lay["next_row"], self._sc, cont, self.capacity, self.n_step,
-                                  self._nstep_discount(), B, A, *out)
+                                  self._nstep_discount(), B, A, *out, **lane)
             if self._pos_offset:  # ... and so must the positive's rows (behind the draw, which writes the idx run)
                 ops.pos_walk(dev, lay["pos_row"], lay.get("pos_run"), lay.get("next_row"), cont, self.capacity,
-                             self._pos_offset, self.n_step, B)
+                             self._pos_offset, self.n_step, B, **lane)
         elif self._pos_offset:
             ops.sample_stage_pos(host_dev, dev, nbytes, lay.get("next_row"), lay["pos_row"], lay.get("pos_run"), self._sc,
                                  cont, self.capacity, self.n_step, self._nstep_discount() if self.n_step > 1 else 1.0,
-                                 self._pos_offset, B, A, *out)
+                                 self._pos_offset, B, A, *out, **lane)
         elif self.n_step > 1:
             ops.sample_stage_nstep(host_dev, dev, nbytes, lay["next_row"], self._sc, cont, self.capacity, self.n_step,
-                                   self._nstep_discount(), B, A, *out)
+                                   self._nstep_discount(), B, A, *out, **lane)
         else:
             ops.sample_stage(host_dev, dev, nbytes, self._sc, B, A, *out)
 
@@ -1281,6 +1391,8 @@ class ReplayBuffer(object):
             lo, hi = span(name)
             if lo != self.idx:
                 raise AssertionError("chunk %s does not continue the buffer at index %d" % (name, self.idx))
+            if lo % self._n_envs or hi % self._n_envs:
+                raise ValueError("chunk %s does not hold whole vector steps of n_envs = %d" % (name, self._n_envs))
             obs, nxt, act, rew, nd = torch.load(os.path.join(save_dir, name), weights_only=False)
             if self.dedup_frames:  # (prioritized: every add of the loop gives its row the maximum)
                 self.add_batch(obs, act, rew, nxt, 1.0 - np.asarray(nd))

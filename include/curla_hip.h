@@ -607,6 +607,25 @@ int curla_sample_stage_pos(const void* host_block, void* device_block, long long
                            long long pos_offset, long long run_offset, const float* scalars, const uint8_t* cont,
                            long long capacity, int n, float discount, int k, int B, int A, float* action, float* reward,
                            float* not_done, void* stream);
+/* The four walks above for a ring that several environments share (ReplayBuffer(n_envs=N)): environment e owns rows
+ * e, e + N, e + 2 N, ... -- a lane of stride N -- and `cont[r] == 1` means that row (r + stride) % capacity continues row
+ * r's episode.  Each entry point is its namesake with `long long stride` behind `capacity`: every `(r + 1) % capacity`
+ * of the definitions above reads `(r + stride) % capacity`, nothing else changes, and stride == 1 gives the namesake's
+ * bits (the namesakes are these with stride 1).  CURLA_ERR_ARG before any launch on what the namesake refuses and on
+ * stride < 1 or capacity % stride != 0.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_nstep_compose_strided(void* device_block, long long next_row_offset, const float* scalars, const uint8_t* cont,
+                                long long capacity, long long stride, int n, float discount, int B, int A, float* action,
+                                float* reward, float* not_done, void* stream);
+int curla_sample_stage_nstep_strided(const void* host_block, void* device_block, long long nbytes,
+                                     long long next_row_offset, const float* scalars, const uint8_t* cont,
+                                     long long capacity, long long stride, int n, float discount, int B, int A,
+                                     float* action, float* reward, float* not_done, void* stream);
+int curla_pos_walk_strided(void* device_block, long long pos_offset, long long run_offset, long long next_row_offset,
+                           const uint8_t* cont, long long capacity, long long stride, int k, int n, int B, void* stream);
+int curla_sample_stage_pos_strided(const void* host_block, void* device_block, long long nbytes, long long next_row_offset,
+                                   long long pos_offset, long long run_offset, const float* scalars, const uint8_t* cont,
+                                   long long capacity, long long stride, int n, float discount, int k, int B, int A,
+                                   float* action, float* reward, float* not_done, void* stream);
 /* Proportional prioritized replay (beyond the reference: ReplayBuffer(prioritized=True); Schaul et al. 2016).
  * Storage, all on the device: `s` float [capacity], the stored value p_i^alpha of every ring row (0 = never written:
  * never drawn) | `sums` double [ceil(capacity / CURLA_PER_CHUNK)], one sum per chunk of CURLA_PER_CHUNK consecutive
@@ -666,6 +685,22 @@ int curla_store_frame(const uint8_t* chw, uint8_t* frames, long long slot, int C
  * bytes of loader slack). */
 int curla_stage_frames_u8(const uint8_t* nchw, uint8_t* frames, long long first_slot, int N, int C, int Hs, int Ws,
                           int top, int left, int Hd, int Wd, void* stream);
+/* ReplayBuffer.add_vec: one step of N environments into ring rows first .. first + N - 1 in ONE launch.  `block` is the
+ * device copy of the staged add block,
+ *   [N obs | N next_obs] planar uint8 [2 N][C][H][W] | pad to 16 bytes | float [N][A + 2] | uint8 [2 N] flags,
+ * the flag bytes present only when `cont` is not NULL.  `obs_ring` / `next_ring`: row 0 of the two rings,
+ * [capacity][H][W][C] each (one allocation, next_ring = obs_ring + capacity H W C, or two); `scalars`: the ring's [capacity][A + 2] rows.
+ *   obs_ring[first + e][y][x][c] = block frame e at [c][y][x],  next_ring[first + e] likewise from block frame N + e
+ *   scalars[first + e][:] = block row e
+ *   cont[first + e] = flag N + e;  has_prev != 0: cont[prev + e] = flag e, prev = (first - N) modulo capacity, the run
+ *   of the step before (it may sit at the ring's end)
+ * C in {3, 6, 9, 12} with H W a multiple of 4 and both rings on a 4-byte boundary moves whole dwords (the transpose of
+ * curla_stage_frames_u8); every other case gives the same bytes one at a time.  Writes the rows named above and nothing
+ * else.  CURLA_ERR_ARG before the launch on: block, obs_ring, next_ring or scalars NULL; block or scalars off 4 bytes;
+ * N < 1, C < 1, H < 1, W < 1, A < 1; capacity % N != 0, first < 0, first % N != 0, first + N > capacity; has_prev with
+ * cont NULL or capacity == N; 2 N H W >= 2^31.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_add_vec(const uint8_t* block, uint8_t* obs_ring, uint8_t* next_ring, float* scalars, uint8_t* cont,
+                  long long capacity, long long first, int has_prev, int N, int C, int H, int W, int A, void* stream);
 /* De-duplicated frame store (next_obs[t] shares k-1 of its k frames with obs[t], and equals obs[t+1]
  * inside an episode, utils.py:238-268): `store` holds every RGB frame once, uint8 [F][H][W][3]; row idx[b] (NULL: b) of
  * `fid` (int32, `fid_stride` entries per row) lists the K frame ids of a stack.  Writes the minibatch of stacks
