@@ -146,6 +146,7 @@ SIGNATURES = {
                              vp, vp],
     "curla_dihedral_u8": [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, vp, vp],
     "curla_grayscale_u8": [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, vp, vp],
+    "curla_affine_u8": [vp, vp, c_int, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp],
     "curla_version": [],
     "curla_abi_version": [],
     "curla_set_option": [ctypes.c_char_p, ctypes.c_char_p],

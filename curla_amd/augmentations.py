@@ -59,7 +59,7 @@ class IdentityAugmentation:
 
     @property
     def sample_kind(self):
-        """The identity is a "ring"; a subclass inherits no kind from it -- it declares its own (the seven below do, and
+        """The identity is a "ring"; a subclass inherits no kind from it -- it declares its own (the classes below do, and
         their subclasses inherit that) or is unknown to ReplayBuffer (None: draw_indices raises)."""
         return "ring" if type(self) is IdentityAugmentation else None
 
@@ -456,6 +456,122 @@ class RandomGrayscale(IdentityAugmentation):
         return self.grey(image_batch, self.draw_flags(image_batch.shape[0]))
 
 
+def _finite_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and bool(np.isfinite(float(v)))
+
+
+class RandomAffine(IdentityAugmentation):
+    """Beyond the reference: the rotate / zoom / sub-pixel shift of kornia's and torchvision's ``RandomAffine`` -- the one
+    augmentation of the uint8 path that RESAMPLES.  A sample is turned by theta in [-degrees, degrees] (positive: counter-
+    clockwise, as ``np.rot90`` turns) about the frame's centre, zoomed by s in ``scale`` and shifted by (ty, tx) in
+    ``translate`` * (H, W) pixels, one draw per sample shared by all frames of the stack, with probability ``p``; pixels
+    from outside the frame repeat the edge (``fill='edge'``) or are black (``fill='zero'``).  ``output_shape ==
+    input_shape``; evaluation is the identity.  The map is defined in integers, so that the device, this file and the
+    tests agree bit for bit: six int32 words per sample, a 16.16 fixed-point INVERSE map from output pixel (y, x) to source
+    coordinates,
+        X = wrap32(m00 x + m01 y + m02)        Y = wrap32(m10 x + m11 y + m12)
+        x0 = X >> 16 (floor)   fx = (X >> 8) & 255          y0 = Y >> 16   fy = (Y >> 8) & 255
+        out[c][y][x] = (P(y0, x0)[c] (256 - fx) (256 - fy) + P(y0, x0 + 1)[c] fx (256 - fy)
+                      + P(y0 + 1, x0)[c] (256 - fx) fy     + P(y0 + 1, x0 + 1)[c] fx fy     + 32768) >> 16
+    with P the source pixel at clamped coordinates (edge) or 0 outside the frame (zero).  With a = cos(theta) / s,
+    b = -sin(theta) / s, (cx, cy) = ((W - 1) / 2, (H - 1) / 2) and (ux, uy) = (cx + tx, cy + ty), in float64:
+        m00 = rint(65536 a)    m01 = rint(65536 b)    m02 = rint(65536 (cx - a ux - b uy))
+        m10 = rint(-65536 b)   m11 = rint(65536 a)    m12 = rint(65536 (cy + b ux - a uy))
+    A clean restatement, not a port.  On the learner path the pixels are blended by ``curla_affine_u8`` and stay uint8
+    (ReplayBuffer); the parameters are drawn on the host from NumPy's global stream."""
+
+    IDENTITY_WORDS = (65536, 0, 0, 0, 65536, 0)
+
+    def __init__(self, input_shape, degrees=10.0, scale=(0.9, 1.1), translate=0.05, fill='edge', p=1.0):
+        shape, self.p = _checked_hw_p("RandomAffine", input_shape, p)
+        super().__init__(shape)
+        if not _finite_number(degrees) or not 0.0 <= float(degrees) <= 180.0:
+            raise ValueError("RandomAffine: degrees must be a finite number in [0, 180], got %r" % (degrees,))
+        if (isinstance(scale, (str, bytes)) or not hasattr(scale, "__len__") or len(scale) != 2
+                or not all(_finite_number(v) for v in scale) or not 0.0 < float(scale[0]) <= float(scale[1])):
+            raise ValueError("RandomAffine: scale must be two finite numbers with 0 < lo <= hi, got %r" % (scale,))
+        if not _finite_number(translate) or not 0.0 <= float(translate) <= 0.5:
+            raise ValueError("RandomAffine: translate must be a number in [0, 0.5], got %r" % (translate,))
+        if not isinstance(fill, str) or fill not in ('edge', 'zero'):
+            raise ValueError("RandomAffine: fill must be 'edge' or 'zero', got %r" % (fill,))
+        self.degrees, self.scale = float(degrees), (float(scale[0]), float(scale[1]))
+        self.translate, self.fill = float(translate), fill
+        # (sufficient for no word and no source coordinate of a pixel of the frame to leave 32 bits: |a|, |b| <= g, and
+        # the centre plus the shift is at most (0.5 + translate) of a side)
+        h, w = self.input_shape
+        g = 1.0 / self.scale[0]
+        if not 65536.0 * (g * (h + w) * (1.5 + self.translate) + max(h, w) / 2.0 + 1.0) < 2.0 ** 31:
+            raise ValueError("RandomAffine: frames of %r at scale >= %r do not fit the 16.16 words of the map"
+                             % (self.input_shape, self.scale[0]))
+
+    def draw_params(self, n):
+        """Five RNG calls, always all and in this order: ``uniform(-degrees, degrees, n)``, ``uniform(scale[0], scale[1],
+        n)``, ``uniform(-translate H, translate H, n)`` (ty), ``uniform(-translate W, translate W, n)`` (tx) and
+        ``rand(n) < p``.  Returns (theta in radians, s, ty, tx, keep)."""
+        h, w = self.input_shape
+        deg = np.random.uniform(-self.degrees, self.degrees, n)
+        s = np.random.uniform(self.scale[0], self.scale[1], n)
+        ty = np.random.uniform(-self.translate * h, self.translate * h, n)
+        tx = np.random.uniform(-self.translate * w, self.translate * w, n)
+        keep = np.random.rand(n) < self.p
+        return np.deg2rad(deg), s, ty, tx, keep
+
+    def words(self, theta, s, ty, tx):
+        """int32 [6][n]: the words m00 m01 m02 m10 m11 m12 of given per-sample parameters (the class docstring's formulas,
+        in float64; theta in radians)."""
+        theta, s, ty, tx = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (theta, s, ty, tx))
+        h, w = self.input_shape
+        a, b = np.cos(theta) / s, -np.sin(theta) / s
+        cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+        ux, uy = cx + tx, cy + ty
+        m = np.stack(np.broadcast_arrays(65536.0 * a, 65536.0 * b, 65536.0 * (cx - a * ux - b * uy),
+                                         -65536.0 * b, 65536.0 * a, 65536.0 * (cy + b * ux - a * uy)))
+        return np.rint(m).astype(np.int64).astype(np.int32)
+
+    sample_kind, index_rows = "scratch", 6
+
+    def draw_index_words(self, n):
+        """The six words of ``draw_params(n)`` in the order m00 ... m12; a sample that is not kept gets the identity's."""
+        theta, s, ty, tx, keep = self.draw_params(n)
+        m = self.words(theta, s, ty, tx)
+        return tuple(np.where(keep, m[k], np.int32(self.IDENTITY_WORDS[k])).astype(np.int32) for k in range(6))
+
+    def scratch_launch(self, ring, rows, period, words, n, out):
+        ops.affine_u8(ring, rows, period, words, 1 if self.fill == 'edge' else 0, n, out)
+
+    def warp(self, image_batch, words):
+        """The map of ``curla_affine_u8`` on a (B, C, H, W) uint8 array with given per-sample words ([6][B], any
+        integers: they are taken modulo 2^32), on the host: the class docstring's formula in int64."""
+        img = np.asarray(image_batch)
+        B, C, H, W = img.shape
+
+        def wrap32(v):
+            return ((v + 2 ** 31) & 0xFFFFFFFF) - 2 ** 31
+
+        m = wrap32(np.stack([np.asarray(w).astype(np.int64).reshape(-1) for w in words]))
+        y, x = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
+        out = np.empty_like(img)
+        for b in range(B):
+            X = wrap32(m[0, b] * x + m[1, b] * y + m[2, b])
+            Y = wrap32(m[3, b] * x + m[4, b] * y + m[5, b])
+            x0, y0, fx, fy = X >> 16, Y >> 16, (X >> 8) & 255, (Y >> 8) & 255
+            acc = np.full((C, H, W), 32768, dtype=np.int64)
+            for yy, wy in ((y0, 256 - fy), (y0 + 1, fy)):
+                for xx, wx in ((x0, 256 - fx), (x0 + 1, fx)):
+                    tap = img[b][:, np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)].astype(np.int64)
+                    if self.fill == 'zero':
+                        tap = tap * ((yy >= 0) & (yy < H) & (xx >= 0) & (xx < W))
+                    acc += tap * (wx * wy)
+            out[b] = (acc >> 16).astype(img.dtype)
+        return out
+
+    def training_augmentation(self, image_batch):
+        """Host-side warp of a (B, C, H, W) uint8 NumPy array, for callers outside the fused path: ``draw_params``,
+        ``words`` (the identity's where a sample is not kept), ``warp``."""
+        image_batch = np.asarray(image_batch)
+        return self.warp(image_batch, self.draw_index_words(image_batch.shape[0]))
+
+
 class Compose(IdentityAugmentation):
     """Beyond the reference: a geometric uint8 augmentation followed by a cutout -- RAD's ``crop-cutout_color`` or
     ``translate-cutout`` -- as ONE augmentation.  ``move`` is a RandomCrop, a RandomShift or a RandomTranslate, ``paint`` a
@@ -734,12 +850,14 @@ class NoisyCover(IdentityAugmentation):
         return out
 
 
-def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30, conv_p=1.0, p=None):
+def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, max_cut=30, conv_p=1.0, p=None,
+                   degrees=10.0, scale=(0.9, 1.1), translate=0.05, fill='edge'):
     """augmentations.py:208-221, plus 'random_shift' (``pad``: its padding), 'cutout' / 'cutout_color' (``min_cut``,
     ``max_cut``: the range of a box side), 'random_conv' (``conv_p``: the probability that a sample is convolved),
     'translate' (``output_shape``: its canvas, None = 8 pixels more per side length) and 'flip' / 'rotate' / 'grayscale'
-    (``p``: the probability that a sample is transformed, None = the class's default) -- all eight beyond the reference --
-    and '<move>+<paint>' with <move> one of 'random_crop', 'random_shift', 'translate' and <paint> one of 'cutout',
+    (``p``: the probability that a sample is transformed, None = the class's default) and 'affine' (``degrees``, ``scale``,
+    ``translate``, ``fill``: RandomAffine's ranges and border rule; ``p``: its probability, None = 1.0) -- all nine beyond
+    the reference -- and '<move>+<paint>' with <move> one of 'random_crop', 'random_shift', 'translate' and <paint> one of 'cutout',
     'cutout_color': a ``Compose`` of the two, the paint built for the move's output_shape."""
     print(f'CHOSEN AUGMENTATION: {name}')
     if '+' in name:
@@ -768,4 +886,6 @@ def make_augmentor(name, input_shape, output_shape=None, *, pad=4, min_cut=10, m
     if name in ('flip', 'rotate', 'grayscale'):
         cls = RandomFlip if name == 'flip' else RandomRotate if name == 'rotate' else RandomGrayscale
         return cls(input_shape) if p is None else cls(input_shape, p)
+    if name == 'affine':
+        return RandomAffine(input_shape, degrees, scale, translate, fill, 1.0 if p is None else p)
     raise ValueError('augmentation is not supported: %s' % name)

@@ -7,6 +7,7 @@
 // float32 NHWC minibatch [B][H][W][C] in [0,255] that the first conv kernel consumes (src kind 2).
 #include "common.h"
 #include "u8_mover.h"  // RandomShift, RandomTranslate and the crop; U8_UNROLL and u32x4 for RandomCutout below
+#include "affine.h"    // RandomAffine: the one mover that resamples
 
 namespace {
 
@@ -964,6 +965,20 @@ int curla_grayscale_u8(const uint8_t* frames, const int64_t* idx, int period, co
   if (frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;  // (as curla_dihedral_u8)
   const GreyOp op{grey, (unsigned)frame, (unsigned)frame};
   return launch_u8_mover(op, frames, idx, period, n, frame, true, out, stream);
+}
+
+int curla_affine_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* m00, const int32_t* m01,
+                    const int32_t* m02, const int32_t* m10, const int32_t* m11, const int32_t* m12, int fill, int n, int C,
+                    int H, int W, uint8_t* out, void* stream) {
+  CURLA_REQUIRE(frames && m00 && m01 && m02 && m10 && m11 && m12 && out && n > 0 && period > 0 && C > 0 && H > 0 && W > 0);
+  CURLA_REQUIRE(fill == 0 || fill == 1);
+  CURLA_REQUIRE(((reinterpret_cast<uintptr_t>(m00) | reinterpret_cast<uintptr_t>(m01) | reinterpret_cast<uintptr_t>(m02) |
+                  reinterpret_cast<uintptr_t>(m10) | reinterpret_cast<uintptr_t>(m11) | reinterpret_cast<uintptr_t>(m12)) & 3) == 0 &&
+                (reinterpret_cast<uintptr_t>(idx) & 7) == 0);
+  const long long frame = (long long)H * W * C;
+  if (frame >= (1LL << 31) - 16) return CURLA_ERR_UNSUPPORTED;  // (as curla_dihedral_u8)
+  const AffOp op{{m00, m01, m02, m10, m11, m12}, fill, H, W, C, (unsigned)frame};
+  return launch_affine_u8(op, frames, idx, period, n, frame, out, stream);
 }
 
 int curla_random_conv(const uint8_t* frames, const int64_t* idx, const float* weights, int B, int C, int H, int W,

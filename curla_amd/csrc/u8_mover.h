@@ -4,7 +4,8 @@
 // DESIGN.md; PaintOp there wraps a mover Op and paints the cutout's box over its bytes before the store.)  Behind them,
 // on the same skeleton: FlipOp (RandomFlip / RandomRotate: pixels in reversed order), with the transposing codes of the
 // dihedral group in a kernel of their own shape (dihedral_u8_kernel: through LDS), and GreyOp (RandomGrayscale: an Op
-// that changes the bytes it moves).
+// that changes the bytes it moves).  RandomAffine, the one kernel that resamples, is not a mover: affine.h, which borrows
+// only the band form of dihedral_u8_kernel and this file's types.
 //
 // A mover gathers a frame of the uint8 NHWC ring per sample (row(s) = idx ? idx[s % period] : s % period) and writes a
 // uint8 NHWC frame per sample (roof: HBM).  A thread owns 16 consecutive OUTPUT bytes of a sample, a "group" (one 16-byte

@@ -1460,7 +1460,7 @@ class CurlSacAgent(object):
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
             raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
                              "(covered: RandomCrop, RandomShift, RandomCutout, RandomTranslate or identity, plain storage with both rings in one "
-                             "allocation or dedup_frames storage -- RandomFlip, RandomRotate and RandomGrayscale like them; ColorJiggle / NoisyCover / RandomConv "
+                             "allocation or dedup_frames storage -- RandomFlip, RandomRotate, RandomGrayscale and RandomAffine like them; ColorJiggle / NoisyCover / RandomConv "
                              "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
                              "CURLA_STAGE_COPY=1; not a prioritized=True buffer, whose draw and priority update are not "
                              "nodes of the graphs)")

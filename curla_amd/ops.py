@@ -882,6 +882,19 @@ def grayscale_u8(frames, idx, period, grey, n, out):
     call("curla_grayscale_u8", ptr(frames), ptr(idx), int(period), ptr(grey), int(n), C, H, W, ptr(out), stream())
 
 
+def affine_u8(frames, idx, period, words, fill, n, out):
+    """RandomAffine of n samples (curla_affine_u8): frames u8 [rows, H, W, C]; sample s is row idx[s % period] (idx None:
+    s % period) resampled through its six 16.16 words m00 m01 m02 m10 m11 m12 (``words``: six int32 [n]; any values, the
+    kernel's rule is total) with ``fill`` 1 = edge pixels repeated, 0 = zeros outside the frame; out u8 [n, H, W, C]."""
+    _, H, W, C = frames.shape
+    words = tuple(words)
+    _check_scratch_u8("affine_u8", frames, idx, period, words, n, out,
+                      tuple(out.shape) == (n, H, W, C) and len(words) == 6 and fill in (0, 1),
+                      ("map words", " under six words and fill 0 or 1"))
+    call("curla_affine_u8", ptr(frames), ptr(idx), int(period), *(ptr(t) for t in words), int(fill), int(n), C, H, W,
+         ptr(out), stream())
+
+
 def nhwc_to_nchw(x, out):
     B, H, W, C = x.shape
     call("curla_nhwc_to_nchw", ptr(x), ptr(out), B, H, W, C, stream())

@@ -839,7 +839,7 @@ class ReplayBuffer(object):
         RandomShift / RandomTranslate, (y0, x0) of a RandomCutout's boxes; zeros when it draws none).  An augmentation of
         four words -- RandomCutout -- returns int32 [12, B], rows 6 + 2j, 6 + 2j + 1 = the other two (its packed sizes
         and colours); one of six -- Compose -- int32 [18, B] by the same rule (word r of tensor j in row 6 (r // 2) + 2 j +
-        r % 2): the move's offsets, the box's (y0, x0), its sizes and colours.
+        r % 2): the move's offsets, the box's (y0, x0), its sizes and colours -- or RandomAffine's six words of the map, m00 m01 | m02 m10 | m11 m12.
         ``prioritized``: returns (u, offsets), u float64 [B] the stratified targets (k + r_k) / B with
         r = np.random.random_sample(B) drawn where the rows are drawn otherwise -- the rows themselves are drawn by
         curla_per_sample from u."""
@@ -882,8 +882,8 @@ class ReplayBuffer(object):
                        weights; a key only this layout has -- the stride keeps ``nbytes`` a multiple of 8)
         An augmentation that draws four index words -- RandomCutout -- appends ``cut`` int32 [2][3B] behind them: the third
         words of obs | next_obs | pos (its packed box sizes), then the fourth (its colour words) -- contiguous runs for
-        one launch of n = 3B.  One that draws six -- Compose -- appends ``cut`` int32 [4][3B]: the third to sixth words, the
-        box's y0 | x0 | sizes | colours.
+        one launch of n = 3B.  One that draws six -- Compose, RandomAffine -- appends ``cut`` int32 [4][3B]: the third to sixth words, the
+        box's y0 | x0 | sizes | colours, or the map's m02 | m10 | m11 | m12.
         ``n_step > 1`` appends ``next_row`` int64 [B] behind them: the bootstrap rows, written by the composing kernel.
         ``pos_offset > 0`` appends ``pos_row`` int64 [2][B] behind them, written by the positive's walk: the rows r whose
         next_obs is the positive, then capacity + r (the same rows in the double ring) -- and for a "scratch" augmentation
@@ -1185,7 +1185,7 @@ class ReplayBuffer(object):
     # control values (RNG stream positions, Adam step factors) that the graph's kernels read from the device copy.
     def graph_supported(self):
         """Graph replay covers every minibatch whose per-update values reach the kernels through the block: the uint8-ring
-        ones (RandomCrop / RandomShift / RandomCutout / RandomTranslate / RandomFlip / RandomRotate / RandomGrayscale / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
+        ones (RandomCrop / RandomShift / RandomCutout / RandomTranslate / RandomFlip / RandomRotate / RandomGrayscale / RandomAffine / identity; plain storage with both rings in one allocation, or ``dedup_frames``, whose stacks
         are gathered into a buffer of the graph's own), and ColorJiggle / NoisyCover / RandomConv constructed with
         ``staged_aug=True`` (either storage).  A ``prioritized`` buffer is not covered (its draw and its priority update are
         not nodes of the captured graphs).  A float augmentation WITHOUT staged_aug draws and uploads its parameters

@@ -805,6 +805,28 @@ int curla_dihedral_u8(const uint8_t* frames, const int64_t* idx, int period, con
  * launch. */
 int curla_grayscale_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* grey, int n, int C, int H,
                        int W, uint8_t* out, void* stream);
+/* RandomAffine, the rotate / zoom / sub-pixel shift of kornia's and torchvision's RandomAffine (beyond the reference: its
+ * augmentations.py resamples nothing): one inverse affine map per sample, shared by all channels of a stack, bilinear in
+ * integers.  m00 m01 m02 m10 m11 m12: int32 [n] each, 16.16 fixed point, from output pixel (y, x) to source coordinates:
+ *   X = wrap32(m00 x + m01 y + m02)          Y = wrap32(m10 x + m11 y + m12)       (two's-complement wrap-around)
+ *   x0 = X >> 16 (arithmetic: floor)         fx = (X >> 8) & 255
+ *   y0 = Y >> 16                             fy = (Y >> 8) & 255
+ *   out[s][y][x][c] = (P(y0, x0)[c] (256 - fx) (256 - fy) + P(y0, x0 + 1)[c] fx (256 - fy)
+ *                    + P(y0 + 1, x0)[c] (256 - fx) fy     + P(y0 + 1, x0 + 1)[c] fx fy     + 32768) >> 16
+ * with P(yy, xx) = frames[row(s)][clamp(yy, 0, H - 1)][clamp(xx, 0, W - 1)] under fill = 1 (edge); under fill = 0 (zero)
+ * frames[row(s)][yy][xx] inside [0, H) x [0, W) and 0 outside.  The identity words are (65536, 0, 0, 0, 65536, 0).  uint8
+ * NHWC in ([rows][H][W][C]) and out ([n][H][W][C]: the source frame's size), row(s) = idx[s % period] (idx NULL:
+ * s % period) as for curla_random_shift_u8.  The rule is total: whatever the words hold, nothing is read outside the source
+ * frame (nor in the slack behind a ring), every output byte is written exactly once and nothing is written outside `out`.
+ * One launch: a workgroup stages the source box of a band of output bytes in LDS with 16-byte loads and blends from there
+ * (from global memory directly where no band's box fits 64 KiB, or where the words wrap inside a band); 8 bytes per lane
+ * and store for a frame of a multiple of 16 bytes with `out` on a 16-byte boundary, the same bytes one at a time
+ * otherwise.  Any C > 0.
+ * Additive: CURLA_ABI_VERSION stays 8.  CURLA_ERR_ARG on a NULL pointer, a word array off 4 bytes, `idx` off 8, n, period,
+ * C, H or W < 1, or fill not 0 or 1; CURLA_ERR_UNSUPPORTED when H W C does not fit 31 bits; both before any launch. */
+int curla_affine_u8(const uint8_t* frames, const int64_t* idx, int period, const int32_t* m00, const int32_t* m01,
+                    const int32_t* m02, const int32_t* m10, const int32_t* m11, const int32_t* m12, int fill, int n, int C,
+                    int H, int W, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""The uint8 movers (curla_random_shift_u8, curla_cutout_u8, curla_translate_u8, curla_dihedral_u8, curla_grayscale_u8;
-csrc/u8_mover.h, augment.hip) against
+"""The uint8 movers (curla_random_shift_u8, curla_cutout_u8, curla_translate_u8, curla_dihedral_u8, curla_grayscale_u8,
+curla_affine_u8; csrc/u8_mover.h, csrc/affine.h, augment.hip) against
 one another and against a plain device-to-device copy, and whole updates with their augmentations:
-python tools/u8_mover_bench.py [--kernels shift,cutout,translate,flip,rotate,grey,copy] [--kinds] [--fused] [--launches K]
-                               [--augs identity,random_shift,cutout_color,translate,flip,rotate,grayscale] [--no-updates]
+python tools/u8_mover_bench.py [--kernels shift,cutout,translate,flip,rotate,grey,affine,copy] [--kinds] [--fused] [--launches K]
+                               [--augs identity,random_shift,cutout_color,translate,flip,rotate,grayscale,affine] [--no-updates]
 Kernels: one launch for a 3B minibatch (obs | next_obs | pos from a double ring, period 2B, as ReplayBuffer issues it),
 B = 512, so n = 1536, at 84 x 84 x 9 and 90 x 160 x 9: the shift (pad 4), the cutout (boxes drawn by RandomCutout's defaults,
 min_cut 10, max_cut 30, random colours), the translate onto a canvas 8 pixels larger per side length (-> 92 x 92 and
 98 x 168, offsets in [0, 8]^2) and ``copy_`` of a uint8 tensor of the frame's 3B * frame bytes.  ``flip``: every sample
 mirrored (its worst case; ``flip-mix``, the drawn mix at p = 0.5, comes with it); ``rotate``: every sample transposing
 (codes 5 and 6, the worst case; on a frame that is not square every sample turned by 180 degrees), with ``rotate-mix``,
-the mix RandomRotate draws at p = 0.3; ``grey``: every sample greyed, with ``grey-mix`` at p = 0.3.  ``--kinds`` adds the
+the mix RandomRotate draws at p = 0.3; ``grey``: every sample greyed, with ``grey-mix`` at p = 0.3; ``affine``: the words
+RandomAffine draws with its defaults (10 degrees, scale 0.9 .. 1.1, 5 % shift, edge fill), with ``affine-id`` (the identity
+words: the same loads and blends, the smallest source box) and ``affine-45`` (every sample turned by 45 degrees: the
+largest box).  ``--kinds`` adds the
 translate onto a canvas of the frame's own size (a plain gather: every group is an inside group, one load and one store),
 to tell what the margin and mixed groups cost.  ``--fused`` adds, for each of the three movers of curla_move_cutout_u8
 (the crop to 76 x 76 and 80 x 144 -- output frames of whole 16-byte groups --, the shift, the translate), three forms: the
@@ -101,9 +104,16 @@ for (H, W, C, B) in GEOMETRIES:
         op = ops.grayscale_u8 if k.startswith("grey") else ops.dihedral_u8
         forms[k] = (lambda op=op, w=i32(w): op(ring, idx2, 2 * B, w, n, out_v), n * frame,
                     f"{what}: {100 * float((np.asarray(w) != 0).mean()):.0f} % of the samples transformed")
+    aff = curla_amd.RandomAffine((H, W))
+    aff_words = {"affine": (aff.draw_index_words(n), "the draw at the defaults"),
+                 "affine-id": (np.array(aff.IDENTITY_WORDS)[:, None].repeat(n, 1), "the identity words"),
+                 "affine-45": (aff.words(np.full(n, np.pi / 4), 1.0, 0.0, 0.0), "every sample turned by 45 degrees")}
+    for k, (w, what) in aff_words.items():
+        forms[k] = (lambda w=[i32(x) for x in w]: ops.affine_u8(ring, idx2, 2 * B, w, 1, n, out_v), n * frame, what)
     names = []
     for k in args.kernels.split(","):
-        names += [k, k + "-mix"] if k in ("flip", "rotate", "grey") else [k] if k else []
+        names += ([k, k + "-mix"] if k in ("flip", "rotate", "grey") else [k, k + "-id", k + "-45"] if k == "affine"
+                  else [k] if k else [])
     names += ["gather"] if args.kinds else []
     if args.fused:
         Hc, Wc = CROPS[(H, W)]
