@@ -230,10 +230,11 @@ def forward_conv(enc, obs):
 
 
 # ------------------------------------------------------------------------------------------------------------ actor
-def _grad_mlp(layers, stride=0, base=None):
-    """Fresh gradient tensors laid out like the MLP's parameters (one zeroed buffer; twins ``stride`` floats apart)."""
+def _grad_mlp(layers, stride=0, base=None, span=None):
+    """Fresh gradient tensors laid out like the MLP's parameters (one zeroed buffer; twins ``stride`` floats apart).
+    ``span``: every module of the MLP with parameters, where ``layers`` (its Linears) are not all of them."""
     if base is None:
-        ps = [t for m in layers for t in (m.weight, m.bias)]
+        ps = [t for m in (span or layers) for t in (m.weight, m.bias)]
         p0 = min(p.data_ptr() for p in ps)
         span = max(p.data_ptr() + 4 * p.numel() for p in ps) - p0
         n = span // 4 + stride
@@ -324,8 +325,14 @@ def actor_forward(actor, z, compute_pi, compute_log_pi, noise):
 
 
 # ------------------------------------------------------------------------------------------------------------ critic
+def _q_modules(q):
+    """The modules of a Q function's trunk that hold parameters, in order: its three Linears and, in a LayerNorm
+    critic, the LayerNorm behind each hidden one."""
+    return [m for m in q.trunk if isinstance(m, (torch.nn.Linear, torch.nn.LayerNorm))]
+
+
 def _q_params(critic):
-    return [t for q in (critic.Q1, critic.Q2) for i in (0, 2, 4) for t in (q.trunk[i].weight, q.trunk[i].bias)]
+    return [t for q in (critic.Q1, critic.Q2) for m in _q_modules(q) for t in (m.weight, m.bias)]
 
 
 class CriticFn(torch.autograd.Function):
@@ -339,7 +346,10 @@ class CriticFn(torch.autograd.Function):
         xa = _empty(B, F + A, like=z)
         ops.concat(z, action, B, F, A, xa)
         h1, h2, q = _empty(2, B, H, like=z), _empty(2, B, H, like=z), _empty(2, B, 1, like=z)
-        _mlp_fwd(xa, 0, critic.twin(), 2, B, F + A, H, 1, h1, h2, q)
+        ctx.ln_saves = (None, None)
+        if critic.layer_norm:  # what the LayerNorms' backward reads, per hidden layer
+            ctx.ln_saves = ([_empty(2, B, H, like=z) for _ in range(2)], [_empty(2, B, like=z) for _ in range(2)])
+        _mlp_fwd(xa, 0, critic.twin(), 2, B, F + A, H, 1, h1, h2, q, ln=critic.twin_ln(*ctx.ln_saves))
         ctx.critic, ctx.xa, ctx.h1, ctx.h2, ctx.B = critic, xa, h1, h2, B
         return q[0], q[1]
 
@@ -350,29 +360,33 @@ class CriticFn(torch.autograd.Function):
         critic, B = ctx.critic, ctx.B
         A, H, F = critic.action_dim, critic.hidden_dim, critic.encoder.feature_dim
         need = ctx.needs_input_grad
+        mods = _q_modules(critic.Q1)
         if dq1 is None and dq2 is None:
-            return (None,) * (3 + 12)
+            return (None,) * (3 + 4 * len(mods))
         dq = torch.zeros((2, B, 1), device=ctx.xa.device, dtype=F32)
         if dq1 is not None:
             dq[0].copy_(dq1)
         if dq2 is not None:
             dq[1].copy_(dq2)
-        layers = [critic.Q1.trunk[0], critic.Q1.trunk[2], critic.Q1.trunk[4]]
-        G = _grad_mlp(layers, critic.twin_stride) if any(need[3:]) else None
+        layers = [m for m in mods if isinstance(m, torch.nn.Linear)]
+        G = _grad_mlp(layers, critic.twin_stride, span=mods) if any(need[3:]) else None
         want_x = need[1] or need[2]
         dxa = _empty(2, B, F + A, like=dq) if want_x else None
+        ln = critic.twin_ln(*ctx.ln_saves)
+        if ln is not None and G is not None:
+            ln.dg, ln.db = [G.view(p) for p in ln.g], [G.view(p) for p in ln.b]
+            ln.partial = torch.empty(ops.mlp_ln_partial_floats(B, H, 2), device=dq.device, dtype=F32)
         _mlp_bwd(ctx.xa, 0, critic.twin(), G, 2, B, F + A, H, 1, ctx.h1, ctx.h2, dq, _empty(2, B, H, like=dq),
-                 _empty(2, B, H, like=dq), dxa)
+                 _empty(2, B, H, like=dq), dxa, ln=ln)
         dz = dact = None
         if want_x:
             dz = _empty(B, F, like=dq) if need[1] else None
             dact = _empty(B, A, like=dq) if need[2] else None
             ops.split_sum(dxa, B * (F + A), B, F, A, dz=dz, dact=dact)
-        pg = [None] * 12
+        pg = [None] * (4 * len(mods))
         if G is not None:
             # (Q2's gradients sit twin_stride floats behind Q1's, as the parameters do)
-            pg = [G.view(p, twin) for twin in (0, 1) for i in (0, 2, 4)
-                  for p in (critic.Q1.trunk[i].weight, critic.Q1.trunk[i].bias)]
+            pg = [G.view(p, twin) for twin in (0, 1) for m in mods for p in (m.weight, m.bias)]
         return (None, dz, dact, *pg)
 
 

@@ -18,6 +18,7 @@ namespace {
 
 #include "reduce.h"        // wave_sum, wave_max, block_sum_256; colsum, colsum3, mean and grad_sqsum kernels
 #include "layernorm.h"     // fc_ln_fwd_kernel<NF>, ln_bwd_kernel<NF>, ln_param_grad_kernel
+#include "mlp_ln.h"        // mlp_ln_relu_fwd_kernel<NF>, mlp_ln_bwd_kernel<NF>, mlp_ln_param_grad_kernel (the critics' LayerNorm)
 #include "mlp_out.h"       // mlp_out_fwd_kernel<HEAD, R, LDSW>, mlp_out_bwd_kernel<GEN>, the policy head's three kernels
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
 #include "curl_head.h"     // curl_head_kernel<NTILE>
@@ -283,6 +284,37 @@ int curla_ln_bwd_partial(const float* dy, const float* dy2, int ld_dy, const flo
 int curla_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, int B, int F, float* dx,
                  float* dgamma, float* dbeta, float* dbias_in, void* stream) {
   return curla_ln_bwd_twin(dy, nullptr, F, xhat, rstd, gamma, B, F, dx, dgamma, dbeta, dbias_in, stream);
+}
+
+int curla_mlp_ln_relu_fwd(float* h, long long strideH, long long strideH2, const float* gamma, const float* beta,
+                          long long strideP, long long strideP2, float* xhat, float* rstd, int save_first, int B, int H,
+                          int nbatch, int nbatch2, float eps, void* stream) {
+  CURLA_REQUIRE(h && gamma && beta && B > 0 && H > 0 && nbatch > 0 && nbatch2 > 0);
+  CURLA_REQUIRE(!xhat == !rstd && (!xhat || (save_first >= 0 && save_first < nbatch2)));
+  if (H > 1024) return CURLA_ERR_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return dispatch_ln_width(H, [&](auto nf) {
+    return launch(mlp_ln_relu_fwd_kernel<nf()>, dim3((B + 3) / 4, nbatch * nbatch2), 256, 0, st, h, strideH, strideH2, gamma,
+                  beta, strideP, strideP2, xhat, rstd, save_first, B, H, nbatch, eps);
+  });
+}
+
+int curla_mlp_ln_bwd(float* dh, long long strideDh, const float* xhat, const float* rstd, const float* gamma,
+                     long long strideP, int B, int H, int nbatch, float* partial, float* dgamma, float* dbeta,
+                     float* dbias, long long strideG, void* stream) {
+  CURLA_REQUIRE(dh && xhat && rstd && gamma && B > 0 && H > 0 && nbatch > 0);
+  const bool params = partial || dgamma || dbeta || dbias;
+  CURLA_REQUIRE(!params || (partial && dgamma && dbeta && dbias));
+  if (H > 1024) return CURLA_ERR_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nparts = (B + 3) / 4;
+  const int rc = dispatch_ln_width(H, [&](auto nf) {
+    return launch(mlp_ln_bwd_kernel<nf()>, dim3(nparts, nbatch), 256, 0, st, dh, strideDh, xhat, rstd, gamma, strideP, B, H,
+                  partial);
+  });
+  if (rc != CURLA_OK || !params) return rc;
+  return launch(mlp_ln_param_grad_kernel, dim3((3 * H + 255) / 256, nbatch), 256, 0, st,
+                static_cast<const float*>(partial), nparts, H, dgamma, dbeta, dbias, strideG);
 }
 
 int curla_colsum(const float* X, int M, int N, int ldx, long long strideX, float* out, long long strideOut, int nbatch,

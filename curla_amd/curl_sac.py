@@ -66,25 +66,71 @@ class _Mlp:
     twins, ``stride`` floats apart)."""
 
     def __init__(self, seq, stride=0, grads=False):
-        lin = [seq[0], seq[2], seq[4]]
+        lin = _linears(seq)
         pick = (lambda p: p.grad) if grads else (lambda p: p)
         self.W = [pick(layer.weight) for layer in lin]
         self.b = [pick(layer.bias) for layer in lin]
         self.stride = stride
 
 
-def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None, head=None):
+def _linears(seq):
+    """The three Linears of a trunk, by type: a LayerNorm critic's sit at 0, 3, 6 instead of 0, 2, 4."""
+    lin = [m for m in seq if isinstance(m, nn.Linear)]
+    assert len(lin) == 3, "a 3-layer MLP"
+    return lin
+
+
+class _MlpLn:
+    """The LayerNorm side of a _Mlp whose hidden layers are Linear - LayerNorm - ReLU (Critic(layer_norm=True)), layer
+    by layer: the LayerNorms' parameters ``g`` / ``b`` (twins and groups addressed as the _Mlp's), the buffers
+    ``xhat`` [2, B, H] / ``rstd`` [2, B] a forward saves for its backward (None: a no-grad pass) and, for a backward
+    that wants parameter gradients, their destinations ``dg`` / ``db`` and the ``partial`` workspace
+    (ops.mlp_ln_partial_floats).  ``save_first``: with _mlp_fwd's ``outer``, the first group that saves."""
+
+    def __init__(self, seq, xhat=None, rstd=None, dg=None, db=None, partial=None, save_first=0):
+        ln = [m for m in seq if isinstance(m, nn.LayerNorm)]
+        assert len(ln) == 2, "a LayerNorm behind each hidden layer"
+        self.g = [m.weight for m in ln]
+        self.b = [m.bias for m in ln]
+        self.xhat, self.rstd, self.dg, self.db, self.partial, self.save_first = xhat, rstd, dg, db, partial, save_first
+
+    def fwd(self, i, h, s, nb, B, H, outer):
+        """LayerNorm + ReLU of hidden layer ``i`` in place on ``h``, which linear_fwd(relu=0) has just written."""
+        saves = self.xhat is not None
+        ops.mlp_ln_relu_fwd(h, B * H, self.g[i], self.b[i], s, B, H, nb, xhat=self.xhat[i] if saves else None,
+                            rstd=self.rstd[i] if saves else None,
+                            outer=None if outer is None else (outer[0], nb * B * H, outer[1]),
+                            save_first=self.save_first if outer is not None and saves else 0)
+
+    def bwd(self, i, dh, s, nb, B, H, dbias):
+        """``dh`` (ReLU-masked by the layer behind) -> the gradient of Linear ``i``'s output, in place; with ``dbias``
+        (that Linear's bias gradient) also the LayerNorm's parameter gradients."""
+        if dbias is None:
+            ops.mlp_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, nb)
+        else:
+            ops.mlp_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, nb, partial=self.partial,
+                           dgamma=self.dg[i], dbeta=self.db[i], dbias=dbias, sg=s)
+
+
+def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None, head=None, ln=None):
     """``outer`` = (n2, sW2): n2 such MLP groups in the same launches, their parameters sW2 floats apart (the target
     critic's and the critic's twins); x [n2][B, din] and h1 / h2 / out [n2][nb][B, .] then.
     ``head`` = (noise, lo, hi, outputs): the MLP is the actor trunk and the policy head (ops.actor_head_fwd with these
-    arguments) follows its last layer -- in the same launch when the layer is small enough."""
+    arguments) follows its last layer -- in the same launch when the layer is small enough.
+    ``ln`` (_MlpLn): a LayerNorm sits between each hidden Linear and its ReLU -- the GEMM leaves the ReLU out and one
+    launch per hidden layer normalises in place."""
     s = P.stride
     o0 = o1 = o2 = None
     if outer is not None:
         n2, sW2 = outer
         o0, o1, o2 = (n2, B * din, sW2, nb * B * H), (n2, nb * B * H, sW2, nb * B * H), (n2, nb * B * H, sW2, nb * B * dout)
-    ops.linear_fwd(x, sx, P.W[0], s, P.b[0], s, h1, B * H, B, H, din, nb, relu=1, outer=o0)
-    ops.linear_fwd(h1, B * H, P.W[1], s, P.b[1], s, h2, B * H, B, H, H, nb, relu=1, outer=o1)
+    relu = 1 if ln is None else 0
+    ops.linear_fwd(x, sx, P.W[0], s, P.b[0], s, h1, B * H, B, H, din, nb, relu=relu, outer=o0)
+    if ln is not None:
+        ln.fwd(0, h1, s, nb, B, H, outer)
+    ops.linear_fwd(h1, B * H, P.W[1], s, P.b[1], s, h2, B * H, B, H, H, nb, relu=relu, outer=o1)
+    if ln is not None:
+        ln.fwd(1, h2, s, nb, B, H, outer)
     small = dout <= ops.MLP_OUT_MAX and H % 4 == 0 and not relu_out
     if head is not None and small and nb == 1 and outer is None:
         noise, lo, hi, outs = head
@@ -99,11 +145,16 @@ def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None,
         ops.actor_head_fwd(out, noise, B, dout // 2, lo, hi, **outs)
 
 
-def _mlp_bwd(x, sx, P, G, nb, B, din, H, dout, h1, h2, dy, dh2, dh1, dx, loss=None):
+def _mlp_bwd(x, sx, P, G, nb, B, din, H, dout, h1, h2, dy, dh2, dh1, dx, loss=None, ln=None):
     """Backward of _mlp_fwd.  G (parameter gradients) and dx are optional.
     ``loss`` = (fields, launch): the output gradient dy is that of a loss over the twin Q values -- ``fields`` for
     ops.mlp_out_bwd_loss, which computes it inside the last layer's backward launch; ``launch()`` runs the loss kernel
-    on its own where that form does not apply."""
+    on its own where that form does not apply.
+    ``ln`` (_MlpLn, with the forward's xhat / rstd): h1 / h2 are the post-LayerNorm ReLU outputs, so the masks below
+    (h2 > 0, mask=h1) are still the ReLUs' and leave dh2 / dh1 as the gradients of the LayerNorms' outputs; one
+    launch per hidden layer turns each, in place, into the gradient of its Linear's output.  The hidden Linears' bias
+    gradients are then column sums of THAT, not of the masked dh: they come from the same launch, and the folds of
+    them into the neighbouring launches are off."""
     s = P.stride
     fused_loss = loss is not None and dout == 1 and nb == 2
     if loss is not None and not fused_loss:
@@ -111,30 +162,38 @@ def _mlp_bwd(x, sx, P, G, nb, B, din, H, dout, h1, h2, dy, dh2, dh1, dx, loss=No
     # the three bias gradients (column sums of dy, dh2, dh1) ride in the launches that walk those matrices anyway --
     # the last layer's backward pass and the first layer's weight-gradient product -- where both take their small forms
     fold = G is not None and dout <= ops.MLP_OUT_MAX and ops.linear_dw_folds_bias(B, H, din, nb)
+    fold_h = fold and ln is None
     if fused_loss:
         ops.mlp_out_bwd_loss(loss[0], h2, B * H, P.W[2], s, dh2, B * H, G.W[2] if G is not None else None, s, B, H,
-                             db_out=G.b[2] if fold else None, db_hidden=G.b[1] if fold else None, sdb=s)
+                             db_out=G.b[2] if fold else None, db_hidden=G.b[1] if fold_h else None, sdb=s)
     elif dout <= ops.MLP_OUT_MAX:  # last layer: data and weight gradient in one pass over h2
         ops.mlp_out_bwd(dy, B * dout, h2, B * H, P.W[2], s, dh2, B * H, G.W[2] if G is not None else None, s, B, dout,
-                        H, nb, db_out=G.b[2] if fold else None, db_hidden=G.b[1] if fold else None, sdb=s)
+                        H, nb, db_out=G.b[2] if fold else None, db_hidden=G.b[1] if fold_h else None, sdb=s)
     else:
         if G is not None:
             ops.linear_dw(dy, B * dout, h2, B * H, G.W[2], s, B, dout, H, nb)
         ops.linear_dx(dy, B * dout, P.W[2], s, dh2, B * H, B, dout, H, nb, mask=h2, smask=B * H)
+    if ln is not None:
+        ln.bwd(1, dh2, s, nb, B, H, G.b[1] if G is not None else None)
     # a layer's weight and data gradient are independent products over the same dy: one launch for the pair
     if G is not None:
         ops.linear_bwd(dh2, B * H, h1, B * H, P.W[1], s, G.W[1], s, dh1, B * H, B, H, H, nb, mask=h1, smask=B * H)
     else:
         ops.linear_dx(dh2, B * H, P.W[1], s, dh1, B * H, B, H, H, nb, mask=h1, smask=B * H)
+    if ln is not None:
+        ln.bwd(0, dh1, s, nb, B, H, G.b[0] if G is not None else None)
     if G is not None and dx is not None:
         ops.linear_bwd(dh1, B * H, x, sx, P.W[0], s, G.W[0], s, dx, B * din, B, H, din, nb,
-                       db=G.b[0] if fold else None, sdb=s)
+                       db=G.b[0] if fold_h else None, sdb=s)
     elif G is not None:
-        ops.linear_dw(dh1, B * H, x, sx, G.W[0], s, B, H, din, nb, colsum=G.b[0] if fold else None, s_colsum=s)
+        ops.linear_dw(dh1, B * H, x, sx, G.W[0], s, B, H, din, nb, colsum=G.b[0] if fold_h else None, s_colsum=s)
     elif dx is not None:
         ops.linear_dx(dh1, B * H, P.W[0], s, dx, B * din, B, H, din, nb)
     if G is not None and not fold:
-        ops.colsum3(dy, dout, dh2, H, dh1, H, B, G.b[2], G.b[1], G.b[0], s, nb)
+        if ln is None:
+            ops.colsum3(dy, dout, dh2, H, dh1, H, B, G.b[2], G.b[1], G.b[0], s, nb)
+        else:  # (the hidden layers' bias gradients are there already)
+            ops.colsum(dy, B, dout, dout, B * dout, G.b[2], s, nb)
 
 
 class Actor(nn.Module):
@@ -195,27 +254,39 @@ class Actor(nn.Module):
 
 
 class QFunction(nn.Module):
-    """MLP for q-function (curl_sac.py:124-139); parameter container."""
+    """MLP for q-function (curl_sac.py:124-139); parameter container.  ``layer_norm``: an ``nn.LayerNorm(hidden_dim)``
+    between each hidden Linear and its ReLU (the Linears are then trunk.0 / .3 / .6, the LayerNorms trunk.1 / .4)."""
 
-    def __init__(self, obs_dim, action_dim, hidden_dim):
+    def __init__(self, obs_dim, action_dim, hidden_dim, layer_norm=False):
         super().__init__()
+        _check_layer_norm_width(layer_norm, hidden_dim)
+        norm = (lambda: [nn.LayerNorm(hidden_dim)]) if layer_norm else (lambda: [])
         self.trunk = nn.Sequential(
-            nn.Linear(obs_dim + action_dim, hidden_dim), nn.ReLU(),
-            nn.Linear(hidden_dim, hidden_dim), nn.ReLU(),
+            nn.Linear(obs_dim + action_dim, hidden_dim), *norm(), nn.ReLU(),
+            nn.Linear(hidden_dim, hidden_dim), *norm(), nn.ReLU(),
             nn.Linear(hidden_dim, 1)
         )
 
 
-class Critic(nn.Module):
-    """Critic network, employs two Q-functions (curl_sac.py:142-180)."""
+def _check_layer_norm_width(layer_norm, hidden_dim):
+    if layer_norm and hidden_dim > ops.MLP_LN_MAX:
+        raise ValueError("critic LayerNorm: hidden_dim = %d is wider than the %d features the LayerNorm kernels take "
+                         "(one wave per row)" % (hidden_dim, ops.MLP_LN_MAX))
 
-    def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters):
+
+class Critic(nn.Module):
+    """Critic network, employs two Q-functions (curl_sac.py:142-180).  ``layer_norm``: QFunction's."""
+
+    def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
+                 layer_norm=False):
         super().__init__()
+        _check_layer_norm_width(layer_norm, hidden_dim)
         self.encoder = CNNEncoder(obs_shape, encoder_feature_dim, num_layers, num_filters, output_logits=True)
-        self.Q1 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim)
-        self.Q2 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim)
+        self.Q1 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim, layer_norm)
+        self.Q2 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim, layer_norm)
         self.action_dim = action_shape[0]
         self.hidden_dim = hidden_dim
+        self.layer_norm = bool(layer_norm)
         self.outputs = dict()
         self.twin_stride = None  # floats between Q1 and Q2 tensors once flattened by the agent
         self.apply(weight_init)
@@ -224,6 +295,16 @@ class Critic(nn.Module):
         if self.twin_stride is None:
             raise RuntimeError("Critic parameters are not in the flat twin layout (constructed outside CurlSacAgent)")
         return _Mlp(self.Q1.trunk, self.twin_stride, grads)
+
+    def twin_ln(self, xhat=None, rstd=None, grads=False, partial=None, save_first=0):
+        """The ``ln=`` argument of _mlp_fwd / _mlp_bwd for ``twin()``: None without LayerNorm.  ``xhat`` / ``rstd``:
+        a pair of buffers each, one per hidden layer; ``grads``: the backward fills the LayerNorm tensors' .grad."""
+        if not self.layer_norm:
+            return None
+        ln = _MlpLn(self.Q1.trunk, xhat, rstd, partial=partial, save_first=save_first)
+        if grads:
+            ln.dg, ln.db = [p.grad for p in ln.g], [p.grad for p in ln.b]
+        return ln
 
     def forward(self, obs, action, detach_encoder=False):
         assert obs.size(0) == action.size(0)  # curl_sac.py:136
@@ -239,7 +320,7 @@ class Critic(nn.Module):
         h1 = torch.empty((2, B, H), device=dev)
         h2 = torch.empty((2, B, H), device=dev)
         q = torch.empty((2, B, 1), device=dev)
-        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, 1, h1, h2, q)
+        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, 1, h1, h2, q, ln=self.twin_ln())
         self.outputs['q1'], self.outputs['q2'] = q[0], q[1]
         return q[0], q[1]
 
@@ -250,9 +331,9 @@ class Critic(nn.Module):
             return
         for name, value in self.outputs.items():
             L.log_histogram('train_critic/%s_hist' % name, value, step)
-        for layer in range(3):
+        for layer in range(3):  # (the three Linears; a LayerNorm critic's LayerNorms are not histogrammed)
             for tag, q in (('q1', self.Q1), ('q2', self.Q2)):
-                L.log_param('train_critic/%s_fc%d' % (tag, layer), q.trunk[2 * layer], step)
+                L.log_param('train_critic/%s_fc%d' % (tag, layer), _linears(q.trunk)[layer], step)
 
 
 class CURL(nn.Module):
@@ -332,6 +413,14 @@ class _Workspace:
         self.tq, self.q = self.q2[0], self.q2[1]
         self.dxa = f(2, B, F + A)
         self.q_dh1, self.q_dh2 = f(2, B, H), f(2, B, H)
+        # critic_layer_norm: what the critic's LayerNorms save for their backward, per hidden layer (the critic and the
+        # actor phase share them; the target critic's passes save nothing) and the workspace of their parameter
+        # gradients' partial sums -- as Critic.twin_ln takes them
+        self.q_ln_saves, self.q_ln_partial = (None, None), None
+        if agent.critic_layer_norm:
+            self.q_xhat1, self.q_xhat2, self.q_rstd1, self.q_rstd2 = f(2, B, H), f(2, B, H), f(2, B), f(2, B)
+            self.q_ln_saves = ([self.q_xhat1, self.q_xhat2], [self.q_rstd1, self.q_rstd2])
+            self.q_ln_partial = f(ops.mlp_ln_partial_floats(B, H, 2))
         self.dq, self.target_q = f(2, B, 1), f(B, 1)
         self.per_w = self.per_value = None  # importance weights / new stored values [B]: a prioritized buffer's updates only
         # scalars: [0] critic loss, [1..4] actor_loss/alpha_loss/entropy/alpha, [5] curl loss, [6] batch reward
@@ -350,8 +439,26 @@ class _NullLog:
     log_histogram = log_param = log_image = log
 
 
-class CurlSacAgent(object):
-    """CURL representation learning with SAC (curl_sac.py:224-465)."""
+class _AgentType(type):
+    """``CurlSacAgent(...)`` takes the reference's arguments and, behind them, this package's own keywords.
+    ``CurlSacAgent.__init__`` keeps the reference's parameter list name for name (curl_sac.py:226-256: the drop-in
+    contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
+    builds them, so the class call takes it off the arguments and leaves it on the instance."""
+
+    def __call__(cls, *args, critic_layer_norm=False, **kwargs):
+        agent = cls.__new__(cls)
+        agent.critic_layer_norm = bool(critic_layer_norm)
+        agent.__init__(*args, **kwargs)
+        return agent
+
+
+class CurlSacAgent(object, metaclass=_AgentType):
+    """CURL representation learning with SAC (curl_sac.py:224-465).
+    ``CurlSacAgent(..., critic_layer_norm=True)`` (a keyword of the class call, not in the reference; default off:
+    nothing changes): an ``nn.LayerNorm(hidden_dim)`` between each hidden Linear of the Q functions and its ReLU, critic
+    and target critic alike -- the critic regulariser of DroQ / RLPD.  ``hidden_dim`` up to 1024 then."""
+
+    critic_layer_norm = False
 
     def __init__(
         self,
@@ -384,6 +491,7 @@ class CurlSacAgent(object):
         detach_encoder=False,
         pixel_sac=False
     ):
+        _check_layer_norm_width(self.critic_layer_norm, hidden_dim)
         self.augmentor = augmentor
         self.device = torch.device(device)
         self.discount = discount
@@ -405,8 +513,10 @@ class CurlSacAgent(object):
         # same construction order as the reference => same RNG stream => same init for a given seed
         self.actor = Actor(obs_shape, action_shape, hidden_dim, encoder_feature_dim, actor_log_std_min,
                            actor_log_std_max, num_layers, num_filters)
-        self.critic = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters)
-        self.critic_target = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters)
+        self.critic = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
+                             layer_norm=self.critic_layer_norm)
+        self.critic_target = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
+                                    layer_norm=self.critic_layer_norm)
         self.critic_target.load_state_dict(self.critic.state_dict())
 
         # tie encoders between actor and critic, and CURL and critic
@@ -1044,20 +1154,22 @@ class CurlSacAgent(object):
                        dict(pi=None if four else ws.pi, log_pi=ws.log_pi, xa=ws.xa2[0] if four else None, rng=rng)))
         if four:
             _mlp_fwd(ws.xa2, 0, self.critic_target.twin(), 2, B, F + A, H, 1, ws.q_h1_2, ws.q_h2_2, ws.q2,
-                     outer=(2, self._twin_outer))
+                     outer=(2, self._twin_outer), ln=self.critic_target.twin_ln(*ws.q_ln_saves, save_first=1))
         else:
             if not merged:
                 tenc.conv_forward(no, ws.acts_tmp)
                 tenc.fc_partial(ws.acts_tmp[-1])
             tenc.ln_from_partial(B, ws.z_t, xa=ws.xa, act=ws.pi)  # xa = cat([z, a'], 1)
-            _mlp_fwd(ws.xa, 0, self.critic_target.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.tq)
+            _mlp_fwd(ws.xa, 0, self.critic_target.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.tq,
+                     ln=self.critic_target.twin_ln())
             # -- current Q estimates + loss + backward (curl_sac.py:357-367)
             if not merged:
                 enc.conv_forward(o, ws.acts_main)
                 enc.fc_partial(ws.acts_main[-1])
             enc.ln_from_partial(B, ws.z_c, xhat=ws.xhat_c, rstd=ws.rstd_c, fc_out=ws.fc_out if rec else None,
                                 xa=ws.xa, act=action)
-            _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q)
+            _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q,
+                     ln=self.critic.twin_ln(*ws.q_ln_saves))
         if rec:  # what critic.log() / encoder.log() histogram: the outputs of THIS forward (curl_sac.py:163-167)
             self.critic.outputs['q1'], self.critic.outputs['q2'] = ws.q[0].clone(), ws.q[1].clone()
             enc.record_from(o, ws.acts_main, ws.fc_out, ws.z_c)
@@ -1079,7 +1191,8 @@ class CurlSacAgent(object):
             per.td_update(ws.q, B, ws.target_q, ws.dq, ws.scalars[0:1], ws.per_w, ws.per_value)
             td = None
         _mlp_bwd(ws.xa, 0, self.critic.twin(), self.critic.twin(grads=True), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.dq,
-                 ws.q_dh2, ws.q_dh1, ws.dxa, loss=td)
+                 ws.q_dh2, ws.q_dh1, ws.dxa, loss=td,
+                 ln=self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial))
         if step % self.log_interval == 0:
             L.log('train_critic/loss', ws.scalars[0], step)
         # (d(loss)/d(z) = dxa[0][:, :F] + dxa[1][:, :F], torch.cat's backward: summed inside the LayerNorm backward)
@@ -1166,7 +1279,8 @@ class CurlSacAgent(object):
                                         xa=ws.xa, rng=rng)))
         if self._records(step):  # what actor.log() histograms (curl_sac.py:92-93): pre-squash mean and std
             self.actor.outputs['mu'], self.actor.outputs['std'] = ws.a_out[:, :A].clone(), ws.log_std.exp()
-        _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q)
+        q_ln = self.critic.twin_ln(*ws.q_ln_saves)  # (the data gradient through the LayerNorms needs them too)
+        _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q, ln=q_ln)
         # actor / alpha losses and d(loss)/dQ: inside the backward launch of the Q functions' last layer
         # backward: Q -> pi -> trunk -> LN -> fc (encoder detached, curl_sac.py:375-376)
         al = (dict(kind=2, A=A, twin_stride=B, q=ws.q, log_pi=ws.log_pi, log_std=ws.log_std, log_alpha=self.log_alpha,
@@ -1175,7 +1289,7 @@ class CurlSacAgent(object):
               lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, self.log_alpha, float(self.target_entropy), B,
                                      ws.scalars[1:5], ws.dq, self.log_alpha.grad))
         _mlp_bwd(ws.xa, 0, self.critic.twin(), None, 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.dq, ws.q_dh2, ws.q_dh1,
-                 ws.dxa, loss=al)
+                 ws.dxa, loss=al, ln=q_ln)
         if step % self.log_interval == 0:
             L.log('train_actor/loss', ws.scalars[1], step)
             L.log('train_actor/target_entropy', self.target_entropy, step)

@@ -466,6 +466,33 @@ def ln_bwd(dy, xhat, rstd, gamma, B, F, dx, dgamma=None, dbeta=None, dbias_in=No
              ptr(dx), ptr(dgamma), ptr(dbeta), ptr(dbias_in), stream())
 
 
+MLP_LN_MAX = 1024  # widest hidden layer the critics' LayerNorm kernels take (one wave per row, 16 features per lane)
+
+
+def mlp_ln_partial_floats(B, H, nb=1):
+    """Size of the workspace ``mlp_ln_bwd`` needs for its parameter gradients: [nb][ceil(B / 4)][3][H]."""
+    return nb * ((B + 3) // 4) * 3 * H
+
+
+def mlp_ln_relu_fwd(h, sh, gamma, beta, sp, B, H, nb=1, xhat=None, rstd=None, outer=None, save_first=0, eps=1e-5):
+    """h[z] <- relu(LayerNorm(h[z]) * gamma[z] + beta[z]) in place on a hidden activation [nb][B, H] that
+    ``linear_fwd(..., relu=0)`` has just written.  ``xhat`` / ``rstd`` (both or neither): saved for the backward.
+    ``outer`` = (n2, sh2, sp2): a second batch level as in linear_fwd; the groups from ``save_first`` on save
+    xhat [n2 - save_first][nb][B, H] and rstd [n2 - save_first][nb][B], the ones in front are no-grad passes."""
+    n2, sh2, sp2 = (1, 0, 0) if outer is None else outer
+    call("curla_mlp_ln_relu_fwd", ptr(h), sh, sh2, ptr(gamma), ptr(beta), sp, sp2, ptr(xhat), ptr(rstd), save_first,
+         B, H, nb, n2, eps, stream())
+
+
+def mlp_ln_bwd(dh, sdh, xhat, rstd, gamma, sp, B, H, nb=1, partial=None, dgamma=None, dbeta=None, dbias=None, sg=0):
+    """Backward of mlp_ln_relu_fwd in place: ``dh`` [nb][B, H], already ReLU-masked by the layer behind, becomes the
+    gradient of the Linear's output.  With ``partial`` (mlp_ln_partial_floats floats) also ``dgamma``, ``dbeta`` and
+    ``dbias`` [H] (twin stride ``sg``): sum_b dh xhat, sum_b dh and the column sums of the new dh -- the bias gradient
+    of the Linear in front.  All four None: the data gradient only."""
+    call("curla_mlp_ln_bwd", ptr(dh), sdh, ptr(xhat), ptr(rstd), ptr(gamma), sp, B, H, nb, ptr(partial), ptr(dgamma),
+         ptr(dbeta), ptr(dbias), sg, stream())
+
+
 def colsum(X, M, N, ldx, sX, out, sOut, nb=1):
     call("curla_colsum", ptr(X), M, N, ldx, sX, ptr(out), sOut, nb, stream())
 

@@ -310,6 +310,33 @@ int curla_ln_bwd_twin(const float* dy, const float* dy2, int ld_dy, const float*
  * backward that follows (curla_fc_bwd_ln / curla_fc_dw_ln) adds them up in one extra workgroup of its own launch. */
 int curla_ln_bwd_partial(const float* dy, const float* dy2, int ld_dy, const float* xhat, const float* rstd,
                          const float* gamma, int B, int F, float* dx, float* partial, int* nparts, void* stream);
+/* LayerNorm(eps) + ReLU behind a hidden layer of the Q functions' MLPs, in place: the reference's trunk
+ * (curl_sac.py:129-139) extended to Linear - LayerNorm - ReLU per hidden layer (CurlSacAgent(critic_layer_norm=True)).
+ * h[o][z] [B][H] at h + z * strideH + o * strideH2 (z < nbatch twins, o < nbatch2 groups of twins) holds the Linear's
+ * output, bias included, and receives relu(xhat * gamma[o][z] + beta[o][z]); gamma / beta [H] at
+ * + z * strideP + o * strideP2, addressed like the weights of curla_gemm_nested.  xhat / rstd (both or neither; NULL:
+ * a no-grad pass writes neither): saved for the groups o >= save_first only, dense, xhat[o - save_first][z][B][H] and
+ * rstd[o - save_first][z][B] (0 <= save_first < nbatch2: the groups in front are no-grad passes in the same launch, the
+ * target critic's).  One wave per row; H <= 1024, CURLA_ERR_UNSUPPORTED above.  CURLA_ERR_ARG on a NULL h / gamma / beta,
+ * B < 1, H < 1, nbatch < 1, nbatch2 < 1, one of xhat / rstd without the other, save_first out of range.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_mlp_ln_relu_fwd(float* h, long long strideH, long long strideH2, const float* gamma, const float* beta,
+                          long long strideP, long long strideP2, float* xhat, float* rstd, int save_first, int B, int H,
+                          int nbatch, int nbatch2, float eps, void* stream);
+/* Its backward (curl_sac.py:129-139 as extended above), in place: dh[z] [B][H] at dh + z * strideDh arrives as the
+ * gradient of the LayerNorm's output, the ReLU's mask already applied by the layer behind (whose mask is h > 0 with h the
+ * post-LayerNorm activation), and leaves as the gradient of the Linear's output,
+ * rstd * (g - mean(g) - xhat * mean(g * xhat)) with g = dh * gamma[z]; xhat [nbatch][B][H], rstd [nbatch][B] dense as
+ * the forward saved them, gamma [H] at + z * strideP.  dgamma, dbeta, dbias ([H] at + z * strideG; all three with
+ * `partial`, or all four NULL: the data gradient only) = sum_b dh_in * xhat, sum_b dh_in, sum_b dh_out -- the last is
+ * the bias gradient of the Linear in front.  `partial`: nbatch * ceil(B / 4) * 3 * H floats of workspace; a workgroup's
+ * four rows are added in row order and a second small launch adds the workgroups' sums in order: no atomics, the
+ * same bits run to run.  H <= 1024, CURLA_ERR_UNSUPPORTED above.  CURLA_ERR_ARG on a NULL dh / xhat / rstd / gamma,
+ * B < 1, H < 1, nbatch < 1, or some but not all of partial / dgamma / dbeta / dbias.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_mlp_ln_bwd(float* dh, long long strideDh, const float* xhat, const float* rstd, const float* gamma,
+                     long long strideP, int B, int H, int nbatch, float* partial, float* dgamma, float* dbeta,
+                     float* dbias, long long strideG, void* stream);
 /* out[z][n] = sum_m X[z][m][n] (bias gradients) */
 int curla_colsum(const float* X, int M, int N, int ldx, long long strideX, float* out, long long strideOut, int nbatch,
                  void* stream);
