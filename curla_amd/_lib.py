@@ -108,6 +108,10 @@ SIGNATURES = {
     "curla_ln_bwd_partial": [vp, vp, c_int, vp, vp, vp, c_int, c_int, vp, vp, vp, vp],
     "curla_mlp_ln_relu_fwd": [vp, c_ll, c_ll, vp, vp, c_ll, c_ll, vp, vp, c_int, c_int, c_int, c_int, c_int, c_float, vp],
     "curla_mlp_ln_bwd": [vp, c_ll, vp, vp, vp, c_ll, c_int, c_int, c_int, vp, vp, vp, vp, c_ll, vp],
+    "curla_mlp_drop_ln_relu_fwd": [vp, c_ll, c_ll, vp, vp, c_ll, c_ll, vp, vp, c_int, c_int, c_int, c_int, c_int, c_float,
+                                   c_float, c_u64, c_u64, vp, c_int, vp],
+    "curla_mlp_drop_ln_bwd": [vp, c_ll, vp, vp, vp, c_ll, c_int, c_int, c_int, vp, vp, vp, vp, c_ll, c_float, c_u64, c_u64,
+                              vp, c_int, vp],
     "curla_colsum": [vp, c_int, c_int, c_int, c_ll, vp, c_ll, c_int, vp],
     "curla_colsum3": [vp, c_int, vp, c_int, vp, c_int, c_int, vp, vp, vp, c_ll, c_int, vp],
     "curla_actor_head_fwd": [vp, vp, c_int, c_int, c_float, c_float, vp, vp, vp, vp, vp, vp, c_int, vp],

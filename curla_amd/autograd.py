@@ -336,10 +336,12 @@ def _q_params(critic):
 
 
 class CriticFn(torch.autograd.Function):
-    """(q1, q2) of the twin Q functions on [z | action] (curl_sac.py:129-139,157-169) in their flat twin layout."""
+    """(q1, q2) of the twin Q functions on [z | action] (curl_sac.py:129-139,157-169) in their flat twin layout.
+    ``drop`` = (p, (seed, counter), tag) or None: a dropout critic's masks (Critic.twin_ln), kept for the backward,
+    which draws them again."""
 
     @staticmethod
-    def forward(ctx, critic, z, action, *q_params):
+    def forward(ctx, critic, z, action, drop, *q_params):
         from .curl_sac import _mlp_fwd
         ctx.set_materialize_grads(False)
         B, A, H, F = z.shape[0], critic.action_dim, critic.hidden_dim, critic.encoder.feature_dim
@@ -349,8 +351,9 @@ class CriticFn(torch.autograd.Function):
         ctx.ln_saves = (None, None)
         if critic.layer_norm:  # what the LayerNorms' backward reads, per hidden layer
             ctx.ln_saves = ([_empty(2, B, H, like=z) for _ in range(2)], [_empty(2, B, like=z) for _ in range(2)])
-        _mlp_fwd(xa, 0, critic.twin(), 2, B, F + A, H, 1, h1, h2, q, ln=critic.twin_ln(*ctx.ln_saves))
-        ctx.critic, ctx.xa, ctx.h1, ctx.h2, ctx.B = critic, xa, h1, h2, B
+        _mlp_fwd(xa, 0, critic.twin(), 2, B, F + A, H, 1, h1, h2, q,
+                 ln=critic.twin_ln(*ctx.ln_saves, drop=drop))
+        ctx.critic, ctx.xa, ctx.h1, ctx.h2, ctx.B, ctx.drop = critic, xa, h1, h2, B, drop
         return q[0], q[1]
 
     @staticmethod
@@ -362,17 +365,17 @@ class CriticFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         mods = _q_modules(critic.Q1)
         if dq1 is None and dq2 is None:
-            return (None,) * (3 + 4 * len(mods))
+            return (None,) * (4 + 4 * len(mods))
         dq = torch.zeros((2, B, 1), device=ctx.xa.device, dtype=F32)
         if dq1 is not None:
             dq[0].copy_(dq1)
         if dq2 is not None:
             dq[1].copy_(dq2)
         layers = [m for m in mods if isinstance(m, torch.nn.Linear)]
-        G = _grad_mlp(layers, critic.twin_stride, span=mods) if any(need[3:]) else None
+        G = _grad_mlp(layers, critic.twin_stride, span=mods) if any(need[4:]) else None
         want_x = need[1] or need[2]
         dxa = _empty(2, B, F + A, like=dq) if want_x else None
-        ln = critic.twin_ln(*ctx.ln_saves)
+        ln = critic.twin_ln(*ctx.ln_saves, drop=ctx.drop)
         if ln is not None and G is not None:
             ln.dg, ln.db = [G.view(p) for p in ln.g], [G.view(p) for p in ln.b]
             ln.partial = torch.empty(ops.mlp_ln_partial_floats(B, H, 2), device=dq.device, dtype=F32)
@@ -387,12 +390,12 @@ class CriticFn(torch.autograd.Function):
         if G is not None:
             # (Q2's gradients sit twin_stride floats behind Q1's, as the parameters do)
             pg = [G.view(p, twin) for twin in (0, 1) for m in mods for p in (m.weight, m.bias)]
-        return (None, dz, dact, *pg)
+        return (None, dz, dact, None, *pg)
 
 
-def critic_forward(critic, z, action):
+def critic_forward(critic, z, action, drop=None):
     action = action.contiguous().float()
-    return CriticFn.apply(critic, z, action, *_q_params(critic))
+    return CriticFn.apply(critic, z, action, drop, *_q_params(critic))
 
 
 # ------------------------------------------------------------------------------------------------------------ CURL

@@ -116,8 +116,10 @@ int dispatch_int(int value, F&& f) {
 
 // ---- counter-based normal draws (policy head, heads.hip; NoisyCover, augment.hip): ONE definition, so that both
 // translation units number and round the stream alike ----
-__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long ctr, unsigned (&out)[4]) {
-  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
+// Philox4x32-10 of the whole 128-bit counter (c0 .. c3) under the key `seed` (Random123's known-answer vectors:
+// tests/test_critic_dropout_host.py restates it)
+__device__ __forceinline__ void philox4x32_10_ctr4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2,
+                                                   unsigned c3, unsigned (&out)[4]) {
   unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
@@ -127,6 +129,28 @@ __device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned 
     k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
   }
   out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+// the normal draws' stream: a 64-bit counter, the upper two words 0
+__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long ctr, unsigned (&out)[4]) {
+  philox4x32_10_ctr4(seed, (unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u, out);
+}
+
+// ---- the critics' dropout masks (mlp_drop_ln.h): the stream of DESIGN.md 7e.  `rows_before` = z * B + r (twin z of
+// the launch's group, row r of B), `chunks` = ceil(H / 256), `q` = f >> 8 for the features f = lane + 64 j, j = 4 q ..
+// 4 q + 3 of one lane: word j & 3 of this ONE evaluation belongs to feature lane + 64 j.  c3 carries the tag (1..255),
+// so it is never 0 and the stream is disjoint from the normal draws' above. ----
+__device__ __forceinline__ void dropout_words(unsigned long long seed, unsigned long long counter, unsigned tag,
+                                              unsigned long long rows_before, int chunks, int q, int lane,
+                                              unsigned (&out)[4]) {
+  const unsigned long long e = (rows_before * (unsigned)chunks + (unsigned)q) * 64ull + (unsigned)lane;
+  philox4x32_10_ctr4(seed, (unsigned)e, (unsigned)(e >> 32), (unsigned)counter,
+                     ((unsigned)(counter >> 32) << 8) | tag, out);
+}
+
+// keep <=> u >= p with u = (word >> 8) 2^-24, exact in float32 and in [0, 1)
+__device__ __forceinline__ bool dropout_keep(unsigned word, float p) {
+  return (float)(word >> 8) * (1.0f / 16777216.0f) >= p;
 }
 
 // standard normal number i of the stream: Box-Muller on two of the four 32-bit outputs of counter i / 4

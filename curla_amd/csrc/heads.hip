@@ -19,6 +19,7 @@ namespace {
 #include "reduce.h"        // wave_sum, wave_max, block_sum_256; colsum, colsum3, mean and grad_sqsum kernels
 #include "layernorm.h"     // fc_ln_fwd_kernel<NF>, ln_bwd_kernel<NF>, ln_param_grad_kernel
 #include "mlp_ln.h"        // mlp_ln_relu_fwd_kernel<NF>, mlp_ln_bwd_kernel<NF>, mlp_ln_param_grad_kernel (the critics' LayerNorm)
+#include "mlp_drop_ln.h"   // mlp_drop_ln_relu_fwd_kernel<NF>, mlp_drop_ln_bwd_kernel<NF> (DroQ's dropout in front of that LayerNorm)
 #include "mlp_out.h"       // mlp_out_fwd_kernel<HEAD, R, LDSW>, mlp_out_bwd_kernel<GEN>, the policy head's three kernels
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
 #include "curl_head.h"     // curl_head_kernel<NTILE>
@@ -228,6 +229,15 @@ int stage_frames_launch(const uint8_t* nchw, size_t src_bytes, uint8_t* out, uin
                 Ws, top, left, Hd, Wd);
 }
 
+// the dropout arguments of curla_mlp_drop_ln_relu_fwd / _bwd, checked: p in [0, 1), the tags of all `groups` in 1..255
+int drop_args(float p, unsigned long long seed, unsigned long long counter, const unsigned long long* rng_dev, int tag,
+              int groups, DropArgs* dr) {
+  CURLA_REQUIRE(p >= 0.f && p < 1.f && tag >= 1 && tag <= 255 && groups >= 1 && tag + 2LL * (groups - 1) <= 255 &&
+                (reinterpret_cast<uintptr_t>(rng_dev) & 7) == 0);  // (p: false for a NaN)
+  dr->p = p, dr->scale = 1.0f / (1.0f - p), dr->seed = seed, dr->counter = counter, dr->rng_dev = rng_dev, dr->tag = tag;
+  return CURLA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -311,6 +321,45 @@ int curla_mlp_ln_bwd(float* dh, long long strideDh, const float* xhat, const flo
   const int rc = dispatch_ln_width(H, [&](auto nf) {
     return launch(mlp_ln_bwd_kernel<nf()>, dim3(nparts, nbatch), 256, 0, st, dh, strideDh, xhat, rstd, gamma, strideP, B, H,
                   partial);
+  });
+  if (rc != CURLA_OK || !params) return rc;
+  return launch(mlp_ln_param_grad_kernel, dim3((3 * H + 255) / 256, nbatch), 256, 0, st,
+                static_cast<const float*>(partial), nparts, H, dgamma, dbeta, dbias, strideG);
+}
+
+int curla_mlp_drop_ln_relu_fwd(float* h, long long strideH, long long strideH2, const float* gamma, const float* beta,
+                               long long strideP, long long strideP2, float* xhat, float* rstd, int save_first, int B,
+                               int H, int nbatch, int nbatch2, float eps, float p, unsigned long long seed,
+                               unsigned long long counter, const unsigned long long* rng_dev, int tag, void* stream) {
+  CURLA_REQUIRE(h && gamma && beta && B > 0 && H > 0 && nbatch > 0 && nbatch2 > 0);
+  CURLA_REQUIRE(!xhat == !rstd && (!xhat || (save_first >= 0 && save_first < nbatch2)));
+  DropArgs dr;
+  const int rc = drop_args(p, seed, counter, rng_dev, tag, nbatch2, &dr);
+  if (rc != CURLA_OK) return rc;
+  if (H > 1024) return CURLA_ERR_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return dispatch_ln_width(H, [&](auto nf) {
+    return launch(mlp_drop_ln_relu_fwd_kernel<nf()>, dim3((B + 3) / 4, nbatch * nbatch2), 256, 0, st, h, strideH, strideH2,
+                  gamma, beta, strideP, strideP2, xhat, rstd, save_first, B, H, nbatch, eps, dr);
+  });
+}
+
+int curla_mlp_drop_ln_bwd(float* dh, long long strideDh, const float* xhat, const float* rstd, const float* gamma,
+                          long long strideP, int B, int H, int nbatch, float* partial, float* dgamma, float* dbeta,
+                          float* dbias, long long strideG, float p, unsigned long long seed, unsigned long long counter,
+                          const unsigned long long* rng_dev, int tag, void* stream) {
+  CURLA_REQUIRE(dh && xhat && rstd && gamma && B > 0 && H > 0 && nbatch > 0);
+  const bool params = partial || dgamma || dbeta || dbias;
+  CURLA_REQUIRE(!params || (partial && dgamma && dbeta && dbias));
+  DropArgs dr;
+  int rc = drop_args(p, seed, counter, rng_dev, tag, 1, &dr);
+  if (rc != CURLA_OK) return rc;
+  if (H > 1024) return CURLA_ERR_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nparts = (B + 3) / 4;
+  rc = dispatch_ln_width(H, [&](auto nf) {
+    return launch(mlp_drop_ln_bwd_kernel<nf()>, dim3(nparts, nbatch), 256, 0, st, dh, strideDh, xhat, rstd, gamma, strideP,
+                  B, H, partial, dr);
   });
   if (rc != CURLA_OK || !params) return rc;
   return launch(mlp_ln_param_grad_kernel, dim3((3 * H + 255) / 256, nbatch), 256, 0, st,

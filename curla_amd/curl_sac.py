@@ -85,31 +85,40 @@ class _MlpLn:
     by layer: the LayerNorms' parameters ``g`` / ``b`` (twins and groups addressed as the _Mlp's), the buffers
     ``xhat`` [2, B, H] / ``rstd`` [2, B] a forward saves for its backward (None: a no-grad pass) and, for a backward
     that wants parameter gradients, their destinations ``dg`` / ``db`` and the ``partial`` workspace
-    (ops.mlp_ln_partial_floats).  ``save_first``: with _mlp_fwd's ``outer``, the first group that saves."""
+    (ops.mlp_ln_partial_floats).  ``save_first``: with _mlp_fwd's ``outer``, the first group that saves.
+    ``drop`` = (p, rng, tag): DroQ's dropout in front of each LayerNorm (Critic(dropout=p)) -- the mask of hidden layer i
+    is drawn under ``rng`` = (seed, counter[, device address]) and tag + i (group o of ``outer`` under tag + i + 2 o;
+    ops.mlp_drop_ln_relu_fwd), in the forward and again in the backward.  None: no dropout, the plain launches."""
 
-    def __init__(self, seq, xhat=None, rstd=None, dg=None, db=None, partial=None, save_first=0):
+    def __init__(self, seq, xhat=None, rstd=None, dg=None, db=None, partial=None, save_first=0, drop=None):
         ln = [m for m in seq if isinstance(m, nn.LayerNorm)]
         assert len(ln) == 2, "a LayerNorm behind each hidden layer"
         self.g = [m.weight for m in ln]
         self.b = [m.bias for m in ln]
         self.xhat, self.rstd, self.dg, self.db, self.partial, self.save_first = xhat, rstd, dg, db, partial, save_first
+        self.drop = drop
 
     def fwd(self, i, h, s, nb, B, H, outer):
         """LayerNorm + ReLU of hidden layer ``i`` in place on ``h``, which linear_fwd(relu=0) has just written."""
         saves = self.xhat is not None
-        ops.mlp_ln_relu_fwd(h, B * H, self.g[i], self.b[i], s, B, H, nb, xhat=self.xhat[i] if saves else None,
-                            rstd=self.rstd[i] if saves else None,
-                            outer=None if outer is None else (outer[0], nb * B * H, outer[1]),
-                            save_first=self.save_first if outer is not None and saves else 0)
+        kw = dict(xhat=self.xhat[i] if saves else None, rstd=self.rstd[i] if saves else None,
+                  outer=None if outer is None else (outer[0], nb * B * H, outer[1]),
+                  save_first=self.save_first if outer is not None and saves else 0)
+        if self.drop is None:
+            ops.mlp_ln_relu_fwd(h, B * H, self.g[i], self.b[i], s, B, H, nb, **kw)
+        else:
+            p, rng, tag = self.drop
+            ops.mlp_drop_ln_relu_fwd(h, B * H, self.g[i], self.b[i], s, B, H, p, rng, tag + i, nb, **kw)
 
     def bwd(self, i, dh, s, nb, B, H, dbias):
         """``dh`` (ReLU-masked by the layer behind) -> the gradient of Linear ``i``'s output, in place; with ``dbias``
         (that Linear's bias gradient) also the LayerNorm's parameter gradients."""
-        if dbias is None:
-            ops.mlp_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, nb)
+        kw = {} if dbias is None else dict(partial=self.partial, dgamma=self.dg[i], dbeta=self.db[i], dbias=dbias, sg=s)
+        if self.drop is None:
+            ops.mlp_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, nb, **kw)
         else:
-            ops.mlp_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, nb, partial=self.partial,
-                           dgamma=self.dg[i], dbeta=self.db[i], dbias=dbias, sg=s)
+            p, rng, tag = self.drop
+            ops.mlp_drop_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, p, rng, tag + i, nb, **kw)
 
 
 def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None, head=None, ln=None):
@@ -255,11 +264,13 @@ class Actor(nn.Module):
 
 class QFunction(nn.Module):
     """MLP for q-function (curl_sac.py:124-139); parameter container.  ``layer_norm``: an ``nn.LayerNorm(hidden_dim)``
-    between each hidden Linear and its ReLU (the Linears are then trunk.0 / .3 / .6, the LayerNorms trunk.1 / .4)."""
+    between each hidden Linear and its ReLU (the Linears are then trunk.0 / .3 / .6, the LayerNorms trunk.1 / .4).
+    ``dropout``: DroQ's dropout probability in front of each LayerNorm -- an attribute, no module of the trunk."""
 
-    def __init__(self, obs_dim, action_dim, hidden_dim, layer_norm=False):
+    def __init__(self, obs_dim, action_dim, hidden_dim, layer_norm=False, dropout=0.0):
         super().__init__()
         _check_layer_norm_width(layer_norm, hidden_dim)
+        self.dropout = _check_dropout(dropout, layer_norm)
         norm = (lambda: [nn.LayerNorm(hidden_dim)]) if layer_norm else (lambda: [])
         self.trunk = nn.Sequential(
             nn.Linear(obs_dim + action_dim, hidden_dim), *norm(), nn.ReLU(),
@@ -274,8 +285,55 @@ def _check_layer_norm_width(layer_norm, hidden_dim):
                          "(one wave per row)" % (hidden_dim, ops.MLP_LN_MAX))
 
 
-class Critic(nn.Module):
-    """Critic network, employs two Q-functions (curl_sac.py:142-180).  ``layer_norm``: QFunction's."""
+def _check_dropout(p, layer_norm):
+    """The critics' dropout probability as a float: 0 <= p < 1, and only in front of a LayerNorm (dropout without the
+    normalisation behind it is the configuration DroQ shows to be harmful; it is not offered)."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("critic dropout: p = %r is not in [0, 1)" % (p,))
+    if p > 0.0 and not layer_norm:
+        raise ValueError("critic dropout needs the critics' LayerNorm (critic_layer_norm=True / layer_norm=True)")
+    return p
+
+
+def _no_drop(tag):
+    return None
+
+
+def _device_generator(device):
+    device = torch.device(device)
+    return torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+
+
+def _reserve_dropout_counter(device):
+    """(seed, counter) of one pass's dropout masks, taken from ``device``'s default torch generator, whose offset moves
+    on by 4 (one Philox counter): torch.manual_seed, get_rng_state / set_rng_state (checkpoints) and the per-rank
+    seeds keep their meaning.  A CPU agent launches nothing (the trace hook's launch lists): position 0 of torch's
+    seed."""
+    if torch.device(device).type != "cuda":
+        return torch.initial_seed(), 0
+    gen = _device_generator(device)
+    off = gen.get_offset()
+    gen.set_offset(off + 4)
+    return gen.initial_seed(), off // 4
+
+
+class _CriticType(type):
+    """``Critic(..., dropout=p)``: the class call takes the keyword, as CurlSacAgent's takes its own (_AgentType), and
+    ``Critic.__init__`` keeps its parameter list with ``layer_norm`` last."""
+
+    def __call__(cls, *args, dropout=0.0, **kwargs):
+        critic = super().__call__(*args, **kwargs)
+        critic.dropout = critic.Q1.dropout = critic.Q2.dropout = _check_dropout(dropout, critic.layer_norm)
+        return critic
+
+
+class Critic(nn.Module, metaclass=_CriticType):
+    """Critic network, employs two Q-functions (curl_sac.py:142-180).  ``layer_norm``: QFunction's; so is
+    ``Critic(..., dropout=p)``, a keyword of the class call.  ``forward`` drops in training mode only
+    (``critic.eval()``: the deterministic Q)."""
+
+    dropout = 0.0
 
     def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
                  layer_norm=False):
@@ -296,21 +354,30 @@ class Critic(nn.Module):
             raise RuntimeError("Critic parameters are not in the flat twin layout (constructed outside CurlSacAgent)")
         return _Mlp(self.Q1.trunk, self.twin_stride, grads)
 
-    def twin_ln(self, xhat=None, rstd=None, grads=False, partial=None, save_first=0):
+    def twin_ln(self, xhat=None, rstd=None, grads=False, partial=None, save_first=0, drop=None):
         """The ``ln=`` argument of _mlp_fwd / _mlp_bwd for ``twin()``: None without LayerNorm.  ``xhat`` / ``rstd``:
-        a pair of buffers each, one per hidden layer; ``grads``: the backward fills the LayerNorm tensors' .grad."""
+        a pair of buffers each, one per hidden layer; ``grads``: the backward fills the LayerNorm tensors' .grad;
+        ``drop`` = (p, rng, tag) or None: this pass's dropout (_MlpLn)."""
         if not self.layer_norm:
             return None
-        ln = _MlpLn(self.Q1.trunk, xhat, rstd, partial=partial, save_first=save_first)
+        ln = _MlpLn(self.Q1.trunk, xhat, rstd, partial=partial, save_first=save_first, drop=drop)
         if grads:
             ln.dg, ln.db = [p.grad for p in ln.g], [p.grad for p in ln.b]
         return ln
 
-    def forward(self, obs, action, detach_encoder=False):
+    DROP_TAG_FORWARD = 7  # the tags of the dropout masks: 1 + 2 * pass + layer, a forward() call is pass 3
+
+    def forward(self, obs, action, detach_encoder=False, dropout_rng=None):
+        """``dropout_rng`` = (seed, counter): the stream position of a training-mode dropout critic's masks (tags 7 / 8);
+        None reserves one counter from the device's torch generator per call."""
         assert obs.size(0) == action.size(0)  # curl_sac.py:136
         z = self.encoder(obs, detach=detach_encoder)
+        drop = None
+        if self.dropout > 0 and self.training:
+            _check_dropout(self.dropout, self.layer_norm)
+            drop = (self.dropout, dropout_rng or _reserve_dropout_counter(z.device), self.DROP_TAG_FORWARD)
         if autograd.wants_graph(z, action, *self.Q1.parameters(), *self.Q2.parameters()):
-            q1, q2 = autograd.critic_forward(self, z, action)  # (differentiable: autograd.CriticFn)
+            q1, q2 = autograd.critic_forward(self, z, action, drop)  # (differentiable: autograd.CriticFn)
             self.outputs['q1'], self.outputs['q2'] = q1.detach(), q2.detach()
             return q1, q2
         B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
@@ -320,7 +387,7 @@ class Critic(nn.Module):
         h1 = torch.empty((2, B, H), device=dev)
         h2 = torch.empty((2, B, H), device=dev)
         q = torch.empty((2, B, 1), device=dev)
-        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, 1, h1, h2, q, ln=self.twin_ln())
+        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, 1, h1, h2, q, ln=self.twin_ln(drop=drop))
         self.outputs['q1'], self.outputs['q2'] = q[0], q[1]
         return q[0], q[1]
 
@@ -445,9 +512,10 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, critic_layer_norm=False, **kwargs):
+    def __call__(cls, *args, critic_dropout=0.0, critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
         agent.critic_layer_norm = bool(critic_layer_norm)
+        agent.critic_dropout = _check_dropout(critic_dropout, agent.critic_layer_norm)
         agent.__init__(*args, **kwargs)
         return agent
 
@@ -456,9 +524,13 @@ class CurlSacAgent(object, metaclass=_AgentType):
     """CURL representation learning with SAC (curl_sac.py:224-465).
     ``CurlSacAgent(..., critic_layer_norm=True)`` (a keyword of the class call, not in the reference; default off:
     nothing changes): an ``nn.LayerNorm(hidden_dim)`` between each hidden Linear of the Q functions and its ReLU, critic
-    and target critic alike -- the critic regulariser of DroQ / RLPD.  ``hidden_dim`` up to 1024 then."""
+    and target critic alike -- the critic regulariser of DroQ / RLPD.  ``hidden_dim`` up to 1024 then.
+    ``critic_dropout=p`` (with ``critic_layer_norm=True`` only; default 0: nothing changes): DroQ's dropout in front of
+    each of those LayerNorms, in every critic pass of ``update()`` -- the target's, the critic's and the actor phase's.
+    No module and no mask buffer: ``p`` is this attribute, the masks are a counter-based stream."""
 
     critic_layer_norm = False
+    critic_dropout = 0.0
 
     def __init__(
         self,
@@ -494,6 +566,10 @@ class CurlSacAgent(object, metaclass=_AgentType):
         _check_layer_norm_width(self.critic_layer_norm, hidden_dim)
         self.augmentor = augmentor
         self.device = torch.device(device)
+        if self.critic_dropout > 0 and self.device.type == "cuda" and \
+                not hasattr(_device_generator(self.device), "get_offset"):
+            raise RuntimeError("critic_dropout: this torch build's device generator exposes no Philox offset "
+                               "(get_offset / set_offset), which the dropout masks' stream positions are taken from")
         self.discount = discount
         self.critic_tau = critic_tau
         self.encoder_tau = encoder_tau
@@ -514,9 +590,9 @@ class CurlSacAgent(object, metaclass=_AgentType):
         self.actor = Actor(obs_shape, action_shape, hidden_dim, encoder_feature_dim, actor_log_std_min,
                            actor_log_std_max, num_layers, num_filters)
         self.critic = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
-                             layer_norm=self.critic_layer_norm)
+                             layer_norm=self.critic_layer_norm, dropout=self.critic_dropout)
         self.critic_target = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
-                                    layer_norm=self.critic_layer_norm)
+                                    layer_norm=self.critic_layer_norm, dropout=self.critic_dropout)
         self.critic_target.load_state_dict(self.critic.state_dict())
 
         # tie encoders between actor and critic, and CURL and critic
@@ -1107,9 +1183,22 @@ class CurlSacAgent(object, metaclass=_AgentType):
 
     _noise_launch = False  # True: this torch build's generator has no get_offset / set_offset
 
+    def _dropout(self, rng, dropout_rng):
+        """A phase's ``drop(tag)`` -> the ``drop=`` argument of Critic.twin_ln for the pass with that tag base (None
+        without dropout).  The masks' stream position: ``dropout_rng`` = (seed, counter) where the caller gives one,
+        else the ``rng`` of the phase's in-kernel policy-noise draw (_noise(): by value, or the control block's slot
+        under capture -- nothing more is reserved and a replay draws what the eager update draws), else (explicit
+        ``noise=``, the ``normal_()`` fallback) one counter reserved from the device generator."""
+        if not self.critic_dropout:
+            return _no_drop
+        p = _check_dropout(self.critic_dropout, self.critic_layer_norm)  # (the attribute may have been edited)
+        pos = dropout_rng or rng or _reserve_dropout_counter(self.device)
+        return lambda tag: (p, pos, tag)
+
     # ------------------------------------------------------------------ phases
-    def update_critic(self, obs, action, reward, next_obs, not_done, L, step, noise=None):
-        """curl_sac.py:349-371."""
+    def update_critic(self, obs, action, reward, next_obs, not_done, L, step, noise=None, dropout_rng=None):
+        """curl_sac.py:349-371.  ``dropout_rng`` = (seed, counter): the stream position of a dropout critic's masks
+        (the target twins under tags 1 / 2, the critic twins under 3 / 4) instead of the phase's own (_dropout)."""
         self._restore_grad_views()
         o, no = _as_ref(obs), _as_ref(next_obs)
         B, A, H = o.B, self.action_dim, self.hidden_dim
@@ -1149,19 +1238,21 @@ class CurlSacAgent(object, metaclass=_AgentType):
         else:
             self.actor.encoder.ln_from_partial(B, ws.z_a)
         nz, rng = self._noise(ws, noise)
+        drop = self._dropout(rng, dropout_rng)
         _mlp_fwd(ws.z_a, 0, _Mlp(self.actor.trunk), 1, B, F, H, 2 * A, ws.a_h1, ws.a_h2, ws.a_out,
                  head=(nz, self.actor.log_std_min, self.actor.log_std_max,
                        dict(pi=None if four else ws.pi, log_pi=ws.log_pi, xa=ws.xa2[0] if four else None, rng=rng)))
         if four:
             _mlp_fwd(ws.xa2, 0, self.critic_target.twin(), 2, B, F + A, H, 1, ws.q_h1_2, ws.q_h2_2, ws.q2,
-                     outer=(2, self._twin_outer), ln=self.critic_target.twin_ln(*ws.q_ln_saves, save_first=1))
+                     outer=(2, self._twin_outer),
+                     ln=self.critic_target.twin_ln(*ws.q_ln_saves, save_first=1, drop=drop(1)))  # (groups: tags 1/2, 3/4)
         else:
             if not merged:
                 tenc.conv_forward(no, ws.acts_tmp)
                 tenc.fc_partial(ws.acts_tmp[-1])
             tenc.ln_from_partial(B, ws.z_t, xa=ws.xa, act=ws.pi)  # xa = cat([z, a'], 1)
             _mlp_fwd(ws.xa, 0, self.critic_target.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.tq,
-                     ln=self.critic_target.twin_ln())
+                     ln=self.critic_target.twin_ln(drop=drop(1)))
             # -- current Q estimates + loss + backward (curl_sac.py:357-367)
             if not merged:
                 enc.conv_forward(o, ws.acts_main)
@@ -1169,7 +1260,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
             enc.ln_from_partial(B, ws.z_c, xhat=ws.xhat_c, rstd=ws.rstd_c, fc_out=ws.fc_out if rec else None,
                                 xa=ws.xa, act=action)
             _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q,
-                     ln=self.critic.twin_ln(*ws.q_ln_saves))
+                     ln=self.critic.twin_ln(*ws.q_ln_saves, drop=drop(3)))
         if rec:  # what critic.log() / encoder.log() histogram: the outputs of THIS forward (curl_sac.py:163-167)
             self.critic.outputs['q1'], self.critic.outputs['q2'] = ws.q[0].clone(), ws.q[1].clone()
             enc.record_from(o, ws.acts_main, ws.fc_out, ws.z_c)
@@ -1192,7 +1283,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
             td = None
         _mlp_bwd(ws.xa, 0, self.critic.twin(), self.critic.twin(grads=True), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.dq,
                  ws.q_dh2, ws.q_dh1, ws.dxa, loss=td,
-                 ln=self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial))
+                 ln=self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial, drop=drop(3)))
         if step % self.log_interval == 0:
             L.log('train_critic/loss', ws.scalars[0], step)
         # (d(loss)/d(z) = dxa[0][:, :F] + dxa[1][:, :F], torch.cat's backward: summed inside the LayerNorm backward)
@@ -1236,7 +1327,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
         if self.log_param_hist_imgs:
             self.critic.log(L, step)
 
-    def update_actor_and_alpha(self, obs, L, step, noise=None):
+    def update_actor_and_alpha(self, obs, L, step, noise=None, dropout_rng=None):
         """curl_sac.py:373-404.  Only the live gradients are produced: the
         actor's own fc/ln/trunk and log_alpha (the reference also deposits
         gradients on critic tensors that are zeroed before any step reads them)."""
@@ -1279,7 +1370,8 @@ class CurlSacAgent(object, metaclass=_AgentType):
                                         xa=ws.xa, rng=rng)))
         if self._records(step):  # what actor.log() histograms (curl_sac.py:92-93): pre-squash mean and std
             self.actor.outputs['mu'], self.actor.outputs['std'] = ws.a_out[:, :A].clone(), ws.log_std.exp()
-        q_ln = self.critic.twin_ln(*ws.q_ln_saves)  # (the data gradient through the LayerNorms needs them too)
+        # (the data gradient through the LayerNorms needs the saves too; dropout: the critic twins under tags 5 / 6)
+        q_ln = self.critic.twin_ln(*ws.q_ln_saves, drop=self._dropout(rng, dropout_rng)(5))
         _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q, ln=q_ln)
         # actor / alpha losses and d(loss)/dQ: inside the backward launch of the Q functions' last layer
         # backward: Q -> pi -> trunk -> LN -> fc (encoder detached, curl_sac.py:375-376)
@@ -1565,8 +1657,8 @@ class CurlSacAgent(object, metaclass=_AgentType):
         pinned block and a copy of their own per call).  Data-parallel updates over RCCL
         ARE captured, collectives included (round 5; the replica check stays on the host, in front of the replay).
         Values the graphs hold as kernel arguments (discount, taus, betas / eps, detach_encoder, the update
-        frequencies, the data-parallel group and schedule, ``max_grad_norm``, ``n_step`` and ``discount`` of an n-step
-        replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
+        frequencies, the data-parallel group and schedule, ``max_grad_norm``, ``critic_dropout``,
+        ``n_step`` and ``discount`` of an n-step replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
         so does ``load_checkpoint``.  A capture that raises leaves the agent's
         state untouched and that update runs eagerly."""
         if self.device.type != "cuda":
@@ -1622,7 +1714,8 @@ class CurlSacAgent(object, metaclass=_AgentType):
                 bool(self.pixel_sac), float(self.target_entropy), float(self.actor.log_std_min),
                 float(self.actor.log_std_max), self.actor_update_freq, self.critic_target_update_freq,
                 self.cpc_update_freq, self._dp_active, self._dp_overlap, id(self._dp_group) if self._dp_active else 0,
-                hyper, self._graph_rb_key(), self._max_grad_norm)
+                hyper, self._graph_rb_key(), self._max_grad_norm) + \
+            ((float(self.critic_dropout),) if self.critic_dropout else ())  # (0: the key of an agent without the keyword)
 
     def _graph_rb_key(self):
         """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value
@@ -1818,7 +1911,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
             "critic_target": self.critic_target.state_dict(), "curl": self.CURL.state_dict(),
             "log_alpha": self.log_alpha.detach().cpu(),
             "optimizers": {k: self._convert_opt_state(o, o.state_dict(), True) for k, o in self._optimizers().items()},
-            "rng": rng,
+            "rng": rng, "critic_dropout": float(self.critic_dropout),
         }, path)
 
     def load_checkpoint(self, path, restore_rng=True):
@@ -1826,6 +1919,9 @@ class CurlSacAgent(object, metaclass=_AgentType):
         ck = torch.load(path, map_location="cpu", weights_only=False)
         if ck.get("format") != "curla_amd.checkpoint.v1":
             raise ValueError("not a curla_amd checkpoint: %r" % (path,))
+        if float(ck.get("critic_dropout", 0.0)) != float(self.critic_dropout):
+            warnings.warn("curla_amd: the checkpoint was written with critic_dropout = %r; this agent keeps its own, %r"
+                          % (ck.get("critic_dropout", 0.0), self.critic_dropout), RuntimeWarning, stacklevel=2)
         self.CURL.load_state_dict(ck["curl"])
         self.actor.load_state_dict(ck["actor"])
         self.critic.load_state_dict(ck["critic"])

@@ -493,6 +493,31 @@ def mlp_ln_bwd(dh, sdh, xhat, rstd, gamma, sp, B, H, nb=1, partial=None, dgamma=
          ptr(dbeta), ptr(dbias), sg, stream())
 
 
+def _drop_args(p, rng, tag):
+    """(p, seed, counter, device address or None, tag) of the two dropout ops; ``rng`` = (seed, counter[, device
+    address]) as for actor_head_fwd."""
+    return float(p), int(rng[0]) & (2 ** 64 - 1), int(rng[1]) & (2 ** 64 - 1), rng[2] if len(rng) > 2 else None, int(tag)
+
+
+def mlp_drop_ln_relu_fwd(h, sh, gamma, beta, sp, B, H, p, rng, tag, nb=1, xhat=None, rstd=None, outer=None, save_first=0,
+                         eps=1e-5):
+    """mlp_ln_relu_fwd on the dropped activation: h[z] <- relu(LayerNorm(m * h[z] / (1 - p)) * gamma[z] + beta[z]).  The
+    keep mask m is a function of ``rng`` = (seed, counter[, device address]), ``tag`` (1..255; group o of ``outer``
+    draws under tag + 2 o) and the element's position (curla_hip.h) and is stored nowhere; with a device address the
+    kernel reads (seed, counter) from there when it runs."""
+    n2, sh2, sp2 = (1, 0, 0) if outer is None else outer
+    call("curla_mlp_drop_ln_relu_fwd", ptr(h), sh, sh2, ptr(gamma), ptr(beta), sp, sp2, ptr(xhat), ptr(rstd), save_first,
+         B, H, nb, n2, eps, *_drop_args(p, rng, tag), stream())
+
+
+def mlp_drop_ln_bwd(dh, sdh, xhat, rstd, gamma, sp, B, H, p, rng, tag, nb=1, partial=None, dgamma=None, dbeta=None,
+                    dbias=None, sg=0):
+    """Backward of mlp_drop_ln_relu_fwd under the same (p, rng, tag), in place: mlp_ln_bwd, then the mask and 1 / (1 - p)
+    on its result -- ``dh`` leaves as the gradient of the Linear's output and ``dbias`` sums that."""
+    call("curla_mlp_drop_ln_bwd", ptr(dh), sdh, ptr(xhat), ptr(rstd), ptr(gamma), sp, B, H, nb, ptr(partial),
+         ptr(dgamma), ptr(dbeta), ptr(dbias), sg, *_drop_args(p, rng, tag), stream())
+
+
 def colsum(X, M, N, ldx, sX, out, sOut, nb=1):
     call("curla_colsum", ptr(X), M, N, ldx, sX, ptr(out), sOut, nb, stream())
 

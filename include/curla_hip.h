@@ -337,6 +337,33 @@ int curla_mlp_ln_relu_fwd(float* h, long long strideH, long long strideH2, const
 int curla_mlp_ln_bwd(float* dh, long long strideDh, const float* xhat, const float* rstd, const float* gamma,
                      long long strideP, int B, int H, int nbatch, float* partial, float* dgamma, float* dbeta,
                      float* dbias, long long strideG, void* stream);
+/* curla_mlp_ln_relu_fwd with DroQ's dropout in front of the LayerNorm (CurlSacAgent(critic_layer_norm=True,
+ * critic_dropout=p): the trunk of curl_sac.py:129-139 as Linear - Dropout(p) - LayerNorm - ReLU per hidden layer):
+ * h receives relu(LN(m * h * s)), s = 1.0f / (1.0f - p), and xhat / rstd are those of the dropped activation.  The keep
+ * mask m is not stored; element (twin z, row r, feature f) of group o is kept where u >= p, with
+ * u = (word >> 8) * 2^-24 and word = output (f >> 6) & 3 of Philox4x32-10 under the key `seed` on the counter
+ * (e & 0xffffffff, e >> 32, counter & 0xffffffff, (((counter >> 32) << 8) | (tag + 2 o)) & 0xffffffff),
+ * e = ((z * B + r) * ceil(H / 256) + (f >> 8)) * 64 + (f & 63).  rng_dev (NULL, or 8-byte aligned device memory): seed
+ * and counter are rng_dev[0] and rng_dev[1], read when the kernel RUNS (captured graphs), and the two by-value arguments
+ * are ignored.  The arguments in front of p and their rules are curla_mlp_ln_relu_fwd's; in addition CURLA_ERR_ARG on
+ * p outside [0, 1), tag outside 1..255, tag + 2 (nbatch2 - 1) > 255, a misaligned rng_dev.  CURLA_ERR_UNSUPPORTED on
+ * H > 1024; an argument error comes first.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_mlp_drop_ln_relu_fwd(float* h, long long strideH, long long strideH2, const float* gamma, const float* beta,
+                               long long strideP, long long strideP2, float* xhat, float* rstd, int save_first, int B,
+                               int H, int nbatch, int nbatch2, float eps, float p, unsigned long long seed,
+                               unsigned long long counter, const unsigned long long* rng_dev, int tag, void* stream);
+/* Its backward (curl_sac.py:129-139 as extended above), in place: curla_mlp_ln_bwd with the mask of the forward call
+ * under the same (p, seed, counter or rng_dev, tag) computed again; dh leaves as the gradient of the Linear's output,
+ * m * s times the gradient of the LayerNorm's input, and dbias sums THAT; dgamma and dbeta as without dropout.  A row
+ * that was dropped entirely leaves as exact zeros.  No mask buffer, no atomics: the same bits run to run.  The
+ * arguments in front of p and their rules are curla_mlp_ln_bwd's; in addition CURLA_ERR_ARG on p outside [0, 1), tag
+ * outside 1..255, a misaligned rng_dev.  CURLA_ERR_UNSUPPORTED on H > 1024; an argument error comes first.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_mlp_drop_ln_bwd(float* dh, long long strideDh, const float* xhat, const float* rstd, const float* gamma,
+                          long long strideP, int B, int H, int nbatch, float* partial, float* dgamma, float* dbeta,
+                          float* dbias, long long strideG, float p, unsigned long long seed, unsigned long long counter,
+                          const unsigned long long* rng_dev, int tag, void* stream);
 /* out[z][n] = sum_m X[z][m][n] (bias gradients) */
 int curla_colsum(const float* X, int M, int N, int ldx, long long strideX, float* out, long long strideOut, int nbatch,
                  void* stream);
