@@ -671,9 +671,14 @@ class RandomConv(IdentityAugmentation):
     def staged_args(self, dev, at, B, obs_shape):
         return dev[at:at + 324 * B].view(torch.float32).view(-1, 81)
 
+    def draw_unstaged(self, B, shape, device):
+        """What ``launch`` draws for a [B, H, W, C] tensor whose parameters are not staged -- all a positive that nobody
+        wants needs (ReplayBuffer.sample_cpc_refs(want_pos=False)): the streams move, nothing is launched."""
+        return self.draw_weights(B)
+
     def launch(self, ring, rows, B, out, staged=None):
         if staged is None:
-            weights = self.draw_weights(B)
+            weights = self.draw_unstaged(B, out.shape, out.device)
             # (one pinned staging block, one asynchronous copy, as ColorJiggle's)
             stage = torch.empty(weights.shape, dtype=torch.float32, pin_memory=out.is_cuda)
             stage.copy_(weights)
@@ -749,9 +754,13 @@ class ColorJiggle(IdentityAugmentation):
         n_par = 16 * B * (obs_shape[0] // 3)
         return dev[at:at + n_par].view(torch.float32).view(-1, 4), dev[at + n_par:at + n_par + 16].view(torch.int32)
 
+    def draw_unstaged(self, B, shape, device):
+        """What ``launch`` draws for a [B, H, W, C] tensor whose parameters are not staged (RandomConv.draw_unstaged)."""
+        return self.draw_params(B * (shape[3] // 3))
+
     def launch(self, ring, rows, B, out, staged=None):
         if staged is None:
-            params, order = self.draw_params(B * (out.shape[3] // 3))
+            params, order = self.draw_unstaged(B, out.shape, out.device)
             # one pinned staging block, one asynchronous copy: a `.to(device)` of a pageable tensor makes the host wait
             # until the stream has drained (two of them per call left ~60 us of idle GPU around every jitter launch)
             n4 = params.numel()
@@ -828,10 +837,15 @@ class NoisyCover(IdentityAugmentation):
         """Device addresses of the colours and of (seed, counter): the kernel reads both when it runs."""
         return dev.data_ptr() + at, dev.data_ptr() + at + 16
 
+    def draw_unstaged(self, B, shape, device):
+        """What ``launch`` draws for a [B, H, W, C] tensor whose parameters are not staged (RandomConv.draw_unstaged):
+        the colours and the noise tensor -- torch's own ``randn`` launch, which is what moves the device generator."""
+        return self.draw_colors(), torch.randn(tuple(shape), device=device)
+
     def launch(self, ring, rows, B, out, staged=None):
         if staged is None:
-            colors = self.draw_colors()
-            noise = torch.randn(tuple(out.shape), device=out.device) * self.std
+            colors, noise = self.draw_unstaged(B, out.shape, out.device)
+            noise = noise * self.std
             ops.noisy_cover(ring, rows, noise, colors, self.top, self.bottom, B, out)
         else:
             ops.noisy_cover_rng(ring, rows, self.std, (0, 0, staged[1]), staged[0], self.top, self.bottom, B, out)

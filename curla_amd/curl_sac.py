@@ -19,6 +19,7 @@ the reference's autograd cannot do:
                  conv(pos; xi') -> bilinear logits (MFMA) -> CE -> backward -> 2x Adam
 => 5 conv-stack forwards + 2 backwards per update instead of the reference's 7 + 2.
 """
+import inspect
 import os
 import warnings
 
@@ -300,8 +301,16 @@ def _no_drop(tag):
     return None
 
 
+def _check_utd_ratio(g):
+    """The update-to-data ratio: an ``int >= 1`` (a bool, a float or a string is not one)."""
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or g < 1:
+        raise ValueError("utd_ratio: %r is not an int >= 1" % (g,))
+    return int(g)
+
+
 def _device_generator(device):
     device = torch.device(device)
+    torch.cuda.init()  # (the generators exist once the runtime is up; a dropout agent may be the process's first use of it)
     return torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
 
 
@@ -512,10 +521,11 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, critic_dropout=0.0, critic_layer_norm=False, **kwargs):
+    def __call__(cls, *args, utd_ratio=1, critic_dropout=0.0, critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
         agent.critic_layer_norm = bool(critic_layer_norm)
         agent.critic_dropout = _check_dropout(critic_dropout, agent.critic_layer_norm)
+        agent.utd_ratio = _check_utd_ratio(utd_ratio)
         agent.__init__(*args, **kwargs)
         return agent
 
@@ -527,10 +537,14 @@ class CurlSacAgent(object, metaclass=_AgentType):
     and target critic alike -- the critic regulariser of DroQ / RLPD.  ``hidden_dim`` up to 1024 then.
     ``critic_dropout=p`` (with ``critic_layer_norm=True`` only; default 0: nothing changes): DroQ's dropout in front of
     each of those LayerNorms, in every critic pass of ``update()`` -- the target's, the critic's and the actor phase's.
-    No module and no mask buffer: ``p`` is this attribute, the masks are a counter-based stream."""
+    No module and no mask buffer: ``p`` is this attribute, the masks are a counter-based stream.
+    ``utd_ratio=G`` (default 1: nothing changes): the update-to-data ratio of DroQ / RLPD -- one ``update()`` call makes
+    G critic steps on G freshly drawn minibatches before the actor steps once (``update``).  An attribute
+    that may be edited between calls."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
+    utd_ratio = 1
 
     def __init__(
         self,
@@ -1146,7 +1160,9 @@ class CurlSacAgent(object, metaclass=_AgentType):
     def _records(self, step):
         """True on the steps whose module outputs the optional histogram / image logging reads
         (log_param_hist_imgs, every LOG_FREQ steps: curl_sac.py:17,112-121,171-180)."""
-        return self.log_param_hist_imgs and step % LOG_FREQ == 0
+        return self.log_param_hist_imgs and step % LOG_FREQ == 0 and not self._utd_leading
+
+    _utd_leading = False  # set by _leading_phases around a leading sub-step of a utd_ratio > 1 call: it records nothing
 
     def _noise(self, ws, noise):
         """(noise buffer, rng): explicit ``noise`` is copied into the buffer (rng None).  Without it
@@ -1566,9 +1582,32 @@ class CurlSacAgent(object, metaclass=_AgentType):
         into its HBM ring (gather + crop fused into the first conv); any other
         buffer is used through the reference's ``sample_cpc()`` tensors.
         ``noise`` (parity tests): (critic-phase, actor-phase) tensors in place of the two ``torch.randn_like`` draws
-        (curl_sac.py:97 via :352 and :375)."""
+        (curl_sac.py:97 via :352 and :375).
+
+        ``utd_ratio = G > 1``: the call draws G minibatches, one after the other, each through the
+        buffer's ordinary route, so NumPy's and torch's host streams and the device generator move exactly as G
+        separate samples and G separate critic phases move them.
+          leading sub-steps (minibatches 0 .. G-2): the critic phase, and the target soft update iff
+              ``step % critic_target_update_freq == 0`` -- ALL sub-steps of a call share the call's ``step`` (DroQ /
+              RLPD users set ``critic_target_update_freq=1``); fused into the critic's Adam launch where a critic-only
+              update fuses it.  No actor phase, no CURL phase, nothing logged or recorded; a curla_amd buffer is told
+              that the positive is not wanted (``sample_cpc_refs(want_pos=False)``).
+          final sub-step (minibatch G-1): the whole update as with ``utd_ratio = 1`` -- every frequency, the logging
+              (each ``train_*`` key once per call) and the records.
+        ``only_cpc=True`` has no critic phase: one minibatch, no leading sub-steps.  A prioritized buffer's sub-step
+        draws from the priorities the previous one left and updates those of its own rows; data parallel, every
+        sub-step reduces its critic bucket as a critic-only update does and ``check_replicas()`` runs at most once, in
+        front of the first; ``set_max_grad_norm`` clips per sub-step.  A sub-step that raises ends the call.
+        The state after the call -- parameters, targets, optimizer state, priorities, generator positions -- is bit
+        for bit that of G-1 critic-only ``update()`` calls (a ``step`` without actor and CURL phase, the same soft-update
+        decision) followed by the ordinary call with ``utd_ratio = 1``.  ``noise`` is a hook for one minibatch and is
+        refused with G > 1."""
         self._restore_grad_views()
         self._check_n_step(replay_buffer)
+        if self.utd_ratio != 1 or type(self.utd_ratio) is not int:  # (the attribute may have been edited)
+            if _check_utd_ratio(self.utd_ratio) > 1 and noise is not None and not only_cpc:
+                raise ValueError("update(noise=...) stands for the draws of one minibatch: not with utd_ratio = %d"
+                                 % self.utd_ratio)
         if noise is None and self._graphs is not None and self._graph_usable(replay_buffer, step, only_cpc):
             return self._update_graphed(replay_buffer, L, step)
         self._update_eager(replay_buffer, L, step, only_cpc, noise)
@@ -1581,25 +1620,66 @@ class CurlSacAgent(object, metaclass=_AgentType):
                              % (replay_buffer.discount, replay_buffer.n_step, self.discount))
 
     def _update_eager(self, replay_buffer, L, step, only_cpc=False, noise=None):
+        leading = 0 if only_cpc else self.utd_ratio - 1
+        for k in range(leading):
+            self._substep_eager(replay_buffer, None, step, leading=True, first=k == 0)
+        self._substep_eager(replay_buffer, L, step, only_cpc, noise, first=leading == 0)
+
+    def _substep_eager(self, replay_buffer, L, step, only_cpc=False, noise=None, leading=False, first=True):
+        """One minibatch of an update: drawn, then its phases.  ``leading``: a sub-step in front of the last one of a
+        utd_ratio > 1 call; ``first``: the call's first sub-step, where the replicas are checked."""
         if hasattr(replay_buffer, "sample_cpc_refs"):
-            sample = replay_buffer.sample_cpc_refs()
+            if leading and self._takes_want_pos(replay_buffer):
+                sample = replay_buffer.sample_cpc_refs(want_pos=False)
+            else:
+                sample = replay_buffer.sample_cpc_refs()
         else:
             sample = replay_buffer.sample_cpc()
 
-        if self._dp_active and self._dp_check_every > 0 and step % self._dp_check_every == 0:
+        if first and self._dp_active and self._dp_check_every > 0 and step % self._dp_check_every == 0:
             self.check_replicas()
-        self._update_phases(sample, L, step, only_cpc, noise)
+        if leading:
+            self._leading_phases(sample, step)
+        else:
+            self._update_phases(sample, L, step, only_cpc, noise)
 
-    def _update_phases(self, sample, L, step, only_cpc=False, noise=None):
-        """The phases of one update on a drawn minibatch (curl_sac.py:431-451)."""
+    _want_pos_known = (None, False)
+
+    def _takes_want_pos(self, replay_buffer):
+        """Whether the buffer's ``sample_cpc_refs`` takes ``want_pos`` (this package's does; a look-alike need not)."""
+        cls, ok = self._want_pos_known
+        if cls is not type(replay_buffer):
+            try:
+                ok = "want_pos" in inspect.signature(replay_buffer.sample_cpc_refs).parameters
+            except (TypeError, ValueError):
+                ok = False
+            self._want_pos_known = (type(replay_buffer), ok)
+        return ok
+
+    def _leading_phases(self, sample, step):
+        """The phases of a leading sub-step (utd_ratio > 1) on a drawn minibatch: logged to nobody, nothing recorded."""
+        self._utd_leading = True
+        try:
+            self._update_phases(sample, _NullLog(), step, leading=True)
+        except BaseException:
+            # no later sub-step runs; the next call starts as after any failed update
+            self._soft_update_hint = self._soft_update_done = False
+            raise
+        finally:
+            self._utd_leading = False
+
+    def _update_phases(self, sample, L, step, only_cpc=False, noise=None, leading=False):
+        """The phases of one update on a drawn minibatch (curl_sac.py:431-451).  ``leading`` (_leading_phases): the critic
+        phase and, by ``step``, the target soft update -- the update kind (actor=False, soft, cpc=False) whatever the
+        other frequencies say."""
         obs, action, reward, next_obs, not_done, cpc_kwargs = sample
         noise_c, noise_a = noise if noise is not None else (None, None)
-        if step % self.log_interval == 0:
+        if step % self.log_interval == 0 and not leading:
             ws = self._ws(action.shape[0])
             ops.mean(reward.contiguous(), reward.numel(), ws.scalars[6:7])
             L.log('train/batch_reward', ws.scalars[6], step)
 
-        do_cpc = (not self.pixel_sac) and step % self.cpc_update_freq == 0
+        do_cpc = (not self.pixel_sac) and step % self.cpc_update_freq == 0 and not leading
         if not only_cpc:
             soft = step % self.critic_target_update_freq == 0
             self._soft_update_hint, self._soft_update_done = soft, False
@@ -1614,7 +1694,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
             # critic's Adam launch.)
             if soft and not self._soft_update_done:
                 self.soft_update_targets()
-            if step % self.actor_update_freq == 0:
+            if step % self.actor_update_freq == 0 and not leading:
                 if do_cpc and isinstance(cpc_kwargs.get("obs_pos"), ObsRef):
                     self._pos_hint = cpc_kwargs["obs_pos"]
                 self._defer_actor_step = do_cpc
@@ -1660,7 +1740,11 @@ class CurlSacAgent(object, metaclass=_AgentType):
         frequencies, the data-parallel group and schedule, ``max_grad_norm``, ``critic_dropout``,
         ``n_step`` and ``discount`` of an n-step replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
         so does ``load_checkpoint``.  A capture that raises leaves the agent's
-        state untouched and that update runs eagerly."""
+        state untouched and that update runs eagerly.
+        ``utd_ratio = G > 1``: a call replays the critic-only kind's graph (actor=False, soft, cpc=False) G-1 times -- the
+        graph an ordinary critic-only step captures, each replay on the next block of the kind's rotation -- and then the
+        step's own kind; a call that runs eagerly (above) runs all its sub-steps eagerly.  No graph holds the ratio: it
+        is not fingerprinted and may be edited between calls."""
         if self.device.type != "cuda":
             raise RuntimeError("update graphs need the HIP device")
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
@@ -1786,10 +1870,28 @@ class CurlSacAgent(object, metaclass=_AgentType):
         if self._graphs and key != self._graph_key_at_capture:
             self._drop_graphs()  # a value the graphs hold as a kernel argument has been edited since the capture
         kind = self._graph_kind(step)
+        leading = self.utd_ratio - 1
+        if leading == 0:
+            return self._graphed_substep(rb, step, kind, key, lambda: self._update_eager(rb, L, step))
+        # utd_ratio > 1: the critic-only kind's graph G-1 times -- the one an ordinary critic-only step captures and
+        # replays, positive's sampling nodes included --, then the step's own kind.  Every sub-step takes the next turn
+        # of its kind's ring, so consecutive replays of one kind read different blocks, and graph_write waits for the
+        # replay that last read a block before the host rewrites it.
+        lead_kind = (False, kind[1], False)
+        for k in range(leading):
+            self._graphed_substep(rb, step, lead_kind, key, lambda k=k: self._substep_eager(
+                rb, None, step, leading=True, first=k == 0), leading=True, first=k == 0)
+        self._graphed_substep(rb, step, kind, key, lambda: self._substep_eager(rb, L, step, first=False), first=False)
+
+    def _graphed_substep(self, rb, step, kind, key, eager, leading=False, first=True):
+        """One minibatch of a graphed update: the replay of ``kind``'s graph (captured here when its turn has none) or,
+        while the kind is warming up and where a capture fails, ``eager()``."""
+        if self._graphs is None:  # (an earlier sub-step of this call has given the graphs up)
+            return eager()
         seen = self._graph_seen.get(kind, 0)
         self._graph_seen[kind] = seen + 1
         if seen < self._graph_warm:  # (first uses allocate workspaces and set kernel attributes: not capturable)
-            return self._update_eager(rb, L, step)
+            return eager()
         ring = self._graphs.setdefault(kind, [])
         turn = (seen - self._graph_warm) % self._graph_depth
         if turn >= len(ring):
@@ -1816,7 +1918,10 @@ class CurlSacAgent(object, metaclass=_AgentType):
             err = None
             try:
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    self._update_phases(rb.graph_refs(st["slot"]), null, step)
+                    if leading:
+                        self._leading_phases(rb.graph_refs(st["slot"]), step)
+                    else:
+                        self._update_phases(rb.graph_refs(st["slot"]), null, step)
             except Exception as e:  # noqa: BLE001
                 err = e
             finally:
@@ -1841,12 +1946,12 @@ class CurlSacAgent(object, metaclass=_AgentType):
                 warnings.warn(f"curla_amd: capturing the update graph of {kind} failed {where} ({err!r}); this update "
                               "runs eagerly" + (" and update graphs are now disabled (every rank of the group does the same)"
                                                 if give_up else " and the capture is tried again next time"),
-                              RuntimeWarning, stacklevel=3)
+                              RuntimeWarning, stacklevel=4)
                 if give_up:
                     self._graphs = None
                 else:
                     self._graph_seen[kind] = seen  # (the slot keeps its empty entry: the same turn captures again)
-                return self._update_eager(rb, L, step)
+                return eager()
             st["graph"] = graph
             self._graph_key_at_capture = key
         # the eager order of host draws: indices, then the three tensors' augmentation parameters (staged_aug: NoisyCover
@@ -1855,7 +1960,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
         aug = rb.draw_aug()
         tail = self._graph_tail(kind, B)
         blk = rb.graph_write(st["slot"], idxs, offs, tail, aug)
-        if self._dp_active and self._dp_check_every > 0 and step % self._dp_check_every == 0:
+        if first and self._dp_active and self._dp_check_every > 0 and step % self._dp_check_every == 0:
             self.check_replicas()
         st["graph"].replay()
         if blk["event"] is None:
@@ -1911,7 +2016,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
             "critic_target": self.critic_target.state_dict(), "curl": self.CURL.state_dict(),
             "log_alpha": self.log_alpha.detach().cpu(),
             "optimizers": {k: self._convert_opt_state(o, o.state_dict(), True) for k, o in self._optimizers().items()},
-            "rng": rng, "critic_dropout": float(self.critic_dropout),
+            "rng": rng, "critic_dropout": float(self.critic_dropout), "utd_ratio": int(self.utd_ratio),
         }, path)
 
     def load_checkpoint(self, path, restore_rng=True):
@@ -1922,6 +2027,9 @@ class CurlSacAgent(object, metaclass=_AgentType):
         if float(ck.get("critic_dropout", 0.0)) != float(self.critic_dropout):
             warnings.warn("curla_amd: the checkpoint was written with critic_dropout = %r; this agent keeps its own, %r"
                           % (ck.get("critic_dropout", 0.0), self.critic_dropout), RuntimeWarning, stacklevel=2)
+        if ck.get("utd_ratio", 1) != self.utd_ratio:  # (a file from before the keyword: 1)
+            warnings.warn("curla_amd: the checkpoint was written with utd_ratio = %r; this agent keeps its own, %r"
+                          % (ck.get("utd_ratio", 1), self.utd_ratio), RuntimeWarning, stacklevel=2)
         self.CURL.load_state_dict(ck["curl"])
         self.actor.load_state_dict(ck["actor"])
         self.critic.load_state_dict(ck["critic"])

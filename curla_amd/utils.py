@@ -859,13 +859,18 @@ class ReplayBuffer(object):
                 offs[6 * (r // 2) + 2 * j + r % 2] = word
         return idxs, offs
 
-    def _float_augmented(self, ring, idx, dev, j, out=None):
+    def _float_augmented(self, ring, idx, dev, j, out=None, draw_only=False):
         """Tensor ``j`` (0 obs, 1 next_obs, 2 pos) of a minibatch as an augmented float NHWC tensor [B, H, W, C] from
         ``ring`` rows ``idx`` (None: rows 0..B-1) (utils.py:168-182 branch: the torch/kornia augmentations).  With
         staged_aug the tensor's parameters are already on the device, in the minibatch's block ``dev`` (_aug_args) --
-        nothing is drawn, allocated or copied here."""
+        nothing is drawn, allocated or copied here.  ``draw_only`` (a positive nobody wants): what the tensor's launch
+        would draw is drawn -- nothing with staged_aug --, nothing is launched and None is returned."""
         B = self.batch_size
         c, h, w = self.obs_shape
+        if draw_only:
+            if not self.staged_aug:
+                self.augmentor.draw_unstaged(B, (B, h, w, c), self.device)
+            return None
         if out is None:
             out = torch.empty((B, h, w, c), dtype=torch.float32, device=self.device)
         self.augmentor.launch(ring, idx, B, out, self._aug_args(dev, j) if self.staged_aug else None)
@@ -981,7 +986,7 @@ class ReplayBuffer(object):
             c32.copy_(torch.from_numpy(np.ascontiguousarray(offs[[6 * (r // 2) + 2 * j + r % 2 for r in range(2, 2 + runs)
                                                                   for j in range(3)]])))
 
-    def _upload_indices(self, idxs, offs, aug=None):
+    def _upload_indices(self, idxs, offs, aug=None, want_pos=True):
         """A minibatch's indices and crop offsets (and, staged_aug, its augmentation parameters ``aug``) into the next
         rotating slot's device block, the transitions' scalars (n_step: composed) into its scalar buffer; returns the
         slot and the guard of handles into it."""
@@ -1008,7 +1013,7 @@ class ReplayBuffer(object):
         else:
             dst.copy_(host, non_blocking=True)
             if self.device.type == "cuda" or _lib_tracing():
-                self._stage(None, dst, host.numel(), slot["scalars"], copied=True)
+                self._stage(None, dst, host.numel(), slot["scalars"], copied=True, want_pos=want_pos)
         if self.device.type == "cuda" and u % every == every - 1:
             ev = torch.cuda.Event()
             ev.record()
@@ -1026,10 +1031,11 @@ class ReplayBuffer(object):
         return (scal[:B * A].view((B,) + tuple(self.actions.shape[1:])), scal[B * A:B * A + B].view(B, 1),
                 scal[B * A + B:].view(B, 1))
 
-    def _stage(self, host_dev, dev, nbytes, out, copied=False):
+    def _stage(self, host_dev, dev, nbytes, out, copied=False, want_pos=True):
         """Staging a minibatch: the transitions' scalars into ``out`` (_scalar_views; n_step > 1: composed) and, with
         pos_offset > 0, the positive's rows into the block.  ``host_dev``, the pinned block's device address: ONE launch,
-        which also brings the block to ``dev``.  ``copied``, the block is in ``dev`` already: a launch each."""
+        which also brings the block to ``dev``.  ``copied``, the block is in ``dev`` already: a launch each -- and
+        without ``want_pos`` none for the positive's walk (in the one launch it rides along as it is)."""
         B, A, lay = self.batch_size, self._n_act, self._layout
         cont = self._cont if self._keep_cont else None
         lane = dict(stride=self._n_envs) if self._n_envs > 1 else {}  # the walks' step (the _strided entry points)
@@ -1040,7 +1046,7 @@ class ReplayBuffer(object):
             if self.n_step > 1:  # the bootstrap rows must be in the block before anything reads pixels
                 ops.nstep_compose(dev, lay["next_row"], self._sc, cont, self.capacity, self.n_step,
                                   self._nstep_discount(), B, A, *out, **lane)
-            if self._pos_offset:  # ... and so must the positive's rows (behind the draw, which writes the idx run)
+            if self._pos_offset and want_pos:  # ... and so must the positive's rows (behind the draw, which writes the idx run)
                 ops.pos_walk(dev, lay["pos_row"], lay.get("pos_run"), lay.get("next_row"), cont, self.capacity,
                              self._pos_offset, self.n_step, B, **lane)
         elif self._pos_offset:
@@ -1058,7 +1064,7 @@ class ReplayBuffer(object):
         if self.device.type != "cuda" and _lib._trace_hook is None:
             raise RuntimeError("sampling pixels needs the HIP device: curla_amd has no CPU fallback for the learner path")
 
-    def _sources(self, slot):
+    def _sources(self, slot, want_pos=True):
         """Where the loaders read the minibatch of ``slot`` from -- which storage, which rows for next_obs: decided
         here and nowhere else.  Returns a _Sources:
           tensors  (ring, rows) of obs, next_obs, pos: ONE ring each, ``rows`` int64 [B] or None for rows 0..B-1;
@@ -1076,7 +1082,9 @@ class ReplayBuffer(object):
                    runs of ``cut`` (RandomCutout's packed box sizes and colour words; Compose's y0, x0, sizes, colours)
         Plain storage reads the rings at the sampled rows.  The frame store first assembles the k frames of every
         sampled stack into the slot's [2B][H][W][3k] uint8 buffer (one gather kernel per tensor; with pos_offset > 0 a third
-        one, the next_obs stacks of the positive's rows, into a buffer of [3B])."""
+        one, the next_obs stacks of the positive's rows, into a buffer of [3B]).
+        Without ``want_pos`` (sample_cpc_refs) nothing is launched for the positive and nothing reads rows its walk would
+        have written: no third gather, and ``run`` is ``idx2`` with period 2B whatever pos_offset says."""
         B, lay, dev = self.batch_size, self._layout, slot["dev"]
         d64 = dev[lay["idx"]:lay["offs"]].view(torch.int64)
         d32 = dev[lay["offs"]:lay["offs_end"]].view(torch.int32)
@@ -1092,7 +1100,7 @@ class ReplayBuffer(object):
             nt = 3 if kp else 2
             both = slot["mb_u8"][:nt * B * self._frame].view(nt * B, h, w, c)
             rings, idx2 = tuple(both[j * B:(j + 1) * B] for j in range(nt)), None
-            for j, r in enumerate((rows, rows_n, rows_p)[:nt]):
+            for j, r in enumerate((rows, rows_n, rows_p)[:nt if want_pos else 2]):
                 ops.gather_stacks(self.frames, self._fid[:, min(j, 1), :], r, B, rings[j])
             rows = rows_n = rows_p = None
             pos, pos2, run = (rings[2 if kp else 0], None), None, None
@@ -1101,6 +1109,8 @@ class ReplayBuffer(object):
             pos = (rings[1 if kp else 0], rows_p)
             pos2 = p64[B:] if kp else rows  # (the double ring's next_obs half: capacity + r)
             run = dev[lay["pos_run"]:lay["pos_run"] + 24 * B].view(torch.int64) if "pos_run" in lay else d64
+            if not want_pos:
+                run, period = d64, 2 * B
         words = (d32[:3 * B], d32[3 * B:])
         if "cut" in lay:
             runs = self._index_rows - 2
@@ -1109,11 +1119,13 @@ class ReplayBuffer(object):
         return _Sources(both, idx2, d32[:2 * B], d32[3 * B:5 * B], ((rings[0], rows), (rings[1], rows_n), pos), off, words,
                         pos2, run, period)
 
-    def _scratch_aug(self, slot, src):
+    def _scratch_aug(self, slot, src, want_pos=True):
         """A "scratch" augmentation: the frames of a minibatch (``src``: _sources) augmented by its ``scratch_launch`` --
         shifted, boxes painted, placed on the canvas -- into the slot's scratch as obs | next_obs | pos; returns the
         [3B][Ho][Wo][C] view ((Ho, Wo) = output_shape).  With ``both`` ONE launch, pos reading the obs rows again (period
-        2B) or, pos_offset > 0, its own rows (period 3B); with the rings in two allocations one launch per tensor."""
+        2B) or, pos_offset > 0, its own rows (period 3B); with the rings in two allocations one launch per tensor.
+        Without ``want_pos`` the one launch is of n = 2B, obs | next_obs, and the third of the per-tensor ones is left out:
+        the scratch's last B rows then hold an earlier minibatch's positives."""
         B = self.batch_size
         oh, ow = self.augmentor.output_shape
         out = slot["shift_u8"][:3 * B * self._scratch_frame()].view(3 * B, oh, ow, self.obs_shape[0])
@@ -1121,9 +1133,9 @@ class ReplayBuffer(object):
         def launch(ring, rows, period, lo, hi):
             self.augmentor.scratch_launch(ring, rows, period, [w[lo:hi] for w in src.words], hi - lo, out[lo:hi])
         if src.both is not None:
-            launch(src.both, src.run, src.period, 0, 3 * B)
+            launch(src.both, src.run, src.period, 0, (3 if want_pos else 2) * B)
         else:
-            for j, (ring, rows) in enumerate(src.tensors):
+            for j, (ring, rows) in enumerate(src.tensors[:3 if want_pos else 2]):
                 launch(ring, rows, B, j * B, (j + 1) * B)
         return out
 
@@ -1138,14 +1150,15 @@ class ReplayBuffer(object):
         obses.pair = (ops.ObsRef.from_ring(shifted, ar[:2 * B], z[:2 * B], z[:2 * B], 2 * B, hw, guard), next_obses)
         return obses, next_obses, pos
 
-    def _assemble(self, slot, guard):
+    def _assemble(self, slot, guard, want_pos=True):
         """The (obs, next_obs, pos) handles of the minibatch whose block and scalars are staged in ``slot`` -- a rotating
         slot (sample_cpc_refs; ``guard`` from _upload_indices) or a captured graph's (graph_refs; ``guard`` None), whose
         launches then write to fixed addresses: the
         gathers of the frame store (_sources), then by the augmentation's kind ring handles (nothing is launched: the first
-        conv layer gathers and crops), the launch(es) into the scratch, or the three float launches."""
+        conv layer gathers and crops), the launch(es) into the scratch, or the three float launches.  Without ``want_pos``
+        the positive's handle is None and nothing is launched that writes the positive alone."""
         B = self.batch_size
-        src = self._sources(slot)
+        src = self._sources(slot, want_pos)
         both, idx2, tensors, off = src.both, src.idx2, src.tensors, src.off
         if self._kind == "float":
             # obs, next_obs and pos (= a copy of obs) are augmented independently (utils.py:173-182); obs and
@@ -1155,11 +1168,14 @@ class ReplayBuffer(object):
             if fb is None:
                 fb = torch.empty((2 * B, h, w, c), dtype=torch.float32, device=self.device)
             outs = fb[:B], fb[B:], slot.get("pos_f32")
-            obses, next_obses, pos = (ops.ObsRef.from_nhwc(self._float_augmented(ring, rows, slot["dev"], j, outs[j]))
-                                      for j, (ring, rows) in enumerate(tensors))
+            obses, next_obses = (ops.ObsRef.from_nhwc(self._float_augmented(ring, rows, slot["dev"], j, outs[j]))
+                                 for j, (ring, rows) in enumerate(tensors[:2]))
+            ring, rows = tensors[2]  # (behind the other two: the order of the host draws)
+            pos = self._float_augmented(ring, rows, slot["dev"], 2, outs[2], draw_only=not want_pos)
+            pos = ops.ObsRef.from_nhwc(pos) if want_pos else None
             obses.pair = (ops.ObsRef.from_nhwc(fb), next_obses)
         elif self._kind == "scratch":
-            obses, next_obses, pos = self._shift_refs(self._scratch_aug(slot, src), guard)
+            obses, next_obses, pos = self._shift_refs(self._scratch_aug(slot, src, want_pos), guard)
         else:
             crop = tuple(self.augmentor.output_shape)
             if both is not None:
@@ -1177,7 +1193,7 @@ class ReplayBuffer(object):
                                       for j, (ring, rows) in enumerate(tensors))
             if both is not None:
                 obses.pair = (ops.ObsRef.from_ring(both, idx2, src.h2, src.w2, 2 * B, crop, guard), next_obses)
-        return obses, next_obses, pos
+        return obses, next_obses, pos if want_pos else None
 
     # ---- dedicated sample slots of captured update graphs (CurlSacAgent.enable_update_graphs) ---------------------
     # A captured graph replays the SAME pointers: its minibatch block lives in its own pinned host slot and its own
@@ -1269,16 +1285,22 @@ class ReplayBuffer(object):
         act, rew, nd = g["scalars"]
         return obses, act, rew, next_obses, nd, dict(obs_anchor=obses, obs_pos=pos, time_anchor=None, time_pos=None)
 
-    def sample_cpc_refs(self, indices=None):
+    def sample_cpc_refs(self, indices=None, want_pos=True):
         """The fused form of sample_cpc: same 6-tuple, but obs / next_obs / pos are
         ``ObsRef`` handles (ring + indices + crop offsets) consumed directly by the
         first conv kernel.  ``indices=(idxs, offs)`` injects pre-drawn indices (tests, DP).
         The handles of one call stay valid until N_SAMPLE_SLOTS further samples have been drawn (using an older
-        one raises)."""
+        one raises).
+        ``want_pos=False`` (a leading sub-step of CurlSacAgent(utd_ratio=G): no CURL phase follows): everything is drawn
+        that is drawn otherwise -- indices, the three tensors' index words and float-augmentation parameters, NoisyCover's
+        noise counters --, so every stream ends where it ends with the positive; nothing is launched whose only output is
+        the positive (the third float-augmentation launch, the positive's share of a scratch augmentation's launch, the
+        positive's gather_stacks of a dedup_frames buffer, the positive's walk where it is a launch of its own), and
+        ``cpc_kwargs["obs_pos"]`` is None.  Where the positive rides in a launch that runs anyway, that launch is unchanged."""
         self._require_cuda()
         idxs, offs = indices if indices is not None else self.draw_indices()
-        slot, guard = self._upload_indices(idxs, offs, self.draw_aug())
-        obses, next_obses, pos = self._assemble(slot, guard)
+        slot, guard = self._upload_indices(idxs, offs, self.draw_aug(), want_pos)
+        obses, next_obses, pos = self._assemble(slot, guard, want_pos)
         if self.prioritized:
             obses.per = self._per_handle(slot, guard)
         actions, rewards, not_dones = slot["scalars"]  # (valid as long as the pixel handles are)
