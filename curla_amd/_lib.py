@@ -84,6 +84,15 @@ SIGNATURES = {
                                       vp, vp, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int, c_double, vp, vp],
     "curla_adam_step2_clip": [vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_double, c_double, c_double, c_double, c_ll,
                               c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int, c_double, vp, vp],
+    # decoupled weight decay (AdamW): the _clip namesakes with a weight_decay behind each eps of the flat run
+    "curla_adamw_step": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int,
+                         c_double, vp, vp],
+    "curla_adamw_step_lerp": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_double, c_ll, vp, vp,
+                              c_size_t, c_float, c_float, c_float, c_float, vp, c_int, c_double, vp, vp],
+    "curla_adamw_step_scalar64": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_double, c_ll, vp, vp,
+                                  vp, vp, vp, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int, c_double, vp, vp],
+    "curla_adamw_step2": [vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_double, c_double, c_double, c_double, c_double,
+                          c_ll, c_double, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_int, c_double, vp, vp],
     "curla_f64_pack": [vp, vp, vp],
     "curla_f64_unpack": [vp, c_double, c_double, vp, vp],
     "curla_gather_transition_scalars": [vp, vp, c_int, c_int, vp, vp, vp, vp],

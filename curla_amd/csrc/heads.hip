@@ -23,7 +23,7 @@ namespace {
 #include "mlp_out.h"       // mlp_out_fwd_kernel<HEAD, R, LDSW>, mlp_out_bwd_kernel<GEN>, the policy head's three kernels
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
 #include "curl_head.h"     // curl_head_kernel<NTILE>
-#include "optim.h"         // soft_update_kernel, soft_update2_kernel, adam_step_kernel<CLIP>, adam_step2_kernel<CLIP>
+#include "optim.h"         // soft_update_kernel, soft_update2_kernel, adam_step_kernel<CLIP, DECAY>, adam_step2_kernel<CLIP, DECAY>
 #include "sample_stage.h"  // a minibatch's index block and scalars: sample_stage_kernel<HOST, NSTEP, POS>, pos_walk_kernel
 #include "ring.h"          // crop_nchw_kernel, store_frame_kernel, gather_stacks_kernel<FAST>, nhwc_to_nchw_kernel
 #include "per.h"           // prioritized replay: per_set's three phases, per_sample_kernel, per_td_kernel
@@ -124,6 +124,11 @@ AdamHyper adam_hyper(double lr, double beta1, double beta2, double eps, long lon
   return h;
 }
 
+// The decay factor of the curla_adamw_* entry points (optim.h decay_one): 1 - lr * weight_decay formed in double and
+// rounded to float once, as torch's AdamW forms it (param.mul_(1 - lr * weight_decay)).
+float decay_factor(double lr, double weight_decay) { return (float)(1.0 - lr * weight_decay); }
+bool weight_decay_ok(double weight_decay) { return weight_decay >= 0. && weight_decay < HUGE_VAL; }  // (false for a NaN)
+
 template <typename... P>
 bool float_pointers(const P*... p) {  // none NULL, none off 4 bytes
   return (... && (p != nullptr && (reinterpret_cast<uintptr_t>(p) & 3) == 0));
@@ -139,11 +144,21 @@ int clip_args(const double* partials, int n_partials, double max_norm, float* st
   return CURLA_OK;
 }
 
+// The clip argument of the curla_adamw_* entry points: partials == NULL is the unclipped launch (n_partials must then be
+// 0; max_norm and stats are not looked at, `grad` is not written), anything else is clip_args'.
+int clip_args_or_none(const double* partials, int n_partials, double max_norm, float* stats, AdamClip* clip) {
+  if (partials) return clip_args(partials, n_partials, max_norm, stats, clip);
+  CURLA_REQUIRE(n_partials == 0);
+  *clip = AdamClip{};
+  return CURLA_OK;
+}
+
 // `grad` is written only by a clipping launch (clip.partials != nullptr): the plain entry points hand in their const
-// gradient and an empty clip.
+// gradient and an empty clip.  `decay` != nullptr (the curla_adamw_* entry points): the kernels that multiply the
+// parameter by *decay first; nullptr: the kernels without weight decay, as they were.
 int adam_step_launch(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                      double beta2, double eps, long long step, const float* dyn, const AdamScalar64& sc, void* stream,
-                     const AdamLerp& lp = AdamLerp{}, const AdamClip& clip = AdamClip{}) {
+                     const AdamLerp& lp = AdamLerp{}, const AdamClip& clip = AdamClip{}, const float* decay = nullptr) {
   CURLA_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1 && beta1 >= 0. && beta1 < 1. &&
                 beta2 >= 0. && beta2 < 1. && (reinterpret_cast<uintptr_t>(dyn) & 3) == 0);
   const AdamHyper hy = adam_hyper(lr, beta1, beta2, eps, step);
@@ -151,26 +166,43 @@ int adam_step_launch(float* param, float* grad, float* exp_avg, float* exp_avg_s
                   (!lp.tgt || (aligned16(lp.tgt) && lp.split % 4 == 0));
   const dim3 grid(nblocks((n + 3) / 4, 256, 8192));
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const float* cgrad = grad;
+  if (decay && clip.partials)
+    return launch(adam_step_kernel<true, true>, grid, 256, 0, st, param, grad, exp_avg, exp_avg_sq, n, vec, hy.w1, hy.b2,
+                  hy.w2, hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip, *decay);
+  if (decay)
+    return launch(adam_step_kernel<false, true>, grid, 256, 0, st, param, cgrad, exp_avg, exp_avg_sq, n, vec, hy.w1, hy.b2,
+                  hy.w2, hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip, *decay);
   if (clip.partials)
-    return launch(adam_step_kernel<true>, grid, 256, 0, st, param, grad, exp_avg, exp_avg_sq, n, vec, hy.w1, hy.b2, hy.w2,
-                  hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip);
-  return launch(adam_step_kernel<false>, grid, 256, 0, st, param, static_cast<const float*>(grad), exp_avg, exp_avg_sq, n,
-                vec, hy.w1, hy.b2, hy.w2, hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip);
+    return launch(adam_step_kernel<true, false>, grid, 256, 0, st, param, grad, exp_avg, exp_avg_sq, n, vec, hy.w1, hy.b2,
+                  hy.w2, hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip, 1.0f);
+  return launch(adam_step_kernel<false, false>, grid, 256, 0, st, param, cgrad, exp_avg, exp_avg_sq, n, vec, hy.w1, hy.b2,
+                hy.w2, hy.step_size, hy.bc2_sqrt, hy.eps, sc, lp, dyn, clip, 1.0f);
 }
 
-// curla_adam_step2 and curla_adam_step2_clip
+// curla_adam_step2, curla_adam_step2_clip and (decay != nullptr: the two optimizers' factors, for the kernels that apply
+// them) curla_adamw_step2
 int adam_step2_launch(float* param, float* grad, float* exp_avg1, float* exp_avg_sq1, float* exp_avg2, float* exp_avg_sq2,
                       size_t n, size_t n_pre, const AdamHyper& h1, const AdamHyper& h2, const float* dyn, void* stream,
-                      const AdamClip& clip = AdamClip{}) {
+                      const AdamClip& clip = AdamClip{}, const float* decay = nullptr) {
   const int vec = (n_pre % 4 == 0) && aligned16(param) && aligned16(grad) && aligned16(exp_avg1) &&
                   aligned16(exp_avg_sq1) && aligned16(exp_avg2) && aligned16(exp_avg_sq2);
   const dim3 grid(nblocks((n + 3) / 4, 256, 8192));
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const float* cgrad = grad;
+  if (decay) {
+    const AdamHyperDecay d1{h1, decay[0]}, d2{h2, decay[1]};
+    if (clip.partials)
+      return launch(adam_step2_kernel<true, true>, grid, 256, 0, st, param, grad, exp_avg1, exp_avg_sq1, exp_avg2,
+                    exp_avg_sq2, n, n_pre, vec, d1, d2, dyn, clip);
+    return launch(adam_step2_kernel<false, true>, grid, 256, 0, st, param, cgrad, exp_avg1, exp_avg_sq1, exp_avg2,
+                  exp_avg_sq2, n, n_pre, vec, d1, d2, dyn, clip);
+  }
   if (clip.partials)
-    return launch(adam_step2_kernel<true>, grid, 256, 0, st, param, grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2, n,
-                  n_pre, vec, h1, h2, dyn, clip);
-  return launch(adam_step2_kernel<false>, grid, 256, 0, st, param, static_cast<const float*>(grad), exp_avg1, exp_avg_sq1,
-                exp_avg2, exp_avg_sq2, n, n_pre, vec, h1, h2, dyn, clip);
+    return launch(adam_step2_kernel<true, false>, grid, 256, 0, st, param, grad, exp_avg1, exp_avg_sq1, exp_avg2,
+                  exp_avg_sq2, n, n_pre, vec, h1, h2, dyn, clip);
+  return launch(adam_step2_kernel<false, false>, grid, 256, 0, st, param, cgrad, exp_avg1, exp_avg_sq1, exp_avg2,
+                exp_avg_sq2, n, n_pre, vec, h1, h2, dyn, clip);
 }
 
 // [a, a + na) and [b, b + nb) share no byte
@@ -737,6 +769,74 @@ int curla_adam_step2_clip(float* param, float* grad, float* exp_avg1, float* exp
   return adam_step2_launch(param, grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2, n, n_pre,
                            adam_hyper(lr1, beta1_1, beta2_1, eps1, step1), adam_hyper(lr2, beta1_2, beta2_2, eps2, step2),
                            dyn, stream, clip);
+}
+
+// Decoupled weight decay (AdamW): the _clip namesakes with a `weight_decay` behind each `eps` of the flat run; partials
+// == NULL is the unclipped launch.
+int curla_adamw_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                     double beta2, double eps, double weight_decay, long long step, const float* dyn,
+                     const double* partials, int n_partials, double max_norm, float* stats, void* stream) {
+  AdamClip clip;
+  const int rc = clip_args_or_none(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(weight_decay_ok(weight_decay) && float_pointers(param, grad, exp_avg, exp_avg_sq));
+  AdamScalar64 none = {};
+  const float d = decay_factor(lr, weight_decay);
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none, stream, AdamLerp{},
+                          clip, &d);
+}
+
+int curla_adamw_step_lerp(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, long long step, const float* dyn, float* target,
+                          size_t split, float tau_a, float one_minus_tau_a, float tau_b, float one_minus_tau_b,
+                          const double* partials, int n_partials, double max_norm, float* stats, void* stream) {
+  AdamClip clip;
+  const int rc = clip_args_or_none(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(weight_decay_ok(weight_decay) && float_pointers(param, grad, exp_avg, exp_avg_sq, target) && split <= n);
+  AdamScalar64 none = {};
+  AdamLerp lp{target, split, tau_a, one_minus_tau_a, tau_b, one_minus_tau_b};
+  const float d = decay_factor(lr, weight_decay);
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, none, stream, lp, clip, &d);
+}
+
+int curla_adamw_step_scalar64(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                              double beta1, double beta2, double eps, double weight_decay, long long step,
+                              const float* dyn, double* param64, const double* grad64, double* exp_avg64,
+                              double* exp_avg_sq64, double lr64, double beta1_64, double beta2_64, double eps64,
+                              long long step64, const double* dyn64, const double* partials, int n_partials,
+                              double max_norm, float* stats, void* stream) {
+  AdamClip clip;
+  int rc = clip_args_or_none(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(weight_decay_ok(weight_decay) && float_pointers(param, grad, exp_avg, exp_avg_sq) &&
+                ((reinterpret_cast<uintptr_t>(param64) | reinterpret_cast<uintptr_t>(grad64) |
+                  reinterpret_cast<uintptr_t>(exp_avg64) | reinterpret_cast<uintptr_t>(exp_avg_sq64)) & 7) == 0);
+  AdamScalar64 sc;
+  rc = scalar64_args(param64, grad64, exp_avg64, exp_avg_sq64, lr64, beta1_64, beta2_64, eps64, step64, dyn64, &sc);
+  if (rc != CURLA_OK) return rc;
+  const float d = decay_factor(lr, weight_decay);  // (the flat run's: the scalar is never decayed)
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, dyn, sc, stream, AdamLerp{},
+                          clip, &d);
+}
+
+int curla_adamw_step2(float* param, float* grad, float* exp_avg1, float* exp_avg_sq1, float* exp_avg2, float* exp_avg_sq2,
+                      size_t n, size_t n_pre, double lr1, double beta1_1, double beta2_1, double eps1,
+                      double weight_decay1, long long step1, double lr2, double beta1_2, double beta2_2, double eps2,
+                      double weight_decay2, long long step2, const float* dyn, const double* partials, int n_partials,
+                      double max_norm, float* stats, void* stream) {
+  AdamClip clip;
+  const int rc = clip_args_or_none(partials, n_partials, max_norm, stats, &clip);
+  if (rc != CURLA_OK) return rc;
+  CURLA_REQUIRE(weight_decay_ok(weight_decay1) && weight_decay_ok(weight_decay2) &&
+                float_pointers(param, grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2) && n > 0 && n_pre <= n &&
+                step1 >= 1 && step2 >= 1 && (reinterpret_cast<uintptr_t>(dyn) & 3) == 0);
+  CURLA_REQUIRE(beta1_1 >= 0. && beta1_1 < 1. && beta2_1 >= 0. && beta2_1 < 1. && beta1_2 >= 0. && beta1_2 < 1. &&
+                beta2_2 >= 0. && beta2_2 < 1.);
+  const float d[2] = {decay_factor(lr1, weight_decay1), decay_factor(lr2, weight_decay2)};
+  return adam_step2_launch(param, grad, exp_avg1, exp_avg_sq1, exp_avg2, exp_avg_sq2, n, n_pre,
+                           adam_hyper(lr1, beta1_1, beta2_1, eps1, step1), adam_hyper(lr2, beta1_2, beta2_2, eps2, step2),
+                           dyn, stream, clip, d);
 }
 
 int curla_host_device_pointer(void* host, void** device) {

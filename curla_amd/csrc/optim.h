@@ -1,6 +1,7 @@
 // The optimiser step over the flat parameter buffers: the target networks' soft update (soft_update_kernel,
 // soft_update2_kernel) and Adam, one step or two back to back, with the float64 scalar and the target lerp that can
-// ride along (adam_step_kernel, adam_step2_kernel), clipping by the global gradient norm included (AdamClip).
+// ride along (adam_step_kernel, adam_step2_kernel), clipping by the global gradient norm (AdamClip) and decoupled weight
+// decay (decay_one: AdamW) included.
 // Included by heads.hip inside its anonymous namespace.
 #pragma once
 
@@ -43,6 +44,15 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   v = v * b2 + (w2 * g) * g;
   const float denom = sqrtf(v) / bc2_sqrt + eps;
   p = p - (step_size * m) / denom;
+}
+
+// Decoupled weight decay (torch.optim.AdamW; Adam with decoupled_weight_decay=True): p <- p * d in front of the Adam
+// update, d = (float)(1 - lr * weight_decay) formed on the host in double as torch forms it.  ONE multiply with one
+// rounding; the update then runs on the decayed parameter.  The gradient, the clip coefficient and the moments do not
+// see d.  (Contraction off here as in adam_one: the product must round before the update's subtraction consumes it.)
+__device__ __forceinline__ float decay_one(float p, float d) {
+#pragma clang fp contract(off)
+  return p * d;
 }
 
 // A float64 scalar parameter stepped by the same launch (log_alpha beside the actor's parameters: the reference steps
@@ -98,15 +108,18 @@ __device__ __forceinline__ float clip_one(float g, float coef) {
 
 // CLIP false is the kernel without clipping, instruction for instruction what it was (the gradient const, no LDS);
 // CLIP true writes the gradient, and only where the coefficient is not 1: each element by the thread that read it.
+// DECAY false is the kernel without weight decay, likewise what it was (`d` is not read); DECAY true multiplies every
+// parameter by d before its update, in the vector path and the scalar tail alike.  The float64 rider is never decayed
+// (its optimizer is its own); the lerp rider reads the stepped, decayed parameter.
 template <bool CLIP>
 using AdamGrad = std::conditional_t<CLIP, float, const float>;
 
-template <bool CLIP>
+template <bool CLIP, bool DECAY>
 __global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, AdamGrad<CLIP>* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, size_t n,
                                                         int vec, float w1, float b2, float w2, float step_size,
                                                         float bc2_sqrt, float eps, AdamScalar64 sc, AdamLerp lp,
-                                                        const float* __restrict__ dyn, AdamClip clip) {
+                                                        const float* __restrict__ dyn, AdamClip clip, float d) {
   float coef = 1.0f;
   if constexpr (CLIP) coef = clip_coef(clip);
   const bool scale = CLIP && coef != 1.0f;
@@ -141,6 +154,7 @@ __global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, A
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pp[e], me = mm[e], ve = vv[e];
+        if constexpr (DECAY) pe = decay_one(pe, d);
         adam_one(pe, gg[e], me, ve, w1, b2, w2, step_size, bc2_sqrt, eps);
         pp[e] = pe, mm[e] = me, vv[e] = ve;
       }
@@ -162,6 +176,7 @@ __global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, A
     if constexpr (CLIP) {
       if (scale) g[i] = gi = clip_one(gi, coef);
     }
+    if constexpr (DECAY) p[i] = decay_one(p[i], d);
     adam_one(p[i], gi, m[i], v[i], w1, b2, w2, step_size, bc2_sqrt, eps);
     if (lp.tgt) lp.tgt[i] = lerp_one(p[i], lp.tgt[i], i < lp.split ? lp.tau_a : lp.tau_b, i < lp.split ? lp.omt_a : lp.omt_b);
   }
@@ -170,16 +185,26 @@ __global__ void __launch_bounds__(256) adam_step_kernel(float* __restrict__ p, A
 // Two Adam steps of two optimizers on the SAME parameters with the same gradient, back to back, in one pass (the
 // reference steps the encoder with encoder_optimizer and then again with cpc_optimizer, curl_sac.py:418-423): elements
 // [0, n_pre) belong to the second optimizer only (CURL.W in front of the encoder in the flat buffer), the rest take
-// step 1 then step 2 exactly as the two launches would (the same per-element operation order).
+// step 1 then step 2 exactly as the two launches would (the same per-element operation order).  With DECAY each
+// optimizer's factor goes in front of its own step, as first.step(); second.step() of two AdamWs: behind n_pre
+// p *= d1, Adam 1, p *= d2, Adam 2; the first n_pre elements p *= d2, Adam 2.
 struct AdamHyper {
   float w1, b2, w2, step_size, bc2_sqrt, eps;
 };
+// ... with the optimizer's decay factor (decay_one): what the DECAY kernels take, so that the kernels without weight
+// decay keep the arguments -- and with them the code -- they had
+struct AdamHyperDecay : AdamHyper {
+  float d;
+};
+template <bool DECAY>
+using AdamHyperOf = std::conditional_t<DECAY, AdamHyperDecay, AdamHyper>;
 
-template <bool CLIP>
+template <bool CLIP, bool DECAY>
 __global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, AdamGrad<CLIP>* __restrict__ g,
                                                          float* __restrict__ m1, float* __restrict__ v1,
                                                          float* __restrict__ m2, float* __restrict__ v2, size_t n,
-                                                         size_t n_pre, int vec, AdamHyper h1, AdamHyper h2,
+                                                         size_t n_pre, int vec, AdamHyperOf<DECAY> h1,
+                                                         AdamHyperOf<DECAY> h2,
                                                          const float* __restrict__ dyn, AdamClip clip) {
   // (adam_step_kernel: the gradient is clipped ONCE, over the whole run, and both steps consume the clipped value)
   float coef = 1.0f;
@@ -205,6 +230,7 @@ __global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float pe = pp[e], me = mm[e], ve = vv[e];
+          if constexpr (DECAY) pe = decay_one(pe, h1.d);
           adam_one(pe, gg[e], me, ve, h1.w1, h1.b2, h1.w2, h1.step_size, h1.bc2_sqrt, h1.eps);
           pp[e] = pe, mm[e] = me, vv[e] = ve;
         }
@@ -215,6 +241,7 @@ __global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pp[e], me = mm[e], ve = vv[e];
+        if constexpr (DECAY) pe = decay_one(pe, h2.d);
         adam_one(pe, gg[e], me, ve, h2.w1, h2.b2, h2.w2, h2.step_size, h2.bc2_sqrt, h2.eps);
         pp[e] = pe, mm[e] = me, vv[e] = ve;
       }
@@ -232,10 +259,12 @@ __global__ void __launch_bounds__(256) adam_step2_kernel(float* __restrict__ p, 
     }
     if (i >= n_pre) {
       float m = m1[i - n_pre], v = v1[i - n_pre];
+      if constexpr (DECAY) pi = decay_one(pi, h1.d);
       adam_one(pi, gi, m, v, h1.w1, h1.b2, h1.w2, h1.step_size, h1.bc2_sqrt, h1.eps);
       m1[i - n_pre] = m, v1[i - n_pre] = v;
     }
     float m = m2[i], v = v2[i];
+    if constexpr (DECAY) pi = decay_one(pi, h2.d);
     adam_one(pi, gi, m, v, h2.w1, h2.b2, h2.w2, h2.step_size, h2.bc2_sqrt, h2.eps);
     m2[i] = m, v2[i] = v;
     p[i] = pi;

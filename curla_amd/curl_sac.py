@@ -31,7 +31,7 @@ from . import autograd, ops
 from .augmentations import Compose, RandomCrop, RandomTranslate
 from .encoder import CNNEncoder
 from .ops import ObsRef
-from .optim import FlatAdam, check_max_grad_norm
+from .optim import FlatAdam, check_max_grad_norm, check_weight_decay
 
 LOG_FREQ = 25_000
 
@@ -521,12 +521,15 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, utd_ratio=1, critic_dropout=0.0, critic_layer_norm=False, **kwargs):
+    def __call__(cls, *args, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0, critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
         agent.critic_layer_norm = bool(critic_layer_norm)
         agent.critic_dropout = _check_dropout(critic_dropout, agent.critic_layer_norm)
         agent.utd_ratio = _check_utd_ratio(utd_ratio)
+        weight_decay = check_weight_decay(weight_decay)
         agent.__init__(*args, **kwargs)
+        if weight_decay != 0:  # (0: the optimizers are built exactly as without the keyword)
+            agent.set_weight_decay(weight_decay)
         return agent
 
 
@@ -540,7 +543,10 @@ class CurlSacAgent(object, metaclass=_AgentType):
     No module and no mask buffer: ``p`` is this attribute, the masks are a counter-based stream.
     ``utd_ratio=G`` (default 1: nothing changes): the update-to-data ratio of DroQ / RLPD -- one ``update()`` call makes
     G critic steps on G freshly drawn minibatches before the actor steps once (``update``).  An attribute
-    that may be edited between calls."""
+    that may be edited between calls.
+    ``weight_decay=wd`` (default 0: nothing changes): decoupled weight decay -- the actor, critic, encoder and cpc
+    optimizers are ``torch.optim.AdamW(..., weight_decay=wd)``, log_alpha's stays plain Adam (``set_weight_decay``;
+    DESIGN.md 7g)."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
@@ -1560,6 +1566,30 @@ class CurlSacAgent(object, metaclass=_AgentType):
                 opt.max_grad_norm = value
         self._max_grad_norm = value  # (captured update graphs hold it by value: _graph_key)
 
+    # ---------------------------------------------------------------- decoupled weight decay (AdamW)
+    @property
+    def weight_decay(self):
+        """The decoupled weight decay of the network optimizers, read from the critic optimizer's param group (the four
+        carry the same value unless their groups were edited one by one); set by ``set_weight_decay``."""
+        return float(self.critic_optimizer.param_groups[0].get("weight_decay", 0))
+
+    def set_weight_decay(self, value):
+        """Decoupled weight decay on the four network optimizers: actor, critic, encoder and cpc become what
+        ``torch.optim.AdamW(..., weight_decay=value)`` is in the reference's place (curl_sac.py:299-313) -- every step
+        multiplies the parameters it steps by ``1 - lr * value`` in front of the Adam update.  log_alpha's optimizer
+        stays plain Adam.  The encoder is decayed by each optimizer that steps it (critic, encoder and cpc), as it would
+        be there; parameters without a gradient at step time (the convs under ``detach_encoder`` in the critic's step)
+        are not, as torch skips them.  ``value``: a finite number >= 0; 0 switches it off (the launches are the plain
+        ones again).  Written into the optimizers' param groups (``weight_decay``, ``decoupled_weight_decay = value !=
+        0``) as torch keeps them: it is part of their ``state_dict()`` and a checkpoint restores it.  With the flat
+        optimizers the multiply is inside the Adam launches (``curla_adamw_*``, optim.py): an update launches as many
+        optimizer kernels as without it."""
+        value = check_weight_decay(value)
+        for opt in (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer):
+            for g in opt.param_groups:
+                g["weight_decay"] = value
+                g["decoupled_weight_decay"] = value != 0
+
     def _clip_torch(self, row, opt):
         """The clipping step of a phase whose optimizer is torch's own (CURLA_TORCH_ADAM=1, a CPU agent): FlatAdam
         clips inside its launches."""
@@ -1744,7 +1774,10 @@ class CurlSacAgent(object, metaclass=_AgentType):
         ``utd_ratio = G > 1``: a call replays the critic-only kind's graph (actor=False, soft, cpc=False) G-1 times -- the
         graph an ordinary critic-only step captures, each replay on the next block of the kind's rotation -- and then the
         step's own kind; a call that runs eagerly (above) runs all its sub-steps eagerly.  No graph holds the ratio: it
-        is not fingerprinted and may be edited between calls."""
+        is not fingerprinted and may be edited between calls.
+        Weight decay (``set_weight_decay``): a captured Adam launch holds its factor ``float32(1 - lr * weight_decay)``
+        by value, so for an optimizer that decays, ``lr`` is fingerprinted too -- an lr schedule on a decaying optimizer
+        re-captures at every change of lr (without weight decay lr travels as data and never re-captures)."""
         if self.device.type != "cuda":
             raise RuntimeError("update graphs need the HIP device")
         if not getattr(replay_buffer, "graph_supported", lambda: False)():
@@ -1789,10 +1822,12 @@ class CurlSacAgent(object, metaclass=_AgentType):
 
     def _graph_key(self):
         """Everything a captured graph holds BY VALUE (kernel arguments baked in at capture): a change of any of it
-        makes the captured graphs stale -- they are dropped and re-captured (``lr`` travels as data and is not here)."""
+        makes the captured graphs stale -- they are dropped and re-captured (``lr`` travels as data and is not here,
+        except for a param group with weight decay: its launch holds 1 - lr * weight_decay by value)."""
         opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer,
                 self.log_alpha_optimizer)
-        hyper = tuple((float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g.get("weight_decay", 0)))
+        hyper = tuple((float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g.get("weight_decay", 0))) +
+                      ((float(g["lr"]),) if g.get("weight_decay", 0) != 0 else ())  # (0: the key without weight decay)
                       for o in opts for g in o.param_groups)
         return (float(self.discount), float(self.critic_tau), float(self.encoder_tau), bool(self.detach_encoder),
                 bool(self.pixel_sac), float(self.target_entropy), float(self.actor.log_std_min),

@@ -14,6 +14,12 @@ checkpoint written from ``state_dict()`` is what torch's Adam would write.
 ``torch.nn.utils.clip_grad_norm_(live parameters, max_grad_norm)`` right in front of ``step()``, as one square-sum launch
 per run (``curla_grad_sqsum``: float64 partial sums in a buffer this optimizer owns) and the coefficient formed and
 applied by the Adam launch that follows (``curla_adam_step*_clip``).  No host read, no allocation in the step.
+
+``weight_decay`` with ``decoupled_weight_decay=True`` is ``torch.optim.AdamW``: every launch of a decaying group is the
+``curla_adamw_*`` form of the launch it would have been, which multiplies each parameter by
+``float32(1 - lr * weight_decay)`` -- one rounding -- in front of its Adam update.  Both live in
+``param_groups`` and ``state_dict()`` as torch writes them and are read from the group at step time.  Coupled L2 decay
+(``decoupled_weight_decay=False``) is not implemented.
 """
 import math
 import numbers
@@ -33,16 +39,33 @@ def check_max_grad_norm(value):
     return float(value)
 
 
+def check_weight_decay(value):
+    """``value`` as a weight decay: a finite number >= 0 as a float; ValueError for a bool, a non-number, NaN, an
+    infinite or a negative value."""
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value) or value < 0:
+        raise ValueError("weight_decay must be a finite number >= 0, got %r" % (value,))
+    return float(value)
+
+
+_NO_CLIP = (0, 0, 0.0, 0)  # the clip arguments (partials, n_partials, max_norm, stats) of an unclipped curla_adamw_* launch
+
+
 class FlatAdam(torch.optim.Adam):
     CLIP_MAX_PARTIALS = 256  # include/curla_hip.h: one Adam workgroup sums a step's partials with one load per thread
     SQSUM_BLOCK = 1024       # elements a square-sum workgroup takes per trip of its grid-stride loop (256 x 16 bytes)
 
-    def __init__(self, params, flat, gflat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, max_grad_norm=None):
+    def __init__(self, params, flat, gflat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, weight_decay=0.0,
+                 decoupled_weight_decay=False, max_grad_norm=None):
         """``params``: Parameters whose ``.data`` are views into ``flat`` and whose ``.grad`` (when not None) are the
         views at the same offsets of ``gflat``.  ``max_grad_norm``: None, or the threshold every step clips its live
         gradient's global norm to (a hyper-parameter, not state: it is neither in ``param_groups`` nor in
-        ``state_dict()``)."""
-        super().__init__(params, lr=lr, betas=betas, eps=eps)
+        ``state_dict()``).  ``weight_decay`` / ``decoupled_weight_decay``: torch.optim.Adam's, kept in the param group
+        as torch keeps them; a non-zero decay must be the decoupled one (AdamW)."""
+        weight_decay = check_weight_decay(weight_decay)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         decoupled_weight_decay=bool(decoupled_weight_decay))
+        for g in self.param_groups:
+            self._decay(g)
         self._flat, self._gflat = flat, gflat
         self._plist = [p for g in self.param_groups for p in g["params"]]
         base = flat.data_ptr()
@@ -156,6 +179,19 @@ class FlatAdam(torch.optim.Adam):
             self._steps[i] += by
 
     # -- the step --------------------------------------------------------------------------------------------
+    @staticmethod
+    def _decay(group):
+        """The group's decoupled weight decay, read at step time (0.0: none -- the launches are the plain ones);
+        NotImplementedError for the Adam options the launches do not implement."""
+        wd = group.get("weight_decay", 0)
+        if group.get("amsgrad", False) or group.get("maximize", False):
+            raise NotImplementedError("FlatAdam implements the options the learner uses: Adam and AdamW, no amsgrad, "
+                                      "no maximize")
+        if wd != 0 and not group.get("decoupled_weight_decay", False):
+            raise NotImplementedError("FlatAdam: weight_decay is implemented in its decoupled form only (AdamW): pass "
+                                      "decoupled_weight_decay=True; coupled L2 decay is not supported")
+        return float(wd)
+
     def _plan(self, gi, group, live):
         """Contiguous runs [a, b) of the flat buffer covered by this group's live parameters (alignment padding
         between two adjacent parameters -- at most 3 floats, always zero gradient -- is bridged), each with the
@@ -184,8 +220,7 @@ class FlatAdam(torch.optim.Adam):
             plans = self._plans[live] = [self._plan(gi, g, live) for gi, g in enumerate(self.param_groups)]
         segs = []
         for group, runs in zip(self.param_groups, plans):
-            if group.get("weight_decay", 0) != 0 or group.get("amsgrad", False) or group.get("maximize", False):
-                raise NotImplementedError("FlatAdam implements the options the learner uses: plain Adam")
+            self._decay(group)
             for a, b, members in runs:
                 # parameters of one run normally share their step count; split the run where they do not
                 k = 0
@@ -223,10 +258,28 @@ class FlatAdam(torch.optim.Adam):
             count += nb
         return base, count, self._max_grad_norm, self.clip_stats.data_ptr()
 
-    def _adam_args(self, lo, hi, t, g):
+    @staticmethod
+    def _hyper(g, t, wd=None):
+        """(lr, beta1, beta2, eps, step) of a launch; a curla_adamw_* launch (``wd`` not None) takes weight_decay
+        behind eps."""
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) + \
+            (() if wd is None else (wd,)) + (t + 1,)
+
+    def _adam_args(self, lo, hi, t, g, wd=None):
         return (self._flat.data_ptr() + 4 * lo, self._gflat.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * (lo - self._lo),
-                self._v.data_ptr() + 4 * (lo - self._lo), hi - lo, float(g["lr"]), float(g["betas"][0]),
-                float(g["betas"][1]), float(g["eps"]), t + 1, self._dyn)
+                self._v.data_ptr() + 4 * (lo - self._lo), hi - lo) + self._hyper(g, t, wd) + (self._dyn,)
+
+    @staticmethod
+    def _launch(form, args, wd, clip, s):
+        """One Adam launch: ``curla_adam_<form>`` / ``curla_adam_<form>_clip`` as ever without weight decay (``wd``
+        None), ``curla_adamw_<form>`` (its clip arguments empty when the launch does not clip) with it; ``args``
+        carry the decay already (_hyper)."""
+        if wd is not None:
+            call("curla_adamw_" + form, *args, *(_NO_CLIP if clip is None else clip), s)
+        elif clip is None:
+            call("curla_adam_" + form, *args, s)
+        else:
+            call("curla_adam_" + form + "_clip", *args, *clip, s)
 
     @staticmethod
     def _pieces(lo, hi, done):
@@ -250,11 +303,9 @@ class FlatAdam(torch.optim.Adam):
             else:
                 clip = self._sqsum(self._touched, s)  # one norm over all the runs of the step
         for group, lo, hi, t in segs:
+            wd = self._decay(group) or None
             for a, b, scaled in self._pieces(lo, hi, done):
-                if clip is None or scaled:
-                    call("curla_adam_step", *self._adam_args(a, b, t, group), s)
-                else:
-                    call("curla_adam_step_clip", *self._adam_args(a, b, t, group), *clip, s)
+                self._launch("step", self._adam_args(a, b, t, group, wd), wd, None if scaled else clip, s)
         return loss
 
     # -- two optimizers, one pass ------------------------------------------------------------------------------
@@ -271,7 +322,9 @@ class FlatAdam(torch.optim.Adam):
         if len(runs) != 1 or len(set(self._steps)) != 1:
             return None
         g = self.param_groups[0]
-        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+        try:
+            self._decay(g)
+        except NotImplementedError:  # (the step the caller then takes raises it)
             return None
         return runs[0][0], runs[0][1], self._steps[0], g
 
@@ -281,6 +334,7 @@ class FlatAdam(torch.optim.Adam):
         """``first.step(); second.step()`` for two FlatAdams over the same flat buffer where first's parameters are the
         tail of second's (the encoder inside [CURL.W | encoder]): one launch that applies both steps per element in
         that order.  Anything else (partial gradients, unequal step counts, other layouts) takes the two steps.
+        With weight decay in either, each optimizer's factor goes in front of its own step (``curla_adamw_step2``).
         With ``max_grad_norm`` set (both must carry the same value) the gradient is clipped ONCE, by its norm over the
         second optimizer's run, and both steps consume the clipped gradient -- in the two separate steps as well
         (_two_steps)."""
@@ -300,16 +354,16 @@ class FlatAdam(torch.optim.Adam):
         elif second._dyn != first._dyn + 8:
             raise RuntimeError("FlatAdam.step_pair: the second optimizer's captured factors must follow the first's")
         flat, gflat = first._flat, first._gflat
+        wda, wdb = first._decay(ga), second._decay(gb)
+        if not (wda or wdb):  # (curla_adamw_step2 takes both decays, one of which may be 0)
+            wda = wdb = None
         args = (flat.data_ptr() + 4 * b0, gflat.data_ptr() + 4 * b0,
                 first._m.data_ptr() + 4 * (a0 - first._lo), first._v.data_ptr() + 4 * (a0 - first._lo),
-                second._m.data_ptr() + 4 * (b0 - second._lo), second._v.data_ptr() + 4 * (b0 - second._lo), b1 - b0, a0 - b0,
-                float(ga["lr"]), float(ga["betas"][0]), float(ga["betas"][1]), float(ga["eps"]), ta + 1,
-                float(gb["lr"]), float(gb["betas"][0]), float(gb["betas"][1]), float(gb["eps"]), tb + 1, first._dyn)
-        if second.max_grad_norm is None:
-            call("curla_adam_step2", *args, stream())
-        else:
-            s = stream()
-            call("curla_adam_step2_clip", *args, *second._sqsum([(b0, b1)], s), s)
+                second._m.data_ptr() + 4 * (b0 - second._lo), second._v.data_ptr() + 4 * (b0 - second._lo), b1 - b0,
+                a0 - b0) + FlatAdam._hyper(ga, ta, wda) + FlatAdam._hyper(gb, tb, wdb) + (first._dyn,)
+        s = stream()
+        clip = None if second.max_grad_norm is None else second._sqsum([(b0, b1)], s)
+        FlatAdam._launch("step2", args, wda, clip, s)
 
     @staticmethod
     def _two_steps(first, second):
@@ -357,13 +411,11 @@ class FlatAdam(torch.optim.Adam):
             for i in range(len(opt._plist)):
                 opt._ensure_state(i)
                 opt._steps[i] = t + 1
-        args = opt._adam_args(lo, hi, t, g) + (target_flat.data_ptr() + 4 * lo, split, float(tau_a), float(1.0 - tau_a),
-                                               float(tau_b), float(1.0 - tau_b))
+        wd = opt._decay(g) or None
+        args = opt._adam_args(lo, hi, t, g, wd) + (target_flat.data_ptr() + 4 * lo, split, float(tau_a),
+                                                   float(1.0 - tau_a), float(tau_b), float(1.0 - tau_b))
         s = stream()
-        if opt.max_grad_norm is None:
-            call("curla_adam_step_lerp", *args, s)
-        else:
-            call("curla_adam_step_lerp_clip", *args, *opt._sqsum([(lo, hi)], s), s)
+        opt._launch("step_lerp", args, wd, None if opt.max_grad_norm is None else opt._sqsum([(lo, hi)], s), s)
         return True
 
     # -- this optimizer and a float64 scalar's, one launch -----------------------------------------------------------
@@ -399,16 +451,14 @@ class FlatAdam(torch.optim.Adam):
             for i in range(len(first._plist)):
                 first._ensure_state(i)
                 first._steps[i] = t + 1
-        args = first._adam_args(lo, hi, t, grp) + (
+        wd = first._decay(grp) or None  # (the flat run's: log_alpha's optimizer is its own and is never decayed)
+        args = first._adam_args(lo, hi, t, grp, wd) + (
             p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), float(g["lr"]),
             float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), t64, getattr(scalar_opt, "_curla_dyn64", None))
-        s = stream()
-        if first.max_grad_norm is None:
-            call("curla_adam_step_scalar64", *args, s)
-        else:  # (the norm is the flat run's: the scalar is not clipped)
-            call("curla_adam_step_scalar64_clip", *args, *first._sqsum([(lo, hi)], s), s)
+        s = stream()  # (the norm is the flat run's: the scalar is not clipped)
+        first._launch("step_scalar64", args, wd, None if first.max_grad_norm is None else first._sqsum([(lo, hi)], s), s)
         if not frozen:
             st["step"] = torch.tensor(float(t64), dtype=torch.float32)
 
 
-__all__ = ["FlatAdam", "check_max_grad_norm"]
+__all__ = ["FlatAdam", "check_max_grad_norm", "check_weight_decay"]

@@ -545,6 +545,40 @@ int curla_adam_step2_clip(float* param, float* grad, float* exp_avg1, float* exp
                           double eps1, long long step1, double lr2, double beta1_2, double beta2_2, double eps2,
                           long long step2, const float* dyn, const double* partials, int n_partials, double max_norm,
                           float* stats, void* stream);
+/* Decoupled weight decay inside the Adam launches: torch.optim.AdamW, i.e. torch.optim.Adam with
+ * decoupled_weight_decay=True.  The four curla_adamw_* entry points are the curla_adam_*_clip namesakes with a `double
+ * weight_decay` right behind each `eps` of the flat run (curla_adamw_step2: one per optimizer; the float64 scalar's eps64
+ * gets none -- the scalar belongs to another optimizer and is never decayed).  Per element: param[i] <- param[i] * d
+ * first, ONE multiply with one rounding, d = (float)(1.0 - lr * weight_decay) formed here on the host in double as torch
+ * forms it; then the Adam update on the decayed parameter.  The gradient, the clip coefficient and the moments do not see
+ * d; the target lerp reads the stepped, decayed parameter.  curla_adamw_step2, in torch's order for first.step();
+ * second.step(): elements behind n_pre take param *= d1, Adam 1, param *= d2, Adam 2; the first n_pre take param *= d2,
+ * Adam 2.  So a launch equals, bit for bit, param *= d over the run followed by the namesake's launch, and with
+ * weight_decay == 0 (d == 1) it equals the namesake's launch.
+ * partials == NULL: the unclipped step -- n_partials must then be 0, max_norm and stats are ignored and `grad` is not
+ * written.  partials != NULL: clipped, as the _clip namesake.
+ * dyn / dyn64 as in the namesakes.  d is evaluated from `lr` and passed to the kernel BY VALUE; it is not part of dyn: a
+ * captured hipGraph holds it, so a graph captured with weight_decay != 0 must be captured again when lr changes.
+ * CURLA_ERR_ARG before any launch on: weight_decay negative, NaN or infinite; partials == NULL with n_partials != 0; and
+ * whatever the _clip namesake refuses.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_adamw_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                     double beta2, double eps, double weight_decay, long long step, const float* dyn,
+                     const double* partials, int n_partials, double max_norm, float* stats, void* stream);
+int curla_adamw_step_lerp(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, long long step, const float* dyn, float* target,
+                          size_t split, float tau_a, float one_minus_tau_a, float tau_b, float one_minus_tau_b,
+                          const double* partials, int n_partials, double max_norm, float* stats, void* stream);
+int curla_adamw_step_scalar64(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                              double beta1, double beta2, double eps, double weight_decay, long long step,
+                              const float* dyn, double* param64, const double* grad64, double* exp_avg64,
+                              double* exp_avg_sq64, double lr64, double beta1_64, double beta2_64, double eps64,
+                              long long step64, const double* dyn64, const double* partials, int n_partials,
+                              double max_norm, float* stats, void* stream);
+int curla_adamw_step2(float* param, float* grad, float* exp_avg1, float* exp_avg_sq1, float* exp_avg2, float* exp_avg_sq2,
+                      size_t n, size_t n_pre, double lr1, double beta1_1, double beta2_1, double eps1,
+                      double weight_decay1, long long step1, double lr2, double beta1_2, double beta2_2, double eps2,
+                      double weight_decay2, long long step2, const float* dyn, const double* partials, int n_partials,
+                      double max_norm, float* stats, void* stream);
 
 /* ---- augmentations that produce float observations (augmentations.py:78-205; kornia arithmetic is not
  * vendored by the reference: PARITY UNPINNED, the algorithm is this build's statement of kornia's documented
