@@ -347,13 +347,14 @@ class CriticFn(torch.autograd.Function):
         B, A, H, F = z.shape[0], critic.action_dim, critic.hidden_dim, critic.encoder.feature_dim
         xa = _empty(B, F + A, like=z)
         ops.concat(z, action, B, F, A, xa)
-        h1, h2, q = _empty(2, B, H, like=z), _empty(2, B, H, like=z), _empty(2, B, 1, like=z)
+        M = critic.out_dim  # (the quantile atoms of a Critic(quantiles=M), else the one Q value)
+        h1, h2, q = _empty(2, B, H, like=z), _empty(2, B, H, like=z), _empty(2, B, M, like=z)
         ctx.ln_saves = (None, None)
         if critic.layer_norm:  # what the LayerNorms' backward reads, per hidden layer
             ctx.ln_saves = ([_empty(2, B, H, like=z) for _ in range(2)], [_empty(2, B, like=z) for _ in range(2)])
-        _mlp_fwd(xa, 0, critic.twin(), 2, B, F + A, H, 1, h1, h2, q,
+        _mlp_fwd(xa, 0, critic.twin(), 2, B, F + A, H, M, h1, h2, q,
                  ln=critic.twin_ln(*ctx.ln_saves, drop=drop))
-        ctx.critic, ctx.xa, ctx.h1, ctx.h2, ctx.B, ctx.drop = critic, xa, h1, h2, B, drop
+        ctx.critic, ctx.xa, ctx.h1, ctx.h2, ctx.B, ctx.drop, ctx.M = critic, xa, h1, h2, B, drop, M
         return q[0], q[1]
 
     @staticmethod
@@ -366,7 +367,8 @@ class CriticFn(torch.autograd.Function):
         mods = _q_modules(critic.Q1)
         if dq1 is None and dq2 is None:
             return (None,) * (4 + 4 * len(mods))
-        dq = torch.zeros((2, B, 1), device=ctx.xa.device, dtype=F32)
+        M = ctx.M
+        dq = torch.zeros((2, B, M), device=ctx.xa.device, dtype=F32)
         if dq1 is not None:
             dq[0].copy_(dq1)
         if dq2 is not None:
@@ -379,7 +381,7 @@ class CriticFn(torch.autograd.Function):
         if ln is not None and G is not None:
             ln.dg, ln.db = [G.view(p) for p in ln.g], [G.view(p) for p in ln.b]
             ln.partial = torch.empty(ops.mlp_ln_partial_floats(B, H, 2), device=dq.device, dtype=F32)
-        _mlp_bwd(ctx.xa, 0, critic.twin(), G, 2, B, F + A, H, 1, ctx.h1, ctx.h2, dq, _empty(2, B, H, like=dq),
+        _mlp_bwd(ctx.xa, 0, critic.twin(), G, 2, B, F + A, H, M, ctx.h1, ctx.h2, dq, _empty(2, B, H, like=dq),
                  _empty(2, B, H, like=dq), dxa, ln=ln)
         dz = dact = None
         if want_x:

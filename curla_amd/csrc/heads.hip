@@ -22,6 +22,7 @@ namespace {
 #include "mlp_drop_ln.h"   // mlp_drop_ln_relu_fwd_kernel<NF>, mlp_drop_ln_bwd_kernel<NF> (DroQ's dropout in front of that LayerNorm)
 #include "mlp_out.h"       // mlp_out_fwd_kernel<HEAD, R, LDSW>, mlp_out_bwd_kernel<GEN>, the policy head's three kernels
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
+#include "tqc.h"           // tqc_critic_loss_kernel, tqc_actor_loss_kernel (truncated quantile critics)
 #include "curl_head.h"     // curl_head_kernel<NTILE>
 #include "optim.h"         // soft_update_kernel, soft_update2_kernel, adam_step_kernel<CLIP, DECAY>, adam_step2_kernel<CLIP, DECAY>
 #include "sample_stage.h"  // a minibatch's index block and scalars: sample_stage_kernel<HOST, NSTEP, POS>, pos_walk_kernel
@@ -586,6 +587,30 @@ int curla_actor_loss(const float* q, long long twin_stride, const float* log_pi,
   CURLA_REQUIRE(q && log_pi && log_std && log_alpha && scalars4 && dq && B > 0 && A > 0 && twin_stride >= B);
   return launch(actor_loss_kernel, dim3(1), 256, 0, static_cast<hipStream_t>(stream), q, twin_stride, log_pi, log_std, A,
                 log_alpha, target_entropy, B, scalars4, dq, dlog_alpha);
+}
+
+int curla_tqc_critic_loss(const float* q, long long q_twin_stride, const float* tq, long long tq_twin_stride,
+                          const float* log_pi, const float* reward, const float* not_done, const double* log_alpha,
+                          float discount, int B, int M, int d, float* dq, long long dq_twin_stride, float* row_loss,
+                          float* loss, void* stream) {
+  CURLA_REQUIRE(q && tq && log_pi && reward && not_done && log_alpha && dq && row_loss && B > 0);
+  CURLA_REQUIRE(M >= 1 && M <= 32 && d >= 0 && d < M);
+  const long long dense = (long long)B * M;
+  CURLA_REQUIRE(q_twin_stride >= dense && tq_twin_stride >= dense && dq_twin_stride >= dense);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch(tqc_critic_loss_kernel, dim3((B + 3) / 4), 256, 0, st, q, q_twin_stride, tq, tq_twin_stride,
+                        log_pi, reward, not_done, log_alpha, discount, B, M, d, dq, dq_twin_stride, row_loss);
+  if (rc != CURLA_OK || !loss) return rc;
+  return launch(mean_kernel, dim3(1), 256, 0, st, row_loss, B, loss);  // the fixed-order mean over rows
+}
+
+int curla_tqc_actor_loss(const float* q, long long q_twin_stride, const float* log_pi, const float* log_std, int A,
+                         const double* log_alpha, float target_entropy, int B, int M, float* scalars4, float* dq,
+                         long long dq_twin_stride, double* dlog_alpha, void* stream) {
+  CURLA_REQUIRE(q && log_pi && log_std && log_alpha && scalars4 && dq && B > 0 && A > 0 && M >= 1 && M <= 32);
+  CURLA_REQUIRE(q_twin_stride >= (long long)B * M && dq_twin_stride >= (long long)B * M);
+  return launch(tqc_actor_loss_kernel, dim3(1), 256, 0, static_cast<hipStream_t>(stream), q, q_twin_stride, log_pi,
+                log_std, A, log_alpha, target_entropy, B, M, scalars4, dq, dq_twin_stride, dlog_alpha);
 }
 
 int curla_curl_ce(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits, void* stream) {

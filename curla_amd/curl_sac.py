@@ -159,14 +159,14 @@ def _mlp_bwd(x, sx, P, G, nb, B, din, H, dout, h1, h2, dy, dh2, dh1, dx, loss=No
     """Backward of _mlp_fwd.  G (parameter gradients) and dx are optional.
     ``loss`` = (fields, launch): the output gradient dy is that of a loss over the twin Q values -- ``fields`` for
     ops.mlp_out_bwd_loss, which computes it inside the last layer's backward launch; ``launch()`` runs the loss kernel
-    on its own where that form does not apply.
+    on its own where that form does not apply (``fields`` None: always -- the quantile losses have no fused form).
     ``ln`` (_MlpLn, with the forward's xhat / rstd): h1 / h2 are the post-LayerNorm ReLU outputs, so the masks below
     (h2 > 0, mask=h1) are still the ReLUs' and leave dh2 / dh1 as the gradients of the LayerNorms' outputs; one
     launch per hidden layer turns each, in place, into the gradient of its Linear's output.  The hidden Linears' bias
     gradients are then column sums of THAT, not of the masked dh: they come from the same launch, and the folds of
     them into the neighbouring launches are off."""
     s = P.stride
-    fused_loss = loss is not None and dout == 1 and nb == 2
+    fused_loss = loss is not None and loss[0] is not None and dout == 1 and nb == 2  # (no fields: the launch alone)
     if loss is not None and not fused_loss:
         loss[1]()
     # the three bias gradients (column sums of dy, dh2, dh1) ride in the launches that walk those matrices anyway --
@@ -263,10 +263,59 @@ class Actor(nn.Module):
             L.log_param('train_actor/fc%d' % n, layer, step)
 
 
-class QFunction(nn.Module):
+def _check_quantiles(m):
+    """The quantile atoms per Q function: 0 (off) or an ``int`` in 1 .. ops.TQC_MAX (a bool, a float or a string is not
+    one)."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m <= ops.TQC_MAX:
+        raise ValueError("critic quantiles: %r is not an int in 0 .. %d (0: off; the %d pooled atoms of a row are one "
+                         "wave's lanes)" % (m, ops.TQC_MAX, 2 * ops.TQC_MAX))
+    return int(m)
+
+
+def _check_drop_quantiles(d, m):
+    """The atoms dropped per network, ``0 <= d < M``; only with quantiles on."""
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 0:
+        raise ValueError("critic_drop_quantiles: %r is not an int >= 0" % (d,))
+    if d and not m:
+        raise ValueError("critic_drop_quantiles = %d needs critic_quantiles > 0" % d)
+    if m and d >= m:
+        raise ValueError("critic_drop_quantiles = %d drops every one of the %d atoms (0 <= d < M)" % (d, m))
+    return int(d)
+
+
+def _widen_last_layers(trunks, m, init=None):
+    """Replace the last Linear (hidden -> 1) of each trunk by a hidden -> ``m`` one, ``init`` applied to it.  The new
+    tensors' draws are taken from a fork of torch's generator, which is put back afterwards: everything else a seed
+    produces -- the layers before, the other networks, CURL.W -- comes out as without quantiles."""
+    with torch.random.fork_rng(devices=[]):
+        for trunk in trunks:
+            wide = nn.Linear(trunk[-1].in_features, m)
+            if init is not None:
+                init(wide)
+            trunk[-1] = wide  # (same position: the state-dict keys stay trunk.4 / trunk.6)
+
+
+class _QFunctionType(type):
+    """``QFunction(..., quantiles=M)``: a keyword of the class call, as ``Critic(..., dropout=p)`` is (_CriticType);
+    ``QFunction.__init__`` keeps its parameter list with ``dropout`` last."""
+
+    def __call__(cls, *args, quantiles=0, **kwargs):
+        quantiles = _check_quantiles(quantiles)
+        q = super().__call__(*args, **kwargs)
+        q.quantiles = quantiles
+        if quantiles:
+            _widen_last_layers([q.trunk], quantiles)
+        return q
+
+
+class QFunction(nn.Module, metaclass=_QFunctionType):
     """MLP for q-function (curl_sac.py:124-139); parameter container.  ``layer_norm``: an ``nn.LayerNorm(hidden_dim)``
     between each hidden Linear and its ReLU (the Linears are then trunk.0 / .3 / .6, the LayerNorms trunk.1 / .4).
-    ``dropout``: DroQ's dropout probability in front of each LayerNorm -- an attribute, no module of the trunk."""
+    ``dropout``: DroQ's dropout probability in front of each LayerNorm -- an attribute, no module of the trunk.
+    ``QFunction(..., quantiles=M)`` (a keyword of the class call; 0: off): the last Linear has M rows, one per quantile
+    atom."""
+
+    quantiles = 0
 
     def __init__(self, obs_dim, action_dim, hidden_dim, layer_norm=False, dropout=0.0):
         super().__init__()
@@ -329,20 +378,33 @@ def _reserve_dropout_counter(device):
 
 class _CriticType(type):
     """``Critic(..., dropout=p)``: the class call takes the keyword, as CurlSacAgent's takes its own (_AgentType), and
-    ``Critic.__init__`` keeps its parameter list with ``layer_norm`` last."""
+    ``Critic.__init__`` keeps its parameter list with ``layer_norm`` last.  ``Critic(..., quantiles=M)`` likewise: the
+    critic is built as without it and the Q functions' last layers are then replaced by M-row ones, initialised like
+    every other Linear (weight_init)."""
 
-    def __call__(cls, *args, dropout=0.0, **kwargs):
+    def __call__(cls, *args, dropout=0.0, quantiles=0, **kwargs):
+        quantiles = _check_quantiles(quantiles)
         critic = super().__call__(*args, **kwargs)
         critic.dropout = critic.Q1.dropout = critic.Q2.dropout = _check_dropout(dropout, critic.layer_norm)
+        critic.quantiles = critic.Q1.quantiles = critic.Q2.quantiles = quantiles
+        if quantiles:
+            _widen_last_layers([critic.Q1.trunk, critic.Q2.trunk], quantiles, weight_init)
         return critic
 
 
 class Critic(nn.Module, metaclass=_CriticType):
     """Critic network, employs two Q-functions (curl_sac.py:142-180).  ``layer_norm``: QFunction's; so is
     ``Critic(..., dropout=p)``, a keyword of the class call.  ``forward`` drops in training mode only
-    (``critic.eval()``: the deterministic Q)."""
+    (``critic.eval()``: the deterministic Q).  ``Critic(..., quantiles=M)`` (0: off): each Q function outputs M quantile
+    atoms and ``forward`` returns ``q1, q2`` of shape [B, M]."""
 
     dropout = 0.0
+    quantiles = 0
+
+    @property
+    def out_dim(self):
+        """The width of a Q function's last layer: its quantile atoms, or the one Q value."""
+        return self.quantiles or 1
 
     def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
                  layer_norm=False):
@@ -395,8 +457,8 @@ class Critic(nn.Module, metaclass=_CriticType):
         ops.concat(z, action.contiguous().float(), B, F, A, xa)
         h1 = torch.empty((2, B, H), device=dev)
         h2 = torch.empty((2, B, H), device=dev)
-        q = torch.empty((2, B, 1), device=dev)
-        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, 1, h1, h2, q, ln=self.twin_ln(drop=drop))
+        q = torch.empty((2, B, self.out_dim), device=dev)
+        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, self.out_dim, h1, h2, q, ln=self.twin_ln(drop=drop))
         self.outputs['q1'], self.outputs['q2'] = q[0], q[1]
         return q[0], q[1]
 
@@ -484,7 +546,8 @@ class _Workspace:
         # twin Q
         # [0] = the target critic's pass over next_obs, [1] = the critic's over obs: one launch per layer for the four
         # Q functions (update_critic); the names without a 2 are the critic's halves, what the backward reads
-        self.xa2, self.q_h1_2, self.q_h2_2, self.q2 = f(2, B, F + A), f(2, 2, B, H), f(2, 2, B, H), f(2, 2, B, 1)
+        M = agent.critic.out_dim  # (critic_quantiles: M atoms per Q function in place of the one Q value)
+        self.xa2, self.q_h1_2, self.q_h2_2, self.q2 = f(2, B, F + A), f(2, 2, B, H), f(2, 2, B, H), f(2, 2, B, M)
         self.xa, self.q_h1, self.q_h2 = self.xa2[1], self.q_h1_2[1], self.q_h2_2[1]
         self.tq, self.q = self.q2[0], self.q2[1]
         self.dxa = f(2, B, F + A)
@@ -497,7 +560,8 @@ class _Workspace:
             self.q_xhat1, self.q_xhat2, self.q_rstd1, self.q_rstd2 = f(2, B, H), f(2, B, H), f(2, B), f(2, B)
             self.q_ln_saves = ([self.q_xhat1, self.q_xhat2], [self.q_rstd1, self.q_rstd2])
             self.q_ln_partial = f(ops.mlp_ln_partial_floats(B, H, 2))
-        self.dq, self.target_q = f(2, B, 1), f(B, 1)
+        self.dq, self.target_q = f(2, B, M), f(B, 1)
+        self.q_row_loss = f(B) if agent.critic_quantiles else None  # the quantile loss per row (ops.tqc_critic_loss)
         self.per_w = self.per_value = None  # importance weights / new stored values [B]: a prioritized buffer's updates only
         # scalars: [0] critic loss, [1..4] actor_loss/alpha_loss/entropy/alpha, [5] curl loss, [6] batch reward
         self.scalars = torch.zeros(8, device=dev, dtype=torch.float32)
@@ -521,8 +585,11 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0, critic_layer_norm=False, **kwargs):
+    def __call__(cls, *args, critic_quantiles=0, critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1,
+                 critic_dropout=0.0, critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
+        agent.critic_quantiles = _check_quantiles(critic_quantiles)
+        agent.critic_drop_quantiles = _check_drop_quantiles(critic_drop_quantiles, agent.critic_quantiles)
         agent.critic_layer_norm = bool(critic_layer_norm)
         agent.critic_dropout = _check_dropout(critic_dropout, agent.critic_layer_norm)
         agent.utd_ratio = _check_utd_ratio(utd_ratio)
@@ -546,11 +613,18 @@ class CurlSacAgent(object, metaclass=_AgentType):
     that may be edited between calls.
     ``weight_decay=wd`` (default 0: nothing changes): decoupled weight decay -- the actor, critic, encoder and cpc
     optimizers are ``torch.optim.AdamW(..., weight_decay=wd)``, log_alpha's stays plain Adam (``set_weight_decay``;
-    DESIGN.md 7g)."""
+    DESIGN.md 7g).
+    ``critic_quantiles=M`` (default 0: nothing changes; 1 .. 32): truncated quantile critics -- each Q function outputs
+    M quantile atoms, the two target networks' atoms are pooled and sorted, the ``critic_drop_quantiles=d`` largest per
+    network dropped (0 <= d < M) and every online atom regressed on the kept ones with the quantile Huber loss; the
+    actor ascends the mean of all atoms.  M shapes the networks; d is an attribute that may be edited
+    between calls.  Not with a prioritized replay buffer."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
     utd_ratio = 1
+    critic_quantiles = 0
+    critic_drop_quantiles = 0
 
     def __init__(
         self,
@@ -609,10 +683,11 @@ class CurlSacAgent(object, metaclass=_AgentType):
         # same construction order as the reference => same RNG stream => same init for a given seed
         self.actor = Actor(obs_shape, action_shape, hidden_dim, encoder_feature_dim, actor_log_std_min,
                            actor_log_std_max, num_layers, num_filters)
+        q_kw = dict(quantiles=self.critic_quantiles) if self.critic_quantiles else {}
         self.critic = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
-                             layer_norm=self.critic_layer_norm, dropout=self.critic_dropout)
+                             layer_norm=self.critic_layer_norm, dropout=self.critic_dropout, **q_kw)
         self.critic_target = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
-                                    layer_norm=self.critic_layer_norm, dropout=self.critic_dropout)
+                                    layer_norm=self.critic_layer_norm, dropout=self.critic_dropout, **q_kw)
         self.critic_target.load_state_dict(self.critic.state_dict())
 
         # tie encoders between actor and critic, and CURL and critic
@@ -1221,6 +1296,13 @@ class CurlSacAgent(object, metaclass=_AgentType):
     def update_critic(self, obs, action, reward, next_obs, not_done, L, step, noise=None, dropout_rng=None):
         """curl_sac.py:349-371.  ``dropout_rng`` = (seed, counter): the stream position of a dropout critic's masks
         (the target twins under tags 1 / 2, the critic twins under 3 / 4) instead of the phase's own (_dropout)."""
+        Mq = self.critic.out_dim  # the Q functions' last-layer width: critic_quantiles atoms, or the one Q value
+        per = getattr(obs, "per", None)
+        if self.critic_quantiles:
+            drop_q = _check_drop_quantiles(self.critic_drop_quantiles, Mq)  # (the attribute may have been edited)
+            if per is not None:
+                raise ValueError("critic_quantiles: a prioritized minibatch is not supported (its priorities are built "
+                                 "on one scalar TD error per Q function): use ReplayBuffer(prioritized=False)")
         self._restore_grad_views()
         o, no = _as_ref(obs), _as_ref(next_obs)
         B, A, H = o.B, self.action_dim, self.hidden_dim
@@ -1265,7 +1347,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
                  head=(nz, self.actor.log_std_min, self.actor.log_std_max,
                        dict(pi=None if four else ws.pi, log_pi=ws.log_pi, xa=ws.xa2[0] if four else None, rng=rng)))
         if four:
-            _mlp_fwd(ws.xa2, 0, self.critic_target.twin(), 2, B, F + A, H, 1, ws.q_h1_2, ws.q_h2_2, ws.q2,
+            _mlp_fwd(ws.xa2, 0, self.critic_target.twin(), 2, B, F + A, H, Mq, ws.q_h1_2, ws.q_h2_2, ws.q2,
                      outer=(2, self._twin_outer),
                      ln=self.critic_target.twin_ln(*ws.q_ln_saves, save_first=1, drop=drop(1)))  # (groups: tags 1/2, 3/4)
         else:
@@ -1273,7 +1355,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
                 tenc.conv_forward(no, ws.acts_tmp)
                 tenc.fc_partial(ws.acts_tmp[-1])
             tenc.ln_from_partial(B, ws.z_t, xa=ws.xa, act=ws.pi)  # xa = cat([z, a'], 1)
-            _mlp_fwd(ws.xa, 0, self.critic_target.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.tq,
+            _mlp_fwd(ws.xa, 0, self.critic_target.twin(), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.tq,
                      ln=self.critic_target.twin_ln(drop=drop(1)))
             # -- current Q estimates + loss + backward (curl_sac.py:357-367)
             if not merged:
@@ -1281,7 +1363,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
                 enc.fc_partial(ws.acts_main[-1])
             enc.ln_from_partial(B, ws.z_c, xhat=ws.xhat_c, rstd=ws.rstd_c, fc_out=ws.fc_out if rec else None,
                                 xa=ws.xa, act=action)
-            _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q,
+            _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.q,
                      ln=self.critic.twin_ln(*ws.q_ln_saves, drop=drop(3)))
         if rec:  # what critic.log() / encoder.log() histogram: the outputs of THIS forward (curl_sac.py:163-167)
             self.critic.outputs['q1'], self.critic.outputs['q2'] = ws.q[0].clone(), ws.q[1].clone()
@@ -1293,7 +1375,12 @@ class CurlSacAgent(object, metaclass=_AgentType):
                    scalars=ws.scalars[0:1], dq=ws.dq),
               lambda: ops.critic_td_loss(ws.q, ws.tq, B, ws.log_pi, reward, not_done, self.log_alpha, self.discount, B,
                                          ws.target_q, ws.scalars[0:1], ws.dq))
-        per = getattr(obs, "per", None)
+        if self.critic_quantiles:
+            # truncated quantile critics: the quantile Huber loss of the critic's atoms against the kept
+            # target atoms and its gradient dq, a launch of its own in front of the last layer's backward
+            td = (None, lambda: ops.tqc_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done,
+                                                    self.log_alpha, self.discount, B, Mq, drop_q, ws.dq, B * Mq,
+                                                    ws.q_row_loss, ws.scalars[0:1]))
         if per is not None:
             # a prioritized minibatch (ReplayBuffer(prioritized=True)): the loss launch on its own, then the importance
             # weights scale dq and the loss in place and the drawn rows get their new priorities -- all on the device --,
@@ -1303,7 +1390,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
             td[1]()
             per.td_update(ws.q, B, ws.target_q, ws.dq, ws.scalars[0:1], ws.per_w, ws.per_value)
             td = None
-        _mlp_bwd(ws.xa, 0, self.critic.twin(), self.critic.twin(grads=True), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.dq,
+        _mlp_bwd(ws.xa, 0, self.critic.twin(), self.critic.twin(grads=True), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.dq,
                  ws.q_dh2, ws.q_dh1, ws.dxa, loss=td,
                  ln=self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial, drop=drop(3)))
         if step % self.log_interval == 0:
@@ -1394,7 +1481,8 @@ class CurlSacAgent(object, metaclass=_AgentType):
             self.actor.outputs['mu'], self.actor.outputs['std'] = ws.a_out[:, :A].clone(), ws.log_std.exp()
         # (the data gradient through the LayerNorms needs the saves too; dropout: the critic twins under tags 5 / 6)
         q_ln = self.critic.twin_ln(*ws.q_ln_saves, drop=self._dropout(rng, dropout_rng)(5))
-        _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.q, ln=q_ln)
+        Mq = self.critic.out_dim
+        _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.q, ln=q_ln)
         # actor / alpha losses and d(loss)/dQ: inside the backward launch of the Q functions' last layer
         # backward: Q -> pi -> trunk -> LN -> fc (encoder detached, curl_sac.py:375-376)
         al = (dict(kind=2, A=A, twin_stride=B, q=ws.q, log_pi=ws.log_pi, log_std=ws.log_std, log_alpha=self.log_alpha,
@@ -1402,7 +1490,11 @@ class CurlSacAgent(object, metaclass=_AgentType):
                    dlog_alpha=self.log_alpha.grad),
               lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, self.log_alpha, float(self.target_entropy), B,
                                      ws.scalars[1:5], ws.dq, self.log_alpha.grad))
-        _mlp_bwd(ws.xa, 0, self.critic.twin(), None, 2, B, F + A, H, 1, ws.q_h1, ws.q_h2, ws.dq, ws.q_dh2, ws.q_dh1,
+        if self.critic_quantiles:  # (the mean of all atoms in place of min(Q1, Q2))
+            al = (None, lambda: ops.tqc_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, self.log_alpha,
+                                                   float(self.target_entropy), B, Mq, ws.scalars[1:5], ws.dq, B * Mq,
+                                                   self.log_alpha.grad))
+        _mlp_bwd(ws.xa, 0, self.critic.twin(), None, 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.dq, ws.q_dh2, ws.q_dh1,
                  ws.dxa, loss=al, ln=q_ln)
         if step % self.log_interval == 0:
             L.log('train_actor/loss', ws.scalars[1], step)
@@ -1768,7 +1860,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
         ARE captured, collectives included (round 5; the replica check stays on the host, in front of the replay).
         Values the graphs hold as kernel arguments (discount, taus, betas / eps, detach_encoder, the update
         frequencies, the data-parallel group and schedule, ``max_grad_norm``, ``critic_dropout``,
-        ``n_step`` and ``discount`` of an n-step replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
+        ``critic_drop_quantiles``, ``n_step`` and ``discount`` of an n-step replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
         so does ``load_checkpoint``.  A capture that raises leaves the agent's
         state untouched and that update runs eagerly.
         ``utd_ratio = G > 1``: a call replays the critic-only kind's graph (actor=False, soft, cpc=False) G-1 times -- the
@@ -1834,7 +1926,9 @@ class CurlSacAgent(object, metaclass=_AgentType):
                 float(self.actor.log_std_max), self.actor_update_freq, self.critic_target_update_freq,
                 self.cpc_update_freq, self._dp_active, self._dp_overlap, id(self._dp_group) if self._dp_active else 0,
                 hyper, self._graph_rb_key(), self._max_grad_norm) + \
-            ((float(self.critic_dropout),) if self.critic_dropout else ())  # (0: the key of an agent without the keyword)
+            ((float(self.critic_dropout),) if self.critic_dropout else ()) + \
+            ((("quantiles", self.critic_quantiles, self.critic_drop_quantiles),) if self.critic_quantiles else ())
+        # (0, for either: the key of an agent without the keyword)
 
     def _graph_rb_key(self):
         """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value
@@ -2052,6 +2146,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
             "log_alpha": self.log_alpha.detach().cpu(),
             "optimizers": {k: self._convert_opt_state(o, o.state_dict(), True) for k, o in self._optimizers().items()},
             "rng": rng, "critic_dropout": float(self.critic_dropout), "utd_ratio": int(self.utd_ratio),
+            "critic_quantiles": int(self.critic_quantiles), "critic_drop_quantiles": int(self.critic_drop_quantiles),
         }, path)
 
     def load_checkpoint(self, path, restore_rng=True):
@@ -2069,6 +2164,10 @@ class CurlSacAgent(object, metaclass=_AgentType):
         self.actor.load_state_dict(ck["actor"])
         self.critic.load_state_dict(ck["critic"])
         self.critic_target.load_state_dict(ck["critic_target"])
+        # (another critic_quantiles has failed above, on the last layers' shapes; the dropped atoms are a number of the
+        # loss alone and come from the file)
+        if self.critic_quantiles and "critic_drop_quantiles" in ck:
+            self.critic_drop_quantiles = _check_drop_quantiles(ck["critic_drop_quantiles"], self.critic_quantiles)
         with torch.no_grad():
             self.log_alpha.copy_(ck["log_alpha"])
         for k, o in self._optimizers().items():

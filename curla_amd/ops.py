@@ -604,6 +604,22 @@ def actor_loss(q, twin_stride, log_pi, log_std, A, log_alpha, target_entropy, B,
          ptr(scalars4), ptr(dq), ptr(dlog_alpha), stream())
 
 
+TQC_MAX = 32  # the most atoms per Q function: a row's 2M pooled target atoms are one wave's 64 lanes (csrc/tqc.h)
+
+
+def tqc_critic_loss(q, sq, tq, stq, log_pi, reward, not_done, log_alpha, discount, B, M, d, dq, sdq, row_loss, loss=None):
+    """Truncated quantile critics' loss (curla_tqc_critic_loss): q / tq / dq [2][B][M] with twin strides sq / stq / sdq
+    (elements), ``d`` atoms dropped per network, row_loss [B], ``loss`` [1] (None: the mean over rows is not taken)."""
+    call("curla_tqc_critic_loss", ptr(q), sq, ptr(tq), stq, ptr(log_pi), ptr(reward), ptr(not_done), ptr(log_alpha),
+         discount, B, M, d, ptr(dq), sdq, ptr(row_loss), ptr(loss), stream())
+
+
+def tqc_actor_loss(q, sq, log_pi, log_std, A, log_alpha, target_entropy, B, M, scalars4, dq, sdq, dlog_alpha):
+    """actor_loss over the mean of the 2M atoms of q [2][B][M] (curla_tqc_actor_loss); dq [2][B][M] = -1 / (2 M B)."""
+    call("curla_tqc_actor_loss", ptr(q), sq, ptr(log_pi), ptr(log_std), A, ptr(log_alpha), target_entropy, B, M,
+         ptr(scalars4), ptr(dq), sdq, ptr(dlog_alpha), stream())
+
+
 def curl_head_supported(B, F_):
     return B % 128 == 0 and B <= 1024 and 49 <= F_ <= 52
 

@@ -442,6 +442,26 @@ int curla_critic_td_loss(const float* q, const float* tq, long long twin_stride,
 int curla_actor_loss(const float* q, long long twin_stride, const float* log_pi, const float* log_std, int A,
                      const double* log_alpha, float target_entropy, int B, float* scalars4, float* dq,
                      double* dlog_alpha, void* stream);
+/* Truncated quantile critics (Kuznetsov et al. 2020) in place of curla_critic_td_loss, for Q functions with M output
+ * atoms (curl_sac.py:129-139 with a last layer of M rows; q, tq, dq are [2][B][M], their twins the given element strides
+ * apart, each >= B M).  Per row: the 2M atoms of `tq` are pooled and ranked (ties in index order), the K = 2 (M - d)
+ * smallest kept, y_j = reward + not_done * discount * (z'_(j) - exp(log_alpha) * log_pi); with u = y_j - q[n][b][i],
+ * tau_i = (2 i + 1) / (2 M), w = |tau_i - [u < 0]| and the Huber loss h (0.5 u^2 for |u| <= 1, |u| - 0.5 beyond):
+ * row_loss[b] = sum_{n,i,j} w h(u) / (2 M K), dq[n][b][i] = -sum_j w clamp(u, -1, 1) / (B 2 M K), and `loss` (may be
+ * NULL) the fixed-order mean of row_loss.  No atomics: a rerun writes the same bits.  CURLA_ERR_ARG on a NULL required
+ * pointer, B < 1, M < 1, M > 32 (the 2M pooled atoms of a row are one wave's lanes), d < 0, d >= M or a stride below B M.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_tqc_critic_loss(const float* q, long long q_twin_stride, const float* tq, long long tq_twin_stride,
+                          const float* log_pi, const float* reward, const float* not_done, const double* log_alpha,
+                          float discount, int B, int M, int d, float* dq, long long dq_twin_stride, float* row_loss,
+                          float* loss, void* stream);
+/* curla_actor_loss for Q functions with M output atoms (curl_sac.py:129-139 with a last layer of M rows): the row's Q
+ * term is the mean of its 2M atoms (no min), dq[n][b][i] = -1 / (2 M B) everywhere; scalars4 and dlog_alpha as
+ * curla_actor_loss leaves them.  CURLA_ERR_ARG on a NULL required pointer, B < 1, A < 1, M < 1, M > 32 or a stride
+ * below B M.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_tqc_actor_loss(const float* q, long long q_twin_stride, const float* log_pi, const float* log_std, int A,
+                         const double* log_alpha, float target_entropy, int B, int M, float* scalars4, float* dq,
+                         long long dq_twin_stride, double* dlog_alpha, void* stream);
 /* CrossEntropyLoss(logits, arange(B)) and d/dlogits (curl_sac.py:221,411-413); `loss` (the mean of row_loss) may be
  * NULL when the scalar is not going to be logged */
 int curla_curl_ce(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits, void* stream);
