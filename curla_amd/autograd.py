@@ -24,6 +24,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
+from .mlp import _Mlp, _linears, _mlp_bwd, _mlp_fwd
 
 F32 = torch.float32
 
@@ -255,7 +256,6 @@ class ActorFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, actor, keep, noise, compute_pi, compute_log_pi, z, *trunk_params):
-        from .curl_sac import _Mlp, _mlp_fwd
         ctx.set_materialize_grads(False)
         B, A, H, F = z.shape[0], actor.action_dim, actor.hidden_dim, actor.encoder.feature_dim
         h1, h2, out = _empty(B, H, like=z), _empty(B, H, like=z), _empty(B, 2 * A, like=z)
@@ -277,7 +277,6 @@ class ActorFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable_hip
     def backward(ctx, *grads):
-        from .curl_sac import _Mlp, _mlp_bwd
         actor = ctx.actor
         z, noise, mu, pi, log_std, tanh_ls = ctx.saved_tensors
         if pi is None:
@@ -296,8 +295,7 @@ class ActorFn(torch.autograd.Function):
         dout = _empty(B, 2 * A, like=z)
         ops.policy_head_bwd(_contig(dmu), _contig(dpi), _contig(dlp), _contig(dls), noise, mu, pi, log_std, tanh_ls, B, A,
                             actor.log_std_min, actor.log_std_max, dout)
-        layers = [actor.trunk[0], actor.trunk[2], actor.trunk[4]]
-        G = _grad_mlp(layers) if any(need[6:]) else None
+        G = _grad_mlp(_linears(actor.trunk)) if any(need[6:]) else None
         dz = _empty(B, F, like=z) if need[5] else None
         _mlp_bwd(z, 0, _Mlp(actor.trunk), G, 1, B, F, H, 2 * A, ctx.h1, ctx.h2, dout, _empty(B, H, like=z),
                  _empty(B, H, like=z), dz)
@@ -311,7 +309,7 @@ def actor_forward(actor, z, compute_pi, compute_log_pi, noise):
         noise = torch.randn((B, A), device=z.device) if noise is None else noise.detach().contiguous().float()
     keep = {}
     outs = ActorFn.apply(actor, keep, noise, bool(compute_pi), bool(compute_log_pi), z,
-                         *[t for i in (0, 2, 4) for t in (actor.trunk[i].weight, actor.trunk[i].bias)])
+                         *[t for m in _linears(actor.trunk) for t in (m.weight, m.bias)])
     if not compute_pi:
         mu, log_std = outs
         pi = log_pi = None
@@ -342,7 +340,6 @@ class CriticFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, critic, z, action, drop, *q_params):
-        from .curl_sac import _mlp_fwd
         ctx.set_materialize_grads(False)
         B, A, H, F = z.shape[0], critic.action_dim, critic.hidden_dim, critic.encoder.feature_dim
         xa = _empty(B, F + A, like=z)
@@ -360,7 +357,6 @@ class CriticFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable_hip
     def backward(ctx, dq1, dq2):
-        from .curl_sac import _mlp_bwd
         critic, B = ctx.critic, ctx.B
         A, H, F = critic.action_dim, critic.hidden_dim, critic.encoder.feature_dim
         need = ctx.needs_input_grad
@@ -373,8 +369,7 @@ class CriticFn(torch.autograd.Function):
             dq[0].copy_(dq1)
         if dq2 is not None:
             dq[1].copy_(dq2)
-        layers = [m for m in mods if isinstance(m, torch.nn.Linear)]
-        G = _grad_mlp(layers, critic.twin_stride, span=mods) if any(need[4:]) else None
+        G = _grad_mlp(_linears(critic.Q1.trunk), critic.twin_stride, span=mods) if any(need[4:]) else None
         want_x = need[1] or need[2]
         dxa = _empty(2, B, F + A, like=dq) if want_x else None
         ln = critic.twin_ln(*ctx.ln_saves, drop=ctx.drop)

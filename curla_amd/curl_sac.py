@@ -25,35 +25,18 @@ import warnings
 
 import numpy as np
 import torch
-import torch.nn as nn
 
-from . import autograd, ops
-from .augmentations import Compose, RandomCrop, RandomTranslate
+from . import ops
+from .agent_acting import _ActingMixin
+from .agent_dp import _DataParallelMixin
+from .agent_graphs import _NullLog, _UpdateGraphsMixin
 from .encoder import CNNEncoder
+from .mlp import _Mlp, _MlpLn, _linears, _mlp_bwd, _mlp_fwd  # noqa: F401
+from .networks import (CURL, LOG_FREQ, Actor, Critic, QFunction, _check_drop_quantiles,  # noqa: F401
+                       _check_dropout, _check_int, _check_layer_norm_width, _check_quantiles, _CriticType,
+                       _device_generator, _QFunctionType, _reserve_dropout_counter, _widen_last_layers, weight_init)
 from .ops import ObsRef
 from .optim import FlatAdam, check_max_grad_norm, check_weight_decay
-
-LOG_FREQ = 25_000
-
-
-def weight_init(m):
-    """The reference's initialisation (curl_sac.py:38-54), applied with ``module.apply``: Linear weights orthogonal
-    with zero bias; Conv2d / ConvTranspose2d "delta-orthogonal" (arXiv:1806.05393) -- every tap zero except the
-    centre one, which is an orthogonal (out x in) matrix with the ReLU gain -- and zero bias.  The draws come from
-    torch's global generator in module order, so a seeded construction reproduces the reference's parameters."""
-    if isinstance(m, nn.Linear):
-        nn.init.orthogonal_(m.weight.data)
-        if m.bias is not None:
-            m.bias.data.zero_()
-        return
-    if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
-        kh, kw = m.weight.shape[2:]
-        assert kh == kw, "square kernels only"
-        m.weight.data.zero_()
-        if m.bias is not None:
-            m.bias.data.zero_()
-        centre = kh // 2
-        nn.init.orthogonal_(m.weight.data[:, :, centre, centre], nn.init.calculate_gain('relu'))
 
 
 def _as_ref(obs):
@@ -62,450 +45,13 @@ def _as_ref(obs):
     return ObsRef.from_tensor(obs.contiguous().float())
 
 
-class _Mlp:
-    """Pointers of a 3-layer MLP (or of the first of two identically laid-out
-    twins, ``stride`` floats apart)."""
-
-    def __init__(self, seq, stride=0, grads=False):
-        lin = _linears(seq)
-        pick = (lambda p: p.grad) if grads else (lambda p: p)
-        self.W = [pick(layer.weight) for layer in lin]
-        self.b = [pick(layer.bias) for layer in lin]
-        self.stride = stride
-
-
-def _linears(seq):
-    """The three Linears of a trunk, by type: a LayerNorm critic's sit at 0, 3, 6 instead of 0, 2, 4."""
-    lin = [m for m in seq if isinstance(m, nn.Linear)]
-    assert len(lin) == 3, "a 3-layer MLP"
-    return lin
-
-
-class _MlpLn:
-    """The LayerNorm side of a _Mlp whose hidden layers are Linear - LayerNorm - ReLU (Critic(layer_norm=True)), layer
-    by layer: the LayerNorms' parameters ``g`` / ``b`` (twins and groups addressed as the _Mlp's), the buffers
-    ``xhat`` [2, B, H] / ``rstd`` [2, B] a forward saves for its backward (None: a no-grad pass) and, for a backward
-    that wants parameter gradients, their destinations ``dg`` / ``db`` and the ``partial`` workspace
-    (ops.mlp_ln_partial_floats).  ``save_first``: with _mlp_fwd's ``outer``, the first group that saves.
-    ``drop`` = (p, rng, tag): DroQ's dropout in front of each LayerNorm (Critic(dropout=p)) -- the mask of hidden layer i
-    is drawn under ``rng`` = (seed, counter[, device address]) and tag + i (group o of ``outer`` under tag + i + 2 o;
-    ops.mlp_drop_ln_relu_fwd), in the forward and again in the backward.  None: no dropout, the plain launches."""
-
-    def __init__(self, seq, xhat=None, rstd=None, dg=None, db=None, partial=None, save_first=0, drop=None):
-        ln = [m for m in seq if isinstance(m, nn.LayerNorm)]
-        assert len(ln) == 2, "a LayerNorm behind each hidden layer"
-        self.g = [m.weight for m in ln]
-        self.b = [m.bias for m in ln]
-        self.xhat, self.rstd, self.dg, self.db, self.partial, self.save_first = xhat, rstd, dg, db, partial, save_first
-        self.drop = drop
-
-    def fwd(self, i, h, s, nb, B, H, outer):
-        """LayerNorm + ReLU of hidden layer ``i`` in place on ``h``, which linear_fwd(relu=0) has just written."""
-        saves = self.xhat is not None
-        kw = dict(xhat=self.xhat[i] if saves else None, rstd=self.rstd[i] if saves else None,
-                  outer=None if outer is None else (outer[0], nb * B * H, outer[1]),
-                  save_first=self.save_first if outer is not None and saves else 0)
-        if self.drop is None:
-            ops.mlp_ln_relu_fwd(h, B * H, self.g[i], self.b[i], s, B, H, nb, **kw)
-        else:
-            p, rng, tag = self.drop
-            ops.mlp_drop_ln_relu_fwd(h, B * H, self.g[i], self.b[i], s, B, H, p, rng, tag + i, nb, **kw)
-
-    def bwd(self, i, dh, s, nb, B, H, dbias):
-        """``dh`` (ReLU-masked by the layer behind) -> the gradient of Linear ``i``'s output, in place; with ``dbias``
-        (that Linear's bias gradient) also the LayerNorm's parameter gradients."""
-        kw = {} if dbias is None else dict(partial=self.partial, dgamma=self.dg[i], dbeta=self.db[i], dbias=dbias, sg=s)
-        if self.drop is None:
-            ops.mlp_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, nb, **kw)
-        else:
-            p, rng, tag = self.drop
-            ops.mlp_drop_ln_bwd(dh, B * H, self.xhat[i], self.rstd[i], self.g[i], s, B, H, p, rng, tag + i, nb, **kw)
-
-
-def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None, head=None, ln=None):
-    """``outer`` = (n2, sW2): n2 such MLP groups in the same launches, their parameters sW2 floats apart (the target
-    critic's and the critic's twins); x [n2][B, din] and h1 / h2 / out [n2][nb][B, .] then.
-    ``head`` = (noise, lo, hi, outputs): the MLP is the actor trunk and the policy head (ops.actor_head_fwd with these
-    arguments) follows its last layer -- in the same launch when the layer is small enough.
-    ``ln`` (_MlpLn): a LayerNorm sits between each hidden Linear and its ReLU -- the GEMM leaves the ReLU out and one
-    launch per hidden layer normalises in place."""
-    s = P.stride
-    o0 = o1 = o2 = None
-    if outer is not None:
-        n2, sW2 = outer
-        o0, o1, o2 = (n2, B * din, sW2, nb * B * H), (n2, nb * B * H, sW2, nb * B * H), (n2, nb * B * H, sW2, nb * B * dout)
-    relu = 1 if ln is None else 0
-    ops.linear_fwd(x, sx, P.W[0], s, P.b[0], s, h1, B * H, B, H, din, nb, relu=relu, outer=o0)
-    if ln is not None:
-        ln.fwd(0, h1, s, nb, B, H, outer)
-    ops.linear_fwd(h1, B * H, P.W[1], s, P.b[1], s, h2, B * H, B, H, H, nb, relu=relu, outer=o1)
-    if ln is not None:
-        ln.fwd(1, h2, s, nb, B, H, outer)
-    small = dout <= ops.MLP_OUT_MAX and H % 4 == 0 and not relu_out
-    if head is not None and small and nb == 1 and outer is None:
-        noise, lo, hi, outs = head
-        ops.mlp_out_head_fwd(h2, P.W[2], P.b[2], out, noise, B, dout // 2, H, lo, hi, **outs)
-        return
-    if small:  # a handful of outputs: row dot products, not a GEMM
-        ops.mlp_out_fwd(h2, B * H, P.W[2], s, P.b[2], s, out, B * dout, B, dout, H, nb, outer=o2)
-    else:
-        ops.linear_fwd(h2, B * H, P.W[2], s, P.b[2], s, out, B * dout, B, dout, H, nb, relu=relu_out, outer=o2)
-    if head is not None:
-        noise, lo, hi, outs = head
-        ops.actor_head_fwd(out, noise, B, dout // 2, lo, hi, **outs)
-
-
-def _mlp_bwd(x, sx, P, G, nb, B, din, H, dout, h1, h2, dy, dh2, dh1, dx, loss=None, ln=None):
-    """Backward of _mlp_fwd.  G (parameter gradients) and dx are optional.
-    ``loss`` = (fields, launch): the output gradient dy is that of a loss over the twin Q values -- ``fields`` for
-    ops.mlp_out_bwd_loss, which computes it inside the last layer's backward launch; ``launch()`` runs the loss kernel
-    on its own where that form does not apply (``fields`` None: always -- the quantile losses have no fused form).
-    ``ln`` (_MlpLn, with the forward's xhat / rstd): h1 / h2 are the post-LayerNorm ReLU outputs, so the masks below
-    (h2 > 0, mask=h1) are still the ReLUs' and leave dh2 / dh1 as the gradients of the LayerNorms' outputs; one
-    launch per hidden layer turns each, in place, into the gradient of its Linear's output.  The hidden Linears' bias
-    gradients are then column sums of THAT, not of the masked dh: they come from the same launch, and the folds of
-    them into the neighbouring launches are off."""
-    s = P.stride
-    fused_loss = loss is not None and loss[0] is not None and dout == 1 and nb == 2  # (no fields: the launch alone)
-    if loss is not None and not fused_loss:
-        loss[1]()
-    # the three bias gradients (column sums of dy, dh2, dh1) ride in the launches that walk those matrices anyway --
-    # the last layer's backward pass and the first layer's weight-gradient product -- where both take their small forms
-    fold = G is not None and dout <= ops.MLP_OUT_MAX and ops.linear_dw_folds_bias(B, H, din, nb)
-    fold_h = fold and ln is None
-    if fused_loss:
-        ops.mlp_out_bwd_loss(loss[0], h2, B * H, P.W[2], s, dh2, B * H, G.W[2] if G is not None else None, s, B, H,
-                             db_out=G.b[2] if fold else None, db_hidden=G.b[1] if fold_h else None, sdb=s)
-    elif dout <= ops.MLP_OUT_MAX:  # last layer: data and weight gradient in one pass over h2
-        ops.mlp_out_bwd(dy, B * dout, h2, B * H, P.W[2], s, dh2, B * H, G.W[2] if G is not None else None, s, B, dout,
-                        H, nb, db_out=G.b[2] if fold else None, db_hidden=G.b[1] if fold_h else None, sdb=s)
-    else:
-        if G is not None:
-            ops.linear_dw(dy, B * dout, h2, B * H, G.W[2], s, B, dout, H, nb)
-        ops.linear_dx(dy, B * dout, P.W[2], s, dh2, B * H, B, dout, H, nb, mask=h2, smask=B * H)
-    if ln is not None:
-        ln.bwd(1, dh2, s, nb, B, H, G.b[1] if G is not None else None)
-    # a layer's weight and data gradient are independent products over the same dy: one launch for the pair
-    if G is not None:
-        ops.linear_bwd(dh2, B * H, h1, B * H, P.W[1], s, G.W[1], s, dh1, B * H, B, H, H, nb, mask=h1, smask=B * H)
-    else:
-        ops.linear_dx(dh2, B * H, P.W[1], s, dh1, B * H, B, H, H, nb, mask=h1, smask=B * H)
-    if ln is not None:
-        ln.bwd(0, dh1, s, nb, B, H, G.b[0] if G is not None else None)
-    if G is not None and dx is not None:
-        ops.linear_bwd(dh1, B * H, x, sx, P.W[0], s, G.W[0], s, dx, B * din, B, H, din, nb,
-                       db=G.b[0] if fold_h else None, sdb=s)
-    elif G is not None:
-        ops.linear_dw(dh1, B * H, x, sx, G.W[0], s, B, H, din, nb, colsum=G.b[0] if fold_h else None, s_colsum=s)
-    elif dx is not None:
-        ops.linear_dx(dh1, B * H, P.W[0], s, dx, B * din, B, H, din, nb)
-    if G is not None and not fold:
-        if ln is None:
-            ops.colsum3(dy, dout, dh2, H, dh1, H, B, G.b[2], G.b[1], G.b[0], s, nb)
-        else:  # (the hidden layers' bias gradients are there already)
-            ops.colsum(dy, B, dout, dout, B * dout, G.b[2], s, nb)
-
-
-class Actor(nn.Module):
-    """MLP actor network (curl_sac.py:57-121)."""
-
-    def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, log_std_min, log_std_max,
-                 num_layers, num_filters):
-        super().__init__()
-        self.encoder = CNNEncoder(obs_shape, encoder_feature_dim, num_layers, num_filters, output_logits=True)
-        self.log_std_min = log_std_min
-        self.log_std_max = log_std_max
-        self.action_dim = action_shape[0]
-        self.hidden_dim = hidden_dim
-        self.trunk = nn.Sequential(
-            nn.Linear(self.encoder.feature_dim, hidden_dim), nn.ReLU(),
-            nn.Linear(hidden_dim, hidden_dim), nn.ReLU(),
-            nn.Linear(hidden_dim, 2 * action_shape[0])
-        )
-        self.outputs = dict()
-        self.apply(weight_init)
-
-    def forward(self, obs, compute_pi=True, compute_log_pi=True, detach_encoder=False, noise=None):
-        """Forward on the HIP kernels; same return tuple as the reference (mu, pi, log_pi, log_std) with pi/log_pi
-        None when not asked for.  ``noise`` replaces torch.randn_like (curl_sac.py:97) and is a constant.
-        Differentiable (autograd.ActorFn) when grad mode is on and the features or a trunk parameter require grad."""
-        z = self.encoder(obs, detach=detach_encoder)
-        if autograd.wants_graph(z, *self.trunk.parameters()):
-            return autograd.actor_forward(self, z, compute_pi, compute_log_pi, noise)
-        B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
-        dev = z.device
-        h1 = torch.empty((B, H), device=dev)
-        h2 = torch.empty((B, H), device=dev)
-        out = torch.empty((B, 2 * A), device=dev)
-        mu = torch.empty((B, A), device=dev)
-        log_std = torch.empty((B, A), device=dev)
-        pi = log_pi = None
-        if compute_pi:
-            if noise is None:
-                noise = torch.randn((B, A), device=dev)
-            pi = torch.empty((B, A), device=dev)
-            log_pi = torch.empty((B, 1), device=dev) if compute_log_pi else None
-        _mlp_fwd(z, 0, _Mlp(self.trunk), 1, B, F, H, 2 * A, h1, h2, out,
-                 head=(noise if compute_pi else None, self.log_std_min, self.log_std_max,
-                       dict(mu=mu, pi=pi, log_pi=log_pi, log_std=log_std)))
-        self.outputs['mu'] = out[:, :A]  # the pre-squash mean, as the reference records it (curl_sac.py:92)
-        self.outputs['std'] = log_std.exp()
-        return mu, pi, log_pi, log_std
-
-    def log(self, L, step, log_freq=LOG_FREQ):
-        """Histograms of the recorded outputs and of the three trunk layers, every ``log_freq`` steps
-        (curl_sac.py:112-121; same keys)."""
-        if step % log_freq:
-            return
-        for name, value in self.outputs.items():
-            L.log_histogram('train_actor/%s_hist' % name, value, step)
-        for n, layer in enumerate((self.trunk[0], self.trunk[2], self.trunk[4]), start=1):
-            L.log_param('train_actor/fc%d' % n, layer, step)
-
-
-def _check_quantiles(m):
-    """The quantile atoms per Q function: 0 (off) or an ``int`` in 1 .. ops.TQC_MAX (a bool, a float or a string is not
-    one)."""
-    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m <= ops.TQC_MAX:
-        raise ValueError("critic quantiles: %r is not an int in 0 .. %d (0: off; the %d pooled atoms of a row are one "
-                         "wave's lanes)" % (m, ops.TQC_MAX, 2 * ops.TQC_MAX))
-    return int(m)
-
-
-def _check_drop_quantiles(d, m):
-    """The atoms dropped per network, ``0 <= d < M``; only with quantiles on."""
-    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 0:
-        raise ValueError("critic_drop_quantiles: %r is not an int >= 0" % (d,))
-    if d and not m:
-        raise ValueError("critic_drop_quantiles = %d needs critic_quantiles > 0" % d)
-    if m and d >= m:
-        raise ValueError("critic_drop_quantiles = %d drops every one of the %d atoms (0 <= d < M)" % (d, m))
-    return int(d)
-
-
-def _widen_last_layers(trunks, m, init=None):
-    """Replace the last Linear (hidden -> 1) of each trunk by a hidden -> ``m`` one, ``init`` applied to it.  The new
-    tensors' draws are taken from a fork of torch's generator, which is put back afterwards: everything else a seed
-    produces -- the layers before, the other networks, CURL.W -- comes out as without quantiles."""
-    with torch.random.fork_rng(devices=[]):
-        for trunk in trunks:
-            wide = nn.Linear(trunk[-1].in_features, m)
-            if init is not None:
-                init(wide)
-            trunk[-1] = wide  # (same position: the state-dict keys stay trunk.4 / trunk.6)
-
-
-class _QFunctionType(type):
-    """``QFunction(..., quantiles=M)``: a keyword of the class call, as ``Critic(..., dropout=p)`` is (_CriticType);
-    ``QFunction.__init__`` keeps its parameter list with ``dropout`` last."""
-
-    def __call__(cls, *args, quantiles=0, **kwargs):
-        quantiles = _check_quantiles(quantiles)
-        q = super().__call__(*args, **kwargs)
-        q.quantiles = quantiles
-        if quantiles:
-            _widen_last_layers([q.trunk], quantiles)
-        return q
-
-
-class QFunction(nn.Module, metaclass=_QFunctionType):
-    """MLP for q-function (curl_sac.py:124-139); parameter container.  ``layer_norm``: an ``nn.LayerNorm(hidden_dim)``
-    between each hidden Linear and its ReLU (the Linears are then trunk.0 / .3 / .6, the LayerNorms trunk.1 / .4).
-    ``dropout``: DroQ's dropout probability in front of each LayerNorm -- an attribute, no module of the trunk.
-    ``QFunction(..., quantiles=M)`` (a keyword of the class call; 0: off): the last Linear has M rows, one per quantile
-    atom."""
-
-    quantiles = 0
-
-    def __init__(self, obs_dim, action_dim, hidden_dim, layer_norm=False, dropout=0.0):
-        super().__init__()
-        _check_layer_norm_width(layer_norm, hidden_dim)
-        self.dropout = _check_dropout(dropout, layer_norm)
-        norm = (lambda: [nn.LayerNorm(hidden_dim)]) if layer_norm else (lambda: [])
-        self.trunk = nn.Sequential(
-            nn.Linear(obs_dim + action_dim, hidden_dim), *norm(), nn.ReLU(),
-            nn.Linear(hidden_dim, hidden_dim), *norm(), nn.ReLU(),
-            nn.Linear(hidden_dim, 1)
-        )
-
-
-def _check_layer_norm_width(layer_norm, hidden_dim):
-    if layer_norm and hidden_dim > ops.MLP_LN_MAX:
-        raise ValueError("critic LayerNorm: hidden_dim = %d is wider than the %d features the LayerNorm kernels take "
-                         "(one wave per row)" % (hidden_dim, ops.MLP_LN_MAX))
-
-
-def _check_dropout(p, layer_norm):
-    """The critics' dropout probability as a float: 0 <= p < 1, and only in front of a LayerNorm (dropout without the
-    normalisation behind it is the configuration DroQ shows to be harmful; it is not offered)."""
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError("critic dropout: p = %r is not in [0, 1)" % (p,))
-    if p > 0.0 and not layer_norm:
-        raise ValueError("critic dropout needs the critics' LayerNorm (critic_layer_norm=True / layer_norm=True)")
-    return p
-
-
 def _no_drop(tag):
     return None
 
 
 def _check_utd_ratio(g):
     """The update-to-data ratio: an ``int >= 1`` (a bool, a float or a string is not one)."""
-    if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or g < 1:
-        raise ValueError("utd_ratio: %r is not an int >= 1" % (g,))
-    return int(g)
-
-
-def _device_generator(device):
-    device = torch.device(device)
-    torch.cuda.init()  # (the generators exist once the runtime is up; a dropout agent may be the process's first use of it)
-    return torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
-
-
-def _reserve_dropout_counter(device):
-    """(seed, counter) of one pass's dropout masks, taken from ``device``'s default torch generator, whose offset moves
-    on by 4 (one Philox counter): torch.manual_seed, get_rng_state / set_rng_state (checkpoints) and the per-rank
-    seeds keep their meaning.  A CPU agent launches nothing (the trace hook's launch lists): position 0 of torch's
-    seed."""
-    if torch.device(device).type != "cuda":
-        return torch.initial_seed(), 0
-    gen = _device_generator(device)
-    off = gen.get_offset()
-    gen.set_offset(off + 4)
-    return gen.initial_seed(), off // 4
-
-
-class _CriticType(type):
-    """``Critic(..., dropout=p)``: the class call takes the keyword, as CurlSacAgent's takes its own (_AgentType), and
-    ``Critic.__init__`` keeps its parameter list with ``layer_norm`` last.  ``Critic(..., quantiles=M)`` likewise: the
-    critic is built as without it and the Q functions' last layers are then replaced by M-row ones, initialised like
-    every other Linear (weight_init)."""
-
-    def __call__(cls, *args, dropout=0.0, quantiles=0, **kwargs):
-        quantiles = _check_quantiles(quantiles)
-        critic = super().__call__(*args, **kwargs)
-        critic.dropout = critic.Q1.dropout = critic.Q2.dropout = _check_dropout(dropout, critic.layer_norm)
-        critic.quantiles = critic.Q1.quantiles = critic.Q2.quantiles = quantiles
-        if quantiles:
-            _widen_last_layers([critic.Q1.trunk, critic.Q2.trunk], quantiles, weight_init)
-        return critic
-
-
-class Critic(nn.Module, metaclass=_CriticType):
-    """Critic network, employs two Q-functions (curl_sac.py:142-180).  ``layer_norm``: QFunction's; so is
-    ``Critic(..., dropout=p)``, a keyword of the class call.  ``forward`` drops in training mode only
-    (``critic.eval()``: the deterministic Q).  ``Critic(..., quantiles=M)`` (0: off): each Q function outputs M quantile
-    atoms and ``forward`` returns ``q1, q2`` of shape [B, M]."""
-
-    dropout = 0.0
-    quantiles = 0
-
-    @property
-    def out_dim(self):
-        """The width of a Q function's last layer: its quantile atoms, or the one Q value."""
-        return self.quantiles or 1
-
-    def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
-                 layer_norm=False):
-        super().__init__()
-        _check_layer_norm_width(layer_norm, hidden_dim)
-        self.encoder = CNNEncoder(obs_shape, encoder_feature_dim, num_layers, num_filters, output_logits=True)
-        self.Q1 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim, layer_norm)
-        self.Q2 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim, layer_norm)
-        self.action_dim = action_shape[0]
-        self.hidden_dim = hidden_dim
-        self.layer_norm = bool(layer_norm)
-        self.outputs = dict()
-        self.twin_stride = None  # floats between Q1 and Q2 tensors once flattened by the agent
-        self.apply(weight_init)
-
-    def twin(self, grads=False):
-        if self.twin_stride is None:
-            raise RuntimeError("Critic parameters are not in the flat twin layout (constructed outside CurlSacAgent)")
-        return _Mlp(self.Q1.trunk, self.twin_stride, grads)
-
-    def twin_ln(self, xhat=None, rstd=None, grads=False, partial=None, save_first=0, drop=None):
-        """The ``ln=`` argument of _mlp_fwd / _mlp_bwd for ``twin()``: None without LayerNorm.  ``xhat`` / ``rstd``:
-        a pair of buffers each, one per hidden layer; ``grads``: the backward fills the LayerNorm tensors' .grad;
-        ``drop`` = (p, rng, tag) or None: this pass's dropout (_MlpLn)."""
-        if not self.layer_norm:
-            return None
-        ln = _MlpLn(self.Q1.trunk, xhat, rstd, partial=partial, save_first=save_first, drop=drop)
-        if grads:
-            ln.dg, ln.db = [p.grad for p in ln.g], [p.grad for p in ln.b]
-        return ln
-
-    DROP_TAG_FORWARD = 7  # the tags of the dropout masks: 1 + 2 * pass + layer, a forward() call is pass 3
-
-    def forward(self, obs, action, detach_encoder=False, dropout_rng=None):
-        """``dropout_rng`` = (seed, counter): the stream position of a training-mode dropout critic's masks (tags 7 / 8);
-        None reserves one counter from the device's torch generator per call."""
-        assert obs.size(0) == action.size(0)  # curl_sac.py:136
-        z = self.encoder(obs, detach=detach_encoder)
-        drop = None
-        if self.dropout > 0 and self.training:
-            _check_dropout(self.dropout, self.layer_norm)
-            drop = (self.dropout, dropout_rng or _reserve_dropout_counter(z.device), self.DROP_TAG_FORWARD)
-        if autograd.wants_graph(z, action, *self.Q1.parameters(), *self.Q2.parameters()):
-            q1, q2 = autograd.critic_forward(self, z, action, drop)  # (differentiable: autograd.CriticFn)
-            self.outputs['q1'], self.outputs['q2'] = q1.detach(), q2.detach()
-            return q1, q2
-        B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
-        dev = z.device
-        xa = torch.empty((B, F + A), device=dev)
-        ops.concat(z, action.contiguous().float(), B, F, A, xa)
-        h1 = torch.empty((2, B, H), device=dev)
-        h2 = torch.empty((2, B, H), device=dev)
-        q = torch.empty((2, B, self.out_dim), device=dev)
-        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, self.out_dim, h1, h2, q, ln=self.twin_ln(drop=drop))
-        self.outputs['q1'], self.outputs['q2'] = q[0], q[1]
-        return q[0], q[1]
-
-    def log(self, L, step, log_freq=LOG_FREQ):
-        """Histograms of the recorded Q values and of both Q trunks, every ``log_freq`` steps
-        (curl_sac.py:171-180; same keys)."""
-        if step % log_freq:
-            return
-        for name, value in self.outputs.items():
-            L.log_histogram('train_critic/%s_hist' % name, value, step)
-        for layer in range(3):  # (the three Linears; a LayerNorm critic's LayerNorms are not histogrammed)
-            for tag, q in (('q1', self.Q1), ('q2', self.Q2)):
-                L.log_param('train_critic/%s_fc%d' % (tag, layer), _linears(q.trunk)[layer], step)
-
-
-class CURL(nn.Module):
-    """CURL head (curl_sac.py:183-222)."""
-
-    def __init__(self, obs_shape, z_dim, critic, critic_target, output_type="continuous"):
-        super().__init__()
-        self.encoder = critic.encoder
-        self.encoder_target = critic_target.encoder
-        self.W = nn.Parameter(torch.rand(z_dim, z_dim))
-        self.output_type = output_type
-
-    def encode(self, x, detach=False, ema=False):
-        """curl_sac.py:196-209: ``ema`` runs the target encoder without grad, ``detach`` detaches the result."""
-        if ema:
-            with torch.no_grad():
-                z_out = self.encoder_target(x)
-        else:
-            z_out = self.encoder(x)
-        return z_out.detach() if detach else z_out
-
-    def compute_logits(self, z_a, z_pos):
-        """(B,B) logits z_a (W z_pos^T) minus the row max (curl_sac.py:211-222),
-        both products on the MFMA GEMM; differentiable through both (autograd.CurlLogitsFn) when grad mode is on and
-        an input or W requires grad."""
-        if autograd.wants_graph(z_a, z_pos, self.W):
-            logits = autograd.CurlLogitsFn.apply(z_a.contiguous(), z_pos.contiguous(), self.W)
-            return logits - torch.max(logits, 1)[0][:, None]
-        B, F = z_a.shape
-        WzT = torch.empty((B, F), device=z_a.device)
-        logits = torch.empty((B, B), device=z_a.device)
-        ops.linear_fwd(z_pos.contiguous(), 0, self.W, 0, None, 0, WzT, 0, B, F, F)
-        ops.linear_fwd(z_a.contiguous(), 0, WzT, 0, None, 0, logits, 0, B, B, F)
-        return logits - torch.max(logits, 1)[0][:, None]
+    return _check_int(g, 1, None, "utd_ratio: %r is not an int >= 1" % (g,))
 
 
 class _Workspace:
@@ -570,15 +116,6 @@ class _Workspace:
         self.logits, self.dlogits, self.row_loss = f(B, B), f(B, B), f(B)
 
 
-class _NullLog:
-    """What a captured update logs to: nothing (logging steps are never captured)."""
-
-    def log(self, *a, **k):
-        pass
-
-    log_histogram = log_param = log_image = log
-
-
 class _AgentType(type):
     """``CurlSacAgent(...)`` takes the reference's arguments and, behind them, this package's own keywords.
     ``CurlSacAgent.__init__`` keeps the reference's parameter list name for name (curl_sac.py:226-256: the drop-in
@@ -600,7 +137,7 @@ class _AgentType(type):
         return agent
 
 
-class CurlSacAgent(object, metaclass=_AgentType):
+class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, metaclass=_AgentType):
     """CURL representation learning with SAC (curl_sac.py:224-465).
     ``CurlSacAgent(..., critic_layer_norm=True)`` (a keyword of the class call, not in the reference; default off:
     nothing changes): an ``nn.LayerNorm(hidden_dim)`` between each hidden Linear of the Q functions and its ReLU, critic
@@ -873,134 +410,6 @@ class CurlSacAgent(object, metaclass=_AgentType):
             self._workspaces[B] = _Workspace(self, B)
         return self._workspaces[B]
 
-    # --------------------------------------------------------------- data parallel
-    def enable_data_parallel(self, process_group=None, single_rank_collectives=False, overlap=None, broadcast=True,
-                             check_every=None):
-        """Synchronous data parallelism (one process per GPU): before every
-        optimizer step the freshly written flat gradient bucket is averaged over
-        ranks (RCCL over xGMI).  RCCL averages inside the collective
-        (ncclAvg); other backends (gloo in the CPU tests) sum and divide.
-
-        ``broadcast``: rank 0's parameters, targets and log_alpha replace every
-        other rank's (three flat buffers + one scalar), so ranks need not have
-        been seeded identically.  ``check_every`` (default 1000 updates, env
-        CURLA_DP_CHECK_EVERY, 0 = never): a checksum of the replicated state is
-        compared across ranks and a mismatch raises -- replicas that drift apart
-        would otherwise train on silently.
-        ``overlap`` (default off, env CURLA_DP_OVERLAP=1 turns it on): each
-        bucket is reduced in two asynchronous pieces issued where their
-        gradients become final -- the twin-Q / fc / LayerNorm gradients (almost
-        all of the bytes) before the conv backward starts, the conv gradients
-        after it -- on the communicator's own stream; the compute stream only
-        waits for them right before ``optimizer.step()``.  Off: one blocking
-        all-reduce per bucket.  Both orders reduce the same elements with the
-        same collective, so the result does not depend on the flag.  The default
-        follows the only measurement available so far (one GPU, one-rank RCCL
-        group): the asynchronous schedule costs 0.12 ms per update more than the
-        blocking one, like everything else that runs next to the persistent conv
-        grids (DESIGN.md sections 6, 7); flip it once an N-GPU run says otherwise.
-        ``single_rank_collectives`` issues the collectives even in a world of one
-        (a 1-GPU check of the exact calls an N-GPU run makes)."""
-        import torch.distributed as dist
-        self._dp_group = process_group if process_group is not None else dist.group.WORLD
-        self._dp_world = dist.get_world_size(self._dp_group)
-        self._dp_active = self._dp_world > 1 or single_rank_collectives
-        self._dp_avg = dist.get_backend(self._dp_group) == "nccl"
-        # A backend without a device path of its own (gloo: the CPU tests, and the two-ranks-on-one-GPU test that RCCL
-        # refuses) gets the buckets through the host: device -> host copy, collective, copy back, all synchronous.
-        self._dp_staged = not self._dp_avg and self.device.type == "cuda"
-        if overlap is None:
-            overlap = os.environ.get("CURLA_DP_OVERLAP", "0") == "1"
-        self._dp_overlap = bool(overlap)
-        if check_every is None:
-            check_every = int(os.environ.get("CURLA_DP_CHECK_EVERY", "1000"))
-        self._dp_check_every = int(check_every)
-        self._dp_pending = []
-        if self._dp_active and broadcast:
-            src = dist.get_global_rank(self._dp_group, 0)
-            with torch.no_grad():
-                for t in (self._critic_flat, self._target_flat, self._actor_flat, self.log_alpha):
-                    if self._dp_staged:
-                        h = t.detach().cpu()
-                        dist.broadcast(h, src=src, group=self._dp_group)
-                        t.copy_(h)
-                    else:
-                        dist.broadcast(t, src=src, group=self._dp_group)
-
-    def _replica_checksum(self):
-        """float64 sums of the replicated state (deterministic: same kernel, same data => same bits)."""
-        with torch.no_grad():
-            return torch.stack([self._critic_flat.sum(dtype=torch.float64), self._target_flat.sum(dtype=torch.float64),
-                                self._actor_flat.sum(dtype=torch.float64), self.log_alpha.detach().to(torch.float64)])
-
-    def check_replicas(self):
-        """Raise if the ranks' parameters differ (costs one 64-byte all-reduce and a host sync)."""
-        if not self._dp_active:
-            return
-        import torch.distributed as dist
-        s = self._replica_checksum()
-        both = torch.stack([s, -s])  # max over ranks of (s, -s) = (max, -min)
-        if self._dp_staged:
-            both = both.cpu()
-        dist.all_reduce(both, op=dist.ReduceOp.MAX, group=self._dp_group)
-        hi, lo = both[0], -both[1]
-        if not bool(torch.equal(hi, lo)):
-            names = ("critic", "critic_target", "actor", "log_alpha")
-            bad = [n for n, a, b in zip(names, hi.tolist(), lo.tolist()) if a != b]
-            raise RuntimeError("data-parallel replicas have diverged (%s differ across ranks): seed every rank "
-                               "identically or keep broadcast=True in enable_data_parallel" % ", ".join(bad))
-
-    def _allreduce(self, *buckets, async_op=False, f64_rider=None):
-        """Average each tensor over the ranks.  async_op: the collectives are only enqueued (they start once
-        the compute stream reaches this point); _allreduce_wait() makes the compute stream wait for them.
-        ``f64_rider`` = (scalar, words): ``scalar`` (one float64 element: log_alpha's gradient) rides in ``words``, the
-        last ops.F64_WORDS elements of the LAST bucket -- packed before the collective, unpacked (= the mean over the
-        ranks, from the exact sum: curla_hip.h curla_f64_pack) once it has completed."""
-        if not self._dp_active:
-            return
-        import torch.distributed as dist
-        if f64_rider is not None:
-            scalar, words = f64_rider
-            assert words.data_ptr() + 4 * words.numel() == buckets[-1].data_ptr() + 4 * buckets[-1].numel()
-            ops.f64_pack(scalar, words)
-        last = len(buckets) - 1
-        for i, t in enumerate(buckets):
-            if t.numel() == 0:
-                continue
-            avg = self._dp_avg and t.dtype == torch.float32  # (a float64 bucket of its own would take the sum path)
-            op = dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM
-            post = []
-            if not avg and not self._dp_staged:
-                post.append(lambda t=t: t.div_(self._dp_world))
-            if f64_rider is not None and i == last:
-                # every path leaves the AVERAGED digits in the words: n_mul makes them the digit sums again
-                post.append(lambda: ops.f64_unpack(f64_rider[1], self._dp_world, self._dp_world, f64_rider[0]))
-            if self._dp_staged:  # (synchronous whatever async_op says: same elements, same sum)
-                h = t.detach().cpu()
-                dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self._dp_group)
-                t.copy_(h.div_(self._dp_world))
-                work = None
-            elif async_op:
-                work = dist.all_reduce(t, op=op, group=self._dp_group, async_op=True)
-            else:
-                dist.all_reduce(t, op=op, group=self._dp_group)
-                work = None
-            if work is not None:
-                self._dp_pending.append((work, post))
-            else:
-                for fn in post:
-                    fn()
-
-    def _allreduce_wait(self):
-        for work, post in self._dp_pending:
-            work.wait()
-            for fn in post:
-                fn()
-        self._dp_pending = []
-
-    def _grad_offset(self, p, flat):
-        return (p.grad.data_ptr() - flat.data_ptr()) // 4
-
     # ------------------------------------------------------------------ reference API
     def train(self, training=True):
         self.training = training
@@ -1011,182 +420,6 @@ class CurlSacAgent(object, metaclass=_AgentType):
     @property
     def alpha(self):
         return self.log_alpha.exp()
-
-    def _stage_obs(self, obs):
-        """One observation for the actor.  uint8 (C, H, W) frames -- what the environment and train.py hand over --
-        go through a pinned host buffer into a one-slot uint8 NHWC device ring and are read by the same fused
-        conv1 loader as a replay minibatch (52 KB over PCIe instead of a pageable 208 KB float copy); anything else
-        takes the reference's torch.FloatTensor(obs) route (curl_sac.py:332-333)."""
-        if not (isinstance(obs, np.ndarray) and obs.dtype == np.uint8 and obs.ndim == 3):
-            return torch.FloatTensor(np.ascontiguousarray(obs)).to(self.device).unsqueeze(0)
-        C, H, W = obs.shape
-        st = self._act_stage.get((C, H, W))
-        if st is None:
-            n = H * W * C
-            pin = torch.empty(n, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
-            ring = torch.zeros(n + 32, dtype=torch.uint8, device=self.device)  # + loader slack (curla_hip.h)
-            st = self._act_stage[(C, H, W)] = (pin, pin.numpy().reshape(H, W, C), ring, ring[:n].view(1, H, W, C))
-        pin, pin_hwc, ring, frames = st
-        np.copyto(pin_hwc, obs.transpose(1, 2, 0))
-        ring[:pin.numel()].copy_(pin, non_blocking=True)
-        return ops.ObsRef.from_ring(frames, None, None, None, 1, (H, W))
-
-    def select_action(self, obs):
-        """curl_sac.py:330-337."""
-        with torch.no_grad():
-            mu, _, _, _ = self.actor(self._stage_obs(obs), compute_pi=False, compute_log_pi=False)
-            return mu.cpu().data.numpy().flatten()
-
-    def sample_action(self, obs, noise=None):
-        """curl_sac.py:339-347."""
-        if obs.shape[-2:] != self.image_shape:
-            obs = self.augmentor.evaluation_augmentation(obs)
-        with torch.no_grad():
-            mu, pi, _, _ = self.actor(self._stage_obs(obs), compute_log_pi=False, noise=noise)
-            return pi.cpu().data.numpy().flatten()
-
-    # ------------------------------------------------------------------ acting on a batch of observations
-    _ACT_PINS = 2  # pinned host blocks per frame shape, used in rotation
-
-    def _act_windows(self):
-        """Frame sizes the batched acting calls take -> origin of the window the encoder reads: its own size (the
-        whole frame) and, under a RandomCrop, the crop's input size (the centre window of
-        RandomCrop.evaluation_augmentation, augmentations.py:26-45).  Under a RandomTranslate also the translate's input
-        size, with None for an origin: such frames are no window of anything, they are centred on a black canvas as
-        RandomTranslate.evaluation_augmentation does (_act_centred), whatever the margins (0 and 1 included).  A Compose
-        acts as its ``move`` does: the cutout's evaluation is the identity."""
-        h, w = self.image_shape
-        windows = {(h, w): (0, 0)}
-        aug = self.augmentor
-        if isinstance(aug, Compose):
-            aug = aug.move
-        if isinstance(aug, (RandomCrop, RandomTranslate)) and tuple(aug.output_shape) == (h, w):
-            H, W = aug.input_shape
-            windows.setdefault((H, W), ((H - h) // 2, (W - w) // 2) if isinstance(aug, RandomCrop) else None)
-        return windows
-
-    def _act_centred(self, x, shape):
-        """(RandomTranslate) N frames of the translate's input size, each centred on a zero canvas of the encoder's size
-        exactly as ``evaluation_augmentation`` centres one: host arrays with NumPy, tensors with torch where they are.
-        Not a hot path: acting on frames of the encoder's own size stages them as before."""
-        N, C, H, W = shape
-        h, w = self.image_shape
-        top, left = (h - H) // 2, (w - W) // 2
-        if torch.is_tensor(x):
-            out = torch.zeros((N, C, h, w), dtype=x.dtype, device=x.device)
-        else:
-            x = np.stack(x) if isinstance(x, list) else x
-            out = np.zeros((N, C, h, w), dtype=x.dtype)
-        out[:, :, top:top + H, left:left + W] = x
-        return out, (N, C, h, w), (0, 0)
-
-    def _act_batch_args(self, obs, noise):
-        """Argument checks of select_actions / sample_actions (they come before anything touches the device).
-        Returns (x, (N, C, H, W), (top, left)); ``x`` is ``obs``, a list of uint8 frames, or a stacked array."""
-        C, A = self.actor.encoder.obs_shape[0], self.action_dim
-        windows = self._act_windows()
-        want = "expected (N, %d, H, W) with N >= 1 and (H, W) = %s" % (C, " or ".join(str(s) for s in windows))
-        x = obs
-        if torch.is_tensor(obs) or isinstance(obs, np.ndarray):
-            shape = tuple(obs.shape)
-        else:
-            x = list(obs)
-            if not x:
-                raise ValueError("empty batch of observations: " + want)
-            shape = (len(x),) + tuple(np.shape(x[0]))
-            if any(tuple(np.shape(f)) != shape[1:] for f in x):
-                raise ValueError("observations of different shapes in one batch: " + want)
-            if not all(isinstance(f, np.ndarray) and f.dtype == np.uint8 for f in x):
-                x = np.stack([np.asarray(f.cpu() if torch.is_tensor(f) else f) for f in x])
-        if len(shape) != 4 or shape[0] < 1 or shape[1] != C or shape[2:] not in windows:
-            raise ValueError("observation batch of shape %s: %s" % (shape, want))
-        if noise is not None and not (torch.is_tensor(noise) and tuple(noise.shape) == (shape[0], A)):
-            raise ValueError("noise of shape %s: expected an (N, A) = (%d, %d) tensor"
-                             % (tuple(getattr(noise, "shape", ())), shape[0], A))
-        from . import _lib
-        if self.device.type != "cuda" and _lib._trace_hook is None:
-            raise RuntimeError("CurlSacAgent.select_actions / sample_actions need a CUDA/HIP device: the acting path "
-                               "has no CPU fallback")
-        window = windows[shape[2:]]
-        if window is None:
-            return self._act_centred(x, shape)
-        return x, shape, window
-
-    def _stage_obs_batch(self, x, shape, window):
-        """N observations for the actor.  uint8 frames go planar, as they are, into a pinned block (one contiguous
-        host copy), over PCIe in one asynchronous copy, and through ONE ops.stage_frames launch -- transpose and
-        centre window fused -- into N slots of a uint8 NHWC device ring that the first conv's loader reads like a
-        replay minibatch; a uint8 CUDA tensor skips the host part.  Anything else takes the reference's
-        torch.FloatTensor route (curl_sac.py:332-333) as a batch.  Blocks and ring are kept per (C, H, W), sized for
-        the largest N seen; a pinned block is written again only after its copy has executed (an event per block)."""
-        N, C, H, W = shape
-        top, left = window
-        h, w = self.image_shape
-        if torch.is_tensor(x) and x.dtype == torch.uint8 and not x.is_cuda:
-            x = x.numpy()
-        on_device = torch.is_tensor(x) and x.dtype == torch.uint8
-        if not (on_device or isinstance(x, list) or (isinstance(x, np.ndarray) and x.dtype == np.uint8)):
-            if torch.is_tensor(x):
-                return x[:, :, top:top + h, left:left + w].to(self.device, torch.float32).contiguous()
-            return torch.FloatTensor(np.ascontiguousarray(x[:, :, top:top + h, left:left + w])).to(self.device)
-        cuda = self.device.type == "cuda"
-        st = self._act_batch_stage.get((C, H, W))
-        if st is None or st["cap"] < N:
-            ring = torch.zeros(N * h * w * C + 32, dtype=torch.uint8, device=self.device)  # + loader slack (curla_hip.h)
-            st = self._act_batch_stage[(C, H, W)] = dict(cap=N, ring=ring, src=None, pins=None, turn=0)
-        n_src = N * C * H * W
-        if on_device:
-            src = x.to(self.device).contiguous()
-        else:
-            if st["src"] is None:
-                cap = st["cap"] * C * H * W
-                st["src"] = torch.empty(cap, dtype=torch.uint8, device=self.device)
-                pins = [torch.empty(cap, dtype=torch.uint8, pin_memory=cuda) for _ in range(self._ACT_PINS)]
-                st["pins"] = [(p, p.numpy(), torch.cuda.Event() if cuda else None) for p in pins]
-            k = st["turn"]
-            st["turn"] = (k + 1) % len(st["pins"])
-            pin, pin_np, event = st["pins"][k]
-            if cuda:
-                event.synchronize()  # (returns at once unless the copy out of this block is still to run)
-            host = pin_np[:n_src].reshape(N, C, H, W)
-            if isinstance(x, list):
-                np.stack(x, out=host)
-            else:
-                np.copyto(host, x)
-            src = st["src"][:n_src].view(N, C, H, W)
-            src.copy_(pin[:n_src].view(N, C, H, W), non_blocking=True)
-            if cuda:
-                event.record()
-        frames = st["ring"][:N * h * w * C].view(N, h, w, C)
-        ops.stage_frames(src, frames, 0, top, left)
-        return ops.ObsRef.from_ring(frames, None, None, None, N, (h, w))
-
-    def select_actions(self, obs, as_tensor=False):
-        """``select_action`` (curl_sac.py:330-337) row by row for N observations in one pass: the (N, A) float32
-        means.  ``obs``: a uint8 array (N, C, H, W), a sequence of N uint8 (C, H, W) frames or a uint8 CUDA tensor
-        (the fast route, _stage_obs_batch); anything else (float arrays) goes the reference's float route.  (H, W) is
-        the encoder's input size or -- under a RandomCrop -- the crop's input size, whose centre window is then cut
-        inside the staging launch, or -- under a RandomTranslate -- the translate's input size, which is then centred on
-        a black canvas like ``evaluation_augmentation`` does; any other size raises ValueError.  Returns a NumPy array (one device -> host
-        copy, one synchronisation), or with ``as_tensor`` the device tensor without synchronising; that tensor is
-        storage of its own, which later acting calls do not touch.  Builds no autograd graph, draws no random
-        numbers, and leaves the update's workspaces, index blocks and captured graphs alone."""
-        x, shape, window = self._act_batch_args(obs, None)
-        with torch.no_grad():
-            mu, _, _, _ = self.actor(self._stage_obs_batch(x, shape, window), compute_pi=False, compute_log_pi=False)
-        return mu if as_tensor else mu.cpu().numpy()
-
-    def sample_actions(self, obs, noise=None, as_tensor=False):
-        """``sample_action`` (curl_sac.py:339-347) row by row for N observations in one pass: the (N, A) float32
-        samples.  ``obs``, the accepted sizes and the return value as in ``select_actions``.  ``noise`` (N, A)
-        replaces the draw; without it the draw is Actor.forward's single ``torch.randn((N, A), device=...)``, so a
-        seeded call equals the call with that tensor passed in."""
-        x, shape, window = self._act_batch_args(obs, noise)
-        if noise is not None:
-            noise = noise.detach().to(self.device, torch.float32).contiguous()
-        with torch.no_grad():
-            _, pi, _, _ = self.actor(self._stage_obs_batch(x, shape, window), compute_log_pi=False, noise=noise)
-        return pi if as_tensor else pi.cpu().numpy()
 
     # ------------------------------------------------------------------ building blocks
     def _encoder_backward(self, ws, obs_ref, dz, xhat, rstd, enc, conv_grads=True, dense_done=None, twin_ld=None,
@@ -1758,7 +991,7 @@ class CurlSacAgent(object, metaclass=_AgentType):
         else:
             sample = replay_buffer.sample_cpc()
 
-        if first and self._dp_active and self._dp_check_every > 0 and step % self._dp_check_every == 0:
+        if self._replica_check_due(step, first):
             self.check_replicas()
         if leading:
             self._leading_phases(sample, step)
@@ -1830,271 +1063,6 @@ class CurlSacAgent(object, metaclass=_AgentType):
             obs_anchor, obs_pos = cpc_kwargs["obs_anchor"], cpc_kwargs["obs_pos"]
             self.update_cpc(obs_anchor, obs_pos, cpc_kwargs, L, step)
         self._finish_actor_step()
-
-    # ---------------------------------------------------------------- captured update graphs
-    def enable_update_graphs(self, replay_buffer, warm=1, depth=2):
-        """Replay ``update()`` from captured hipGraphs (kernels only enqueue, take no host syncs and
-        allocate nothing, so a whole update can be captured).  One graph per KIND of step -- (actor phase?, target soft
-        update?, CURL phase?): with train.py's frequencies that is "even" and "odd" -- is captured the first time the
-        kind comes up after ``warm`` eager updates of it, and replayed from then on: the host's work per update shrinks
-        to drawing the indices (NumPy, the reference's stream and order), writing them and ~80 bytes of per-update
-        control values into a pinned block, and one graph launch.  What changes from update to update is DATA the
-        captured kernels read on the device: the minibatch's indices / crop offsets (as before), the Philox stream
-        position of each policy-noise draw and every optimizer's two step-dependent Adam factors (curla_hip.h: the
-        ``rng_dev`` / ``dyn`` arguments); the block's staging kernel is the first node of the graph.
-        A ``ReplayBuffer(..., staged_aug=True)`` with ColorJiggle, NoisyCover or RandomConv is covered the same way: the host draws
-        the three tensors' parameters per replay (``draw_aug``: torch's CPU generator / NumPy, in the eager order; for
-        NoisyCover also the Philox positions of the three in-kernel noise draws, taken from the device generator IN
-        FRONT of the two policy draws, as an eager staged update takes them) and writes them into the block behind the
-        indices; the jitter / cover / convolution launches are nodes that read the block's device copy.  A ``dedup_frames`` buffer
-        needs no flag: its gather_stacks launches are nodes that read the frame-id table when the graph runs.
-        (ColorJiggle's arithmetic stays PARITY UNPINNED, graphed or not: augmentations.py.)
-        ``depth`` graphs are captured per kind, each with its own pinned block, and used in rotation: the host may then
-        prepare update n + 2 depth - 1 while the GPU still reads the block of update n (with one graph per kind it would
-        wait for the replay two updates back before every update).
-        Results are bit-identical to the eager path (tests/test_gpu_graph.py).  Steps the graphs do not cover run
-        eagerly, in any mix: logging steps (``step % log_interval == 0``: they compute extra scalars), histogram /
-        image recording steps, ``only_cpc``, other replay buffers, data-parallel runs on a backend other than RCCL.  A
-        float augmentation on a buffer built WITHOUT ``staged_aug=True`` is refused here (its parameters go through a
-        pinned block and a copy of their own per call).  Data-parallel updates over RCCL
-        ARE captured, collectives included (round 5; the replica check stays on the host, in front of the replay).
-        Values the graphs hold as kernel arguments (discount, taus, betas / eps, detach_encoder, the update
-        frequencies, the data-parallel group and schedule, ``max_grad_norm``, ``critic_dropout``,
-        ``critic_drop_quantiles``, ``n_step`` and ``discount`` of an n-step replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
-        so does ``load_checkpoint``.  A capture that raises leaves the agent's
-        state untouched and that update runs eagerly.
-        ``utd_ratio = G > 1``: a call replays the critic-only kind's graph (actor=False, soft, cpc=False) G-1 times -- the
-        graph an ordinary critic-only step captures, each replay on the next block of the kind's rotation -- and then the
-        step's own kind; a call that runs eagerly (above) runs all its sub-steps eagerly.  No graph holds the ratio: it
-        is not fingerprinted and may be edited between calls.
-        Weight decay (``set_weight_decay``): a captured Adam launch holds its factor ``float32(1 - lr * weight_decay)``
-        by value, so for an optimizer that decays, ``lr`` is fingerprinted too -- an lr schedule on a decaying optimizer
-        re-captures at every change of lr (without weight decay lr travels as data and never re-captures)."""
-        if self.device.type != "cuda":
-            raise RuntimeError("update graphs need the HIP device")
-        if not getattr(replay_buffer, "graph_supported", lambda: False)():
-            raise ValueError("enable_update_graphs: this replay buffer / augmentation is not graph-replayable "
-                             "(covered: RandomCrop, RandomShift, RandomCutout, RandomTranslate or identity, plain storage with both rings in one "
-                             "allocation or dedup_frames storage -- RandomFlip, RandomRotate, RandomGrayscale and RandomAffine like them; ColorJiggle / NoisyCover / RandomConv "
-                             "only on a ReplayBuffer constructed with staged_aug=True; pinned index slots, i.e. not "
-                             "CURLA_STAGE_COPY=1; not a prioritized=True buffer, whose draw and priority update are not "
-                             "nodes of the graphs)")
-        opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer)
-        if not all(isinstance(o, FlatAdam) and "step" not in vars(o) for o in opts) or \
-                type(self.log_alpha_optimizer) is not torch.optim.Adam or self._noise_launch:
-            raise ValueError("enable_update_graphs needs the FlatAdam optimizers and the in-kernel policy noise")
-        self._graphs = {}
-        self._graph_rb = replay_buffer
-        self._graph_warm = int(warm)
-        self._graph_depth = max(1, int(depth))
-        self._graph_seen = {}
-        self._graph_key_at_capture = None
-
-    def disable_update_graphs(self):
-        self._graphs = None
-
-    def _graph_kind(self, step):
-        return (step % self.actor_update_freq == 0, step % self.critic_target_update_freq == 0,
-                (not self.pixel_sac) and step % self.cpc_update_freq == 0)
-
-    def _graph_usable(self, replay_buffer, step, only_cpc):
-        # data parallel: RCCL collectives are capturable (they are enqueued on streams like kernels); a backend that is
-        # staged through the host (gloo) is not
-        # (_dp_avg: the group's backend is RCCL; every other backend takes the sum-and-divide / staged path)
-        return (replay_buffer is self._graph_rb and not only_cpc and not (self._dp_active and not self._dp_avg)
-                and not self._records(step) and step % self.log_interval != 0 and self.training)
-
-    def _graph_live(self, opt):
-        """The parameters ``opt``'s step touches in a captured update (None: all).  Under detach_encoder the critic's
-        convs have no gradient at step time (curl_sac.py:358): Adam skips them and their step counts stay behind."""
-        if opt is self.critic_optimizer and self.detach_encoder:
-            convs = {id(p) for m in self.critic.encoder.convs for p in (m.weight, m.bias)}
-            return [p for p in opt._plist if id(p) not in convs]
-        return None
-
-    def _graph_key(self):
-        """Everything a captured graph holds BY VALUE (kernel arguments baked in at capture): a change of any of it
-        makes the captured graphs stale -- they are dropped and re-captured (``lr`` travels as data and is not here,
-        except for a param group with weight decay: its launch holds 1 - lr * weight_decay by value)."""
-        opts = (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer,
-                self.log_alpha_optimizer)
-        hyper = tuple((float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g.get("weight_decay", 0))) +
-                      ((float(g["lr"]),) if g.get("weight_decay", 0) != 0 else ())  # (0: the key without weight decay)
-                      for o in opts for g in o.param_groups)
-        return (float(self.discount), float(self.critic_tau), float(self.encoder_tau), bool(self.detach_encoder),
-                bool(self.pixel_sac), float(self.target_entropy), float(self.actor.log_std_min),
-                float(self.actor.log_std_max), self.actor_update_freq, self.critic_target_update_freq,
-                self.cpc_update_freq, self._dp_active, self._dp_overlap, id(self._dp_group) if self._dp_active else 0,
-                hyper, self._graph_rb_key(), self._max_grad_norm) + \
-            ((float(self.critic_dropout),) if self.critic_dropout else ()) + \
-            ((("quantiles", self.critic_quantiles, self.critic_drop_quantiles),) if self.critic_quantiles else ())
-        # (0, for either: the key of an agent without the keyword)
-
-    def _graph_rb_key(self):
-        """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value
-        (n_envs as the stride of the chain walks)."""
-        rb = getattr(self, "_graph_rb", None)
-        n = getattr(rb, "n_step", 1)
-        return ((n, float(rb.discount)) if n > 1 else (1, None)) + (getattr(rb, "pos_offset", 0), getattr(rb, "n_envs", 1))
-
-    def _graph_tail(self, kind, B):
-        """The 80 control bytes of one graphed update (ReplayBuffer.GRAPH_TAIL) -- and the host-side bookkeeping of
-        everything they stand for: the torch generator's offset moves on as _noise() would move it, every optimizer that
-        steps in this kind of update counts its step.  Only called once the update's graph exists (a capture that failed
-        has run eagerly instead), so there is nothing to take back."""
-        do_actor, _, do_cpc = kind
-        u64 = np.zeros(4, dtype=np.uint64)
-        gen = torch.cuda.default_generators[self.device.index if self.device.index is not None
-                                            else torch.cuda.current_device()]
-        n = B * self.action_dim
-        for j in range(2 if do_actor else 1):  # critic-phase draw, then the actor phase's (curl_sac.py:352, 378)
-            off = gen.get_offset()
-            gen.set_offset(off + 4 * ((n + 3) // 4))
-            u64[2 * j], u64[2 * j + 1] = np.uint64(gen.initial_seed() & (2 ** 64 - 1)), np.uint64(off // 4)
-        f64 = np.zeros(2, dtype=np.float64)
-        f32 = np.zeros(8, dtype=np.float32)
-        steps = [(0, self.critic_optimizer)]
-        if do_actor:
-            steps.append((1, self.actor_optimizer))
-            lo = self.log_alpha_optimizer
-            g, p = lo.param_groups[0], lo.param_groups[0]["params"][0]
-            st = lo.state[p]
-            if len(st) == 0:
-                st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
-            t64 = int(round(float(st["step"]))) + 1
-            b1, b2 = float(g["betas"][0]), float(g["betas"][1])
-            f64[0], f64[1] = float(g["lr"]) / (1.0 - b1 ** float(t64)), (1.0 - b2 ** float(t64)) ** 0.5
-            st["step"] = torch.tensor(float(t64), dtype=torch.float32)
-        if do_cpc:
-            steps += [(2, self.encoder_optimizer), (3, self.cpc_optimizer)]
-        for slot, opt in steps:
-            live = self._graph_live(opt)
-            f32[2 * slot], f32[2 * slot + 1] = opt.hyper_floats(opt.next_step(live))
-            opt.advance(live)
-        return u64.tobytes() + f64.tobytes() + f32.tobytes()
-
-    GRAPH_CAPTURE_RETRIES = 3  # failed captures (on any rank) after which update graphs are switched off
-
-    def _graph_capture_agreed(self, ok):
-        """True when the capture succeeded on EVERY rank of the data-parallel group (one rank: ``ok`` itself)."""
-        if not (self._dp_active and self._dp_world > 1):
-            return bool(ok)
-        import torch.distributed as dist
-        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=self.device)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self._dp_group)
-        return bool(int(flag.item()))
-
-    def _drop_graphs(self):
-        """Forget the captured graphs (they are re-captured after ``warm`` further eager updates of each kind)."""
-        if self._graphs is not None:
-            torch.cuda.synchronize()
-            self._graphs = {}
-            self._graph_seen = {}
-            self._graph_key_at_capture = None
-
-    def _update_graphed(self, rb, L, step):
-        self._check_n_step(rb)
-        key = self._graph_key()
-        if self._graphs and key != self._graph_key_at_capture:
-            self._drop_graphs()  # a value the graphs hold as a kernel argument has been edited since the capture
-        kind = self._graph_kind(step)
-        leading = self.utd_ratio - 1
-        if leading == 0:
-            return self._graphed_substep(rb, step, kind, key, lambda: self._update_eager(rb, L, step))
-        # utd_ratio > 1: the critic-only kind's graph G-1 times -- the one an ordinary critic-only step captures and
-        # replays, positive's sampling nodes included --, then the step's own kind.  Every sub-step takes the next turn
-        # of its kind's ring, so consecutive replays of one kind read different blocks, and graph_write waits for the
-        # replay that last read a block before the host rewrites it.
-        lead_kind = (False, kind[1], False)
-        for k in range(leading):
-            self._graphed_substep(rb, step, lead_kind, key, lambda k=k: self._substep_eager(
-                rb, None, step, leading=True, first=k == 0), leading=True, first=k == 0)
-        self._graphed_substep(rb, step, kind, key, lambda: self._substep_eager(rb, L, step, first=False), first=False)
-
-    def _graphed_substep(self, rb, step, kind, key, eager, leading=False, first=True):
-        """One minibatch of a graphed update: the replay of ``kind``'s graph (captured here when its turn has none) or,
-        while the kind is warming up and where a capture fails, ``eager()``."""
-        if self._graphs is None:  # (an earlier sub-step of this call has given the graphs up)
-            return eager()
-        seen = self._graph_seen.get(kind, 0)
-        self._graph_seen[kind] = seen + 1
-        if seen < self._graph_warm:  # (first uses allocate workspaces and set kernel attributes: not capturable)
-            return eager()
-        ring = self._graphs.setdefault(kind, [])
-        turn = (seen - self._graph_warm) % self._graph_depth
-        if turn >= len(ring):
-            ring.append(dict(slot=sum(len(r) for r in self._graphs.values()), graph=None))
-        st = ring[turn]
-        B = rb.batch_size
-        if st["graph"] is None:
-            # capture FIRST, commit the host's bookkeeping (NumPy draw, generator offset, step counts) only once the
-            # capture has succeeded: nothing inside the captured region draws from NumPy, torch's CPU generator or
-            # moves the device generator (draw_indices / draw_aug / _graph_tail run after it), so a capture that raises (a first-use attribute call after an
-            # option change, a HIP call from another thread) has touched only the phase-to-phase hints below, which are
-            # reset, and this update runs eagerly
-            blk = rb.graph_block(st["slot"])
-            base = blk["dev"].data_ptr() + blk["tail"]
-            dyn = {self.critic_optimizer: base + 48, self.actor_optimizer: base + 56, self.encoder_optimizer: base + 64,
-                   self.cpc_optimizer: base + 72}
-            self._graph_cap = dict(rng=(base, base + 16), n_noise=0)
-            for opt, addr in dyn.items():
-                opt._dyn = addr
-            self.log_alpha_optimizer._curla_dyn64 = base + 32
-            null = _NullLog()
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            err = None
-            try:
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    if leading:
-                        self._leading_phases(rb.graph_refs(st["slot"]), step)
-                    else:
-                        self._update_phases(rb.graph_refs(st["slot"]), null, step)
-            except Exception as e:  # noqa: BLE001
-                err = e
-            finally:
-                self._graph_cap = None
-                for opt in dyn:
-                    opt._dyn = None
-                self.log_alpha_optimizer._curla_dyn64 = None
-            if err is not None:
-                # what _update_phases sets from one phase to the next and had no chance to clear
-                self._pos_hint = self._anchor_cache = self._pos_cache = None
-                self._pos_fc_done = self._soft_update_hint = self._soft_update_done = False
-                self._defer_actor_step = self._actor_step_pending = False
-                self._dp_pending = []
-            # data parallel: every rank captures at the same step; ONE rank replaying while another runs eagerly would
-            # still pair up collective for collective, but the ranks would sit on different schedules indefinitely with
-            # nothing checking it -- so the outcome is agreed on (one host-side flag, at capture time only)
-            ok_everywhere = self._graph_capture_agreed(err is None)
-            if not ok_everywhere:
-                self._graph_failures = getattr(self, "_graph_failures", 0) + 1
-                where = "on this rank" if err is not None else "on another rank"
-                give_up = self._graph_failures >= self.GRAPH_CAPTURE_RETRIES
-                warnings.warn(f"curla_amd: capturing the update graph of {kind} failed {where} ({err!r}); this update "
-                              "runs eagerly" + (" and update graphs are now disabled (every rank of the group does the same)"
-                                                if give_up else " and the capture is tried again next time"),
-                              RuntimeWarning, stacklevel=4)
-                if give_up:
-                    self._graphs = None
-                else:
-                    self._graph_seen[kind] = seen  # (the slot keeps its empty entry: the same turn captures again)
-                return eager()
-            st["graph"] = graph
-            self._graph_key_at_capture = key
-        # the eager order of host draws: indices, then the three tensors' augmentation parameters (staged_aug: NoisyCover
-        # reserves its noise counters on the device generator here), then the policy draws of _graph_tail
-        idxs, offs = rb.draw_indices()
-        aug = rb.draw_aug()
-        tail = self._graph_tail(kind, B)
-        blk = rb.graph_write(st["slot"], idxs, offs, tail, aug)
-        if first and self._dp_active and self._dp_check_every > 0 and step % self._dp_check_every == 0:
-            self.check_replicas()
-        st["graph"].replay()
-        if blk["event"] is None:
-            blk["event"] = torch.cuda.Event()
-        blk["event"].record()
 
     def save(self, model_dir, augmentation, step):
         """curl_sac.py:453-456 (same three files, reference tensor layouts)."""

@@ -1,0 +1,326 @@
+"""Actor / QFunction / Critic / CURL with the reference's API (curl_sac.py:38-222), and their argument checks."""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import autograd, ops
+from .encoder import CNNEncoder
+from .mlp import _Mlp, _MlpLn, _linears, _mlp_fwd
+
+LOG_FREQ = 25_000
+
+
+def weight_init(m):
+    """The reference's initialisation (curl_sac.py:38-54), applied with ``module.apply``: Linear weights orthogonal
+    with zero bias; Conv2d / ConvTranspose2d "delta-orthogonal" (arXiv:1806.05393) -- every tap zero except the
+    centre one, which is an orthogonal (out x in) matrix with the ReLU gain -- and zero bias.  The draws come from
+    torch's global generator in module order, so a seeded construction reproduces the reference's parameters."""
+    if isinstance(m, nn.Linear):
+        nn.init.orthogonal_(m.weight.data)
+        if m.bias is not None:
+            m.bias.data.zero_()
+        return
+    if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+        kh, kw = m.weight.shape[2:]
+        assert kh == kw, "square kernels only"
+        m.weight.data.zero_()
+        if m.bias is not None:
+            m.bias.data.zero_()
+        centre = kh // 2
+        nn.init.orthogonal_(m.weight.data[:, :, centre, centre], nn.init.calculate_gain('relu'))
+
+
+class Actor(nn.Module):
+    """MLP actor network (curl_sac.py:57-121)."""
+
+    def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, log_std_min, log_std_max,
+                 num_layers, num_filters):
+        super().__init__()
+        self.encoder = CNNEncoder(obs_shape, encoder_feature_dim, num_layers, num_filters, output_logits=True)
+        self.log_std_min = log_std_min
+        self.log_std_max = log_std_max
+        self.action_dim = action_shape[0]
+        self.hidden_dim = hidden_dim
+        self.trunk = nn.Sequential(
+            nn.Linear(self.encoder.feature_dim, hidden_dim), nn.ReLU(),
+            nn.Linear(hidden_dim, hidden_dim), nn.ReLU(),
+            nn.Linear(hidden_dim, 2 * action_shape[0])
+        )
+        self.outputs = dict()
+        self.apply(weight_init)
+
+    def forward(self, obs, compute_pi=True, compute_log_pi=True, detach_encoder=False, noise=None):
+        """Forward on the HIP kernels; same return tuple as the reference (mu, pi, log_pi, log_std) with pi/log_pi
+        None when not asked for.  ``noise`` replaces torch.randn_like (curl_sac.py:97) and is a constant.
+        Differentiable (autograd.ActorFn) when grad mode is on and the features or a trunk parameter require grad."""
+        z = self.encoder(obs, detach=detach_encoder)
+        if autograd.wants_graph(z, *self.trunk.parameters()):
+            return autograd.actor_forward(self, z, compute_pi, compute_log_pi, noise)
+        B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
+        dev = z.device
+        h1 = torch.empty((B, H), device=dev)
+        h2 = torch.empty((B, H), device=dev)
+        out = torch.empty((B, 2 * A), device=dev)
+        mu = torch.empty((B, A), device=dev)
+        log_std = torch.empty((B, A), device=dev)
+        pi = log_pi = None
+        if compute_pi:
+            if noise is None:
+                noise = torch.randn((B, A), device=dev)
+            pi = torch.empty((B, A), device=dev)
+            log_pi = torch.empty((B, 1), device=dev) if compute_log_pi else None
+        _mlp_fwd(z, 0, _Mlp(self.trunk), 1, B, F, H, 2 * A, h1, h2, out,
+                 head=(noise if compute_pi else None, self.log_std_min, self.log_std_max,
+                       dict(mu=mu, pi=pi, log_pi=log_pi, log_std=log_std)))
+        self.outputs['mu'] = out[:, :A]  # the pre-squash mean, as the reference records it (curl_sac.py:92)
+        self.outputs['std'] = log_std.exp()
+        return mu, pi, log_pi, log_std
+
+    def log(self, L, step, log_freq=LOG_FREQ):
+        """Histograms of the recorded outputs and of the three trunk layers, every ``log_freq`` steps
+        (curl_sac.py:112-121; same keys)."""
+        if step % log_freq:
+            return
+        for name, value in self.outputs.items():
+            L.log_histogram('train_actor/%s_hist' % name, value, step)
+        for n, layer in enumerate(_linears(self.trunk), start=1):
+            L.log_param('train_actor/fc%d' % n, layer, step)
+
+
+def _check_int(v, lo, hi, message):
+    """``v`` as an ``int`` in lo .. hi (``hi`` None: no upper bound); ValueError(message) for anything else -- a bool, a
+    float or a string is not an int."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+        raise ValueError(message)
+    return int(v)
+
+
+def _check_quantiles(m):
+    """The quantile atoms per Q function: 0 (off) or an ``int`` in 1 .. ops.TQC_MAX (a bool, a float or a string is not
+    one)."""
+    return _check_int(m, 0, ops.TQC_MAX, "critic quantiles: %r is not an int in 0 .. %d (0: off; the %d pooled atoms "
+                      "of a row are one wave's lanes)" % (m, ops.TQC_MAX, 2 * ops.TQC_MAX))
+
+
+def _check_drop_quantiles(d, m):
+    """The atoms dropped per network, ``0 <= d < M``; only with quantiles on."""
+    d = _check_int(d, 0, None, "critic_drop_quantiles: %r is not an int >= 0" % (d,))
+    if d and not m:
+        raise ValueError("critic_drop_quantiles = %d needs critic_quantiles > 0" % d)
+    if m and d >= m:
+        raise ValueError("critic_drop_quantiles = %d drops every one of the %d atoms (0 <= d < M)" % (d, m))
+    return d
+
+
+def _widen_last_layers(trunks, m, init=None):
+    """Replace the last Linear (hidden -> 1) of each trunk by a hidden -> ``m`` one, ``init`` applied to it.  The new
+    tensors' draws are taken from a fork of torch's generator, which is put back afterwards: everything else a seed
+    produces -- the layers before, the other networks, CURL.W -- comes out as without quantiles."""
+    with torch.random.fork_rng(devices=[]):
+        for trunk in trunks:
+            wide = nn.Linear(trunk[-1].in_features, m)
+            if init is not None:
+                init(wide)
+            trunk[-1] = wide  # (same position: the state-dict keys stay trunk.4 / trunk.6)
+
+
+class _QFunctionType(type):
+    """``QFunction(..., quantiles=M)``: a keyword of the class call, as ``Critic(..., dropout=p)`` is (_CriticType);
+    ``QFunction.__init__`` keeps its parameter list with ``dropout`` last."""
+
+    def __call__(cls, *args, quantiles=0, **kwargs):
+        quantiles = _check_quantiles(quantiles)
+        q = super().__call__(*args, **kwargs)
+        q.quantiles = quantiles
+        if quantiles:
+            _widen_last_layers([q.trunk], quantiles)
+        return q
+
+
+class QFunction(nn.Module, metaclass=_QFunctionType):
+    """MLP for q-function (curl_sac.py:124-139); parameter container.  ``layer_norm``: an ``nn.LayerNorm(hidden_dim)``
+    between each hidden Linear and its ReLU (the Linears are then trunk.0 / .3 / .6, the LayerNorms trunk.1 / .4).
+    ``dropout``: DroQ's dropout probability in front of each LayerNorm -- an attribute, no module of the trunk.
+    ``QFunction(..., quantiles=M)`` (a keyword of the class call; 0: off): the last Linear has M rows, one per quantile
+    atom."""
+
+    quantiles = 0
+
+    def __init__(self, obs_dim, action_dim, hidden_dim, layer_norm=False, dropout=0.0):
+        super().__init__()
+        _check_layer_norm_width(layer_norm, hidden_dim)
+        self.dropout = _check_dropout(dropout, layer_norm)
+        norm = (lambda: [nn.LayerNorm(hidden_dim)]) if layer_norm else (lambda: [])
+        self.trunk = nn.Sequential(
+            nn.Linear(obs_dim + action_dim, hidden_dim), *norm(), nn.ReLU(),
+            nn.Linear(hidden_dim, hidden_dim), *norm(), nn.ReLU(),
+            nn.Linear(hidden_dim, 1)
+        )
+
+
+def _check_layer_norm_width(layer_norm, hidden_dim):
+    if layer_norm and hidden_dim > ops.MLP_LN_MAX:
+        raise ValueError("critic LayerNorm: hidden_dim = %d is wider than the %d features the LayerNorm kernels take "
+                         "(one wave per row)" % (hidden_dim, ops.MLP_LN_MAX))
+
+
+def _check_dropout(p, layer_norm):
+    """The critics' dropout probability as a float: 0 <= p < 1, and only in front of a LayerNorm (dropout without the
+    normalisation behind it is the configuration DroQ shows to be harmful; it is not offered)."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("critic dropout: p = %r is not in [0, 1)" % (p,))
+    if p > 0.0 and not layer_norm:
+        raise ValueError("critic dropout needs the critics' LayerNorm (critic_layer_norm=True / layer_norm=True)")
+    return p
+
+
+def _device_generator(device):
+    device = torch.device(device)
+    torch.cuda.init()  # (the generators exist once the runtime is up; a dropout agent may be the process's first use of it)
+    return torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+
+
+def _reserve_dropout_counter(device):
+    """(seed, counter) of one pass's dropout masks, taken from ``device``'s default torch generator, whose offset moves
+    on by 4 (one Philox counter): torch.manual_seed, get_rng_state / set_rng_state (checkpoints) and the per-rank
+    seeds keep their meaning.  A CPU agent launches nothing (the trace hook's launch lists): position 0 of torch's
+    seed."""
+    if torch.device(device).type != "cuda":
+        return torch.initial_seed(), 0
+    gen = _device_generator(device)
+    off = gen.get_offset()
+    gen.set_offset(off + 4)
+    return gen.initial_seed(), off // 4
+
+
+class _CriticType(type):
+    """``Critic(..., dropout=p)``: the class call takes the keyword, as CurlSacAgent's takes its own (_AgentType), and
+    ``Critic.__init__`` keeps its parameter list with ``layer_norm`` last.  ``Critic(..., quantiles=M)`` likewise: the
+    critic is built as without it and the Q functions' last layers are then replaced by M-row ones, initialised like
+    every other Linear (weight_init)."""
+
+    def __call__(cls, *args, dropout=0.0, quantiles=0, **kwargs):
+        quantiles = _check_quantiles(quantiles)
+        critic = super().__call__(*args, **kwargs)
+        critic.dropout = critic.Q1.dropout = critic.Q2.dropout = _check_dropout(dropout, critic.layer_norm)
+        critic.quantiles = critic.Q1.quantiles = critic.Q2.quantiles = quantiles
+        if quantiles:
+            _widen_last_layers([critic.Q1.trunk, critic.Q2.trunk], quantiles, weight_init)
+        return critic
+
+
+class Critic(nn.Module, metaclass=_CriticType):
+    """Critic network, employs two Q-functions (curl_sac.py:142-180).  ``layer_norm``: QFunction's; so is
+    ``Critic(..., dropout=p)``, a keyword of the class call.  ``forward`` drops in training mode only
+    (``critic.eval()``: the deterministic Q).  ``Critic(..., quantiles=M)`` (0: off): each Q function outputs M quantile
+    atoms and ``forward`` returns ``q1, q2`` of shape [B, M]."""
+
+    dropout = 0.0
+    quantiles = 0
+
+    @property
+    def out_dim(self):
+        """The width of a Q function's last layer: its quantile atoms, or the one Q value."""
+        return self.quantiles or 1
+
+    def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
+                 layer_norm=False):
+        super().__init__()
+        _check_layer_norm_width(layer_norm, hidden_dim)
+        self.encoder = CNNEncoder(obs_shape, encoder_feature_dim, num_layers, num_filters, output_logits=True)
+        self.Q1 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim, layer_norm)
+        self.Q2 = QFunction(self.encoder.feature_dim, action_shape[0], hidden_dim, layer_norm)
+        self.action_dim = action_shape[0]
+        self.hidden_dim = hidden_dim
+        self.layer_norm = bool(layer_norm)
+        self.outputs = dict()
+        self.twin_stride = None  # floats between Q1 and Q2 tensors once flattened by the agent
+        self.apply(weight_init)
+
+    def twin(self, grads=False):
+        if self.twin_stride is None:
+            raise RuntimeError("Critic parameters are not in the flat twin layout (constructed outside CurlSacAgent)")
+        return _Mlp(self.Q1.trunk, self.twin_stride, grads)
+
+    def twin_ln(self, xhat=None, rstd=None, grads=False, partial=None, save_first=0, drop=None):
+        """The ``ln=`` argument of _mlp_fwd / _mlp_bwd for ``twin()``: None without LayerNorm.  ``xhat`` / ``rstd``:
+        a pair of buffers each, one per hidden layer; ``grads``: the backward fills the LayerNorm tensors' .grad;
+        ``drop`` = (p, rng, tag) or None: this pass's dropout (_MlpLn)."""
+        if not self.layer_norm:
+            return None
+        ln = _MlpLn(self.Q1.trunk, xhat, rstd, partial=partial, save_first=save_first, drop=drop)
+        if grads:
+            ln.dg, ln.db = [p.grad for p in ln.g], [p.grad for p in ln.b]
+        return ln
+
+    DROP_TAG_FORWARD = 7  # the tags of the dropout masks: 1 + 2 * pass + layer, a forward() call is pass 3
+
+    def forward(self, obs, action, detach_encoder=False, dropout_rng=None):
+        """``dropout_rng`` = (seed, counter): the stream position of a training-mode dropout critic's masks (tags 7 / 8);
+        None reserves one counter from the device's torch generator per call."""
+        assert obs.size(0) == action.size(0)  # curl_sac.py:136
+        z = self.encoder(obs, detach=detach_encoder)
+        drop = None
+        if self.dropout > 0 and self.training:
+            _check_dropout(self.dropout, self.layer_norm)
+            drop = (self.dropout, dropout_rng or _reserve_dropout_counter(z.device), self.DROP_TAG_FORWARD)
+        if autograd.wants_graph(z, action, *self.Q1.parameters(), *self.Q2.parameters()):
+            q1, q2 = autograd.critic_forward(self, z, action, drop)  # (differentiable: autograd.CriticFn)
+            self.outputs['q1'], self.outputs['q2'] = q1.detach(), q2.detach()
+            return q1, q2
+        B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
+        dev = z.device
+        xa = torch.empty((B, F + A), device=dev)
+        ops.concat(z, action.contiguous().float(), B, F, A, xa)
+        h1 = torch.empty((2, B, H), device=dev)
+        h2 = torch.empty((2, B, H), device=dev)
+        q = torch.empty((2, B, self.out_dim), device=dev)
+        _mlp_fwd(xa, 0, self.twin(), 2, B, F + A, H, self.out_dim, h1, h2, q, ln=self.twin_ln(drop=drop))
+        self.outputs['q1'], self.outputs['q2'] = q[0], q[1]
+        return q[0], q[1]
+
+    def log(self, L, step, log_freq=LOG_FREQ):
+        """Histograms of the recorded Q values and of both Q trunks, every ``log_freq`` steps
+        (curl_sac.py:171-180; same keys)."""
+        if step % log_freq:
+            return
+        for name, value in self.outputs.items():
+            L.log_histogram('train_critic/%s_hist' % name, value, step)
+        for layer in range(3):  # (the three Linears; a LayerNorm critic's LayerNorms are not histogrammed)
+            for tag, q in (('q1', self.Q1), ('q2', self.Q2)):
+                L.log_param('train_critic/%s_fc%d' % (tag, layer), _linears(q.trunk)[layer], step)
+
+
+class CURL(nn.Module):
+    """CURL head (curl_sac.py:183-222)."""
+
+    def __init__(self, obs_shape, z_dim, critic, critic_target, output_type="continuous"):
+        super().__init__()
+        self.encoder = critic.encoder
+        self.encoder_target = critic_target.encoder
+        self.W = nn.Parameter(torch.rand(z_dim, z_dim))
+        self.output_type = output_type
+
+    def encode(self, x, detach=False, ema=False):
+        """curl_sac.py:196-209: ``ema`` runs the target encoder without grad, ``detach`` detaches the result."""
+        if ema:
+            with torch.no_grad():
+                z_out = self.encoder_target(x)
+        else:
+            z_out = self.encoder(x)
+        return z_out.detach() if detach else z_out
+
+    def compute_logits(self, z_a, z_pos):
+        """(B,B) logits z_a (W z_pos^T) minus the row max (curl_sac.py:211-222),
+        both products on the MFMA GEMM; differentiable through both (autograd.CurlLogitsFn) when grad mode is on and
+        an input or W requires grad."""
+        if autograd.wants_graph(z_a, z_pos, self.W):
+            logits = autograd.CurlLogitsFn.apply(z_a.contiguous(), z_pos.contiguous(), self.W)
+            return logits - torch.max(logits, 1)[0][:, None]
+        B, F = z_a.shape
+        WzT = torch.empty((B, F), device=z_a.device)
+        logits = torch.empty((B, B), device=z_a.device)
+        ops.linear_fwd(z_pos.contiguous(), 0, self.W, 0, None, 0, WzT, 0, B, F, F)
+        ops.linear_fwd(z_a.contiguous(), 0, WzT, 0, None, 0, logits, 0, B, B, F)
+        return logits - torch.max(logits, 1)[0][:, None]

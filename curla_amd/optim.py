@@ -47,6 +47,18 @@ def check_weight_decay(value):
     return float(value)
 
 
+def _scalar_adam_state(opt):
+    """(param, group, state) of a plain ``torch.optim.Adam`` over one parameter (log_alpha's), the state initialised
+    as torch's Adam initialises it (non-capturable: the step count lives on the host)."""
+    g = opt.param_groups[0]
+    p = g["params"][0]
+    st = opt.state[p]
+    if len(st) == 0:
+        st["step"] = torch.tensor(0.0, dtype=torch.float32)
+        st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
+    return p, g, st
+
+
 _NO_CLIP = (0, 0, 0.0, 0)  # the clip arguments (partials, n_partials, max_norm, stats) of an unclipped curla_adamw_* launch
 
 
@@ -438,11 +450,8 @@ class FlatAdam(torch.optim.Adam):
             first.step()
             scalar_opt.step()
             return
-        st = scalar_opt.state[p]
-        if len(st) == 0:  # as torch's Adam initialises it (non-capturable: the step count lives on the host)
-            st["step"] = torch.tensor(0.0, dtype=torch.float32)
-            st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
-        elif st["step"].is_cuda:
+        st = _scalar_adam_state(scalar_opt)[2]
+        if st["step"].is_cuda:
             st["step"] = st["step"].cpu()
         t64 = int(round(float(st["step"]))) + 1
         lo, hi, t, grp = run
