@@ -52,6 +52,11 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// ReLU that keeps a NaN, as torch.relu does: fmaxf(x, 0) returns the number when the other operand is NaN, so a NaN
+// activation left the forward as 0 and vanished.  IEEE-754 maximum (v_maximum3_f32 on gfx950, one instruction like the
+// v_max_f32 it replaces); max(-0, +0) = +0 as before.
+__device__ __forceinline__ float relu_keep_nan(float x) { return __builtin_elementwise_maximum(x, 0.f); }
+
 static inline int curla_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? CURLA_OK : CURLA_ERR_LAUNCH;

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(Src s, const float* __res
           acc = fmaf(v, wk[dy * 3 + dx], acc);
         }
     }
-    out[o] = acc > 0.f ? acc : 0.f;
+    out[o] = relu_keep_nan(acc);  // (common.h: a NaN stays a NaN, as in the 32-filter kernels)
   }
 }
 

@@ -26,11 +26,11 @@
 // VALU per step (192 MFMAs): 16 packed adds (input transform), ~50 for the output transform / ReLU / stores of the
 // completed row, 4 address increments -- against ~190 in the banded form.
 //
-// Strips.  An image row has PW = ceil(Wo / 2) pairs.  Columns 16k .. 16k+15 form full strip k (Ho steps).  The b =
-// PW mod 16 remaining columns are cut into vertical segments of nr rows so that 16 lanes are (column, segment)
-// units: a remainder strip takes nr steps and its lanes start at different rows.  (Ho, Wo) = (35, 35): one full
-// strip (35 steps) + 2 columns x 7 segments of 5 rows (5 steps) = 40 steps against 39.4 ideal.
+// Strips: full strips of 16 pair columns and remainder strips of (column, segment) units, planned on the host
+// (conv_plan.h: rw::Geom, rw::plan).
 #pragma once
+
+#include "conv_plan.h"
 
 namespace rw {
 
@@ -49,17 +49,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p, in
                                            __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
-struct Geom {
-  int Hi, Wi;    // input rows / columns
-  int Ho, Wo;    // output rows / columns (forward: Hi-2, Wi-2; data gradient: Hi+2, Wi+2)
-  int nfull;     // full strips
-  int brem;      // remaining pair columns (0..15)
-  int nr;        // rows per segment of the remainder strips
-  int nseg;      // segments per remaining column = ceil(Ho / nr)
-  int ntr;       // remainder strips = ceil(brem * nseg / 16)
-  int steps;     // steps per sample = nfull * Ho + ntr * nr
-};
-
 struct Problem {
   const float* in;
   const float* w;    // OIHW [32][32][3][3]
@@ -74,33 +63,6 @@ struct Args {
   Geom g[kMaxLayers];
   Problem p[kMaxLayers][2];  // second problem: B = 0 when absent
 };
-
-// host: strips of `per` columns over `cols` column units and Ho rows (see "Strips" above): full strips of Ho steps,
-// and the remaining columns cut into vertical segments of nr rows so that `per` lane groups are (column, segment) units
-inline void plan_units(Geom& g, int Ho, int cols, int per) {
-  g.nfull = cols / per, g.brem = cols % per;
-  g.nr = g.nseg = g.ntr = 0;
-  if (g.brem) {
-    // segments of nr rows: brem * ceil(Ho / nr) units on `per` lane groups per strip; cost = strips x nr steps
-    long best = -1;
-    for (int nr = 1; nr <= Ho; ++nr) {
-      const int nseg = (Ho + nr - 1) / nr;
-      const int ntr = (g.brem * nseg + per - 1) / per;
-      // a step costs the same whatever it computes; short segments also spend 2 of their nr + 2 row loads on halo
-      const long cost = (long)ntr * nr * 64 + (long)ntr * 2 * 8;
-      if (best < 0 || cost <= best) best = cost, g.nr = nr, g.nseg = nseg, g.ntr = ntr;
-    }
-  }
-  g.steps = g.nfull * Ho + g.ntr * g.nr;
-}
-
-// strip plan of the stride-1 forward / data gradient: 16 pixel-pair columns per wave
-inline Geom plan(int Hi, int Wi, int Ho, int Wo) {
-  Geom g;
-  g.Hi = Hi, g.Wi = Wi, g.Ho = Ho, g.Wo = Wo;
-  plan_units(g, Ho, (Wo + 1) / 2, 16);
-  return g;
-}
 
 // Winograd F(2,3) filter transform of one (row tap, cout, cin): x-taps g0 g1 g2 -> the four position weights
 __device__ __forceinline__ void filter_transform(float g0, float g1, float g2, float (&u)[4]) {
@@ -296,7 +258,7 @@ __device__ __forceinline__ void run_layer(const Geom& G, const Problem& P0, cons
           f32x4 yb = S.m[mt][1] - S.m[mt][2] - S.m[mt][3];
           if (MODE == MODE_FWD) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ya[r] = fmaxf(ya[r], 0.f), yb[r] = fmaxf(yb[r], 0.f);
+            for (int r = 0; r < 4; ++r) ya[r] = relu_keep_nan(ya[r]), yb[r] = relu_keep_nan(yb[r]);
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) ya[r] = mk[0][mt][r] > 0.f ? ya[r] : 0.f, yb[r] = mk[1][mt][r] > 0.f ? yb[r] : 0.f;

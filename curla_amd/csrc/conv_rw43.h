@@ -41,13 +41,7 @@ using rw::uniform_rsrc;
 
 constexpr int kWFloats = 3 * 6 * 2 * 2 * 256;  // transformed filter of one problem in LDS: [dy][pos][q][mt][kq][li][e]
 
-// strip plan: 16 pixel-QUAD columns per wave
-inline Geom plan(int Hi, int Wi, int Ho, int Wo) {
-  Geom g;
-  g.Hi = Hi, g.Wi = Wi, g.Ho = Ho, g.Wo = Wo;
-  rw::plan_units(g, Ho, (Wo + 3) / 4, 16);
-  return g;
-}
+// (strip plan, 16 pixel-QUAD columns per wave: rw43::plan, conv_plan.h)
 
 // (explicit fmaf / no contraction: the same weights must give the same bits whichever code path transforms them -- the
 // first or the second problem of a launch -- or a sample's result would depend on the launch it is computed in)
@@ -278,7 +272,7 @@ __device__ __forceinline__ void run_layer(const Geom& G, const Problem& P0, cons
           for (int p = 0; p < 4; ++p) {
             if (MODE == MODE_FWD) {
 #pragma unroll
-              for (int r = 0; r < 4; ++r) y[p][r] = fmaxf(y[p][r], 0.f);
+              for (int r = 0; r < 4; ++r) y[p][r] = relu_keep_nan(y[p][r]);
             } else {
 #pragma unroll
               for (int r = 0; r < 4; ++r) y[p][r] = mk[p][mt][r] > 0.f ? y[p][r] : 0.f;

@@ -32,13 +32,7 @@ struct WgradArgs {
   int two_d;        // Winograd in both directions (conv_rw_wgrad2.h)
 };
 
-// strips of 4 pair columns (one per lane group)
-inline Geom plan4(int Hi, int Wi, int Ho, int Wo) {
-  Geom g;
-  g.Hi = Hi, g.Wi = Wi, g.Ho = Ho, g.Wo = Wo;
-  plan_units(g, Ho, (Wo + 1) / 2, 4);
-  return g;
-}
+// (strips of 4 pair columns, one per lane group: rw::plan4, conv_plan.h)
 
 // gradient pair -> A operands of the four Winograd positions (g0, g0+g1, g0-g1, g1) and the bias-gradient sum, as ONE
 // opaque block: written as plain C++ the compiler's SLP vectoriser pairs these adds with the NEXT step's (packed

@@ -22,14 +22,7 @@
 
 namespace rw {
 
-// strips of 4 pair columns over the gradient image in units of ROW PAIRS (Geom::Ho = pair rows)
-inline Geom plan4p(int Hi, int Wi, int Ho, int Wo) {
-  Geom g;
-  g.Hi = Hi, g.Wi = Wi, g.Wo = Wo;
-  g.Ho = (Ho + 1) / 2;
-  plan_units(g, g.Ho, (Wo + 1) / 2, 4);
-  return g;
-}
+// (strips of 4 pair columns over the gradient image in units of ROW PAIRS, Geom::Ho = pair rows: rw::plan4p, conv_plan.h)
 
 struct Wg2Loads {
   f32x2 d[2][4];  // input rows 2s + 2, 2s + 3: window pixel c, (cin tile 0, cin tile 1)

@@ -49,8 +49,7 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kWBytes = 3 * 4 * 2 * 3 * 64 * 16;  // split filter of one problem in LDS: [dy][pos][mt][part][lane][8 bf16]
 
-// strip plan: 16 pixel-pair columns per wave (conv_rw.h's)
-inline Geom plan(int Hi, int Wi, int Ho, int Wo) { return rw::plan(Hi, Wi, Ho, Wo); }
+// (strip plan, 16 pixel-pair columns per wave as conv_rw.h: rwb::plan, conv_plan.h)
 
 struct B3 {
   u32x4 h, m, l;  // 8 bf16 each: element j in the low / high half of word j >> 1
@@ -253,7 +252,7 @@ __device__ __forceinline__ void run_layer(const Geom& G, const Problem& P0, cons
           f32x4 yb = S.m[mt][1] - S.m[mt][2] - S.m[mt][3];
           if (MODE == MODE_FWD) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ya[r] = fmaxf(ya[r], 0.f), yb[r] = fmaxf(yb[r], 0.f);
+            for (int r = 0; r < 4; ++r) ya[r] = relu_keep_nan(ya[r]), yb[r] = relu_keep_nan(yb[r]);
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) ya[r] = mk[0][mt][r] > 0.f ? ya[r] : 0.f, yb[r] = mk[1][mt][r] > 0.f ? yb[r] : 0.f;

@@ -31,6 +31,7 @@ def _report():
     with open("gpurun_out/kernel_parity.txt", "a") as f:
         for n, e in REPORT:
             f.write(f"{n:60s} {e:.3e}\n")
+    del REPORT[:]  # (other modules use check and this fixture too: each line is written once)
 
 
 @pytest.fixture(scope="module")
@@ -1151,9 +1152,9 @@ def test_conv_s1_backward_one_launch(ops, s1_impl, s1_wgrad, B, H, W):
     x = torch.relu(rnd(B, H, W, 32, seed=91)).cuda()
     g = rnd(B, H - 2, W - 2, 32, seed=92).cuda()
     w = (rnd(32, 32, 3, 3, seed=93) * 0.1).cuda()
-    ws1 = torch.zeros(ops.wgrad_workspace_floats(32), device="cuda")
-    ws2 = torch.zeros_like(ws1)
-    gin1, gin2 = torch.empty_like(x), torch.full_like(x, float("nan"))
+    ws1 = torch.full((ops.wgrad_workspace_floats(32),), float("nan"), device="cuda")  # (no slab may rest on what was there)
+    ws2 = torch.full_like(ws1, float("nan"))
+    gin1, gin2 = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
     n1 = ops.conv_s1_wgrad_slabs(x, g, ws1)
     ops.conv_s1_dgrad(g, w, x, gin1)
     n2 = ops.conv_s1_bwd_slabs(x, g, w, gin2, ws2)
@@ -1166,7 +1167,7 @@ def test_conv_s1_backward_one_launch(ops, s1_impl, s1_wgrad, B, H, W):
     else:
         check(f"bwd_slabs dW {B}x{H}x{W}", dw2.cpu(), dw1.cpu(), 2e-6)
         check(f"bwd_slabs db {B}x{H}x{W}", db2.cpu(), db1.cpu(), 2e-6)
-    ws3, gin3, dw3, db3 = torch.zeros_like(ws1), torch.empty_like(x), torch.empty_like(dw1), torch.empty_like(db1)
+    ws3, gin3, dw3, db3 = torch.full_like(ws1, float("nan")), torch.empty_like(x), torch.empty_like(dw1), torch.empty_like(db1)
     n3 = ops.conv_s1_bwd_slabs(x, g, w, gin3, ws3)
     ops.wgrad_reduce_multi([(ws3, n3, dw3, db3)])
     assert n3 == n2 and torch.equal(dw3, dw2) and torch.equal(db3, db2)  # run-to-run reproducible
@@ -1516,7 +1517,7 @@ def test_generic_filter_counts_against_pytorch(ops, nf):
     # weight gradient from each source, all slabs summed by ONE reduction launch
     g2d = nhwc(g2)
     g1 = torch.full((B, Ho, Wo, nf), float("nan"), device="cuda")
-    ws1 = torch.empty(ops.wgrad_workspace_floats(nf), device="cuda")
+    ws1 = torch.full((ops.wgrad_workspace_floats(nf),), float("nan"), device="cuda")
     n1 = ops.conv_s1_bwd_slabs(out1, g2d, d_w1, g1, ws1)
     a1d = a1.detach().clone().requires_grad_(True)
     torch.relu(F.conv2d(a1d, w1_, b1_)).backward(g2)
@@ -1525,7 +1526,7 @@ def test_generic_filter_counts_against_pytorch(ops, nf):
     ops.conv_s1_dgrad(g2d, d_w1, out1, gd)
     assert torch.equal(gd, g1)
     for name, o in srcs:
-        ws0 = torch.empty(ops.wgrad_workspace_floats(C), device="cuda")
+        ws0 = torch.full((ops.wgrad_workspace_floats(C),), float("nan"), device="cuda")
         n0 = ops.conv1_wgrad_slabs(o, g1, ws0, nf)
         dw0, db0 = torch.full((nf, C, 3, 3), float("nan"), device="cuda"), torch.full((nf,), float("nan"), device="cuda")
         dw1, db1 = torch.full((nf, nf, 3, 3), float("nan"), device="cuda"), torch.full((nf,), float("nan"), device="cuda")
