@@ -24,7 +24,7 @@ namespace {
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
 #include "tqc.h"           // tqc_critic_loss_kernel, tqc_actor_loss_kernel (truncated quantile critics)
 #include "curl_head.h"     // curl_head_kernel<NTILE>
-#include "optim.h"         // soft_update_kernel, soft_update2_kernel, adam_step_kernel<CLIP, DECAY>, adam_step2_kernel<CLIP, DECAY>
+#include "optim.h"         // soft_update_kernel, soft_update2_kernel, shrink_perturb2_kernel, adam_step_kernel<CLIP, DECAY>, adam_step2_kernel<CLIP, DECAY>
 #include "sample_stage.h"  // a minibatch's index block and scalars: sample_stage_kernel<HOST, NSTEP, POS>, pos_walk_kernel
 #include "ring.h"          // crop_nchw_kernel, store_frame_kernel, gather_stacks_kernel<FAST>, nhwc_to_nchw_kernel
 #include "per.h"           // prioritized replay: per_set's three phases, per_sample_kernel, per_td_kernel
@@ -671,6 +671,16 @@ int curla_soft_update2(const float* param, float* target, size_t n, size_t split
   CURLA_REQUIRE(param && target && n > 0 && split <= n);
   return launch(soft_update2_kernel, dim3(nblocks(n, 256)), 256, 0, static_cast<hipStream_t>(stream), param, target, n,
                 split, tau_a, one_minus_tau_a, tau_b, one_minus_tau_b);
+}
+
+int curla_shrink_perturb2(float* param, float* target, const float* fresh, size_t n, size_t split, float keep_a,
+                          float new_a, float keep_b, float new_b, void* stream) {
+  // (a NaN keep fails both comparisons; the pointers' low bits: floats)
+  CURLA_REQUIRE(float_pointers(param, fresh) && (reinterpret_cast<uintptr_t>(target) & 3) == 0 && n > 0 && split <= n &&
+                keep_a >= 0.f && keep_a <= 1.f && keep_b >= 0.f && keep_b <= 1.f);
+  const int vec = aligned16(param) && aligned16(fresh) && aligned16(target);  // (NULL counts as aligned: not accessed)
+  return launch(shrink_perturb2_kernel, dim3(nblocks(vec ? (n + 3) / 4 : n, 256, 8192)), 256, 0,
+                static_cast<hipStream_t>(stream), param, target, fresh, n, split, vec, keep_a, new_a, keep_b, new_b);
 }
 
 int curla_adam_step_lerp(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,

@@ -1,5 +1,5 @@
 // The optimiser step over the flat parameter buffers: the target networks' soft update (soft_update_kernel,
-// soft_update2_kernel) and Adam, one step or two back to back, with the float64 scalar and the target lerp that can
+// soft_update2_kernel), the shrink-and-perturb of a network reset (shrink_perturb2_kernel) and Adam, one step or two back to back, with the float64 scalar and the target lerp that can
 // ride along (adam_step_kernel, adam_step2_kernel), clipping by the global gradient norm (AdamClip) and decoupled weight
 // decay (decay_one: AdamW) included.
 // Included by heads.hip inside its anonymous namespace.
@@ -27,6 +27,76 @@ __global__ void soft_update2_kernel(const float* p, float* tgt, size_t n, size_t
 #pragma clang fp contract(off)
     const bool a = i < split;
     tgt[i] = (a ? tau_a : tau_b) * p[i] + (a ? omt_a : omt_b) * tgt[i];
+  }
+}
+
+// Shrink and perturb (network resets): p <- keep * p + new * fresh over one flat block whose first `split`
+// elements take (keep_a, new_a) and the rest (keep_b, new_b), soft_update2_kernel's range convention; the target copy
+// (tgt != nullptr) takes the same formula on its own old value with the same fresh value.
+//   0 < keep < 1 : two products and a sum, each rounding once (no fused multiply-add), as soft_update_kernel
+//   keep == 0    : p = fresh by SELECTION -- the old value is not read, so a NaN or Inf in it does not survive
+//   keep == 1    : the element is neither read nor written (a stored -0.0 stays -0.0), in either array
+// `keep` is uniform over a wave except in the one wave that straddles `split`.
+__device__ __forceinline__ void shrink_perturb_one(float* p, float* t, const float* f, float keep, float nw) {
+#pragma clang fp contract(off)
+  if (keep == 1.0f) return;
+  const float fr = *f;
+  if (keep == 0.0f) {
+    *p = fr;
+    if (t) *t = fr;
+    return;
+  }
+  *p = keep * *p + nw * fr;
+  if (t) *t = keep * *t + nw * fr;
+}
+
+// vec: p, tgt (when given) and fresh are 16-byte aligned -- 16-byte accesses over the whole float4s that lie on one side
+// of `split`, element by element in the one that straddles it and in the tail; else element by element throughout.
+__global__ void __launch_bounds__(256) shrink_perturb2_kernel(float* p, float* tgt, const float* fresh, size_t n,
+                                                              size_t split, int vec, float keep_a, float new_a,
+                                                              float keep_b, float new_b) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (vec) {
+    const size_t n4 = n >> 2;
+    for (size_t i = tid; i < n4; i += stride) {
+      const size_t base = i << 2;
+      if (base < split && base + 4 > split) {  // the one float4 with elements on both sides
+        for (int e = 0; e < 4; ++e) {
+          const bool a = base + e < split;
+          shrink_perturb_one(p + base + e, tgt ? tgt + base + e : nullptr, fresh + base + e, a ? keep_a : keep_b,
+                             a ? new_a : new_b);
+        }
+        continue;
+      }
+      const bool a = base < split;
+      const float keep = a ? keep_a : keep_b, nw = a ? new_a : new_b;
+      if (keep == 1.0f) continue;
+      const f32x4 ff = reinterpret_cast<const f32x4*>(fresh)[i];
+      if (keep == 0.0f) {
+        reinterpret_cast<f32x4*>(p)[i] = ff;
+        if (tgt) reinterpret_cast<f32x4*>(tgt)[i] = ff;
+        continue;
+      }
+      {
+#pragma clang fp contract(off)
+        f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pp[e] = keep * pp[e] + nw * ff[e];
+        reinterpret_cast<f32x4*>(p)[i] = pp;
+        if (tgt) {
+          f32x4 tt = reinterpret_cast<f32x4*>(tgt)[i];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) tt[e] = keep * tt[e] + nw * ff[e];
+          reinterpret_cast<f32x4*>(tgt)[i] = tt;
+        }
+      }
+    }
+    done = n4 << 2;
+  }
+  for (size_t i = done + tid; i < n; i += stride) {
+    const bool a = i < split;
+    shrink_perturb_one(p + i, tgt ? tgt + i : nullptr, fresh + i, a ? keep_a : keep_b, a ? new_a : new_b);
   }
 }
 

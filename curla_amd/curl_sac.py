@@ -30,6 +30,7 @@ from . import ops
 from .agent_acting import _ActingMixin
 from .agent_dp import _DataParallelMixin
 from .agent_graphs import _NullLog, _UpdateGraphsMixin
+from .agent_reset import _check_reset_interval, _check_reset_keep, _check_reset_seed, _ResetMixin
 from .encoder import CNNEncoder
 from .mlp import _Mlp, _MlpLn, _linears, _mlp_bwd, _mlp_fwd  # noqa: F401
 from .networks import (CURL, LOG_FREQ, Actor, Critic, QFunction, _check_drop_quantiles,  # noqa: F401
@@ -122,9 +123,13 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, critic_quantiles=0, critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1,
-                 critic_dropout=0.0, critic_layer_norm=False, **kwargs):
+    def __call__(cls, *args, reset_interval=0, reset_encoder_keep=1.0, reset_seed=0, critic_quantiles=0,
+                 critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0, critic_layer_norm=False,
+                 **kwargs):
         agent = cls.__new__(cls)
+        agent.reset_interval = _check_reset_interval(reset_interval)
+        agent.reset_encoder_keep = _check_reset_keep(reset_encoder_keep)
+        agent.reset_seed = _check_reset_seed(reset_seed)
         agent.critic_quantiles = _check_quantiles(critic_quantiles)
         agent.critic_drop_quantiles = _check_drop_quantiles(critic_drop_quantiles, agent.critic_quantiles)
         agent.critic_layer_norm = bool(critic_layer_norm)
@@ -137,7 +142,7 @@ class _AgentType(type):
         return agent
 
 
-class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, metaclass=_AgentType):
+class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetMixin, metaclass=_AgentType):
     """CURL representation learning with SAC (curl_sac.py:224-465).
     ``CurlSacAgent(..., critic_layer_norm=True)`` (a keyword of the class call, not in the reference; default off:
     nothing changes): an ``nn.LayerNorm(hidden_dim)`` between each hidden Linear of the Q functions and its ReLU, critic
@@ -155,7 +160,11 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, metacla
     M quantile atoms, the two target networks' atoms are pooled and sorted, the ``critic_drop_quantiles=d`` largest per
     network dropped (0 <= d < M) and every online atom regressed on the kept ones with the quantile Huber loss; the
     actor ascends the mean of all atoms.  M shapes the networks; d is an attribute that may be edited
-    between calls.  Not with a prioritized replay buffer."""
+    between calls.  Not with a prioritized replay buffer.
+    ``reset_interval=N`` (default 0: nothing changes): every N steps ``update()`` first calls ``reset_networks()`` -- the
+    heads re-initialised, the encoder shrunk and perturbed with ``reset_encoder_keep`` (default 1.0: kept as it is), the
+    optimizers started over --, the fresh values drawn from a stream of the agent's own seeded by ``reset_seed``
+    (agent_reset.py).  The first two are attributes that may be edited between calls."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
@@ -216,6 +225,10 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, metacla
         self.pixel_sac = pixel_sac
         self.action_dim = action_shape[0]
         self.hidden_dim = hidden_dim
+        # what reset_networks() builds fresh networks from, and puts log_alpha back to
+        self._net_args = (tuple(obs_shape), tuple(action_shape), hidden_dim, encoder_feature_dim, actor_log_std_min,
+                          actor_log_std_max, num_layers, num_filters)
+        self._init_log_alpha = float(np.log(init_temperature))
 
         # same construction order as the reference => same RNG stream => same init for a given seed
         self.actor = Actor(obs_shape, action_shape, hidden_dim, encoder_feature_dim, actor_log_std_min,
@@ -959,6 +972,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, metacla
         refused with G > 1."""
         self._restore_grad_views()
         self._check_n_step(replay_buffer)
+        self._maybe_reset(step)  # (reset_interval: in front of every sub-step, graphed or not)
         if self.utd_ratio != 1 or type(self.utd_ratio) is not int:  # (the attribute may have been edited)
             if _check_utd_ratio(self.utd_ratio) > 1 and noise is not None and not only_cpc:
                 raise ValueError("update(noise=...) stands for the draws of one minibatch: not with utd_ratio = %d"
@@ -1115,6 +1129,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, metacla
             "optimizers": {k: self._convert_opt_state(o, o.state_dict(), True) for k, o in self._optimizers().items()},
             "rng": rng, "critic_dropout": float(self.critic_dropout), "utd_ratio": int(self.utd_ratio),
             "critic_quantiles": int(self.critic_quantiles), "critic_drop_quantiles": int(self.critic_drop_quantiles),
+            **self._reset_checkpoint(),
         }, path)
 
     def load_checkpoint(self, path, restore_rng=True):
@@ -1145,6 +1160,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, metacla
             np.random.set_state(ck["rng"]["numpy"])
             if self.device.type == "cuda" and "cuda" in ck["rng"]:
                 torch.cuda.set_rng_state(ck["rng"]["cuda"], self.device)
+        self._load_reset_checkpoint(ck)
         self._anchor_cache = None
         # captured graphs hold the addresses of log_alpha's Adam moments, which load_state_dict has just replaced
         self._drop_graphs()

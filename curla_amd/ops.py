@@ -708,6 +708,15 @@ def soft_update2(param_flat, target_flat, split, tau_a, tau_b):
          float(1 - tau_a), float(tau_b), float(1 - tau_b), stream())
 
 
+def shrink_perturb2(param_flat, target_flat, fresh_flat, split, keep_a, keep_b):
+    """``p <- keep * p + (1 - keep) * fresh`` over a flat block whose first ``split`` elements use keep_a and the rest
+    keep_b; ``target_flat`` (or None) takes the same on its own values.  keep 0 copies ``fresh``, keep 1 touches nothing
+    (curla_hip.h); 1 - keep is formed in double and rounded to fp32 once, as soft_update2 forms 1 - tau."""
+    assert fresh_flat.numel() == param_flat.numel() and (target_flat is None or target_flat.numel() == param_flat.numel())
+    call("curla_shrink_perturb2", ptr(param_flat), ptr(target_flat), ptr(fresh_flat), param_flat.numel(), int(split),
+         float(keep_a), 1.0 - float(keep_a), float(keep_b), 1.0 - float(keep_b), stream())
+
+
 def gather_transition_scalars(sc, idx, B, A, act, rew, nd):
     call("curla_gather_transition_scalars", ptr(sc), ptr(idx), B, A, ptr(act), ptr(rew), ptr(nd), stream())
 

@@ -158,6 +158,20 @@ class FlatAdam(torch.optim.Adam):
                 self._steps[i] = int(round(float(st["step"])))
                 st["step"] = torch.tensor(float(self._steps[i]), dtype=torch.float32)
 
+    @torch.no_grad()
+    def reset_state(self):
+        """Back to the state of a newly built optimizer without giving up an address (CurlSacAgent.reset_networks): the
+        moment mirrors are FILLED with zeros in place on the current stream -- a fill, not a multiply: a NaN does not
+        survive, and a captured graph keeps reading the same buffers --, every step count is 0, the launch plans stay.
+        Parameters that have state keep its entries (views of the mirrors), with ``step`` 0."""
+        self._m.zero_()
+        self._v.zero_()
+        self._steps = [0] * len(self._plist)
+        for p in self._plist:
+            st = self.state.get(p)
+            if st:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+
     # -- captured graphs: the step-dependent factors as data ------------------------------------------------------
     def live_indices(self, live=None):
         """Indices of the parameters a step touches: ``live`` (an iterable of Parameters) or all of them."""

@@ -484,6 +484,17 @@ int curla_soft_update(const float* param, float* target, size_t n, float tau, fl
  * curl_sac.py:442-445) */
 int curla_soft_update2(const float* param, float* target, size_t n, size_t split, float tau_a, float one_minus_tau_a,
                        float tau_b, float one_minus_tau_b, void* stream);
+/* Shrink and perturb for network resets (Nikishin et al. 2022; D'Oro et al. 2023): one flat block with
+ * curla_soft_update2's range convention -- elements [0, split) use (keep_a, new_a), [split, n) (keep_b, new_b).
+ *   0 < keep < 1 : param[i] = keep * param[i] + new * fresh[i], the two products and the sum rounding once each (no
+ *                  fused multiply-add); target[i] (target may be NULL) the same formula on its own old value
+ *   keep == 0    : param[i] = target[i] = fresh[i] by selection: the old values are not read (a NaN does not survive)
+ *   keep == 1    : the element is neither read nor written, in either array
+ * The caller forms new = (float)(1 - keep) in double.  16-byte accesses when param, target and fresh are 16-byte
+ * aligned, element-wise otherwise.  CURLA_ERR_ARG: a NULL param or fresh, n == 0, split > n, a keep outside [0, 1] or
+ * NaN.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_shrink_perturb2(float* param, float* target, const float* fresh, size_t n, size_t split, float keep_a,
+                          float new_a, float keep_b, float new_b, void* stream);
 
 /* One torch.optim.Adam step (weight_decay 0, amsgrad off; the reference's five optimizers, curl_sac.py:299-313) over a
  * flat run of n fp32 parameters with their gradient and moment runs: replaces torch's multi-tensor Adam launches
