@@ -55,6 +55,7 @@ int g_ablate = 0;
 #endif
 
 #include "conv_rw.h"
+#include "conv1_plan.h"  // (host-only: the first layer's plans; after conv_plan.h, which conv_rw.h includes)
 
 // Row-walk kernels (conv_rw.h).  Forward: 512-thread workgroups, ONE per CU, persistent over the samples they own;
 // 96 KB of LDS hold the transformed filters of both problems of a layer, so the eight waves draw their steps from one
@@ -195,7 +196,8 @@ __global__ __launch_bounds__(512, 2) void wgrad1_rw_kernel(rw::Wgrad1Args a) {
 
 // workgroup shape of the uint8 row-walk forward: two 512-thread workgroups per CU (4 waves per SIMD).  Five 256-thread
 // ones (5 waves per SIMD, what ~100 VGPRs allow) were slower inside update(): 402 against 407 update()/s
-constexpr int kC1U8Threads = 512, kC1U8PerCU = 2;
+using conv1::kC1U8PerCU;
+using conv1::kC1U8Threads;
 
 // first layer straight from the uint8 ring in row-walk form (conv1_u8_rw.h): 512-thread workgroups, two per CU, equal
 // shares of the pool of steps of both minibatches (the second with its own weights: both images sit in LDS)
@@ -215,7 +217,8 @@ __global__ __launch_bounds__(kC1U8Threads, kC1U8PerCU) void conv1_u8_rw_fwd_kern
 
 // ... and on the bf16 matrix cores (uint8 pixels are exact in bf16: one part for the pixels, three for the weights; C <= 10).
 // The weight fragments take 72 registers (148 in all): three 256-thread workgroups per CU (3 waves per SIMD)
-constexpr int kC1U8bThreads = 256, kC1U8bPerCU = 3;
+using conv1::kC1U8bPerCU;
+using conv1::kC1U8bThreads;
 template <int C>
 __global__ __launch_bounds__(kC1U8bThreads, kC1U8bPerCU) void conv1_u8_rwb_fwd_kernel(rw::Conv1U8Args a) {
   __shared__ __attribute__((aligned(16))) unsigned char lds_imgb[2 * rw::kConv1U8B3ImageBytes];
@@ -355,15 +358,11 @@ BwdShape select_bwd_shape(S1Form dgrad, int B, int Ho, int Wo) {
 enum class S1WgradForm { X, XY };
 S1WgradForm select_s1_wgrad_form() { return curla_opt(kOptS1Wgrad) == kS1WgradX ? S1WgradForm::X : S1WgradForm::XY; }
 
-// bytes of a crop row kept as bytes in LDS (conv1_row_bytes of conv1_band.h) / floats of one kept as floats
-// (conv1_row_stride), and the tallest band of 2 th + 1 byte rows within `budget` bytes
-int u8_row_bytes(int Wc, int C) { return ((Wc * C + 15) & ~15) + 16; }
-int f32_row_floats(int Wc, int C) { return ((Wc * C + 3) & ~3) + 4; }
-int u8_band_rows(int Ho, int RSb, size_t budget) {
-  int th = Ho;
-  while (th > 1 && (size_t)(2 * th + 1) * RSb > budget) --th;
-  return th;
-}
+// (the arithmetic of the first layer's plans and form choices is host-only code, conv1_plan.h: the functions below read
+// the options and the CU count and hand them over)
+using conv1::Conv1F32Form;
+using conv1::Conv1U8Form;
+using conv1::Wgrad1U8Form;
 
 // First-layer forward from the uint8 ring (option conv1_u8).  Rw = the LDS-free row walk (conv1_u8_rw.h) and Rwb = the same
 // on the bf16 matrix cores, where an input row's 3 C operand bytes are one k-step of 32; Hybrid = conv1_u8_walk_kernel
@@ -377,24 +376,14 @@ int u8_band_rows(int Ho, int RSb, size_t budget) {
 //   A shape beyond the row walk's index limits, and hybrid / band, take Hybrid where the whole crop is one band of LDS
 //   that leaves room for two workgroups per CU and a row is at most 64 16-byte runs (its staging gives a lane one run of
 //   a row) -- unless the option says band; else Band.
-enum class Conv1U8Form { Rwb, Rw, Hybrid, Band };
-constexpr size_t kConv1U8BandBudget = 76 * 1024;
 Conv1U8Form select_conv1_u8_form(int C, int Hs, int Ws, int Wc, int Btotal, int Ho, int Wo) {
-  const int opt = curla_opt(kOptConv1U8);
-  const bool walk_asked = opt == kConv1U8Auto || opt == kConv1U8Rw || opt == kConv1U8Rwb;
-  const bool walk_fits =
-      (long long)Hs * Ws * C < (1LL << 30) && (long long)Btotal * Ho * ((Wo + 15) / 16 + 1) < (1LL << 28);
-  if (walk_asked && walk_fits) return opt != kConv1U8Rw && 3 * C <= 32 ? Conv1U8Form::Rwb : Conv1U8Form::Rw;
-  const bool one_band = u8_band_rows(Ho, u8_row_bytes(Wc, C), kConv1U8BandBudget) == Ho;
-  return one_band && Wc * C <= 64 * 16 && opt != kConv1U8Band ? Conv1U8Form::Hybrid : Conv1U8Form::Band;
+  return conv1::select_conv1_u8_form(curla_opt(kOptConv1U8), C, Hs, Ws, Wc, Btotal, Ho, Wo);
 }
 
 // First layer and its weight gradient from a float tensor (option conv1_f32): the row walk with nothing staged
 // (conv1_rw.h) for NHWC minibatches within its 30-bit byte offsets, else the banded kernels.
-enum class Conv1F32Form { Rw, Band };
 Conv1F32Form select_conv1_f32_form(int src_kind, int C, int Hc, int Wc) {
-  const bool rw = src_kind == kSrcF32Nhwc && curla_opt(kOptConv1F32) == kConv1F32Rw && (long long)Hc * Wc * C * 4 < (1LL << 30);
-  return rw ? Conv1F32Form::Rw : Conv1F32Form::Band;
+  return conv1::select_conv1_f32_form(curla_opt(kOptConv1F32), src_kind == kSrcF32Nhwc, C, Hc, Wc);
 }
 
 // First-layer weight gradient from the uint8 ring, input band kept as bytes (option wgrad1_u8).  B16 = the
@@ -403,11 +392,8 @@ Conv1F32Form select_conv1_f32_form(int src_kind, int C, int Hc, int Wc) {
 // MFMA (wgrad1_u8_kernel), two 512-thread workgroups per CU.  F32FourWave (CURLA_ABLATE builds only) = four 256-thread
 // ones: measured at 84x84x9, B = 512, 77.4 us against the 71.9 us of two 512-thread workgroups -- the shorter bands'
 // extra halo rows and slabs cost more than the finer interleaving buys.
-enum class Wgrad1U8Form { B16, F32, F32FourWave };
-constexpr size_t kWgrad1U8BandBudget = 76 * 1024, kWgrad1U8BandBudget4 = 38 * 1024;
 Wgrad1U8Form select_wgrad1_u8_form(int C, int Wc, int Wo) {
-  if ((ABL_HOST & 1024) && (size_t)(2 * 4 + 1) * u8_row_bytes(Wc, C) <= kWgrad1U8BandBudget4) return Wgrad1U8Form::F32FourWave;
-  return curla_opt(kOptWgrad1U8) != kWgrad1U8F32 && Wo >= 8 && 3 * C <= 32 ? Wgrad1U8Form::B16 : Wgrad1U8Form::F32;
+  return conv1::select_wgrad1_u8_form(curla_opt(kOptWgrad1U8), (ABL_HOST & 1024) != 0, C, Wc, Wo);
 }
 
 // ------------------------------ host side: stride-1 layers ------------------------------
@@ -488,66 +474,28 @@ rw::WgradArgs wgrad_args(const float* in, const float* g, float* workspace, int 
 }
 
 // ------------------------------ host side: first layer, banded forms ------------------------------
+// band height of the float banded kernels within `lds_budget` (conv1_plan.h)
 int plan_band_conv1(int Ho, int Wo, int Wc, int C, int g_px_per_row, size_t lds_budget) {
-  const int RS = f32_row_floats(Wc, C);
-  int best = 1;
-  double best_eff = -1.0;
-  for (int th = 1; th <= Ho; ++th) {
-    const size_t bytes = ((size_t)(2 * th + 1) * RS + (size_t)g_px_per_row * th * kLdsPix) * sizeof(float);
-    if (bytes > lds_budget) break;
-    const int nb = (Ho + th - 1) / th;
-    double work = 0, slots = 0;
-    for (int bnd = 0; bnd < nb; ++bnd) {
-      const int tha = (bnd == nb - 1) ? Ho - bnd * th : th;
-      const int tiles = (tha * Wo + 15) / 16;
-      work += tha * Wo / 16.0;
-      slots += ((tiles + 7) / 8) * 8;
-    }
-    const double eff = work / slots * (2.0 * th) / (2.0 * th + 1 + 2);
-    if (eff > best_eff) best_eff = eff, best = th;
-  }
-  return best;
-}
-
-// near-equal bands of 2 th + 1 byte rows within `budget`: th and nbands of a banded uint8 kernel
-template <typename A>
-void plan_u8_bands(A& a, int RSb, size_t budget) {
-  const int th = u8_band_rows(a.Ho, RSb, budget);
-  a.nbands = (a.Ho + th - 1) / th;
-  a.th = (a.Ho + a.nbands - 1) / a.nbands;
+  return conv1::plan_band_conv1(Ho, Wo, Wc, C, g_px_per_row, lds_budget, kLdsPix);
 }
 
 // Conv1U8Form::Hybrid / Band: the band stays bytes in LDS, the tallest that leaves room for two workgroups per CU; the
 // same bytes first hold the kernels' k-major weight image.  Fills a.th / a.nbands, returns the LDS bytes of the launch.
 size_t plan_conv1_u8_band(Conv1Args& a) {
-  const int RSb = u8_row_bytes(a.Wc, a.C);
-  plan_u8_bands(a, RSb, kConv1U8BandBudget);
-  const size_t weights = (size_t)3 * ((3 * a.C + 3) & ~3) * 32 * sizeof(float);
-  return std::max<size_t>((size_t)(2 * a.th + 1) * RSb + 32, weights);
+  const conv1::Bands b = conv1::plan_u8_bands(a.Ho, conv1::u8_row_bytes(a.Wc, a.C), conv1::kConv1U8BandBudget);
+  a.th = b.th, a.nbands = b.nbands;
+  return conv1::conv1_u8_band_lds(a.th, a.Wc, a.C);
 }
 
 // The uint8 weight gradient's bands (two 512-thread workgroups per CU of <= 76 KB of LDS each; F32FourWave: four
 // 256-thread ones of <= 38 KB) and the LDS of its final cross-wave sum.  Fills a.th / a.nbands / a.lds_bytes, returns the
 // LDS bytes of the launch.
 size_t plan_wgrad1_u8(Wgrad1Args& a, Wgrad1U8Form form) {
-  const int C = a.C, nwaves = form == Wgrad1U8Form::F32FourWave ? 4 : 8;
-  const int RSb = u8_row_bytes(a.Wc, C);
-  plan_u8_bands(a, RSb, nwaves == 4 ? kWgrad1U8BandBudget4 : kWgrad1U8BandBudget);
-  size_t lds = (((size_t)(2 * a.th + 1) * RSb + 15) & ~(size_t)15) + 32;
-  lds = std::max<size_t>(lds, (size_t)(32 * C * 9 + 32) * sizeof(float));  // the slab
-  lds = std::max<size_t>(lds, (size_t)nwaves * 1024);                      // the final cross-wave sum: one tile of every wave
-  // ... and all of a wave's tiles at once (ONE pass of the sum: 48.3 -> 44.8 us at 84x84x9) where two workgroups of that
-  // size still share a CU
-  if (nwaves == 8) {
-    const int k9 = 9 * C, ntiles = 2 * ((k9 % 16 == 1) ? k9 / 16 : (k9 + 15) / 16);
-    const size_t one_pass = (size_t)ntiles * nwaves * 1024;
-    if (one_pass <= 80 * 1024) lds = std::max<size_t>(lds, one_pass);
-  }
-  if (form == Wgrad1U8Form::B16) {
-    const int ntd = (3 * C + 15) / 16;
-    const size_t one_pass = (size_t)(2 * 3 * ntd) * nwaves * 1024;
-    if (one_pass <= 80 * 1024) lds = std::max<size_t>(lds, one_pass);
-  }
+  const int nwaves = form == Wgrad1U8Form::F32FourWave ? 4 : 8;
+  const conv1::Bands b = conv1::plan_u8_bands(a.Ho, conv1::u8_row_bytes(a.Wc, a.C),
+                                              nwaves == 4 ? conv1::kWgrad1U8BandBudget4 : conv1::kWgrad1U8BandBudget);
+  a.th = b.th, a.nbands = b.nbands;
+  const size_t lds = conv1::wgrad1_u8_lds(a.th, a.Wc, a.C, nwaves, form == Wgrad1U8Form::B16);
   a.lds_bytes = (unsigned)lds;
   return lds;
 }
@@ -714,14 +662,11 @@ static int launch_conv1_u8_rw(Conv1U8Form form, const Conv1Args& a, hipStream_t 
   ra.g.Hi = a.Hc, ra.g.Wi = a.Wc, ra.g.Ho = a.Ho, ra.g.Wo = a.Wo;
   rw::plan_units(ra.g, a.Ho, a.Wo, 16);
   // kC1U8PerCU (bf16: kC1U8bPerCU) workgroups per CU; fewer when a workgroup's share of the pool of steps would drop
-  // below 8 steps per wave
+  // below 8 steps per wave (conv1_plan.h)
   const long long pool = (long long)(a.B + a.B2) * ra.g.steps;
   const bool b16 = form == Conv1U8Form::Rwb;
   const int threads = b16 ? kC1U8bThreads : kC1U8Threads;
-  const int cap = (b16 ? kC1U8bPerCU : kC1U8PerCU) * curla_cu_count();
-  const int share = 8 * (threads / 64);
-  const int want = (int)((pool + share - 1) / share);
-  const int grid = want < cap ? (want < 1 ? 1 : want) : cap;
+  const int grid = conv1::conv1_u8_rw_grid(pool, threads, b16 ? kC1U8bPerCU : kC1U8PerCU, curla_cu_count());
   if (b16)
     return dispatch_int<9, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_rwb_fwd_kernel<cc()>, grid, threads, 0, st, ra); });
   return dispatch_int<9, 12, 6, 3>(a.C, [&](auto cc) { return launch(conv1_u8_rw_fwd_kernel<cc()>, grid, threads, 0, st, ra); });
@@ -754,10 +699,9 @@ static int launch_conv1_rw(const Conv1Args& a, hipStream_t st) {
 // any source, band staged as floats in LDS (Conv1F32Form::Band): two workgroups per CU so one stages while the other
 // computes
 static int launch_conv1_band(int src_kind, Conv1Args& a, hipStream_t st) {
-  a.th = plan_band_conv1(a.Ho, a.Wo, a.Wc, a.C, 0, 76 * 1024);
+  a.th = plan_band_conv1(a.Ho, a.Wo, a.Wc, a.C, 0, conv1::kConv1F32BandBudget);
   a.nbands = (a.Ho + a.th - 1) / a.th;
-  const size_t lds = std::max<size_t>(((size_t)(2 * a.th + 1) * f32_row_floats(a.Wc, a.C) + 8) * sizeof(float),
-                              (size_t)32 * a.C * 9 * sizeof(float));
+  const size_t lds = conv1::f32_band_lds(a.th, a.Wc, a.C, conv1::conv1_weight_image_bytes(a.C));
   const int grid = std::min(a.B * a.nbands, 2 * curla_cu_count());
   return dispatch_int<9, 12, 6, 3>(a.C, [&](auto cc) {
     return dispatch_src(src_kind, [&](auto src) { return launch(conv1_fwd_kernel<src(), cc()>, grid, 512, lds, st, a); });
@@ -919,7 +863,7 @@ static int launch_wgrad1(const void* src, int src_kind, const int64_t* idx, cons
   a.scale = scale;
   a.lds_bytes = 0;
   a.dbg = ABL_HOST;
-  const size_t slab_bytes = (size_t)(32 * C * 9 + 32) * sizeof(float);
+  const size_t slab_bytes = conv1::wgrad1_slab_bytes(C);
   int& grid = *nslabs;  // one slab per workgroup
   if (src_kind == kSrcU8Ring && !(ABL_HOST & 256)) {
     // uint8 ring, input band kept as bytes
@@ -946,9 +890,9 @@ static int launch_wgrad1(const void* src, int src_kind, const int64_t* idx, cons
     return dispatch_int<12, 9, 6, 3>(C, [&](auto cc) { return launch(wgrad1_rw_kernel<cc()>, grid, 512, slab_bytes, st, ra); });
   }
   // any source, band staged as floats in LDS: input rows only, one workgroup per CU
-  a.th = plan_band_conv1(a.Ho, a.Wo, Wc, C, 0, 150 * 1024);
+  a.th = plan_band_conv1(a.Ho, a.Wo, Wc, C, 0, conv1::kWgrad1F32BandBudget);
   a.nbands = (a.Ho + a.th - 1) / a.th;
-  const size_t lds = std::max<size_t>(((size_t)(2 * a.th + 1) * f32_row_floats(Wc, C) + 8) * sizeof(float), slab_bytes);
+  const size_t lds = conv1::f32_band_lds(a.th, Wc, C, slab_bytes);
   grid = std::min(B * a.nbands, curla_cu_count());
   return dispatch_int<9, 12, 6, 3>(C, [&](auto cc) {
     return dispatch_src(src_kind, [&](auto s) { return launch(wgrad1_kernel<s(), cc()>, grid, 512, lds, st, a); });

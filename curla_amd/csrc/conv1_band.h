@@ -166,8 +166,14 @@ __global__ __launch_bounds__(512) void conv1_fwd_kernel(Conv1Args a) {
       f32x4 acc[2] = {bias4[0], bias4[1]};  // bias through the accumulators' initial values
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        acc[0] = mfma16(wr[s][0], bv[s], acc[0]);
-        acc[1] = mfma16(wr[s][1], bv[s], acc[1]);
+        float v = bv[s];
+        // the last k-step of a tap row reaches past the window's 3 C floats into the NEXT pixel's first channels (the
+        // zeroed slack at the row's end): their weight is zero, but 0 x NaN (or Inf) is NaN -- in an output whose
+        // window does not hold that pixel.  (Selected where it is used: in front of the loop it made the first MFMA wait
+        // for the last read.)
+        if (KR > 3 * C && s % KQ == KQ - 1) v = 4 * (KQ - 1) + kq >= 3 * C ? 0.f : v;
+        acc[0] = mfma16(wr[s][0], v, acc[0]);
+        acc[1] = mfma16(wr[s][1], v, acc[1]);
       }
       if (pv) {
         float* o = out_item + (__mul24(ty, a.Wo) + x) * 32;
@@ -175,7 +181,7 @@ __global__ __launch_bounds__(512) void conv1_fwd_kernel(Conv1Args a) {
         for (int mt = 0; mt < 2; ++mt) {
           f32x4 v = acc[mt];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+          for (int r = 0; r < 4; ++r) v[r] = relu_keep_nan(v[r]);
           act_store(reinterpret_cast<f32x4*>(o + mt * 16), v);
         }
       }
@@ -435,7 +441,7 @@ __global__ __launch_bounds__(512) void conv1_fwd_u8_kernel(Conv1Args a) {
       for (int mt = 0; mt < 2; ++mt) {
         f32x4 v = acc[mt];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+        for (int r = 0; r < 4; ++r) v[r] = relu_keep_nan(v[r]);
         act_store(reinterpret_cast<f32x4*>(a.out + g + mt * 16), v);
       }
     }
@@ -578,7 +584,7 @@ __global__ __launch_bounds__(512, 2) void conv1_u8_walk_kernel(Conv1Args a, rw::
       for (int mt = 0; mt < 2; ++mt) {
         f32x4 v = acc[mt];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = rw::relu_bits(v[r]);
+        for (int r = 0; r < 4; ++r) v[r] = relu_keep_nan(v[r]);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), rout,
                                                vo + mt * 64u, 0, CURLA_ACT_STORE_POLICY);
       }

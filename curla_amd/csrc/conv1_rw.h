@@ -14,13 +14,8 @@
 
 namespace rw {
 
-// ReLU as one integer max on the bit pattern (positive floats order like their bits, everything with the sign bit set
-// is a negative integer): fmaxf(x, 0) costs two instructions on an MFMA result, which is not known to be canonical --
-// IEEE mode makes the compiler quiet it first (v_max_f32 x, x, x)
-__device__ __forceinline__ float relu_bits(float x) {
-  const int b = __builtin_bit_cast(int, x);
-  return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
+// (ReLU of the first-layer forwards: relu_keep_nan, common.h -- one instruction on an MFMA result like the integer max
+// on the bit pattern these kernels used, which turned a NaN with its sign bit set into 0)
 
 struct Conv1Args {
   const float* src;   // [B][Hc][Wc][C] float NHWC in [0, 255]
@@ -90,7 +85,10 @@ __device__ __forceinline__ void conv1_body(const Conv1Args& a, const int bid, co
       // the lane group's E values of input row 2 Y + r: ((2 Y + r) Wc + 2x) C + E kq floats into the sample; the lane's own
       // first row is part of its offset (lanes of a remainder strip start at different rows), r advances through the
       // (wave-uniform) scalar offset; a lane without a column and rows past the image are out of range (zeros, nothing stored)
-      const unsigned vin = lane_on ? (unsigned)(((2 * Y * a.Wc + 2 * x) * C + E * kq) * 4) : 0x80000000u;
+      // (C = 3: the last lane group's whole run lies past the window's 3 C floats -- the next pixel, under zero weights;
+      // 0 x NaN is NaN, so it reads out of range, i.e. zeros, like a lane without a column)
+      const bool reads = lane_on && E * kq < 3 * C;
+      const unsigned vin = reads ? (unsigned)(((2 * Y * a.Wc + 2 * x) * C + E * kq) * 4) : 0x80000000u;
       unsigned vo = lane_on ? (unsigned)((Y * a.Wo + x) * 128 + kq * 16) : 0x80000000u;
 
       struct Row {
@@ -114,7 +112,13 @@ __device__ __forceinline__ void conv1_body(const Conv1Args& a, const int bid, co
           const Row& R = dy == 0 ? r0 : dy == 1 ? r1 : r2;
 #pragma unroll
           for (int e = 0; e < E; ++e) {
-            const float v = R.v[e >> 2][e & 3];
+            float v = R.v[e >> 2][e & 3];
+            // the last lane group's values past the window's 3 C floats are the NEXT pixel's first channels: their
+            // weight is zero, but 0 x NaN (or Inf) is NaN -- in an output whose window does not hold that pixel
+            // (C = 6, 9: part of its run; C = 3 reads nothing, above; C = 12 has no such values)
+            if constexpr (4 * E > 3 * C && 3 * E < 3 * C) {
+              if (3 * E + e >= 3 * C) v = kq == 3 ? 0.f : v;
+            }
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
               acc[mt] = mfma16(wr[dy][e][mt], v, (dy == 0 && e == 0) ? bias4[mt] : acc[mt]);
@@ -125,7 +129,7 @@ __device__ __forceinline__ void conv1_body(const Conv1Args& a, const int bid, co
         for (int mt = 0; mt < 2; ++mt) {
           f32x4 v = acc[mt];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = relu_bits(v[r]);
+          for (int r = 0; r < 4; ++r) v[r] = relu_keep_nan(v[r]);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), rout,
                                                  vo + mt * 64u, 0, CURLA_ACT_STORE_POLICY);
         }

@@ -246,7 +246,7 @@ __device__ __forceinline__ void conv1_u8_body(const Conv1U8Args& a, const float*
         for (int mt = 0; mt < 2; ++mt) {
           f32x4 v = acc[mt];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = relu_bits(v[r]);
+          for (int r = 0; r < 4; ++r) v[r] = relu_keep_nan(v[r]);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), rout,
                                                  vo + mt * 64u, 0, CURLA_ACT_STORE_POLICY);
         }
@@ -469,7 +469,7 @@ __device__ __forceinline__ void conv1_u8b_body(const Conv1U8Args& a, const unsig
         for (int mt = 0; mt < 2; ++mt) {
           f32x4 v = acc[mt];
 #pragma unroll
-          for (int rr = 0; rr < 4; ++rr) v[rr] = relu_bits(v[rr]);
+          for (int rr = 0; rr < 4; ++rr) v[rr] = relu_keep_nan(v[rr]);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), rout, vo + mt * 64u, 0, CURLA_ACT_STORE_POLICY);
         }
         vo += out_row;
