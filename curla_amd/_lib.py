@@ -68,6 +68,9 @@ SIGNATURES = {
     "curla_critic_td_loss": [vp, vp, c_ll, vp, vp, vp, vp, c_float, c_int, vp, vp, vp, vp],
     "curla_soft_update2": [vp, vp, c_size_t, c_size_t, c_float, c_float, c_float, c_float, vp],
     "curla_shrink_perturb2": [vp, vp, vp, c_size_t, c_size_t, c_float, c_float, c_float, c_float, vp],
+    "curla_dormant_colsum": [vp, c_ll, c_int, c_int, c_int, vp, c_ll, vp],
+    "curla_dormant_mask": [vp, c_int, c_int, c_float, vp, vp, vp, vp, vp],
+    "curla_redo_recycle": [vp, vp, vp, vp, c_ll, c_int, vp, c_int, vp, c_int, c_int, c_int, vp],
     "curla_adam_step": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_ll, vp, vp],
     "curla_adam_step_lerp": [vp, vp, vp, vp, c_size_t, c_double, c_double, c_double, c_double, c_ll, vp, vp, c_size_t,
                              c_float, c_float, c_float, c_float, vp],

@@ -90,7 +90,8 @@ class _UpdateGraphsMixin:
         # staged through the host (gloo) is not
         # (_dp_avg: the group's backend is RCCL; every other backend takes the sum-and-divide / staged path)
         return (replay_buffer is self._graph_rb and not only_cpc and not (self._dp_active and not self._dp_avg)
-                and not self._records(step) and step % self.log_interval != 0 and self.training)
+                and not self._records(step) and step % self.log_interval != 0 and self.training
+                and not self._redo_due(step, only_cpc))  # (a redo step's update runs eagerly: DESIGN.md 7j)
 
     def _graph_live(self, opt):
         """The parameters ``opt``'s step touches in a captured update (None: all).  Under detach_encoder the critic's

@@ -113,6 +113,19 @@ class _ResetMixin:
         self._stage_params(a, self._actor_flat, own, actor.named_parameters(), fc=self.actor.encoder.fc)
         return stage
 
+    def _upload_fresh(self, draw=True):
+        """``_stage_fresh()`` and its two host-to-device copies, enqueued on the current stream (the events let the
+        next staging wait for them); returns the staging buffers.  ``draw=False`` (measurements: the device's share
+        without the host's draw) sends the values staged last again and leaves the reset stream where it is."""
+        stage = self._stage_fresh() if draw else self._reset_staging()
+        for st in stage.values():
+            st["dev"].copy_(st["host"], non_blocking=True)
+            if st["dev"].is_cuda:
+                if st["event"] is None:
+                    st["event"] = torch.cuda.Event()
+                st["event"].record()
+        return stage
+
     # ------------------------------------------------------------------ the reset
     @torch.no_grad()
     def reset_networks(self, encoder_keep=None, alpha=True):
@@ -133,13 +146,7 @@ class _ResetMixin:
         if self.device.type != "cuda" and _lib._trace_hook is None:
             raise RuntimeError("CurlSacAgent.reset_networks needs a CUDA/HIP device: the learner path has no CPU fallback")
         self._finish_actor_step()
-        stage = self._stage_fresh()
-        for st in stage.values():
-            st["dev"].copy_(st["host"], non_blocking=True)
-            if st["dev"].is_cuda:
-                if st["event"] is None:
-                    st["event"] = torch.cuda.Event()
-                st["event"].record()
+        stage = self._upload_fresh()
         lay = self._lay
         (w0, w1), (e0, e1), (_, q1) = lay["w"], lay["enc"], lay["q"]
         cf, tf, sc = self._critic_flat, self._target_flat, stage["critic"]["dev"]

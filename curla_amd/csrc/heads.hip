@@ -24,6 +24,7 @@ namespace {
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
 #include "tqc.h"           // tqc_critic_loss_kernel, tqc_actor_loss_kernel (truncated quantile critics)
 #include "curl_head.h"     // curl_head_kernel<NTILE>
+#include "redo.h"          // dormant_colsum_kernel, dormant_mask_kernel, redo_recycle_kernel (dormant-neuron scores, ReDo)
 #include "optim.h"         // soft_update_kernel, soft_update2_kernel, shrink_perturb2_kernel, adam_step_kernel<CLIP, DECAY>, adam_step2_kernel<CLIP, DECAY>
 #include "sample_stage.h"  // a minibatch's index block and scalars: sample_stage_kernel<HOST, NSTEP, POS>, pos_walk_kernel
 #include "ring.h"          // crop_nchw_kernel, store_frame_kernel, gather_stacks_kernel<FAST>, nhwc_to_nchw_kernel
@@ -681,6 +682,46 @@ int curla_shrink_perturb2(float* param, float* target, const float* fresh, size_
   const int vec = aligned16(param) && aligned16(fresh) && aligned16(target);  // (NULL counts as aligned: not accessed)
   return launch(shrink_perturb2_kernel, dim3(nblocks(vec ? (n + 3) / 4 : n, 256, 8192)), 256, 0,
                 static_cast<hipStream_t>(stream), param, target, fresh, n, split, vec, keep_a, new_a, keep_b, new_b);
+}
+
+int curla_dormant_colsum(const float* h, long long h_stride, int nb, int B, int H, float* sums, long long sums_stride,
+                         void* stream) {
+  CURLA_REQUIRE(float_pointers(h, sums) && B >= 1 && H >= 1 && nb >= 1 && h_stride >= (long long)B * H &&
+                sums_stride >= H);
+  return launch(dormant_colsum_kernel, dim3((H + 63) / 64, nb), 64, 0, static_cast<hipStream_t>(stream), h, h_stride, B, H,
+                sums, sums_stride);
+}
+
+int curla_dormant_mask(const float* sums, int L, int H, float tau, float* score, int* mask, int* count, float* fraction,
+                       void* stream) {
+  CURLA_REQUIRE(float_pointers(sums, score, fraction) && float_pointers(mask, count) && L >= 1 && H >= 1 &&
+                tau >= 0.f);  // (false for a NaN)
+  return launch(dormant_mask_kernel, dim3(L), 256, 0, static_cast<hipStream_t>(stream), sums, H, tau, score, mask, count,
+                fraction);
+}
+
+int curla_redo_recycle(float* param, float* m, float* v, const float* fresh, long long stride, int nb,
+                       const CurlaRedoSeg* segs, int nsegs, const int* mask, int L, int H, int mask_twin, void* stream) {
+  CURLA_REQUIRE(float_pointers(param, m, v, fresh) && float_pointers(mask) && segs && nb >= 1 && H >= 1 && L >= 1 &&
+                nsegs >= 1 && nsegs <= kMaxRedoSegs && mask_twin >= 0 && (long long)(nb - 1) * mask_twin < L);
+  const int top = L - 1 - (nb - 1) * mask_twin;  // the last mask row network 0 may name
+  const bool vec = aligned16(param) && aligned16(m) && aligned16(v) && aligned16(fresh) && aligned16(mask) &&
+                   (nb == 1 || stride % 4 == 0);
+  RedoSegs a = {};
+  long long most = 0;
+  for (int i = 0; i < nsegs; ++i) {
+    const CurlaRedoSeg& s = segs[i];
+    CURLA_REQUIRE(s.rows >= 1 && s.cols >= 1 && s.offset >= 0 && s.row_layer >= -1 && s.row_layer <= top &&
+                  s.col_layer >= -1 && s.col_layer <= top);
+    CURLA_REQUIRE((s.row_layer < 0 || s.rows == H) && (s.col_layer < 0 || s.cols == H));
+    const long long count = (long long)s.rows * s.cols;
+    CURLA_REQUIRE(nb == 1 || s.offset + count <= stride);
+    a.s[i] = RedoSeg{s.offset, s.rows, s.cols, s.row_layer, s.col_layer, vec && s.offset % 4 == 0 && s.cols % 4 == 0};
+    const long long work = a.s[i].vec ? count / 4 : count;
+    most = work > most ? work : most;
+  }
+  return launch(redo_recycle_kernel, dim3(nblocks((size_t)most, 256, 1024), nsegs, nb), 256, 0,
+                static_cast<hipStream_t>(stream), param, m, v, fresh, stride, a, mask, H, mask_twin);
 }
 
 int curla_adam_step_lerp(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr,

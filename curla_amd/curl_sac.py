@@ -30,6 +30,7 @@ from . import ops
 from .agent_acting import _ActingMixin
 from .agent_dp import _DataParallelMixin
 from .agent_graphs import _NullLog, _UpdateGraphsMixin
+from .agent_redo import _check_redo_interval, _check_redo_recycle, _check_redo_tau, _RedoMixin
 from .agent_reset import _check_reset_interval, _check_reset_keep, _check_reset_seed, _ResetMixin
 from .encoder import CNNEncoder
 from .mlp import _Mlp, _MlpLn, _linears, _mlp_bwd, _mlp_fwd  # noqa: F401
@@ -123,10 +124,13 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, reset_interval=0, reset_encoder_keep=1.0, reset_seed=0, critic_quantiles=0,
-                 critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0, critic_layer_norm=False,
-                 **kwargs):
+    def __call__(cls, *args, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0, reset_encoder_keep=1.0,
+                 reset_seed=0, critic_quantiles=0, critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1,
+                 critic_dropout=0.0, critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
+        agent.redo_interval = _check_redo_interval(redo_interval)
+        agent.redo_tau = _check_redo_tau(redo_tau)
+        agent.redo_recycle = _check_redo_recycle(redo_recycle)
         agent.reset_interval = _check_reset_interval(reset_interval)
         agent.reset_encoder_keep = _check_reset_keep(reset_encoder_keep)
         agent.reset_seed = _check_reset_seed(reset_seed)
@@ -142,7 +146,7 @@ class _AgentType(type):
         return agent
 
 
-class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetMixin, metaclass=_AgentType):
+class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetMixin, _RedoMixin, metaclass=_AgentType):
     """CURL representation learning with SAC (curl_sac.py:224-465).
     ``CurlSacAgent(..., critic_layer_norm=True)`` (a keyword of the class call, not in the reference; default off:
     nothing changes): an ``nn.LayerNorm(hidden_dim)`` between each hidden Linear of the Q functions and its ReLU, critic
@@ -164,7 +168,12 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     ``reset_interval=N`` (default 0: nothing changes): every N steps ``update()`` first calls ``reset_networks()`` -- the
     heads re-initialised, the encoder shrunk and perturbed with ``reset_encoder_keep`` (default 1.0: kept as it is), the
     optimizers started over --, the fresh values drawn from a stream of the agent's own seeded by ``reset_seed``
-    (agent_reset.py).  The first two are attributes that may be edited between calls."""
+    (agent_reset.py).  The first two are attributes that may be edited between calls.
+    ``redo_interval=N`` (default 0: nothing changes): every update whose step is a multiple of N ends with a redo pass
+    (``redo_pass``) on its minibatch -- the dormant-neuron scores of the six hidden layers of Q1, Q2 and the actor trunk
+    (``dormant_counts``, ``dormant_fractions``, ``dormant_report()``) and, unless ``redo_recycle=False``, ReDo's recycling
+    of the units whose score is <= ``redo_tau`` (default 0.1) with fresh values from the reset stream (agent_redo.py;
+    DESIGN.md 7j).  All three are attributes that may be edited between calls."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
@@ -1011,6 +1020,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             self._leading_phases(sample, step)
         else:
             self._update_phases(sample, L, step, only_cpc, noise)
+            if self._redo_due(step, only_cpc):  # (redo_interval: behind the optimizer steps of the final sub-step)
+                self._redo_scheduled(sample[0], sample[1], L, step)
 
     _want_pos_known = (None, False)
 
@@ -1129,7 +1140,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             "optimizers": {k: self._convert_opt_state(o, o.state_dict(), True) for k, o in self._optimizers().items()},
             "rng": rng, "critic_dropout": float(self.critic_dropout), "utd_ratio": int(self.utd_ratio),
             "critic_quantiles": int(self.critic_quantiles), "critic_drop_quantiles": int(self.critic_drop_quantiles),
-            **self._reset_checkpoint(),
+            **self._reset_checkpoint(), **self._redo_checkpoint(),
         }, path)
 
     def load_checkpoint(self, path, restore_rng=True):
@@ -1161,6 +1172,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             if self.device.type == "cuda" and "cuda" in ck["rng"]:
                 torch.cuda.set_rng_state(ck["rng"]["cuda"], self.device)
         self._load_reset_checkpoint(ck)
+        self._load_redo_checkpoint(ck)
         self._anchor_cache = None
         # captured graphs hold the addresses of log_alpha's Adam moments, which load_state_dict has just replaced
         self._drop_graphs()

@@ -717,6 +717,38 @@ def shrink_perturb2(param_flat, target_flat, fresh_flat, split, keep_a, keep_b):
          float(keep_a), 1.0 - float(keep_a), float(keep_b), 1.0 - float(keep_b), stream())
 
 
+def dormant_colsum(h, sh, nb, B, H, sums, s_sums):
+    """sums[n][j] = sum_b |h[n][b][j]| (float32, b in index order) for the ``nb`` networks of ``h`` [nb][B][H], network n
+    ``sh`` elements into ``h`` and ``s_sums`` into ``sums`` (curla_dormant_colsum)."""
+    call("curla_dormant_colsum", ptr(h), sh, nb, B, H, ptr(sums), s_sums, stream())
+
+
+def dormant_mask(sums, L, H, tau, score, mask, count, fraction):
+    """Scores, int32 masks, int32 counts and float32 fractions of the ``L`` layers of ``sums`` [L][H] at the threshold
+    ``tau`` (curla_dormant_mask)."""
+    call("curla_dormant_mask", ptr(sums), L, H, float(tau), ptr(score), ptr(mask), ptr(count), ptr(fraction), stream())
+
+
+REDO_MAX_SEGS = 12  # include/curla_hip.h CURLA_REDO_MAX_SEGS
+
+
+class _RedoSeg(ctypes.Structure):  # CurlaRedoSeg
+    _fields_ = [("offset", ctypes.c_longlong), ("rows", ctypes.c_int), ("cols", ctypes.c_int),
+                ("row_layer", ctypes.c_int), ("col_layer", ctypes.c_int)]
+
+
+def redo_recycle(param, m, v, fresh, stride, nb, segs, mask, L, H, mask_twin):
+    """ReDo's recycling of one flat block (curla_redo_recycle): ``segs`` = [(offset, rows, cols, row_layer, col_layer)],
+    -1 for a mask a segment does not have; ``param`` / ``m`` / ``v`` / ``fresh`` are tensors or addresses of the block's
+    first element in the four arrays, network n ``stride`` elements in, with mask rows ``n * mask_twin`` further on."""
+    arr = (_RedoSeg * len(segs))()
+    for a, sg in zip(arr, segs):
+        a.offset, a.rows, a.cols, a.row_layer, a.col_layer = (int(x) for x in sg)
+    addr = [x.data_ptr() if hasattr(x, "data_ptr") else x for x in (param, m, v, fresh)]
+    call("curla_redo_recycle", *addr, int(stride), nb, ctypes.addressof(arr), len(segs), ptr(mask), L, H, mask_twin,
+         stream())
+
+
 def gather_transition_scalars(sc, idx, B, A, act, rew, nd):
     call("curla_gather_transition_scalars", ptr(sc), ptr(idx), B, A, ptr(act), ptr(rew), ptr(nd), stream())
 

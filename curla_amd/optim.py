@@ -172,6 +172,13 @@ class FlatAdam(torch.optim.Adam):
             if st:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
 
+    def moment_addresses(self, off, n):
+        """Device addresses of ``exp_avg`` / ``exp_avg_sq`` of the flat buffer's elements [off, off + n): the moment
+        mirrors follow the flat layout from this optimizer's first parameter on (CurlSacAgent.redo_pass)."""
+        if off < self._lo or off + n > self._hi:
+            raise ValueError("FlatAdam: elements [%d, %d) are not all this optimizer's" % (off, off + n))
+        return self._m.data_ptr() + 4 * (off - self._lo), self._v.data_ptr() + 4 * (off - self._lo)
+
     # -- captured graphs: the step-dependent factors as data ------------------------------------------------------
     def live_indices(self, live=None):
         """Indices of the parameters a step touches: ``live`` (an iterable of Parameters) or all of them."""

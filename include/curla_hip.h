@@ -496,6 +496,46 @@ int curla_soft_update2(const float* param, float* target, size_t n, size_t split
 int curla_shrink_perturb2(float* param, float* target, const float* fresh, size_t n, size_t split, float keep_a,
                           float new_a, float keep_b, float new_b, void* stream);
 
+/* Dormant-neuron scores and ReDo recycling (Sokar et al. 2023) for the hidden layers of the 3-layer MLPs (the actor trunk,
+ * the Q functions).  Three launches' worth of entry points; no atomics, every sum in a fixed order: a rerun writes the
+ * same bits.
+ * curla_dormant_colsum: sums[n][j] = sum over b of |h[n][b][j]| in float32, b in index order, for the nb networks of
+ * h [nb][B][H] (post-ReLU activations; network n `h_stride` elements in, >= B H) into sums (network n `sums_stride`
+ * elements in, >= H).  A launch of its own so that data-parallel ranks can add their sums up before thresholding.
+ * CURLA_ERR_ARG on a NULL pointer, B < 1, H < 1, nb < 1 or a stride below the extent it spans.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_dormant_colsum(const float* h, long long h_stride, int nb, int B, int H, float* sums, long long sums_stride,
+                         void* stream);
+/* Per layer l of sums [L][H] (dense): total = sum_j (double) sums[l][j] in a fixed order, mean = total / H,
+ * score[l][j] = (float)((double) sums[l][j] / mean), mask[l][j] (int32: 1 dormant, 0 not) = mean == 0 or
+ * score[l][j] <= tau compared in float32 -- a NaN sum or total masks nothing --, count[l] (int32) the masked units and
+ * fraction[l] = (float)((double) count[l] / H).  CURLA_ERR_ARG on a NULL pointer, L < 1, H < 1, tau negative or NaN.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_dormant_mask(const float* sums, int L, int H, float tau, float* score, int* mask, int* count, float* fraction,
+                       void* stream);
+/* ReDo's recycling over flat parameter blocks.  param, m, v (Adam's moments) and fresh share one layout; network n of
+ * the nb lies `stride` elements in.  A segment is a [rows][cols] matrix (a vector: cols 1) `offset` elements into the
+ * block with the mask row of its output units, row_layer, and of its input units, col_layer (-1: it has none; network n
+ * takes mask rows row_layer + n * mask_twin and col_layer + n * mask_twin of mask [L][H], curla_dormant_mask's).  Per
+ * element (i, j), r = the row mask of i, c = the column mask of j:
+ *   c      : param = 0            (the outgoing weights of a dormant unit; zero wins where a row and a column cross)
+ *   else r : param = fresh        (the incoming weights, the bias, a LayerNorm's weight / bias)
+ *   else   : not written          (a stored -0.0 or NaN stays)
+ * and m = v = 0 exactly where param is written.  param, m and v are never read.  16-byte accesses in a segment when the
+ * four arrays and mask are 16-byte aligned and stride, its offset and cols are multiples of 4, element-wise otherwise
+ * (tested per launch and per segment).  CURLA_ERR_ARG on a NULL pointer, nb < 1, H < 1, L < 1, nsegs outside
+ * 1 .. CURLA_REDO_MAX_SEGS, a segment with rows < 1, cols < 1, offset < 0, a layer outside -1 .. L - 1 - (nb - 1)
+ * mask_twin, rows != H under a row mask or cols != H under a column mask, mask_twin < 0, or (nb > 1) a stride below the
+ * end of a segment.  Additive: CURLA_ABI_VERSION stays 8. */
+#define CURLA_REDO_MAX_SEGS 12
+typedef struct CurlaRedoSeg {
+  long long offset;
+  int rows, cols;
+  int row_layer, col_layer;
+} CurlaRedoSeg;
+int curla_redo_recycle(float* param, float* m, float* v, const float* fresh, long long stride, int nb,
+                       const CurlaRedoSeg* segs, int nsegs, const int* mask, int L, int H, int mask_twin, void* stream);
+
 /* One torch.optim.Adam step (weight_decay 0, amsgrad off; the reference's five optimizers, curl_sac.py:299-313) over a
  * flat run of n fp32 parameters with their gradient and moment runs: replaces torch's multi-tensor Adam launches
  * (~70 workgroups on a 256-CU chip).  `step` is the 1-based count of this step; the hyper-parameters are doubles as in the
