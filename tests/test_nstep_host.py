@@ -224,7 +224,7 @@ def test_n_step_1_is_the_buffer_as_it_was(kw, explicit):
                          if isinstance(v, (torch.Tensor, np.ndarray))}
     assert shapes(one) == shapes(default)  # every allocation, name by name
     assert one._d_add_sc.numel() == A + 2
-    for attr in ("_cont", "_cont_h", "_last_next"):
+    for attr in ("_cont", "_cont_h", "_last_next", "_chain"):
         assert not hasattr(one, attr)
     assert torch.equal(one._sc[:12], default._sc[:12])
     assert torch.equal(one.frames, default.frames) if kw else torch.equal(one._both, default._both)

@@ -176,7 +176,7 @@ def test_a_positive_three_steps_ahead_keeps_the_flags_of_n_step_3(dedup, tmp_pat
 @pytest.mark.parametrize("dedup", [False, True])
 def test_a_positive_one_step_ahead_keeps_no_flags(dedup):
     rb = _filled(pos_offset=1, dedup_frames=dedup)
-    for attr in ("_cont", "_cont_h", "_last_next", "_cont_off"):
+    for attr in ("_cont", "_cont_h", "_last_next", "_chain", "_cont_off"):
         assert not hasattr(rb, attr)
     assert rb._d_add.numel() == _filled(dedup_frames=dedup)._d_add.numel()  # no flag bytes in the add block
     t = _traced(lambda: rb.sample_cpc_refs(indices=_idx()))
