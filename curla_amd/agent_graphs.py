@@ -236,17 +236,14 @@ class _UpdateGraphsMixin:
                         self._update_phases(rb.graph_refs(st["slot"]), null, step)
             except Exception as e:  # noqa: BLE001
                 err = e
+                # what the phases set for each other and had no chance to clear; collectives enqueued under the failed
+                # capture are dropped without waiting for them (_graph_cap is still set)
+                self._reset_handover()
             finally:
                 self._graph_cap = None
                 for opt in dyn:
                     opt._dyn = None
                 self.log_alpha_optimizer._curla_dyn64 = None
-            if err is not None:
-                # what _update_phases sets from one phase to the next and had no chance to clear
-                self._pos_hint = self._anchor_cache = self._pos_cache = None
-                self._pos_fc_done = self._soft_update_hint = self._soft_update_done = False
-                self._defer_actor_step = self._actor_step_pending = False
-                self._dp_pending = []
             # data parallel: every rank captures at the same step; ONE rank replaying while another runs eagerly would
             # still pair up collective for collective, but the ranks would sit on different schedules indefinitely with
             # nothing checking it -- so the outcome is agreed on (one host-side flag, at capture time only)

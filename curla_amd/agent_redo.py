@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .encoder import CNNEncoder
-from .mlp import _Mlp, _linears, _mlp_fwd
+from .mlp import _linears
 from .networks import _check_int
 from .ops import ObsRef
 from .optim import FlatAdam
@@ -161,7 +161,7 @@ class _RedoMixin:
         o = obs if isinstance(obs, ObsRef) else ObsRef.from_tensor(obs.contiguous().float())
         action = action.contiguous()
         B, A, H = o.B, self.action_dim, self.hidden_dim
-        enc, aenc, F = self.critic.encoder, self.actor.encoder, self.critic.encoder.feature_dim
+        enc, aenc = self.critic.encoder, self.actor.encoder
         ws, buf = self._ws(B), self._redo_buffers()
 
         # the forward: the tied convs once, the critic's and the actor's fc / ln on their output, the twins over
@@ -169,9 +169,8 @@ class _RedoMixin:
         h = enc.conv_forward(o, ws.acts_tmp)
         CNNEncoder.fc_partial_multi([(aenc, h), (enc, h)])
         CNNEncoder.ln_from_partial_multi(B, [(aenc, ws.z_a, {}), (enc, ws.z_c, dict(xa=ws.xa, act=action))], A)
-        _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, self.critic.out_dim, ws.q_h1, ws.q_h2, ws.q,
-                 ln=self.critic.twin_ln())
-        _mlp_fwd(ws.z_a, 0, _Mlp(self.actor.trunk), 1, B, F, H, 2 * A, ws.a_h1, ws.a_h2, ws.a_out)
+        self._twin_fwd(ws, self.critic, self.critic.twin_ln(), ws.q)
+        self._actor_fwd(ws)
 
         # sums [6][H]: the twins' layers interleave (Q1.h1, Q1.h2, Q2.h1, Q2.h2), so a twin launch writes every other row
         sums, n = buf["sums"], len(LAYERS)
@@ -188,9 +187,7 @@ class _RedoMixin:
             ops.redo_recycle(cf[q0:], mq[0], mq[1], stage["critic"]["dev"][q0:], qs, 2, seg_q, buf["mask"], n, H, 2)
             ops.redo_recycle(af[a0:], ma[0], ma[1], stage["actor"]["dev"][a0:], af.numel() - a0, 1, seg_a, buf["mask"],
                              n, H, 0)
-        # the workspace no longer holds what the update's phases left for each other
-        self._anchor_cache = self._pos_cache = None
-        self._pos_fc_done = False
+        self._drop_encoder_caches()
         self.redo_count += 1
 
     def _redo_allreduce(self, sums):

@@ -168,8 +168,7 @@ class _ResetMixin:
         if alpha:
             self.log_alpha.fill_(self._init_log_alpha)
             _zero_torch_adam(self.log_alpha_optimizer)
-        self._anchor_cache = self._pos_cache = None
-        self._pos_fc_done = False
+        self._drop_encoder_caches()
         self.reset_count += 1
 
     def _maybe_reset(self, step):

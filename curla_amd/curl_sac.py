@@ -288,10 +288,6 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         self._install_grad_views()
 
         self._workspaces = {}
-        self._anchor_cache = None
-        self._pos_cache = None   # the obs_pos handle whose target-encoder activations sit in the workspace
-        self._pos_hint = None    # set by update(): the positives the actor phase may encode along the way
-        self._pos_fc_done = False  # ... and whose fc product it then leaves in the target encoder's partial buffer
         self._dp_group = None
         self._dp_world = 1
         self._dp_active = False
@@ -421,8 +417,38 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
                     p.grad = v
 
     _curl_unfused = False       # the CURL head as separate launches (set per agent from CURLA_CURL_HEAD=unfused)
-    _soft_update_hint = False   # set by update() around update_critic(): a target soft update follows the critic's step
-    _soft_update_done = False
+
+    # ------------------------------------------------------------------ what the phases hand to each other
+    # Ten attributes, here at their idle values.  update() sets the hints around the phase they are for and clears them
+    # again, so a phase called by hand sees idle values; a call that raises goes through _reset_handover().
+    _soft_update_hint = False    # hint to update_critic(): a target soft update follows the critic's step
+    _soft_update_done = False    # ... and the critic's Adam launch has made it
+    _pos_hint = None             # hint to the actor phase: the positives it may encode along the way
+    _defer_actor_step = False    # hint to the actor phase: the CURL phase follows (overlapped data parallel)
+    _actor_step_pending = False  # the actor phase has left its optimizer steps to _finish_actor_step()
+    _actor_norm_log = None       # (logger, step) of a logging step while clipping is on, until the actor's step is taken
+    _utd_leading = False         # set by _leading_phases around a leading sub-step (utd_ratio > 1): it records nothing
+    _anchor_cache = None         # the encoder caches: the obs whose critic features (ws.z_c) the actor phase left,
+    _pos_cache = None            # the obs_pos handle whose target-encoder activations sit in the workspace
+    _pos_fc_done = False         # ... and whose features the actor phase has finished as well (ws.z_pos)
+
+    def _drop_encoder_caches(self):
+        """The workspace no longer holds what one phase left for the next (the critic phase's start, a reset, a redo
+        pass, a loaded checkpoint)."""
+        self._anchor_cache = self._pos_cache = None
+        self._pos_fc_done = False
+
+    def _reset_handover(self):
+        """Back to the state a fresh ``update()`` call finds, after a call that raised: pending data-parallel work is
+        waited for (not while a graph capture is open, which must not wait on a collective) and dropped, a deferred
+        actor step with it, every hint and cache idle."""
+        if self._dp_pending and self._graph_cap is None:
+            self._allreduce_wait()
+        self._dp_pending = []
+        self._soft_update_hint = self._soft_update_done = self._defer_actor_step = self._actor_step_pending = False
+        self._utd_leading = False
+        self._pos_hint = self._actor_norm_log = None
+        self._drop_encoder_caches()
 
     def _ws(self, B):
         if B not in self._workspaces:
@@ -498,8 +524,6 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         (log_param_hist_imgs, every LOG_FREQ steps: curl_sac.py:17,112-121,171-180)."""
         return self.log_param_hist_imgs and step % LOG_FREQ == 0 and not self._utd_leading
 
-    _utd_leading = False  # set by _leading_phases around a leading sub-step of a utd_ratio > 1 call: it records nothing
-
     def _noise(self, ws, noise):
         """(noise buffer, rng): explicit ``noise`` is copied into the buffer (rng None).  Without it
         (``torch.randn_like``, curl_sac.py:97) the policy-head launch draws the numbers itself and writes them into the
@@ -547,145 +571,207 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         pos = dropout_rng or rng or _reserve_dropout_counter(self.device)
         return lambda tag: (p, pos, tag)
 
+    def _encoder_backward_reduced(self, ws, obs_ref, dz, lo, hi, **kw):
+        """``_encoder_backward`` of the critic's encoder from ``dz`` (``kw``: its further arguments) and the data-parallel
+        reduction of the bucket [lo, hi) of the critic's flat gradient -- [convs | fc, ln | Q1 | Q2] in the critic phase,
+        [W | convs | fc, ln] in the CURL phase, whose encoder gradients are reduced ONCE for both optimizers.
+        Overlapped schedule: the dense piece, from fc.weight's offset to hi, is final before the conv backward starts:
+        it goes asynchronously in ``dense_done`` and is reduced underneath it; the front piece goes after the conv
+        backward, then the compute stream waits for both.  Blocking schedule: one all-reduce of the whole bucket after
+        the backward."""
+        enc, g = self.critic.encoder, self._critic_gflat
+        if self._dp_active and self._dp_overlap:
+            cut = self._grad_offset(enc.fc.weight, g)
+            self._encoder_backward(ws, obs_ref, dz, ws.xhat_c, ws.rstd_c, enc,
+                                   dense_done=lambda: self._allreduce(g[cut:hi], async_op=True), **kw)
+            self._allreduce(g[lo:cut], async_op=True)
+            self._allreduce_wait()
+        else:
+            self._encoder_backward(ws, obs_ref, dz, ws.xhat_c, ws.rstd_c, enc, **kw)
+            self._allreduce(g[lo:hi])
+
+    # -- the network passes: shapes and buffers are the workspace's and the agent's, stated here and nowhere else
+    def _actor_fwd(self, ws, noise=None, **outs):
+        """The actor trunk over ws.z_a into ws.a_out; with ``noise``, the policy head behind it, which writes ``outs``
+        (ops.actor_head_fwd's: mu, pi, log_pi, log_std, tanh_ls, xa, rng)."""
+        B, F = ws.z_a.shape
+        head = None if noise is None else (noise, self.actor.log_std_min, self.actor.log_std_max, outs)
+        _mlp_fwd(ws.z_a, 0, _Mlp(self.actor.trunk), 1, B, F, self.hidden_dim, 2 * self.action_dim, ws.a_h1, ws.a_h2,
+                 ws.a_out, head=head)
+
+    def _twin_fwd(self, ws, net, ln, out=None, outer=None):
+        """The twin Q functions of ``net`` (the critic or the target) over ws.xa into ``out`` (ws.q / ws.tq), ``ln`` their
+        _MlpLn.  ``outer`` = (2, floats from the target's parameters to the critic's): the target's twins over
+        ws.xa2[0] and the critic's over ws.xa2[1] as one batch into ws.q2 (``net`` is the target)."""
+        _, B, FA = ws.xa2.shape
+        x, h1, h2, out = (ws.xa, ws.q_h1, ws.q_h2, out) if outer is None else (ws.xa2, ws.q_h1_2, ws.q_h2_2, ws.q2)
+        _mlp_fwd(x, 0, net.twin(), 2, B, FA, self.hidden_dim, net.out_dim, h1, h2, out, outer=outer, ln=ln)
+
+    def _twin_bwd(self, ws, ln, loss, grads):
+        """Backward of the critic's twins over ws.xa from ``loss`` (_mlp_bwd's descriptor) into ws.dxa; ``grads``: the
+        twins' parameter gradients as well (the critic phase; the actor phase takes the data gradient alone)."""
+        (_, B, FA), net = ws.xa2.shape, self.critic
+        _mlp_bwd(ws.xa, 0, net.twin(), net.twin(grads=True) if grads else None, 2, B, FA, self.hidden_dim, net.out_dim,
+                 ws.q_h1, ws.q_h2, ws.dq, ws.q_dh2, ws.q_dh1, ws.dxa, loss=loss, ln=ln)
+
+    # -- the loss descriptors of _twin_bwd: (fields, launch) -- ``fields`` for the form computed inside the backward
+    #    launch of the Q functions' last layer, ``launch()`` the loss kernel on its own where that form does not apply
+    def _critic_loss(self, ws, reward, not_done, per, drop_q):
+        """target_Q = r + not_done * gamma * (min Q' - alpha log pi'), the two MSE terms and their gradient dq
+        (curl_sac.py:353-361).  ``critic_quantiles``: the quantile Huber loss of the critic's atoms against
+        the kept target atoms, always a launch of its own.  ``per``, a prioritized minibatch: the loss is launched here,
+        the importance weights scale dq and the loss in place and the drawn rows get their new priorities -- all on the
+        device --, and the backward runs on the weighted dq it finds: no descriptor, None."""
+        B, Mq = ws.log_pi.shape[0], self.critic.out_dim
+        la, gamma, total = self.log_alpha, self.discount, ws.scalars[0:1]
+        if self.critic_quantiles:
+            loss = (None, lambda: ops.tqc_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done, la, gamma,
+                                                      B, Mq, drop_q, ws.dq, B * Mq, ws.q_row_loss, total))
+        else:
+            loss = (dict(kind=1, twin_stride=B, q=ws.q, target_q_twin=ws.tq, log_pi=ws.log_pi, reward=reward,
+                         not_done=not_done, log_alpha=la, discount=gamma, target_q=ws.target_q, scalars=total, dq=ws.dq),
+                    lambda: ops.critic_td_loss(ws.q, ws.tq, B, ws.log_pi, reward, not_done, la, gamma, B, ws.target_q,
+                                               total, ws.dq))
+        if per is None:
+            return loss
+        if ws.per_w is None:
+            ws.per_w, ws.per_value = (torch.empty(B, device=ws.dq.device, dtype=torch.float32) for _ in range(2))
+        loss[1]()
+        per.td_update(ws.q, B, ws.target_q, ws.dq, total, ws.per_w, ws.per_value)
+        return None
+
+    def _actor_loss(self, ws):
+        """The actor / alpha losses and d(loss)/dQ (curl_sac.py:377-401); ``critic_quantiles``: over the mean of all
+        atoms in place of min(Q1, Q2), a launch of its own."""
+        B, A, Mq = ws.log_pi.shape[0], self.action_dim, self.critic.out_dim
+        la, te, out = self.log_alpha, float(self.target_entropy), ws.scalars[1:5]
+        if self.critic_quantiles:
+            return None, lambda: ops.tqc_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, la, te, B, Mq, out, ws.dq,
+                                                    B * Mq, la.grad)
+        return (dict(kind=2, A=A, twin_stride=B, q=ws.q, log_pi=ws.log_pi, log_std=ws.log_std, log_alpha=la,
+                     target_entropy=te, scalars=out, dq=ws.dq, dlog_alpha=la.grad),
+                lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, la, te, B, out, ws.dq, la.grad))
+
+    # -- the critic phase's forward: a' ~ pi(. | z'), the target's twins over [z' | a'], the critic's over [z | a]
+    #    (curl_sac.py:350-358), by one of three routes; each returns the phase's ``drop`` (_dropout)
+    def _critic_forward(self, ws, o, no, online, noise, dropout_rng):
+        """``online``: what the critic encoder's LayerNorm launch is given beside z (its saves, xa = [z | a], the
+        record's fc_out)."""
+        B = o.B
+        pair = getattr(o, "pair", None)
+        if pair is None or pair[1] is not no or pair[0].B != 2 * B:
+            return self._q_unmerged(ws, o, no, online, noise, dropout_rng)
+        # obs and next_obs both go through the online convs (the actor's are tied to the critic's): the buffer handed
+        # them over as one [obs | next_obs] handle, so they take ONE launch per layer (2B samples), the target encoder's
+        # pass over next_obs rides in the same launches (second problem, own weights) and the three fc products --
+        # all three activation tensors are there -- take one
+        enc, tenc = self.critic.encoder, self.critic_target.encoder
+        enc.conv_forward2(pair[0], ws.acts_pair, tenc, no, ws.acts_tmp)
+        CNNEncoder.fc_partial_multi([(self.actor.encoder, ws.acts_pair[-1][B:]), (tenc, ws.acts_tmp[-1]),
+                                     (enc, ws.acts_main[-1])])
+        route = self._q_merged if self._twin_outer is None else self._q_four
+        return route(ws, B, online, noise, dropout_rng)
+
+    def _next_policy(self, ws, noise, dropout_rng, **outs):
+        """The phase's noise draw and dropout stream, then the actor trunk over ws.z_a and the policy head, which writes
+        log_pi and ``outs``."""
+        nz, rng = self._noise(ws, noise)
+        drop = self._dropout(rng, dropout_rng)
+        self._actor_fwd(ws, nz, log_pi=ws.log_pi, rng=rng, **outs)
+        return drop
+
+    def _q_four(self, ws, B, online, noise, dropout_rng):
+        """Four Q functions in one batch: the target's twins over [z' | a'] and the critic's over [z | a] are four MLPs
+        of one shape and share their three launches, the three encoders' features (actor, target, critic) their one
+        -- the action columns of [z' | a'] are then written by the policy head.  (Dropout groups: tags 1 / 2, 3 / 4.)"""
+        enc, tq = self.critic.encoder, self.critic_target
+        CNNEncoder.ln_from_partial_multi(B, [(self.actor.encoder, ws.z_a, {}), (tq.encoder, ws.z_t, dict(xa=ws.xa2[0])),
+                                             (enc, ws.z_c, online)], self.action_dim)
+        drop = self._next_policy(ws, noise, dropout_rng, pi=None, xa=ws.xa2[0])
+        self._twin_fwd(ws, tq, tq.twin_ln(*ws.q_ln_saves, save_first=1, drop=drop(1)), outer=(2, self._twin_outer))
+        return drop
+
+    def _q_merged(self, ws, B, online, noise, dropout_rng):
+        """Merged convs, separate Q passes (CURLA_FOUR_Q=0)."""
+        self.actor.encoder.ln_from_partial(B, ws.z_a)
+        drop = self._next_policy(ws, noise, dropout_rng, pi=ws.pi, xa=None)
+        self._target_q(ws, B, drop)
+        self._online_q(ws, B, online, drop)
+        return drop
+
+    def _q_unmerged(self, ws, o, no, online, noise, dropout_rng):
+        """Fully separate passes (a buffer without the [obs | next_obs] handle): every conv stack on its own."""
+        B = o.B
+        enc, aenc, tenc = self.critic.encoder, self.actor.encoder, self.critic_target.encoder
+        aenc.fc_partial(enc.conv_forward(no, ws.acts_tmp))  # tied convs, online weights
+        aenc.ln_from_partial(B, ws.z_a)
+        drop = self._next_policy(ws, noise, dropout_rng, pi=ws.pi, xa=None)
+        tenc.fc_partial(tenc.conv_forward(no, ws.acts_tmp))
+        self._target_q(ws, B, drop)
+        enc.fc_partial(enc.conv_forward(o, ws.acts_main))
+        self._online_q(ws, B, online, drop)
+        return drop
+
+    def _target_q(self, ws, B, drop):
+        tq = self.critic_target
+        tq.encoder.ln_from_partial(B, ws.z_t, xa=ws.xa, act=ws.pi)  # xa = cat([z', a'], 1)
+        self._twin_fwd(ws, tq, tq.twin_ln(drop=drop(1)), ws.tq)
+
+    def _online_q(self, ws, B, online, drop):
+        self.critic.encoder.ln_from_partial(B, ws.z_c, **online)  # xa = cat([z, a], 1)
+        self._twin_fwd(ws, self.critic, self.critic.twin_ln(*ws.q_ln_saves, drop=drop(3)), ws.q)
+
+    def _critic_step(self):
+        """critic_optimizer.step() (curl_sac.py:367) -- with the target soft update update() has announced right behind
+        it (:442-445) in the same launch where the optimizer is the flat one: the update reads what the step writes, so
+        both share one pass over the critic's flat parameters."""
+        opt, hidden, fused = self.critic_optimizer, [], False
+        if self.detach_encoder:  # convs received no gradient: Adam must skip them (grad None in the reference)
+            hidden = [(p, p.grad) for m in self.critic.encoder.convs for p in (m.weight, m.bias)]
+            for p, _ in hidden:
+                p.grad = None
+        elif self._soft_update_hint:
+            (e0, e1), (_, q1) = self._lay["enc"], self._lay["q"]
+            fused = self._soft_update_done = FlatAdam.step_with_lerp(opt, self._target_flat, e0, q1, e1 - e0,
+                                                                     self.encoder_tau, self.critic_tau)
+        if not fused:
+            self._clip_torch(0, opt)
+            opt.step()
+        for p, g in hidden:
+            p.grad = g
+
     # ------------------------------------------------------------------ phases
     def update_critic(self, obs, action, reward, next_obs, not_done, L, step, noise=None, dropout_rng=None):
         """curl_sac.py:349-371.  ``dropout_rng`` = (seed, counter): the stream position of a dropout critic's masks
         (the target twins under tags 1 / 2, the critic twins under 3 / 4) instead of the phase's own (_dropout)."""
-        Mq = self.critic.out_dim  # the Q functions' last-layer width: critic_quantiles atoms, or the one Q value
-        per = getattr(obs, "per", None)
+        per, drop_q = getattr(obs, "per", None), 0
         if self.critic_quantiles:
-            drop_q = _check_drop_quantiles(self.critic_drop_quantiles, Mq)  # (the attribute may have been edited)
+            drop_q = _check_drop_quantiles(self.critic_drop_quantiles, self.critic.out_dim)  # (it may have been edited)
             if per is not None:
                 raise ValueError("critic_quantiles: a prioritized minibatch is not supported (its priorities are built "
                                  "on one scalar TD error per Q function): use ReplayBuffer(prioritized=False)")
         self._restore_grad_views()
         o, no = _as_ref(obs), _as_ref(next_obs)
-        B, A, H = o.B, self.action_dim, self.hidden_dim
-        enc, F = self.critic.encoder, self.critic.encoder.feature_dim
-        ws = self._ws(B)
-        self._anchor_cache = self._pos_cache = None
-        self._pos_fc_done = False
+        ws, enc = self._ws(o.B), self.critic.encoder
+        self._drop_encoder_caches()
         action, reward, not_done = action.contiguous(), reward.contiguous(), not_done.contiguous()
-
-        # -- target (no_grad block, curl_sac.py:350-355)
-        # obs and next_obs both go through the online convs (the actor's are tied to the critic's): when the buffer
-        # handed them over as one [obs | next_obs] handle they take ONE launch per layer (2B samples)
-        pair = getattr(o, "pair", None)
-        merged = pair is not None and pair[1] is no and pair[0].B == 2 * B
-        tenc = self.critic_target.encoder
-        if merged:
-            # ... and the target encoder's pass over next_obs rides in the same launches (second problem, own weights)
-            enc.conv_forward2(pair[0], ws.acts_pair, tenc, no, ws.acts_tmp)
-            h_next = ws.acts_pair[-1][B:]
-        else:
-            enc.conv_forward(no, ws.acts_tmp)                   # tied convs, online weights
-            h_next = ws.acts_tmp[-1]
-        if merged:  # all three activation tensors are there: the three fc products in one launch
-            CNNEncoder.fc_partial_multi([(self.actor.encoder, h_next), (tenc, ws.acts_tmp[-1]), (enc, ws.acts_main[-1])])
-        else:
-            self.actor.encoder.fc_partial(h_next)
-        # the target critic's twins over [z', a'] and the critic's over [z, a] (curl_sac.py:353-358) are four MLPs of
-        # one shape: with all conv outputs there they share their three launches, and the three encoders' features
-        # (actor, target, critic) their one -- the action columns of [z' | a'] are then written by the policy head
-        four = merged and self._twin_outer is not None
+        # -- target (no_grad block, curl_sac.py:350-355) and current Q estimates (:357-358)
         rec = self._records(step)
-        if four:
-            CNNEncoder.ln_from_partial_multi(B, [
-                (self.actor.encoder, ws.z_a, {}), (tenc, ws.z_t, dict(xa=ws.xa2[0])),
-                (enc, ws.z_c, dict(xhat=ws.xhat_c, rstd=ws.rstd_c, fc_out=ws.fc_out if rec else None, xa=ws.xa,
-                                   act=action))], A)
-        else:
-            self.actor.encoder.ln_from_partial(B, ws.z_a)
-        nz, rng = self._noise(ws, noise)
-        drop = self._dropout(rng, dropout_rng)
-        _mlp_fwd(ws.z_a, 0, _Mlp(self.actor.trunk), 1, B, F, H, 2 * A, ws.a_h1, ws.a_h2, ws.a_out,
-                 head=(nz, self.actor.log_std_min, self.actor.log_std_max,
-                       dict(pi=None if four else ws.pi, log_pi=ws.log_pi, xa=ws.xa2[0] if four else None, rng=rng)))
-        if four:
-            _mlp_fwd(ws.xa2, 0, self.critic_target.twin(), 2, B, F + A, H, Mq, ws.q_h1_2, ws.q_h2_2, ws.q2,
-                     outer=(2, self._twin_outer),
-                     ln=self.critic_target.twin_ln(*ws.q_ln_saves, save_first=1, drop=drop(1)))  # (groups: tags 1/2, 3/4)
-        else:
-            if not merged:
-                tenc.conv_forward(no, ws.acts_tmp)
-                tenc.fc_partial(ws.acts_tmp[-1])
-            tenc.ln_from_partial(B, ws.z_t, xa=ws.xa, act=ws.pi)  # xa = cat([z, a'], 1)
-            _mlp_fwd(ws.xa, 0, self.critic_target.twin(), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.tq,
-                     ln=self.critic_target.twin_ln(drop=drop(1)))
-            # -- current Q estimates + loss + backward (curl_sac.py:357-367)
-            if not merged:
-                enc.conv_forward(o, ws.acts_main)
-                enc.fc_partial(ws.acts_main[-1])
-            enc.ln_from_partial(B, ws.z_c, xhat=ws.xhat_c, rstd=ws.rstd_c, fc_out=ws.fc_out if rec else None,
-                                xa=ws.xa, act=action)
-            _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.q,
-                     ln=self.critic.twin_ln(*ws.q_ln_saves, drop=drop(3)))
+        online = dict(xhat=ws.xhat_c, rstd=ws.rstd_c, fc_out=ws.fc_out if rec else None, xa=ws.xa, act=action)
+        drop = self._critic_forward(ws, o, no, online, noise, dropout_rng)
         if rec:  # what critic.log() / encoder.log() histogram: the outputs of THIS forward (curl_sac.py:163-167)
             self.critic.outputs['q1'], self.critic.outputs['q2'] = ws.q[0].clone(), ws.q[1].clone()
             enc.record_from(o, ws.acts_main, ws.fc_out, ws.z_c)
-        # target_Q = r + not_done * gamma * (min Q' - alpha log pi'), the two MSE terms and their gradient dq: computed
-        # inside the backward launch of the Q functions' last layer (a launch of its own otherwise)
-        td = (dict(kind=1, twin_stride=B, q=ws.q, target_q_twin=ws.tq, log_pi=ws.log_pi, reward=reward,
-                   not_done=not_done, log_alpha=self.log_alpha, discount=self.discount, target_q=ws.target_q,
-                   scalars=ws.scalars[0:1], dq=ws.dq),
-              lambda: ops.critic_td_loss(ws.q, ws.tq, B, ws.log_pi, reward, not_done, self.log_alpha, self.discount, B,
-                                         ws.target_q, ws.scalars[0:1], ws.dq))
-        if self.critic_quantiles:
-            # truncated quantile critics (DESIGN.md 7h): the quantile Huber loss of the critic's atoms against the kept
-            # target atoms and its gradient dq, a launch of its own in front of the last layer's backward
-            td = (None, lambda: ops.tqc_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done,
-                                                    self.log_alpha, self.discount, B, Mq, drop_q, ws.dq, B * Mq,
-                                                    ws.q_row_loss, ws.scalars[0:1]))
-        if per is not None:
-            # a prioritized minibatch (ReplayBuffer(prioritized=True)): the loss launch on its own, then the importance
-            # weights scale dq and the loss in place and the drawn rows get their new priorities -- all on the device --,
-            # and the backward pass runs on the weighted dq
-            if ws.per_w is None:
-                ws.per_w, ws.per_value = (torch.empty(B, device=ws.dq.device, dtype=torch.float32) for _ in range(2))
-            td[1]()
-            per.td_update(ws.q, B, ws.target_q, ws.dq, ws.scalars[0:1], ws.per_w, ws.per_value)
-            td = None
-        _mlp_bwd(ws.xa, 0, self.critic.twin(), self.critic.twin(grads=True), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.dq,
-                 ws.q_dh2, ws.q_dh1, ws.dxa, loss=td,
-                 ln=self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial, drop=drop(3)))
+        # -- loss + backward (curl_sac.py:359-367)
+        loss = self._critic_loss(ws, reward, not_done, per, drop_q)
+        self._twin_bwd(ws, self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial, drop=drop(3)), loss,
+                       grads=True)
         if step % self.log_interval == 0:
             L.log('train_critic/loss', ws.scalars[0], step)
         # (d(loss)/d(z) = dxa[0][:, :F] + dxa[1][:, :F], torch.cat's backward: summed inside the LayerNorm backward)
-        # data parallel: the bucket is [convs | fc, ln | Q1 | Q2]; everything behind the convs is final before the
-        # conv backward starts and is reduced underneath it
-        lay = self._lay
-        e0, total = lay["enc"][0], lay["total"]
-        if self._dp_active and self._dp_overlap:
-            cut = self._grad_offset(enc.fc.weight, self._critic_gflat)
-            self._encoder_backward(ws, o, ws.dxa, ws.xhat_c, ws.rstd_c, enc, conv_grads=not self.detach_encoder,
-                                   dense_done=lambda: self._allreduce(self._critic_gflat[cut:total], async_op=True),
-                                   twin_ld=F + A)
-            self._allreduce(self._critic_gflat[e0:cut], async_op=True)
-            self._allreduce_wait()
-        else:
-            self._encoder_backward(ws, o, ws.dxa, ws.xhat_c, ws.rstd_c, enc, conv_grads=not self.detach_encoder,
-                                   twin_ld=F + A)
-            self._allreduce(self._critic_gflat[e0:total])
-        if self.detach_encoder:  # convs received no gradient: Adam must skip them (grad None in the reference)
-            saved = [(p, p.grad) for m in enc.convs for p in (m.weight, m.bias)]
-            for p, _ in saved:
-                p.grad = None
-            self._clip_torch(0, self.critic_optimizer)
-            self.critic_optimizer.step()
-            for p, g in saved:
-                p.grad = g
-        else:
-            # update() announces a target soft update right behind this step (curl_sac.py:442-445): it reads what the
-            # step writes, so both share one pass over the critic's flat parameters when the optimizer is the flat one
-            fused = False
-            if self._soft_update_hint:
-                (e0, e1), (_, q1) = lay["enc"], lay["q"]
-                fused = FlatAdam.step_with_lerp(self.critic_optimizer, self._target_flat, e0, q1, e1 - e0,
-                                                self.encoder_tau, self.critic_tau)
-                self._soft_update_done = fused
-            if not fused:
-                self._clip_torch(0, self.critic_optimizer)
-                self.critic_optimizer.step()
+        self._encoder_backward_reduced(ws, o, ws.dxa, self._lay["enc"][0], self._lay["total"],
+                                       conv_grads=not self.detach_encoder, twin_ld=ws.xa.shape[1])
+        self._critic_step()
         if self._max_grad_norm is not None and step % self.log_interval == 0:
             L.log('train_critic/grad_norm', self.grad_clip_stats[0, 0], step)
         if self.log_param_hist_imgs:
@@ -697,105 +783,76 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         gradients on critic tensors that are zeroed before any step reads them)."""
         self._restore_grad_views()
         o = _as_ref(obs)
-        B, A, H = o.B, self.action_dim, self.hidden_dim
-        enc, aenc, F = self.critic.encoder, self.actor.encoder, self.critic.encoder.feature_dim
-        ws = self._ws(B)
-
+        B, A, ws = o.B, self.action_dim, self._ws(o.B)
+        enc, aenc, tenc = self.critic.encoder, self.actor.encoder, self.critic_target.encoder
         # one conv pass feeds actor.fc, critic.fc and (even steps) the CURL anchor branch; when update() knows that the
         # CURL phase follows with unchanged target weights, the target encoder's pass over the positives rides in the
         # same launches (second problem) and update_cpc finds its activations ready
-        pos = self._pos_hint
-        self._pos_hint = None
+        pos, self._pos_hint = self._pos_hint, None
         if pos is not None:
-            enc.conv_forward2(o, ws.acts_main, self.critic_target.encoder, pos, ws.acts_tmp)
+            enc.conv_forward2(o, ws.acts_main, tenc, pos, ws.acts_tmp)
             self._pos_cache = pos
         else:
             enc.conv_forward(o, ws.acts_main)
+        # actor.fc and critic.fc read the same conv output, one launch; so are the features: actor's, critic's (kept
+        # for the CURL anchor branch; the action columns of xa = cat([z, pi], 1) come from the policy head below) --
+        # and, third problem of both launches, the positives' target features
         h = ws.acts_main[-1]
-        fcs = [(aenc, h), (enc, h)]  # actor.fc and critic.fc read the same conv output
-        if pos is not None:  # ... and the positives' target features are ready too: third problem of the launch
-            fcs.append((self.critic_target.encoder, ws.acts_tmp[-1]))
-            self._pos_fc_done = True
-        CNNEncoder.fc_partial_multi(fcs)
-        # ... and so are the features: actor's, critic's (kept for the CURL anchor branch; the action columns of
-        # xa = cat([z, pi], 1) come from the policy head below) and the positives'
+        fcs = [(aenc, h), (enc, h)]
         lns = [(aenc, ws.z_a, dict(xhat=ws.xhat_a, rstd=ws.rstd_a)),
                (enc, ws.z_c, dict(xhat=ws.xhat_c, rstd=ws.rstd_c, xa=ws.xa))]
         if pos is not None:
-            lns.append((self.critic_target.encoder, ws.z_pos, {}))
+            fcs.append((tenc, ws.acts_tmp[-1]))
+            lns.append((tenc, ws.z_pos, {}))
+            self._pos_fc_done = True
+        CNNEncoder.fc_partial_multi(fcs)
         CNNEncoder.ln_from_partial_multi(B, lns, A)
         self._anchor_cache = obs
 
-        trunk = _Mlp(self.actor.trunk)
         nz, rng = self._noise(ws, noise)
-        lo, hi = self.actor.log_std_min, self.actor.log_std_max
-        _mlp_fwd(ws.z_a, 0, trunk, 1, B, F, H, 2 * A, ws.a_h1, ws.a_h2, ws.a_out,
-                 head=(nz, lo, hi, dict(mu=ws.mu, pi=ws.pi, log_pi=ws.log_pi, log_std=ws.log_std, tanh_ls=ws.tanh_ls,
-                                        xa=ws.xa, rng=rng)))
+        self._actor_fwd(ws, nz, mu=ws.mu, pi=ws.pi, log_pi=ws.log_pi, log_std=ws.log_std, tanh_ls=ws.tanh_ls, xa=ws.xa,
+                        rng=rng)
         if self._records(step):  # what actor.log() histograms (curl_sac.py:92-93): pre-squash mean and std
             self.actor.outputs['mu'], self.actor.outputs['std'] = ws.a_out[:, :A].clone(), ws.log_std.exp()
         # (the data gradient through the LayerNorms needs the saves too; dropout: the critic twins under tags 5 / 6)
         q_ln = self.critic.twin_ln(*ws.q_ln_saves, drop=self._dropout(rng, dropout_rng)(5))
-        Mq = self.critic.out_dim
-        _mlp_fwd(ws.xa, 0, self.critic.twin(), 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.q, ln=q_ln)
-        # actor / alpha losses and d(loss)/dQ: inside the backward launch of the Q functions' last layer
+        self._twin_fwd(ws, self.critic, q_ln, ws.q)
         # backward: Q -> pi -> trunk -> LN -> fc (encoder detached, curl_sac.py:375-376)
-        al = (dict(kind=2, A=A, twin_stride=B, q=ws.q, log_pi=ws.log_pi, log_std=ws.log_std, log_alpha=self.log_alpha,
-                   target_entropy=float(self.target_entropy), scalars=ws.scalars[1:5], dq=ws.dq,
-                   dlog_alpha=self.log_alpha.grad),
-              lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, self.log_alpha, float(self.target_entropy), B,
-                                     ws.scalars[1:5], ws.dq, self.log_alpha.grad))
-        if self.critic_quantiles:  # (DESIGN.md 7h: the mean of all atoms in place of min(Q1, Q2))
-            al = (None, lambda: ops.tqc_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, self.log_alpha,
-                                                   float(self.target_entropy), B, Mq, ws.scalars[1:5], ws.dq, B * Mq,
-                                                   self.log_alpha.grad))
-        _mlp_bwd(ws.xa, 0, self.critic.twin(), None, 2, B, F + A, H, Mq, ws.q_h1, ws.q_h2, ws.dq, ws.q_dh2, ws.q_dh1,
-                 ws.dxa, loss=al, ln=q_ln)
+        self._twin_bwd(ws, q_ln, self._actor_loss(ws), grads=False)
         if step % self.log_interval == 0:
             L.log('train_actor/loss', ws.scalars[1], step)
             L.log('train_actor/target_entropy', self.target_entropy, step)
             L.log('train_actor/entropy', ws.scalars[3], step)
         # d(loss)/d(pi) = the action columns of dxa summed over the twin, read in place
-        ops.actor_head_bwd(None, self.log_alpha, 1.0 / B, nz, ws.pi, ws.log_std, ws.tanh_ls, B, A, lo, hi, ws.a_dout,
-                           twin_dxa=ws.dxa, F=F)
-        _mlp_bwd(ws.z_a, 0, trunk, _Mlp(self.actor.trunk, grads=True), 1, B, F, H, 2 * A, ws.a_h1, ws.a_h2, ws.a_dout,
-                 ws.a_dh2, ws.a_dh1, ws.dz)
-        streams = ops.fc_bwd_streams(F, enc.flat_dim)
-        ln = ops.ln_bwd(ws.dz, ws.xhat_a, ws.rstd_a, aenc.ln.weight, B, F, ws.dfc, dgamma=aenc.ln.weight.grad,
-                        dbeta=aenc.ln.bias.grad, dbias_in=aenc.fc.bias.grad, defer=ws.ln_partial if streams else None)
-        if streams:
-            ops.fc_dw(ws.dfc, h, aenc.fc.weight.grad, B, F, enc.flat_dim, ln=ln)
-        else:
-            ops.linear_dw(ws.dfc, 0, h, 0, aenc.fc.weight.grad, 0, B, F, enc.flat_dim)
-
-        # data parallel: ONE collective for the phase -- the bucket [fc, ln | trunk | words], log_alpha's float64
-        # gradient riding in the words (round 5: an 8-byte all-reduce of its own).  Overlapped schedule: the collective is
-        # asynchronous and, when update() has announced that the CURL phase follows, this phase's two optimizer steps
-        # are taken only after that phase has been enqueued (_finish_actor_step): the CURL phase reads nothing they
-        # write (the actor's own fc / ln / trunk and log_alpha), so the numbers are the reference order's
-        # (curl_sac.py:393-404 before :418-423) and the all-reduce runs underneath the CURL phase's convolutions.
-        rider = (self.log_alpha.grad, self._la_words)
-        if self._dp_active and self._dp_overlap:
-            self._allreduce(self._actor_gbucket, async_op=True, f64_rider=rider)
-            if self._defer_actor_step and not self.log_param_hist_imgs:
-                self._actor_step_pending = True
-            else:
-                self._allreduce_wait()
-        else:
-            self._allreduce(self._actor_gbucket, f64_rider=rider)
-        # (the norm is logged once the step that takes it has been enqueued: a deferred step is not, yet)
-        self._actor_norm_log = (L, step) if self._max_grad_norm is not None and step % self.log_interval == 0 else None
-        if not self._actor_step_pending:
-            self._actor_steps()
+        F, trunk = aenc.feature_dim, self.actor.trunk
+        ops.actor_head_bwd(None, self.log_alpha, 1.0 / B, nz, ws.pi, ws.log_std, ws.tanh_ls, B, A, self.actor.log_std_min,
+                           self.actor.log_std_max, ws.a_dout, twin_dxa=ws.dxa, F=F)
+        _mlp_bwd(ws.z_a, 0, _Mlp(trunk), _Mlp(trunk, grads=True), 1, B, F, self.hidden_dim, 2 * A, ws.a_h1, ws.a_h2,
+                 ws.a_dout, ws.a_dh2, ws.a_dh1, ws.dz)
+        self._encoder_backward(ws, o, ws.dz, ws.xhat_a, ws.rstd_a, aenc, conv_grads=False)
+        self._actor_reduce_and_step(L, step)
         if self.log_param_hist_imgs:
             self.actor.log(L, step)
         if step % self.log_interval == 0:
             L.log('train_alpha/loss', ws.scalars[2], step)
             L.log('train_alpha/value', ws.scalars[4], step)
 
-    _defer_actor_step = False    # set by update(): the CURL phase follows the actor phase (overlapped data parallel)
-    _actor_step_pending = False  # the actor phase has left its optimizer steps to _finish_actor_step()
-    _actor_norm_log = None       # (logger, step) of a logging step while clipping is on, until the actor's step is taken
+    def _actor_reduce_and_step(self, L, step):
+        """The actor phase's reduction and optimizer steps.  Data parallel: ONE collective for the phase -- the bucket
+        [fc, ln | trunk | words], log_alpha's float64 gradient riding in the words.  Overlapped schedule: the collective
+        is asynchronous and, when update() has announced that the CURL phase follows, the two optimizer steps are taken
+        only after that phase has been enqueued (_finish_actor_step): the CURL phase reads nothing they write (the
+        actor's own fc / ln / trunk and log_alpha), so the numbers are the reference order's (curl_sac.py:393-404
+        before :418-423) and the all-reduce runs underneath the CURL phase's convolutions."""
+        overlap = self._dp_active and self._dp_overlap
+        self._allreduce(self._actor_gbucket, async_op=overlap, f64_rider=(self.log_alpha.grad, self._la_words))
+        self._actor_step_pending = bool(overlap and self._defer_actor_step and not self.log_param_hist_imgs)
+        # (the norm is logged once the step that takes it has been enqueued: a deferred step is not, yet)
+        self._actor_norm_log = (L, step) if self._max_grad_norm is not None and step % self.log_interval == 0 else None
+        if not self._actor_step_pending:
+            if overlap:
+                self._allreduce_wait()
+            self._actor_steps()
 
     def _actor_steps(self):
         # actor_optimizer.step() ... log_alpha_optimizer.step() (curl_sac.py:393-404): nothing in between reads
@@ -817,18 +874,25 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             self._allreduce_wait()
             self._actor_steps()
 
+    def _cpc_steps(self):
+        # encoder_optimizer.step() ... cpc_optimizer.step() (curl_sac.py:418-423)
+        if isinstance(self.encoder_optimizer, FlatAdam):
+            FlatAdam.step_pair(self.encoder_optimizer, self.cpc_optimizer)  # both steps in one pass over the encoder
+        else:
+            self._clip_torch(2, self.cpc_optimizer)  # [W | encoder], once: both steps consume the clipped gradient
+            self.encoder_optimizer.step()
+            self.cpc_optimizer.step()
+
     def update_cpc(self, obs_anchor, obs_pos, cpc_kwargs, L, step):
         """curl_sac.py:406-423."""
         self._restore_grad_views()
         oa, op_ = _as_ref(obs_anchor), _as_ref(obs_pos)
-        B = oa.B
+        B, ws = oa.B, self._ws(oa.B)
         enc, tenc, F = self.critic.encoder, self.critic_target.encoder, self.critic.encoder.feature_dim
-        ws = self._ws(B)
         need_anchor = self._anchor_cache is None or self._anchor_cache is not obs_anchor
         need_pos = self._pos_cache is None or self._pos_cache is not obs_pos
         pos_fc_done = self._pos_fc_done and not need_pos
-        self._anchor_cache = self._pos_cache = None
-        self._pos_fc_done = False
+        self._drop_encoder_caches()
         if need_anchor and need_pos:   # (odd steps) both passes in one launch per layer, own weights each
             enc.conv_forward2(oa, ws.acts_main, tenc, op_, ws.acts_tmp)
         elif need_anchor:
@@ -859,24 +923,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             ops.linear_dx(ws.dlogits, 0, ws.WzT, 0, ws.dz, 0, B, B, F)             # d z_a
             ops.linear_dw(ws.dlogits, 0, ws.z_c, 0, ws.dWzT, 0, B, B, F)           # d (W z_pos^T)^T
             ops.linear_dw(ws.dWzT, 0, ws.z_pos, 0, W.grad, 0, B, F, F)             # d W
-        # data parallel: the bucket is [W | convs | fc, ln]; the encoder gradients are reduced ONCE and consumed by
-        # both encoder_optimizer and cpc_optimizer
-        e1 = self._lay["enc"][1]
-        if self._dp_active and self._dp_overlap:
-            cut = self._grad_offset(enc.fc.weight, self._critic_gflat)
-            self._encoder_backward(ws, oa, ws.dz, ws.xhat_c, ws.rstd_c, enc, ln_token=token,
-                                   dense_done=lambda: self._allreduce(self._critic_gflat[cut:e1], async_op=True))
-            self._allreduce(self._critic_gflat[0:cut], async_op=True)
-            self._allreduce_wait()
-        else:
-            self._encoder_backward(ws, oa, ws.dz, ws.xhat_c, ws.rstd_c, enc, ln_token=token)
-            self._allreduce(self._critic_gflat[0:e1])
-        if isinstance(self.encoder_optimizer, FlatAdam):
-            FlatAdam.step_pair(self.encoder_optimizer, self.cpc_optimizer)  # both steps in one pass over the encoder
-        else:
-            self._clip_torch(2, self.cpc_optimizer)  # [W | encoder], once: both steps consume the clipped gradient
-            self.encoder_optimizer.step()
-            self.cpc_optimizer.step()
+        self._encoder_backward_reduced(ws, oa, ws.dz, 0, self._lay["enc"][1], ln_token=token)
+        self._cpc_steps()
         if step % self.log_interval == 0:
             L.log('train/curl_loss', ws.scalars[5], step)
             if self._max_grad_norm is not None:
@@ -1039,19 +1087,23 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     def _leading_phases(self, sample, step):
         """The phases of a leading sub-step (utd_ratio > 1) on a drawn minibatch: logged to nobody, nothing recorded."""
         self._utd_leading = True
-        try:
+        try:  # (one that raises: no later sub-step runs, _update_phases has reset the hand-over state)
             self._update_phases(sample, _NullLog(), step, leading=True)
-        except BaseException:
-            # no later sub-step runs; the next call starts as after any failed update
-            self._soft_update_hint = self._soft_update_done = False
-            raise
         finally:
             self._utd_leading = False
 
     def _update_phases(self, sample, L, step, only_cpc=False, noise=None, leading=False):
         """The phases of one update on a drawn minibatch (curl_sac.py:431-451).  ``leading`` (_leading_phases): the critic
         phase and, by ``step``, the target soft update -- the update kind (actor=False, soft, cpc=False) whatever the
-        other frequencies say."""
+        other frequencies say.  A phase that raises: the next call starts as a fresh one (_reset_handover) -- the
+        collective of a deferred actor step is waited for and dropped with the step, not left to a later update."""
+        try:
+            self._phases(sample, L, step, only_cpc, noise, leading)
+        except BaseException:
+            self._reset_handover()
+            raise
+
+    def _phases(self, sample, L, step, only_cpc, noise, leading):
         obs, action, reward, next_obs, not_done, cpc_kwargs = sample
         noise_c, noise_a = noise if noise is not None else (None, None)
         if step % self.log_interval == 0 and not leading:
@@ -1062,11 +1114,10 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         do_cpc = (not self.pixel_sac) and step % self.cpc_update_freq == 0 and not leading
         if not only_cpc:
             soft = step % self.critic_target_update_freq == 0
+            # (the hints are set around the phase they are for: a phase called by hand sees idle values)
             self._soft_update_hint, self._soft_update_done = soft, False
-            try:
-                self.update_critic(obs, action, reward, next_obs, not_done, L, step, noise=noise_c)
-            finally:
-                self._soft_update_hint = False
+            self.update_critic(obs, action, reward, next_obs, not_done, L, step, noise=noise_c)
+            self._soft_update_hint = False
             # The target soft update reads the critic's parameters, which the actor phase does not touch (it steps the
             # actor's own tensors and log_alpha): applied BEFORE the actor phase it gives the same numbers as after
             # it (curl_sac.py:437-445), and the target encoder is then final when the actor phase encodes obs -- so
@@ -1078,11 +1129,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
                 if do_cpc and isinstance(cpc_kwargs.get("obs_pos"), ObsRef):
                     self._pos_hint = cpc_kwargs["obs_pos"]
                 self._defer_actor_step = do_cpc
-                try:
-                    self.update_actor_and_alpha(obs, L, step, noise=noise_a)
-                finally:
-                    self._pos_hint = None
-                    self._defer_actor_step = False
+                self.update_actor_and_alpha(obs, L, step, noise=noise_a)
+                self._pos_hint, self._defer_actor_step = None, False
 
         if do_cpc:
             obs_anchor, obs_pos = cpc_kwargs["obs_anchor"], cpc_kwargs["obs_pos"]
@@ -1173,7 +1221,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
                 torch.cuda.set_rng_state(ck["rng"]["cuda"], self.device)
         self._load_reset_checkpoint(ck)
         self._load_redo_checkpoint(ck)
-        self._anchor_cache = None
+        self._drop_encoder_caches()
         # captured graphs hold the addresses of log_alpha's Adam moments, which load_state_dict has just replaced
         self._drop_graphs()
         return ck["step"]
