@@ -66,6 +66,7 @@ SIGNATURES = {
     "curla_fc_ln_fwd": [vp, c_int, c_ll, c_int, vp, vp, vp, c_int, c_int, c_float, vp, vp, vp, vp, c_int, vp, vp, c_int,
                         vp],
     "curla_critic_td_loss": [vp, vp, c_ll, vp, vp, vp, vp, c_float, c_int, vp, vp, vp, vp],
+    "curla_critic_td_loss_views": [vp, vp, c_ll, vp, vp, vp, vp, c_float, c_int, vp, vp, vp, vp],
     "curla_soft_update2": [vp, vp, c_size_t, c_size_t, c_float, c_float, c_float, c_float, vp],
     "curla_shrink_perturb2": [vp, vp, vp, c_size_t, c_size_t, c_float, c_float, c_float, c_float, vp],
     "curla_dormant_colsum": [vp, c_ll, c_int, c_int, c_int, vp, c_ll, vp],
@@ -143,6 +144,7 @@ SIGNATURES = {
     "curla_tqc_critic_loss": [vp, c_ll, vp, c_ll, vp, vp, vp, vp, c_float, c_int, c_int, c_int, vp, c_ll, vp, vp, vp],
     "curla_tqc_actor_loss": [vp, c_ll, vp, vp, c_int, vp, c_float, c_int, c_int, vp, vp, c_ll, vp, vp],
     "curla_curl_ce": [vp, c_int, c_int, vp, vp, vp, vp],
+    "curla_curl_ce_views": [vp, c_int, c_int, vp, vp, vp, vp],
     "curla_mean": [vp, c_int, vp, vp],
     "curla_soft_update": [vp, vp, c_size_t, c_float, c_float, vp],
     "curla_crop_nchw": [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp],

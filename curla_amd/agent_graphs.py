@@ -116,15 +116,18 @@ class _UpdateGraphsMixin:
                 self.cpc_update_freq, self._dp_active, self._dp_overlap, id(self._dp_group) if self._dp_active else 0,
                 hyper, self._graph_rb_key(), self._max_grad_norm) + \
             ((float(self.critic_dropout),) if self.critic_dropout else ()) + \
-            ((("quantiles", self.critic_quantiles, self.critic_drop_quantiles),) if self.critic_quantiles else ())
-        # (0, for either: the key of an agent without the keyword)
+            ((("quantiles", self.critic_quantiles, self.critic_drop_quantiles),) if self.critic_quantiles else ()) + \
+            ((("aug_views", 2),) if self.aug_views == 2 else ())
+        # (0, for either, and one view: the key of an agent without the keyword)
 
     def _graph_rb_key(self):
         """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value
         (n_envs as the stride of the chain walks)."""
         rb = getattr(self, "_graph_rb", None)
         n = getattr(rb, "n_step", 1)
-        return ((n, float(rb.discount)) if n > 1 else (1, None)) + (getattr(rb, "pos_offset", 0), getattr(rb, "n_envs", 1))
+        views = getattr(rb, "aug_views", 1)  # (held by no graph: the entry makes a changed buffer re-capture)
+        return ((n, float(rb.discount)) if n > 1 else (1, None)) + \
+            (getattr(rb, "pos_offset", 0), getattr(rb, "n_envs", 1)) + ((("aug_views", views),) if views == 2 else ())
 
     def _graph_tail(self, kind, B):
         """The 80 control bytes of one graphed update (ReplayBuffer.GRAPH_TAIL) -- and the host-side bookkeeping of
@@ -178,6 +181,7 @@ class _UpdateGraphsMixin:
 
     def _update_graphed(self, rb, L, step):
         self._check_n_step(rb)
+        self._check_aug_views(rb)
         key = self._graph_key()
         if self._graphs and key != self._graph_key_at_capture:
             self._drop_graphs()  # a value the graphs hold as a kernel argument has been edited since the capture

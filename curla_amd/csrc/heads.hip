@@ -21,7 +21,7 @@ namespace {
 #include "mlp_ln.h"        // mlp_ln_relu_fwd_kernel<NF>, mlp_ln_bwd_kernel<NF>, mlp_ln_param_grad_kernel (the critics' LayerNorm)
 #include "mlp_drop_ln.h"   // mlp_drop_ln_relu_fwd_kernel<NF>, mlp_drop_ln_bwd_kernel<NF> (DroQ's dropout in front of that LayerNorm)
 #include "mlp_out.h"       // mlp_out_fwd_kernel<HEAD, R, LDSW>, mlp_out_bwd_kernel<GEN>, the policy head's three kernels
-#include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss, actor_loss, curl_ce
+#include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss(_views), actor_loss, curl_ce<VIEWS>
 #include "tqc.h"           // tqc_critic_loss_kernel, tqc_actor_loss_kernel (truncated quantile critics)
 #include "curl_head.h"     // curl_head_kernel<NTILE>
 #include "redo.h"          // dormant_colsum_kernel, dormant_mask_kernel, redo_recycle_kernel (dormant-neuron scores, ReDo)
@@ -582,6 +582,15 @@ int curla_critic_td_loss(const float* q, const float* tq, long long twin_stride,
                 reward, not_done, log_alpha, discount, B, target_q, loss, dq);
 }
 
+int curla_critic_td_loss_views(const float* q, const float* tq, long long twin_stride, const float* log_pi,
+                               const float* reward, const float* not_done, const double* log_alpha, float discount,
+                               int B, float* target_q, float* loss, float* dq, void* stream) {
+  CURLA_REQUIRE(q && tq && log_pi && reward && not_done && log_alpha && target_q && loss && dq && B > 0 && B % 2 == 0 &&
+                twin_stride >= B);
+  return launch(critic_td_loss_views_kernel, dim3(1), 256, 0, static_cast<hipStream_t>(stream), q, tq, twin_stride, log_pi,
+                reward, not_done, log_alpha, discount, B, target_q, loss, dq);
+}
+
 int curla_actor_loss(const float* q, long long twin_stride, const float* log_pi, const float* log_std, int A,
                      const double* log_alpha, float target_entropy, int B, float* scalars4, float* dq,
                      double* dlog_alpha, void* stream) {
@@ -617,7 +626,15 @@ int curla_tqc_actor_loss(const float* q, long long q_twin_stride, const float* l
 int curla_curl_ce(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits, void* stream) {
   CURLA_REQUIRE(logits && row_loss && B > 0 && ld >= B);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = launch(curl_ce_kernel, dim3((B + 3) / 4), 256, 0, st, logits, B, ld, row_loss, dlogits);
+  const int rc = launch(curl_ce_kernel<false>, dim3((B + 3) / 4), 256, 0, st, logits, B, ld, row_loss, dlogits);
+  if (rc != CURLA_OK || !loss) return rc;
+  return launch(mean_kernel, dim3(1), 256, 0, st, row_loss, B, loss);  // only when it is logged
+}
+
+int curla_curl_ce_views(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits, void* stream) {
+  CURLA_REQUIRE(logits && row_loss && B > 0 && B % 2 == 0 && ld >= B);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch(curl_ce_kernel<true>, dim3((B + 3) / 4), 256, 0, st, logits, B, ld, row_loss, dlogits);
   if (rc != CURLA_OK || !loss) return rc;
   return launch(mean_kernel, dim3(1), 256, 0, st, row_loss, B, loss);  // only when it is logged
 }

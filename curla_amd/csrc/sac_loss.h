@@ -76,6 +76,52 @@ __global__ void critic_td_loss_kernel(const float* q, const float* tq, long long
   if (threadIdx.x == 0) loss[0] = s1 * inv + s2 * inv;
 }
 
+// One position's TD target by the operations the loop of critic_td_loss_kernel compiles to for gfx950 -- alpha * log_pi
+// and not_done * discount rounded (one packed multiply), the subtraction from the min rounded, the last multiply-add
+// fused -- stated explicitly: a loop with other surroundings is contracted otherwise (the subtraction fused as well), and
+// two identical views must give that kernel's target bit for bit (tests/test_gpu_aug_views.py holds the two together).
+__device__ __forceinline__ float td_target_pinned(float tq1, float tq2, float alpha, float log_pi, float reward,
+                                                  float not_done, float discount) {
+#pragma clang fp contract(off)
+  const float v = fminf(tq1, tq2) - alpha * log_pi;
+  return __builtin_fmaf(not_done * discount, v, reward);
+}
+
+// critic_td_loss_kernel over two augmented views of every transition (DrQ's K = 2, M = 2; B even): positions p and
+// p + H, H = B / 2, are one transition seen twice.  Both get the mean of their two targets, tbar = 0.5 (t_p + t_{p+H}),
+// each t by the arithmetic above; loss = (1 / H) sum over all B positions and both twins of (q - tbar)^2 -- the two
+// views' MSEs over H transitions, summed --, dq = 2 (q - tbar) (1 / H).  One thread per pair, so target_q's two copies
+// are one value; the block sums are the fixed-order ones.
+__global__ void critic_td_loss_views_kernel(const float* q, const float* tq, long long sTwin, const float* log_pi,
+                                            const float* reward, const float* not_done, const double* log_alpha,
+                                            float discount, int B, float* target_q, float* loss, float* dq) {
+  __shared__ float sm[4];
+  float a1 = 0.f, a2 = 0.f;
+  const int H = B / 2;
+  const float inv = 1.f / H;
+  const float alpha = (float)exp(*log_alpha);
+  for (int p = threadIdx.x; p < H; p += 256) {
+    float t2[2];
+    for (int k = 0; k < 2; ++k) {
+      const int b = p + k * H;
+      t2[k] = td_target_pinned(tq[b], tq[sTwin + b], alpha, log_pi[b], reward[b], not_done[b], discount);
+    }
+    const float t = 0.5f * (t2[0] + t2[1]);
+    for (int k = 0; k < 2; ++k) {
+      const int b = p + k * H;
+      target_q[b] = t;
+      const float d1 = q[b] - t, d2 = q[sTwin + b] - t;
+      a1 += d1 * d1;
+      a2 += d2 * d2;
+      dq[b] = 2.f * d1 * inv;
+      dq[sTwin + b] = 2.f * d2 * inv;
+    }
+  }
+  const float s1 = block_sum_256(a1, sm);
+  const float s2 = block_sum_256(a2, sm);
+  if (threadIdx.x == 0) loss[0] = s1 * inv + s2 * inv;
+}
+
 // actor/alpha losses and their seeds                                  (curl_sac.py:378-399)
 // scalars: [0] actor_loss [1] alpha_loss [2] entropy mean [3] alpha
 __global__ void actor_loss_kernel(const float* q, long long sTwin, const float* log_pi, const float* log_std, int A,
@@ -109,16 +155,22 @@ __global__ void actor_loss_kernel(const float* q, long long sTwin, const float* 
 }
 
 // CURL InfoNCE: loss = mean_a( logsumexp_b(l[a][:]) - l[a][a] ); dl = (softmax - I)/B
+// VIEWS (two augmented views per transition, B even): row a's partner column (a + B/2) % B -- the other view of the
+// anchor's own transition, no negative -- is left out of the max and of the sum, and its dl is exactly 0.
+template <bool VIEWS>
 __global__ void curl_ce_kernel(const float* logits, int B, int ld, float* row_loss, float* dlogits) {
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= B) return;
   const float* l = logits + (size_t)row * ld;
+  const int partner = VIEWS ? (row + B / 2) % B : -1;
   float mx = -INFINITY;
-  for (int j = lane; j < B; j += 64) mx = fmaxf(mx, l[j]);
+  for (int j = lane; j < B; j += 64)
+    if (!VIEWS || j != partner) mx = fmaxf(mx, l[j]);
   mx = wave_max(mx);
   float se = 0.f;
-  for (int j = lane; j < B; j += 64) se += expf(l[j] - mx);
+  for (int j = lane; j < B; j += 64)
+    if (!VIEWS || j != partner) se += expf(l[j] - mx);
   se = wave_sum(se);
   const float lse = logf(se) + mx;
   if (lane == 0) row_loss[row] = lse - l[row];
@@ -126,7 +178,7 @@ __global__ void curl_ce_kernel(const float* logits, int B, int ld, float* row_lo
     const float inv = 1.f / B;
     for (int j = lane; j < B; j += 64) {
       const float p = expf(l[j] - lse);
-      dlogits[(size_t)row * ld + j] = (p - (j == row ? 1.f : 0.f)) * inv;
+      dlogits[(size_t)row * ld + j] = VIEWS && j == partner ? 0.f : (p - (j == row ? 1.f : 0.f)) * inv;
     }
   }
 }

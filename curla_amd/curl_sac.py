@@ -51,6 +51,11 @@ def _no_drop(tag):
     return None
 
 
+def _check_views(v):
+    """The augmented views per transition: the ``int`` 1 or 2 (a bool, a float or a string is not one)."""
+    return _check_int(v, 1, 2, "aug_views: %r is not the int 1 or 2" % (v,))
+
+
 def _check_utd_ratio(g):
     """The update-to-data ratio: an ``int >= 1`` (a bool, a float or a string is not one)."""
     return _check_int(g, 1, None, "utd_ratio: %r is not an int >= 1" % (g,))
@@ -124,8 +129,8 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0, reset_encoder_keep=1.0,
-                 reset_seed=0, critic_quantiles=0, critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1,
+    def __call__(cls, *args, aug_views=1, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0,
+                 reset_encoder_keep=1.0, reset_seed=0, critic_quantiles=0, critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1,
                  critic_dropout=0.0, critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
         agent.redo_interval = _check_redo_interval(redo_interval)
@@ -139,6 +144,11 @@ class _AgentType(type):
         agent.critic_layer_norm = bool(critic_layer_norm)
         agent.critic_dropout = _check_dropout(critic_dropout, agent.critic_layer_norm)
         agent.utd_ratio = _check_utd_ratio(utd_ratio)
+        if _check_views(aug_views) == 2:  # (1: the instance is the one without the keyword, down to its __dict__)
+            if agent.critic_quantiles:
+                raise ValueError("aug_views = 2 is not combined with critic_quantiles > 0: the mean of two views' "
+                                 "targets would have to be one of their pooled, truncated atom sets, which is out of scope")
+            agent.aug_views = 2
         weight_decay = check_weight_decay(weight_decay)
         agent.__init__(*args, **kwargs)
         if weight_decay != 0:  # (0: the optimizers are built exactly as without the keyword)
@@ -173,13 +183,19 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     (``redo_pass``) on its minibatch -- the dormant-neuron scores of the six hidden layers of Q1, Q2 and the actor trunk
     (``dormant_counts``, ``dormant_fractions``, ``dormant_report()``) and, unless ``redo_recycle=False``, ReDo's recycling
     of the units whose score is <= ``redo_tau`` (default 0.1) with fresh values from the reset stream (agent_redo.py;
-    DESIGN.md 7j).  All three are attributes that may be edited between calls."""
+    DESIGN.md 7j).  All three are attributes that may be edited between calls.
+    ``aug_views=2`` (default 1: nothing changes; with a ``ReplayBuffer(aug_views=2)``, and ``update`` checks that the two
+    agree): DrQ's K = 2, M = 2 -- a minibatch of B positions is B / 2 transitions, each under two independent
+    augmentations at positions b and b + B / 2.  The critic phase regresses both views' Q estimates on the mean of the two
+    views' TD targets, the CURL phase does not count a position's partner among its negatives; the actor phase sees all B
+    positions.  Fixed at construction.  Not with ``critic_quantiles``."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
     utd_ratio = 1
     critic_quantiles = 0
     critic_drop_quantiles = 0
+    aug_views = 1
 
     def __init__(
         self,
@@ -619,14 +635,21 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     def _critic_loss(self, ws, reward, not_done, per, drop_q):
         """target_Q = r + not_done * gamma * (min Q' - alpha log pi'), the two MSE terms and their gradient dq
         (curl_sac.py:353-361).  ``critic_quantiles``: the quantile Huber loss of the critic's atoms against
-        the kept target atoms, always a launch of its own.  ``per``, a prioritized minibatch: the loss is launched here,
-        the importance weights scale dq and the loss in place and the drawn rows get their new priorities -- all on the
-        device --, and the backward runs on the weighted dq it finds: no descriptor, None."""
+        the kept target atoms, always a launch of its own.  ``aug_views = 2``: both views' estimates against
+        the mean of the two views' targets, a launch of its own as well.  ``per``, a prioritized minibatch: the loss is
+        launched here, the importance weights scale dq and the loss in place and the drawn rows get their new priorities
+        -- all on the device --, and the backward runs on the weighted dq it finds: no descriptor, None."""
         B, Mq = ws.log_pi.shape[0], self.critic.out_dim
         la, gamma, total = self.log_alpha, self.discount, ws.scalars[0:1]
         if self.critic_quantiles:
             loss = (None, lambda: ops.tqc_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done, la, gamma,
                                                       B, Mq, drop_q, ws.dq, B * Mq, ws.q_row_loss, total))
+        elif self.aug_views == 2:
+            if per is not None:
+                raise ValueError("aug_views = 2: a prioritized minibatch is not supported (its rows are drawn per "
+                                 "position): use ReplayBuffer(prioritized=False)")
+            return None, lambda: ops.critic_td_loss_views(ws.q, ws.tq, B, ws.log_pi, reward, not_done, la, gamma, B,
+                                                          ws.target_q, total, ws.dq)
         else:
             loss = (dict(kind=1, twin_stride=B, q=ws.q, target_q_twin=ws.tq, log_pi=ws.log_pi, reward=reward,
                          not_done=not_done, log_alpha=la, discount=gamma, target_q=ws.target_q, scalars=total, dq=ws.dq),
@@ -913,13 +936,15 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         # logits, cross-entropy, d z_a, the LayerNorm backward and the partial sums of dW in ONE launch where the
         # shapes allow (and the fc backward is a streaming kernel, whose extra workgroup finishes the partial sums)
         token = None
-        if ops.curl_head_supported(B, F) and ops.fc_bwd_streams(F, enc.flat_dim) and not self._curl_unfused:
+        views = self.aug_views == 2  # (the partner column is no negative: the unfused route, the fused head has no mask)
+        if ops.curl_head_supported(B, F) and ops.fc_bwd_streams(F, enc.flat_dim) and not self._curl_unfused and not views:
             token = ops.curl_head(ws.z_c, ws.z_pos, ws.WzT, ws.xhat_c, ws.rstd_c, enc.ln.weight, B, F, ws.row_loss, ws.dfc,
                                   ws.ln_partial, ws.w_partial, enc.ln.weight.grad, enc.ln.bias.grad, enc.fc.bias.grad,
                                   W.grad, loss=ws.scalars[5:6] if logged else None, logits=ws.logits, dz=ws.dz)
         else:
             ops.linear_fwd(ws.z_c, 0, ws.WzT, 0, None, 0, ws.logits, 0, B, B, F)   # z_a (W z_pos^T)
-            ops.curl_ce(ws.logits, B, B, ws.row_loss, ws.scalars[5:6] if logged else None, ws.dlogits)
+            ce = ops.curl_ce_views if views else ops.curl_ce
+            ce(ws.logits, B, B, ws.row_loss, ws.scalars[5:6] if logged else None, ws.dlogits)
             ops.linear_dx(ws.dlogits, 0, ws.WzT, 0, ws.dz, 0, B, B, F)             # d z_a
             ops.linear_dw(ws.dlogits, 0, ws.z_c, 0, ws.dWzT, 0, B, B, F)           # d (W z_pos^T)^T
             ops.linear_dw(ws.dWzT, 0, ws.z_pos, 0, W.grad, 0, B, F, F)             # d W
@@ -1029,6 +1054,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         refused with G > 1."""
         self._restore_grad_views()
         self._check_n_step(replay_buffer)
+        self._check_aug_views(replay_buffer)
         self._maybe_reset(step)  # (reset_interval: in front of every sub-step, graphed or not)
         if self.utd_ratio != 1 or type(self.utd_ratio) is not int:  # (the attribute may have been edited)
             if _check_utd_ratio(self.utd_ratio) > 1 and noise is not None and not only_cpc:
@@ -1044,6 +1070,14 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         if getattr(replay_buffer, "n_step", 1) > 1 and replay_buffer.discount != self.discount:
             raise ValueError("replay_buffer.discount = %r (n_step = %d) differs from the agent's discount = %r"
                              % (replay_buffer.discount, replay_buffer.n_step, self.discount))
+
+    def _check_aug_views(self, replay_buffer):
+        """The agent's losses pair position b with b + B / 2 exactly when the buffer draws them as one transition: the two
+        must say the same (a buffer without the attribute draws one view)."""
+        views = getattr(replay_buffer, "aug_views", 1)
+        if views != self.aug_views:
+            raise ValueError("replay_buffer.aug_views = %r differs from the agent's aug_views = %r"
+                             % (views, self.aug_views))
 
     def _update_eager(self, replay_buffer, L, step, only_cpc=False, noise=None):
         leading = 0 if only_cpc else self.utd_ratio - 1
@@ -1188,6 +1222,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             "optimizers": {k: self._convert_opt_state(o, o.state_dict(), True) for k, o in self._optimizers().items()},
             "rng": rng, "critic_dropout": float(self.critic_dropout), "utd_ratio": int(self.utd_ratio),
             "critic_quantiles": int(self.critic_quantiles), "critic_drop_quantiles": int(self.critic_drop_quantiles),
+            **({"aug_views": 2} if self.aug_views == 2 else {}),  # (1: the file of an agent without the keyword)
             **self._reset_checkpoint(), **self._redo_checkpoint(),
         }, path)
 
@@ -1202,6 +1237,9 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         if ck.get("utd_ratio", 1) != self.utd_ratio:  # (a file from before the keyword: 1)
             warnings.warn("curla_amd: the checkpoint was written with utd_ratio = %r; this agent keeps its own, %r"
                           % (ck.get("utd_ratio", 1), self.utd_ratio), RuntimeWarning, stacklevel=2)
+        if ck.get("aug_views", 1) != self.aug_views:  # (a file from before the keyword: 1)
+            warnings.warn("curla_amd: the checkpoint was written with aug_views = %r; this agent keeps its own, %r"
+                          % (ck.get("aug_views", 1), self.aug_views), RuntimeWarning, stacklevel=2)
         self.CURL.load_state_dict(ck["curl"])
         self.actor.load_state_dict(ck["actor"])
         self.critic.load_state_dict(ck["critic"])

@@ -599,6 +599,13 @@ def critic_td_loss(q, tq, twin_stride, log_pi, reward, not_done, log_alpha, disc
          discount, B, ptr(target_q), ptr(loss), ptr(dq), stream())
 
 
+def critic_td_loss_views(q, tq, twin_stride, log_pi, reward, not_done, log_alpha, discount, B, target_q, loss, dq):
+    """critic_td_loss over two augmented views per transition (curla_critic_td_loss_views; B even): positions b and
+    b + B/2 share the mean of their two targets, loss and dq are over B/2 transitions."""
+    call("curla_critic_td_loss_views", ptr(q), ptr(tq), twin_stride, ptr(log_pi), ptr(reward), ptr(not_done),
+         ptr(log_alpha), discount, B, ptr(target_q), ptr(loss), ptr(dq), stream())
+
+
 def actor_loss(q, twin_stride, log_pi, log_std, A, log_alpha, target_entropy, B, scalars4, dq, dlog_alpha):
     call("curla_actor_loss", ptr(q), twin_stride, ptr(log_pi), ptr(log_std), A, ptr(log_alpha), target_entropy, B,
          ptr(scalars4), ptr(dq), ptr(dlog_alpha), stream())
@@ -639,6 +646,11 @@ def curl_head(z_a, z_pos, wz, xhat, rstd, gamma, B, F_, row_loss, dfc, ln_partia
 
 def curl_ce(logits, B, ld, row_loss, loss, dlogits=None):
     call("curla_curl_ce", ptr(logits), B, ld, ptr(row_loss), ptr(loss), ptr(dlogits), stream())
+
+
+def curl_ce_views(logits, B, ld, row_loss, loss, dlogits=None):
+    """curl_ce without row a's partner column (a + B/2) % B among the negatives (curla_curl_ce_views; B even)."""
+    call("curla_curl_ce_views", ptr(logits), B, ld, ptr(row_loss), ptr(loss), ptr(dlogits), stream())
 
 
 def mean(x, n, out):

@@ -91,7 +91,16 @@ class ReplayBuffer(_ReplayWriteMixin, _ReplaySampleMixin):
     reset stack and so breaks the chain by itself, as a time-limit truncation does.  The newest N rows always carry 0.
     ``add`` refuses such a buffer; ``add_batch`` and ``load`` take whole vector steps in row order (step-major,
     environment-minor).  Not combined with ``dedup_frames`` (its match of recent frames is per stream).  Read-only after
-    construction.  ``n_envs=1`` (default): nothing is allocated, launched or laid out differently."""
+    construction.  ``n_envs=1`` (default): nothing is allocated, launched or laid out differently.
+
+    ``aug_views=2`` (beyond the reference; DrQ, Kostrikov et al. 2021, K = M = 2) makes a minibatch of B positions hold
+    B / 2 transitions, each at positions b and b + B / 2: ``draw_indices`` draws ``randint(0, n, size=B // 2)`` where it
+    draws B rows otherwise and returns them tiled twice.  Everything behind the rows is per position and unchanged -- the
+    augmentation's words, ``draw_aug``, the block, the launches --, so the two positions of a transition get independent
+    augmentations of obs, next_obs and the positive, and share action, reward, not_done (and the n-step composition and
+    the positive's walk, which start from the same row).  ``batch_size`` must be even; not with ``prioritized=True``.
+    Injected ``indices=`` are taken as they are.  The learner's half is ``CurlSacAgent(aug_views=2)``, which checks that
+    the two agree.  Read-only after construction.  ``aug_views=1`` (default): the draws are the ones above."""
 
     N_SAMPLE_SLOTS = 2  # minibatches whose references may be alive at once (the current one + one drawn ahead)
     EVENT_EVERY = 8     # index uploads per recorded event (16 pinned slots)
@@ -102,7 +111,18 @@ class ReplayBuffer(_ReplayWriteMixin, _ReplaySampleMixin):
 
     def __init__(self, obs_shape, action_shape, capacity, batch_size, device, augmentor, transform=None,
                  dedup_frames=False, frame_capacity=None, staged_aug=False, n_step=1, discount=None,
-                 prioritized=False, per_alpha=0.6, per_beta=0.4, per_eps=1e-6, pos_offset=0, n_envs=1):
+                 prioritized=False, per_alpha=0.6, per_beta=0.4, per_eps=1e-6, pos_offset=0, n_envs=1, aug_views=1):
+        self._aug_views = _checked_int("aug_views", aug_views, 1)
+        if self._aug_views > 2:
+            raise ValueError("aug_views must be 1 or 2, got %r" % (aug_views,))
+        if self._aug_views == 2:
+            if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size % 2 != 0:
+                raise ValueError("aug_views = 2 puts the two views of a transition at positions b and b + batch_size / 2: "
+                                 "batch_size = %r is not an even int" % (batch_size,))
+            if prioritized:
+                raise ValueError("aug_views = 2 is not combined with prioritized=True: a prioritized buffer's rows are "
+                                 "drawn on the device from per-position targets, so two positions cannot be told to "
+                                 "draw one transition")
         self._n_envs = _checked_int("n_envs", n_envs, 1)
         if capacity % n_envs != 0:
             raise ValueError("capacity = %d is not a multiple of n_envs = %d" % (capacity, n_envs))
@@ -222,6 +242,11 @@ class ReplayBuffer(_ReplayWriteMixin, _ReplaySampleMixin):
     def n_envs(self):
         """Environments that share the ring (class docstring); fixed at construction: it decides the row layout."""
         return self._n_envs
+
+    @property
+    def aug_views(self):
+        """Augmented views per drawn transition, 1 or 2 (class docstring); fixed at construction."""
+        return self._aug_views
 
     # ------------------------------------------------------------------ persistence
     def stacks(self, lo, hi, which=0):

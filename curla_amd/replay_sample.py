@@ -145,13 +145,18 @@ class _ReplaySampleMixin:
         m00 m01 | m02 m10 | m11 m12.
         ``prioritized``: returns (u, offsets), u float64 [B] the stratified targets (k + r_k) / B with
         r = np.random.random_sample(B) drawn where the rows are drawn otherwise -- the rows themselves are drawn by
-        curla_per_sample from u."""
+        curla_per_sample from u.
+        ``aug_views = 2``: ``np.random.randint(0, n, size=B // 2)`` in the place of the B rows, returned tiled twice
+        (``idxs[b + B // 2] == idxs[b]``); the words behind it are drawn for all B positions as ever."""
         B = self.batch_size
         if self.prioritized:
             # the stratified targets instead of the rows: u_k = (k + r_k) / B; the rows are drawn on the device
             if not self.full and self.idx == 0:
                 raise ValueError("cannot sample an empty prioritized buffer")
             idxs = (np.arange(B) + np.random.random_sample(B)) / B
+        elif self._aug_views == 2:
+            # B / 2 transitions, each at positions b and b + B / 2; what follows draws per position as ever
+            idxs = np.tile(np.random.randint(0, self.capacity if self.full else self.idx, size=B // 2), 2)
         else:
             idxs = np.random.randint(0, self.capacity if self.full else self.idx, size=B)
         if self._kind is None:

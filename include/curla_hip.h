@@ -437,6 +437,15 @@ int curla_critic_loss(const float* q, long long twin_stride, const float* target
 int curla_critic_td_loss(const float* q, const float* tq, long long twin_stride, const float* log_pi,
                          const float* reward, const float* not_done, const double* log_alpha, float discount, int B,
                          float* target_q, float* loss, float* dq, void* stream);
+/* curla_critic_td_loss over two augmented views of every transition (DrQ, Kostrikov et al. 2021, K = 2 and M = 2): B is
+ * even and positions b and b + B/2 are one transition under two augmentations.  Each position's target is formed as
+ * above, the pair's mean tbar = 0.5 (t_b + t_{b+B/2}) is written to both places of target_q, loss = (1 / (B/2)) * the
+ * sum over all B positions and both twins of (q - tbar)^2 (the two views' MSEs over B/2 transitions, summed) and dq =
+ * 2 (q - tbar) / (B/2).  One workgroup, fixed-order sums, nothing written between the twins' blocks.  CURLA_ERR_ARG on
+ * a NULL pointer, B < 2, an odd B or twin_stride < B.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_critic_td_loss_views(const float* q, const float* tq, long long twin_stride, const float* log_pi,
+                               const float* reward, const float* not_done, const double* log_alpha, float discount,
+                               int B, float* target_q, float* loss, float* dq, void* stream);
 /* actor_loss, alpha_loss, entropy, alpha -> scalars4; dq = d actor_loss/dq; dlog_alpha (float64 like the
  * reference's log_alpha, curl_sac.py:292) (curl_sac.py:378-399) */
 int curla_actor_loss(const float* q, long long twin_stride, const float* log_pi, const float* log_std, int A,
@@ -465,6 +474,13 @@ int curla_tqc_actor_loss(const float* q, long long q_twin_stride, const float* l
 /* CrossEntropyLoss(logits, arange(B)) and d/dlogits (curl_sac.py:221,411-413); `loss` (the mean of row_loss) may be
  * NULL when the scalar is not going to be logged */
 int curla_curl_ce(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits, void* stream);
+/* curla_curl_ce for a minibatch of two augmented views per transition (B even): row a's partner column (a + B/2) % B
+ * holds the other view of the anchor's own transition and is no negative -- it is left out of the row's logsumexp and
+ * its dlogits entry is exactly 0; everything else as above (the mean is still over the B rows).  What curla_curl_ce
+ * gives on logits whose partner entries are -inf, bit for bit.  CURLA_ERR_ARG on an odd B.  Additive: CURLA_ABI_VERSION
+ * stays 8. */
+int curla_curl_ce_views(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits,
+                        void* stream);
 /* The CURL head in one launch (curl_sac.py:211-222,406-417 and their autograd), given the anchor features z_a, the
  * positives' z_pos and wz = (W z_pos^T)^T = z_pos W^T, all [B][F]: logits = z_a wz^T (optionally stored), row_loss[a] =
  * logsumexp(logits[a]) - logits[a][a] (their mean into `loss` when it is not NULL), dlogits = (softmax - I) / B
