@@ -16,8 +16,7 @@
 // ---------------------------------------------------------------------------
 __device__ float g_zero16[16];  // where lanes past a reduction range point their operand load (see conv.hip g_zero_px)
 
-constexpr int kFcMaxSteps = 16;  // F <= 64
-
+// (kFcMaxSteps, F <= 64: fc_plan.h)
 struct FcBwdArgs {
   const float* dz;    // [B][F]
   const float* W;     // fc_dx: weight [F][K];  fc_dw: x [B][K]

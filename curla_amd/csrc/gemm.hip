@@ -13,13 +13,14 @@
 //
 // This file: the host side -- the builder of the kernels' argument block, the launch helper, the run-time -> template
 // dispatch that names every instantiation, the C ABI (include/curla_hip.h).  The kernels live in the headers included
-// in place below; which of them a product takes is decided in gemm_plan.h, host-only code.
+// in place below; which of them a product takes is decided in gemm_plan.h and fc_plan.h, host-only code.
 #include <stdlib.h>
 #include <string.h>
 
 #include "common.h"
 #include "options.h"
 #include "gemm_plan.h"
+#include "fc_plan.h"
 
 namespace {
 
@@ -104,15 +105,12 @@ int launch_pair(PairKernel kernel, int threads, const LinearBwdPlan& q, const Ge
   return launch(kernel, (unsigned)(q.n1 + q.n2), threads, 0, st, g1, g2, (int)q.n1, q.gx1, q.gy1, q.gx2, q.gy2, (int)q.n2);
 }
 
-// The one-pass kernel of the encoder fc backward: dx = true, both products (F = 50: 3 tiles on the matrix pipe + 2
-// features on VALU FMAs; F = 49, 51, 52: 4 tiles); dx = false, its weight-gradient half alone (F = 50).  One workgroup
-// per 64 columns and one more for the deferred LayerNorm sums where there are any.
-int launch_fc_bwd(bool dx, const FcBwdArgs& gx, float* dW, const LnReduce& lnr, hipStream_t st) {
-  const int grid = (gx.K + 63) / 64 + (lnr.partial ? 1 : 0);
-  const size_t lds = (size_t)4 * 4 * 4 * 64 * sizeof(f32x4);  // (the 3 + 2 form needs less: 48 KB + 2 KB)
-  if (!dx) return launch(fc_bwd_kernel<13, 3, 2, false>, grid, 256, lds, st, gx, dW, lnr);
-  if (gx.F == 50) return launch(fc_bwd_kernel<13, 3, 2, true>, grid, 256, lds, st, gx, dW, lnr);
-  return launch(fc_bwd_kernel<13, 4, 0, true>, grid, 256, lds, st, gx, dW, lnr);
+// the one-pass kernel of the encoder fc backward as fc_plan.h planned it (fc_one_pass_plan)
+int launch_fc_bwd(const FcOnePassPlan& p, const FcBwdArgs& gx, float* dW, const LnReduce& lnr, hipStream_t st) {
+  const size_t lds = (size_t)p.lds;
+  if (!p.dx) return launch(fc_bwd_kernel<13, 3, 2, false>, p.grid, 256, lds, st, gx, dW, lnr);
+  if (p.nt == 3) return launch(fc_bwd_kernel<13, 3, 2, true>, p.grid, 256, lds, st, gx, dW, lnr);
+  return launch(fc_bwd_kernel<13, 4, 0, true>, p.grid, 256, lds, st, gx, dW, lnr);
 }
 
 }  // namespace
@@ -208,12 +206,10 @@ int curla_gemm_multi(int nprob, const float* const* A, const float* const* B, fl
 int curla_fc_fwd_multi(int nprob, const float* const* x, const float* const* W, float* const* partial, int B, int F, int K,
                        int nsplit, long long split_stride, int x_blocked, void* stream) {
   CURLA_REQUIRE(nprob > 0 && nprob <= 4 && x && W && partial && B > 0 && F > 0 && K > 0 && nsplit > 0);
-  // the instantiated shapes: 50..64 even features (50: three tiles + two features on FMAs), whole 128-row groups, 32-wide
-  // k-slices, at least one slice per split, 32-bit byte offsets; everything else: CURLA_ERR_UNSUPPORTED (the caller
-  // takes curla_gemm_multi)
-  if (F < 50 || F > 64 || F % 2 != 0 || B % 128 != 0 || K % 32 != 0 || nsplit > K / 32 ||
-      (long long)B * K * 4 >= (1LL << 31) || (long long)F * K * 4 >= (1LL << 31) || split_stride % 2 != 0)
-    return CURLA_ERR_UNSUPPORTED;
+  // the instantiated shapes (fc_plan.h); everything else: CURLA_ERR_UNSUPPORTED (the caller takes curla_gemm_multi)
+  FcFwdPlan p;
+  const int prc = fc_fwd_plan(nprob, B, F, K, nsplit, split_stride, curla_opt(kOptGemmMfma), p);
+  if (prc != CURLA_OK) return prc;
   FcFwdArgs g;
   for (int i = 0; i < 4; ++i) {
     g.x[i] = i < nprob ? x[i] : nullptr, g.W[i] = i < nprob ? W[i] : nullptr, g.out[i] = i < nprob ? partial[i] : nullptr;
@@ -222,23 +218,21 @@ int curla_fc_fwd_multi(int nprob, const float* const* x, const float* const* W, 
       if (!aligned16(x[i]) || !aligned16(W[i]) || (reinterpret_cast<uintptr_t>(partial[i]) & 7)) return CURLA_ERR_UNSUPPORTED;
     }
   }
-  g.nprob = nprob, g.B = B, g.F = F, g.K = K, g.nsplit = nsplit, g.nrg = B / 128, g.split_stride = split_stride;
+  g.nprob = nprob, g.B = B, g.F = F, g.K = K, g.nsplit = nsplit, g.nrg = p.nrg, g.split_stride = split_stride;
   g.blocked = x_blocked ? 1 : 0;
-  const int grid = nprob * g.nrg * nsplit;
-  const size_t lds = (size_t)2 * 64 * kFcPitch * sizeof(float);
+  const size_t lds = (size_t)p.lds;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool b3 = curla_opt(kOptGemmMfma) != kGemmMfmaF32;  // option gemm_mfma: f32 keeps the f32-input MFMA
-  if (F == 50) {
-    if (b3) return launch(fc_fwd_kernel<3, 2, true>, grid, 256, lds, st, g);
-    return launch(fc_fwd_kernel<3, 2, false>, grid, 256, lds, st, g);
+  if (p.nt == 3) {
+    if (p.b3) return launch(fc_fwd_kernel<3, 2, true>, p.grid, 256, lds, st, g);
+    return launch(fc_fwd_kernel<3, 2, false>, p.grid, 256, lds, st, g);
   }
-  if (b3) return launch(fc_fwd_kernel<4, 0, true>, grid, 256, lds, st, g);
-  return launch(fc_fwd_kernel<4, 0, false>, grid, 256, lds, st, g);
+  if (p.b3) return launch(fc_fwd_kernel<4, 0, true>, p.grid, 256, lds, st, g);
+  return launch(fc_fwd_kernel<4, 0, false>, p.grid, 256, lds, st, g);
 }
 
 static int fc_bwd_check(const float* dz, const float* big, const float* out, int B, int F, int K) {
   CURLA_REQUIRE(dz && big && out && B > 0 && F > 0 && K > 0);
-  if (F > 4 * kFcMaxSteps || (K % 4) != 0 || !aligned16(big) || !aligned16(out)) return CURLA_ERR_UNSUPPORTED;
+  if (fc_bwd_shape(F, K) != CURLA_OK || !aligned16(big) || !aligned16(out)) return CURLA_ERR_UNSUPPORTED;
   return CURLA_OK;
 }
 
@@ -249,12 +243,12 @@ int curla_fc_dx(const float* dz, const float* W, const float* mask, float* dx, i
   FcBwdArgs g;
   g.dz = dz, g.W = W, g.mask = mask, g.out = dx, g.B = B, g.F = F, g.K = K;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int grid = (K + 63) / 64;
-  const int ks = (F + 3) / 4;
-  if (ks <= 4) return launch(fc_dx_kernel<4>, grid, 256, 0, st, g);
-  if (ks <= 8) return launch(fc_dx_kernel<8>, grid, 256, 0, st, g);
-  if (ks <= 13) return launch(fc_dx_kernel<13>, grid, 256, 0, st, g);
-  return launch(fc_dx_kernel<16>, grid, 256, 0, st, g);
+  FcDxPlan p;
+  if ((rc = fc_dx_plan(F, K, p)) != CURLA_OK) return rc;
+  if (p.ks == 4) return launch(fc_dx_kernel<4>, p.grid, 256, 0, st, g);
+  if (p.ks == 8) return launch(fc_dx_kernel<8>, p.grid, 256, 0, st, g);
+  if (p.ks == 13) return launch(fc_dx_kernel<13>, p.grid, 256, 0, st, g);
+  return launch(fc_dx_kernel<16>, p.grid, 256, 0, st, g);
 }
 
 // a separate launch for the deferred LayerNorm sums, for the shapes whose fc backward does not take the one-pass kernel
@@ -275,19 +269,19 @@ static int fc_dw_impl(const float* dz, const float* x, float* dW, int B, int F, 
   FcBwdArgs g;
   g.dz = dz, g.W = x, g.mask = nullptr, g.out = dW, g.B = B, g.F = F, g.K = K;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (F == 50 && B % 16 == 0 && (long long)B * K * 4 < (1LL << 31)) {  // the one-pass kernel's weight-gradient half
+  FcDwPlan p;
+  if ((rc = fc_dw_plan(B, F, K, lnr.partial != nullptr, p)) != CURLA_OK) return rc;
+  if (p.one_pass) {  // the one-pass kernel's weight-gradient half
     FcBwdArgs gx;
     gx.dz = dz, gx.W = nullptr, gx.mask = x, gx.out = nullptr, gx.B = B, gx.F = F, gx.K = K;
-    return launch_fc_bwd(false, gx, dW, lnr, st);
+    return launch_fc_bwd(p.op, gx, dW, lnr, st);
   }
-  if (lnr.partial && (rc = launch(ln_reduce_kernel, 1, 256, 0, st, lnr)) != CURLA_OK) return rc;
-  const int grid = (K + 63) / 64;
-  const int nt = (F + 15) / 16;
-  const size_t lds = (size_t)4 * nt * 4 * 64 * sizeof(f32x4);  // 16 KB per feature tile
-  if (nt == 1) return launch(fc_dw_kernel<1>, grid, 256, lds, st, g);
-  if (nt == 2) return launch(fc_dw_kernel<2>, grid, 256, lds, st, g);
-  if (nt == 3) return launch(fc_dw_kernel<3>, grid, 256, lds, st, g);
-  return launch(fc_dw_kernel<4>, grid, 256, lds, st, g);
+  if (p.ln_launch && (rc = launch(ln_reduce_kernel, 1, 256, 0, st, lnr)) != CURLA_OK) return rc;
+  const size_t lds = (size_t)p.lds;  // 16 KB per feature tile
+  if (p.nt == 1) return launch(fc_dw_kernel<1>, p.grid, 256, lds, st, g);
+  if (p.nt == 2) return launch(fc_dw_kernel<2>, p.grid, 256, lds, st, g);
+  if (p.nt == 3) return launch(fc_dw_kernel<3>, p.grid, 256, lds, st, g);
+  return launch(fc_dw_kernel<4>, p.grid, 256, lds, st, g);
 }
 
 int curla_fc_dw(const float* dz, const float* x, float* dW, int B, int F, int K, void* stream) {
@@ -307,16 +301,16 @@ static int fc_bwd_impl(const float* dz, const float* W, const float* x, float* d
   int rc = fc_bwd_check(dz, W, dx, B, F, K);
   if (rc != CURLA_OK) return rc;
   if ((rc = fc_bwd_check(dz, x, dW, B, F, K)) != CURLA_OK) return rc;
-  const int ks = (F + 3) / 4, nt = (F + 15) / 16;
-  // the one-pass kernel is instantiated for 49..52 features, whole 16-row tiles and matrices below 2 GB (32-bit buffer
-  // offsets); anything else takes the two streaming kernels
-  if (ks != 13 || nt != 4 || B % 16 != 0 || (long long)B * K * 4 >= (1LL << 31)) {  // (i.e. F = 49..52)
+  // the one-pass kernel where it is instantiated (fc_plan.h); anything else takes the two streaming kernels
+  FcBwdPlan p;
+  if ((rc = fc_bwd_plan(B, F, K, lnr.partial != nullptr, p)) != CURLA_OK) return rc;
+  if (p.two_launches) {
     if ((rc = curla_fc_dx(dz, W, x, dx, B, F, K, stream)) != CURLA_OK) return rc;
     return fc_dw_impl(dz, x, dW, B, F, K, stream, lnr);
   }
   FcBwdArgs gx;
   gx.dz = dz, gx.W = W, gx.mask = x, gx.out = dx, gx.B = B, gx.F = F, gx.K = K;
-  return launch_fc_bwd(true, gx, dW, lnr, static_cast<hipStream_t>(stream));
+  return launch_fc_bwd(p.op, gx, dW, lnr, static_cast<hipStream_t>(stream));
 }
 
 int curla_fc_bwd(const float* dz, const float* W, const float* x, float* dx, float* dW, int B, int F, int K,

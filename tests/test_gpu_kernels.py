@@ -1278,6 +1278,8 @@ def test_fc_backward_one_launch(ops):
         ops.fc_bwd(dz, W, x, dx2, dw2, B, Fd, K)
         assert torch.equal(dx1, dx2)
         if one_pass:
+            # (dw1: at 50 features the weight-gradient half of the one-pass kernel, else fc_dw_kernel)
+            check(f"fc_dw dW {B}x{Fd}x{K}", dw1.cpu(), dz.cpu().double().t().mm(x.cpu().double()), 2e-5)
             check(f"fc_bwd dW {B}x{Fd}x{K}", dw2.cpu(), dz.cpu().double().t().mm(x.cpu().double()).float(), 2e-5)
             dw3 = torch.empty_like(dw1)
             ops.fc_bwd(dz, W, x, torch.empty_like(dx1), dw3, B, Fd, K)
