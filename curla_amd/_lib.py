@@ -143,6 +143,9 @@ SIGNATURES = {
     "curla_actor_loss": [vp, c_ll, vp, vp, c_int, vp, c_float, c_int, vp, vp, vp, vp],
     "curla_tqc_critic_loss": [vp, c_ll, vp, c_ll, vp, vp, vp, vp, c_float, c_int, c_int, c_int, vp, c_ll, vp, vp, vp],
     "curla_tqc_actor_loss": [vp, c_ll, vp, vp, c_int, vp, c_float, c_int, c_int, vp, vp, c_ll, vp, vp],
+    "curla_hlg_critic_loss": [vp, c_ll, vp, c_ll, vp, vp, vp, vp, c_float, c_int, c_int, c_float, c_float, c_float, c_int,
+                              vp, c_ll, vp, vp, vp, vp],
+    "curla_hlg_actor_loss": [vp, c_ll, vp, vp, c_int, vp, c_float, c_int, c_int, c_float, c_float, vp, vp, vp, c_ll, vp, vp],
     "curla_curl_ce": [vp, c_int, c_int, vp, vp, vp, vp],
     "curla_curl_ce_views": [vp, c_int, c_int, vp, vp, vp, vp],
     "curla_mean": [vp, c_int, vp, vp],

@@ -1,4 +1,6 @@
 """CurlSacAgent's captured update graphs: a hipGraph per kind of step, replayed with the per-update values as data."""
+import contextlib
+import gc
 import warnings
 
 import numpy as np
@@ -6,6 +8,22 @@ import torch
 
 from .networks import _device_generator
 from .optim import FlatAdam, _scalar_adam_state
+
+
+@contextlib.contextmanager
+def _collector_held_off():
+    """Python's cyclic collector off for the length of a graph capture, and back as it was -- also when the capture
+    raises.  A collection that starts inside the captured region finalizes whatever dead cycles the process holds,
+    other agents' ``torch.cuda.CUDAGraph`` objects among them, and finalizers that call the runtime are not legal under
+    a capturing stream: a whole-suite run on an MI355X aborted in exactly that place ("Found on the
+    way").  Nothing is collected here; what is dead stays so until the capture has ended."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class _NullLog:
@@ -48,7 +66,8 @@ class _UpdateGraphsMixin:
         ARE captured, collectives included (round 5; the replica check stays on the host, in front of the replay).
         Values the graphs hold as kernel arguments (discount, taus, betas / eps, detach_encoder, the update
         frequencies, the data-parallel group and schedule, ``max_grad_norm``, ``critic_dropout``,
-        ``critic_drop_quantiles``, ``n_step`` and ``discount`` of an n-step replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
+        ``critic_drop_quantiles``, ``critic_value_range``, ``critic_bin_sigma``, ``n_step`` and ``discount`` of an n-step
+        replay buffer) are fingerprinted at capture: editing one of them drops the graphs and they are captured again;
         so does ``load_checkpoint``.  A capture that raises leaves the agent's
         state untouched and that update runs eagerly.
         ``utd_ratio = G > 1``: a call replays the critic-only kind's graph (actor=False, soft, cpc=False) G-1 times -- the
@@ -117,8 +136,10 @@ class _UpdateGraphsMixin:
                 hyper, self._graph_rb_key(), self._max_grad_norm) + \
             ((float(self.critic_dropout),) if self.critic_dropout else ()) + \
             ((("quantiles", self.critic_quantiles, self.critic_drop_quantiles),) if self.critic_quantiles else ()) + \
-            ((("aug_views", 2),) if self.aug_views == 2 else ())
-        # (0, for either, and one view: the key of an agent without the keyword)
+            ((("aug_views", 2),) if self.aug_views == 2 else ()) + \
+            ((("bins", self.critic_bins) + tuple(float(v) for v in self.critic_value_range) +
+              (float(self.critic_bin_sigma),),) if self.critic_bins else ())
+        # (0, for any of the three, and one view: the key of an agent without the keyword)
 
     def _graph_rb_key(self):
         """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value
@@ -233,7 +254,7 @@ class _UpdateGraphsMixin:
             graph = torch.cuda.CUDAGraph()
             err = None
             try:
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                with _collector_held_off(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
                     if leading:
                         self._leading_phases(rb.graph_refs(st["slot"]), step)
                     else:

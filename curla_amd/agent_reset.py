@@ -61,7 +61,7 @@ class _ResetMixin:
         generator standing at the reset stream's state; the state behind the draws is the stream's new one.  The
         global generator is put back (fork_rng); the device generator and NumPy's state are not involved."""
         obs_shape, action_shape, hidden, feat, ls_min, ls_max, layers, filters = self._net_args
-        q_kw = dict(quantiles=self.critic_quantiles) if self.critic_quantiles else {}
+        q_kw = self._critic_width_kw()
         with torch.random.fork_rng(devices=[]):
             torch.set_rng_state(self._reset_stream())
             actor = Actor(obs_shape, action_shape, hidden, feat, ls_min, ls_max, layers, filters)

@@ -23,6 +23,7 @@ namespace {
 #include "mlp_out.h"       // mlp_out_fwd_kernel<HEAD, R, LDSW>, mlp_out_bwd_kernel<GEN>, the policy head's three kernels
 #include "sac_loss.h"      // concat / split_sum, td_target, critic_loss, critic_td_loss(_views), actor_loss, curl_ce<VIEWS>
 #include "tqc.h"           // tqc_critic_loss_kernel, tqc_actor_loss_kernel (truncated quantile critics)
+#include "hlgauss.h"       // hlg_critic_loss_kernel<VIEWS>, hlg_actor_rows_kernel, hlg_actor_scalars_kernel (the HL-Gauss critic)
 #include "curl_head.h"     // curl_head_kernel<NTILE>
 #include "redo.h"          // dormant_colsum_kernel, dormant_mask_kernel, redo_recycle_kernel (dormant-neuron scores, ReDo)
 #include "optim.h"         // soft_update_kernel, soft_update2_kernel, shrink_perturb2_kernel, adam_step_kernel<CLIP, DECAY>, adam_step2_kernel<CLIP, DECAY>
@@ -621,6 +622,39 @@ int curla_tqc_actor_loss(const float* q, long long q_twin_stride, const float* l
   CURLA_REQUIRE(q_twin_stride >= (long long)B * M && dq_twin_stride >= (long long)B * M);
   return launch(tqc_actor_loss_kernel, dim3(1), 256, 0, static_cast<hipStream_t>(stream), q, q_twin_stride, log_pi,
                 log_std, A, log_alpha, target_entropy, B, M, scalars4, dq, dq_twin_stride, dlog_alpha);
+}
+
+int curla_hlg_critic_loss(const float* q, long long q_twin_stride, const float* tq, long long tq_twin_stride,
+                          const float* log_pi, const float* reward, const float* not_done, const double* log_alpha,
+                          float discount, int B, int M, float v_min, float v_max, float sigma, int views, float* dq,
+                          long long dq_twin_stride, float* target_q, float* row_loss, float* loss, void* stream) {
+  CURLA_REQUIRE(q && tq && log_pi && reward && not_done && log_alpha && dq && target_q && row_loss && B > 0);
+  CURLA_REQUIRE(M >= 2 && M <= kHlgMax && std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max);
+  CURLA_REQUIRE(std::isfinite(sigma) && sigma > 0.f && (views == 0 || (views == 1 && B % 2 == 0)));
+  const long long dense = (long long)B * M;
+  CURLA_REQUIRE(q_twin_stride >= dense && tq_twin_stride >= dense && dq_twin_stride >= dense);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const auto kernel = views ? hlg_critic_loss_kernel<true> : hlg_critic_loss_kernel<false>;
+  const int rc = launch(kernel, dim3((B + 3) / 4), 256, 0, st, q, q_twin_stride, tq, tq_twin_stride, log_pi, reward,
+                        not_done, log_alpha, discount, B, M, v_min, v_max, sigma, dq, dq_twin_stride, target_q, row_loss);
+  if (rc != CURLA_OK || !loss) return rc;
+  // the fixed-order sum over rows, over N = B transitions (B / 2 with views)
+  return launch(hlg_row_sum_kernel, dim3(1), 256, 0, st, row_loss, B, 1.f / (float)(views ? B / 2 : B), loss);
+}
+
+int curla_hlg_actor_loss(const float* q, long long q_twin_stride, const float* log_pi, const float* log_std, int A,
+                         const double* log_alpha, float target_entropy, int B, int M, float v_min, float v_max,
+                         float* row_q, float* scalars4, float* dq, long long dq_twin_stride, double* dlog_alpha,
+                         void* stream) {
+  CURLA_REQUIRE(q && log_pi && log_std && log_alpha && row_q && scalars4 && dq && B > 0 && A > 0);
+  CURLA_REQUIRE(M >= 2 && M <= kHlgMax && std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max);
+  CURLA_REQUIRE(q_twin_stride >= (long long)B * M && dq_twin_stride >= (long long)B * M);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch(hlg_actor_rows_kernel, dim3((B + 3) / 4), 256, 0, st, q, q_twin_stride, B, M, v_min, v_max, row_q,
+                        dq, dq_twin_stride);
+  if (rc != CURLA_OK) return rc;
+  return launch(hlg_actor_scalars_kernel, dim3(1), 256, 0, st, row_q, log_pi, log_std, A, log_alpha, target_entropy, B,
+                scalars4, dlog_alpha);
 }
 
 int curla_curl_ce(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits, void* stream) {

@@ -35,7 +35,8 @@ from .agent_reset import _check_reset_interval, _check_reset_keep, _check_reset_
 from .encoder import CNNEncoder
 from .mlp import _Mlp, _MlpLn, _linears, _mlp_bwd, _mlp_fwd  # noqa: F401
 from .networks import (CURL, LOG_FREQ, Actor, Critic, QFunction, _check_drop_quantiles,  # noqa: F401
-                       _check_dropout, _check_int, _check_layer_norm_width, _check_quantiles, _CriticType,
+                       _check_bin_sigma, _check_bins, _check_dropout, _check_int, _check_layer_norm_width,
+                       _check_quantiles, _check_value_range, _CriticType,
                        _device_generator, _QFunctionType, _reserve_dropout_counter, _widen_last_layers, weight_init)
 from .ops import ObsRef
 from .optim import FlatAdam, check_max_grad_norm, check_weight_decay
@@ -114,7 +115,9 @@ class _Workspace:
             self.q_ln_saves = ([self.q_xhat1, self.q_xhat2], [self.q_rstd1, self.q_rstd2])
             self.q_ln_partial = f(ops.mlp_ln_partial_floats(B, H, 2))
         self.dq, self.target_q = f(2, B, M), f(B, 1)
-        self.q_row_loss = f(B) if agent.critic_quantiles else None  # the quantile loss per row (ops.tqc_critic_loss)
+        # the quantile loss per row (ops.tqc_critic_loss); critic_bins: the cross-entropies per row (ops.hlg_critic_loss)
+        # in the critic phase, min(Q1, Q2) per row (ops.hlg_actor_loss) in the actor phase
+        self.q_row_loss = f(B) if agent.critic_quantiles or agent.critic_bins else None
         self.per_w = self.per_value = None  # importance weights / new stored values [B]: a prioritized buffer's updates only
         # scalars: [0] critic loss, [1..4] actor_loss/alpha_loss/entropy/alpha, [5] curl loss, [6] batch reward
         self.scalars = torch.zeros(8, device=dev, dtype=torch.float32)
@@ -130,8 +133,9 @@ class _AgentType(type):
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
     def __call__(cls, *args, aug_views=1, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0,
-                 reset_encoder_keep=1.0, reset_seed=0, critic_quantiles=0, critic_drop_quantiles=0, weight_decay=0.0, utd_ratio=1,
-                 critic_dropout=0.0, critic_layer_norm=False, **kwargs):
+                 reset_encoder_keep=1.0, reset_seed=0, critic_quantiles=0, critic_drop_quantiles=0, critic_bins=0,
+                 critic_value_range=None, critic_bin_sigma=0.75, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0,
+                 critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
         agent.redo_interval = _check_redo_interval(redo_interval)
         agent.redo_tau = _check_redo_tau(redo_tau)
@@ -144,6 +148,19 @@ class _AgentType(type):
         agent.critic_layer_norm = bool(critic_layer_norm)
         agent.critic_dropout = _check_dropout(critic_dropout, agent.critic_layer_norm)
         agent.utd_ratio = _check_utd_ratio(utd_ratio)
+        bin_sigma = _check_bin_sigma(critic_bin_sigma)
+        if _check_bins(critic_bins):  # (0: the instance is the one without the keyword, down to its __dict__)
+            if agent.critic_quantiles:
+                raise ValueError("critic_bins > 0 is not combined with critic_quantiles > 0: a Q function's last layer is "
+                                 "the logits of one categorical distribution or a set of quantile atoms")
+            if critic_value_range is None:
+                raise ValueError("critic_bins = %d needs critic_value_range=(v_min, v_max), the range of the returns the "
+                                 "bins cover" % critic_bins)
+            agent.critic_bins = int(critic_bins)
+            agent.critic_value_range = _check_value_range(critic_value_range)
+            agent.critic_bin_sigma = bin_sigma
+        elif critic_value_range is not None:
+            raise ValueError("critic_value_range needs critic_bins > 0")
         if _check_views(aug_views) == 2:  # (1: the instance is the one without the keyword, down to its __dict__)
             if agent.critic_quantiles:
                 raise ValueError("aug_views = 2 is not combined with critic_quantiles > 0: the mean of two views' "
@@ -188,7 +205,14 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     agree): DrQ's K = 2, M = 2 -- a minibatch of B positions is B / 2 transitions, each under two independent
     augmentations at positions b and b + B / 2.  The critic phase regresses both views' Q estimates on the mean of the two
     views' TD targets, the CURL phase does not count a position's partner among its negatives; the actor phase sees all B
-    positions.  Fixed at construction.  Not with ``critic_quantiles``."""
+    positions.  Fixed at construction.  Not with ``critic_quantiles``.
+    ``critic_bins=M`` (default 0: nothing changes; 2 .. 256) with ``critic_value_range=(v_min, v_max)`` (required then;
+    finite, v_min < v_max) and ``critic_bin_sigma=s`` (default 0.75; finite, > 0): the categorical HL-Gauss critic -- each
+    Q function outputs M logits over M equal bins of the value range, Q is the softmax's expectation of the bin centres,
+    and the critic is trained by cross-entropy on the histogram of a Gaussian of standard deviation s bin widths around
+    the clamped scalar TD target; the actor ascends min(Q1, Q2) through the softmax.  M shapes the
+    networks; the range and s are attributes that may be edited between calls.  ``target_clip_fraction()`` tells whether
+    the range fits.  With ``aug_views=2``; not with ``critic_quantiles``, not with a prioritized replay buffer."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
@@ -196,6 +220,10 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     critic_quantiles = 0
     critic_drop_quantiles = 0
     aug_views = 1
+    critic_bins = 0
+    critic_value_range = None
+    critic_bin_sigma = 0.75
+    _hlg_last_B = None  # critic_bins: the batch size of the last critic phase (target_clip_fraction's workspace)
 
     def __init__(
         self,
@@ -258,7 +286,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         # same construction order as the reference => same RNG stream => same init for a given seed
         self.actor = Actor(obs_shape, action_shape, hidden_dim, encoder_feature_dim, actor_log_std_min,
                            actor_log_std_max, num_layers, num_filters)
-        q_kw = dict(quantiles=self.critic_quantiles) if self.critic_quantiles else {}
+        q_kw = self._critic_width_kw()
         self.critic = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
                              layer_norm=self.critic_layer_norm, dropout=self.critic_dropout, **q_kw)
         self.critic_target = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
@@ -630,13 +658,42 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         _mlp_bwd(ws.xa, 0, net.twin(), net.twin(grads=True) if grads else None, 2, B, FA, self.hidden_dim, net.out_dim,
                  ws.q_h1, ws.q_h2, ws.dq, ws.q_dh2, ws.q_dh1, ws.dxa, loss=loss, ln=ln)
 
+    def _critic_width_kw(self):
+        """The keywords that widen the Q functions' last layers, for every place that builds a Critic."""
+        if self.critic_bins:
+            return dict(bins=self.critic_bins, value_range=self.critic_value_range)
+        return dict(quantiles=self.critic_quantiles) if self.critic_quantiles else {}
+
+    def _hlg_params(self):
+        """(v_min, v_max, sigma) of the HL-Gauss critic as they stand now -- the range and the smoothing may have been
+        edited --, checked; the critics' own ``value_range`` (bin_centres, expected) follows the agent's."""
+        v_min, v_max = rng = _check_value_range(self.critic_value_range)
+        self.critic.value_range = self.critic_target.value_range = rng
+        return v_min, v_max, _check_bin_sigma(self.critic_bin_sigma) * (v_max - v_min) / self.critic_bins
+
+    def target_clip_fraction(self):
+        """The share of the last critic phase's TD targets that the clamp moved onto ``v_min`` or ``v_max``: near 0 with
+        a value range that fits, towards 1 with one the returns have left -- the HL-Gauss critic's own failure mode.  A
+        host read of the workspace (it waits for the device); not part of ``update()``."""
+        if not self.critic_bins:
+            raise RuntimeError("target_clip_fraction: this agent has no categorical critic (critic_bins=M)")
+        ws = self._workspaces.get(self._hlg_last_B)
+        if ws is None:
+            raise RuntimeError("target_clip_fraction: no critic phase has run yet")
+        v_min, v_max = (np.float32(v) for v in _check_value_range(self.critic_value_range))
+        t = ws.target_q.detach().reshape(-1).cpu().numpy()
+        return float(((t == v_min) | (t == v_max)).mean())
+
     # -- the loss descriptors of _twin_bwd: (fields, launch) -- ``fields`` for the form computed inside the backward
     #    launch of the Q functions' last layer, ``launch()`` the loss kernel on its own where that form does not apply
-    def _critic_loss(self, ws, reward, not_done, per, drop_q):
+    def _critic_loss(self, ws, reward, not_done, per, drop_q, hlg=None):
         """target_Q = r + not_done * gamma * (min Q' - alpha log pi'), the two MSE terms and their gradient dq
         (curl_sac.py:353-361).  ``critic_quantiles``: the quantile Huber loss of the critic's atoms against
         the kept target atoms, always a launch of its own.  ``aug_views = 2``: both views' estimates against
-        the mean of the two views' targets, a launch of its own as well.  ``per``, a prioritized minibatch: the loss is
+        the mean of the two views' targets, a launch of its own as well.  ``critic_bins``: the two
+        cross-entropies of the critic's logits against the Gaussian histogram of the clamped TD target, with or without
+        views, always a launch of its own; ``hlg`` = (v_min, v_max, sigma) as update_critic has checked them.  ``per``, a
+        prioritized minibatch: the loss is
         launched here, the importance weights scale dq and the loss in place and the drawn rows get their new priorities
         -- all on the device --, and the backward runs on the weighted dq it finds: no descriptor, None."""
         B, Mq = ws.log_pi.shape[0], self.critic.out_dim
@@ -644,6 +701,11 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         if self.critic_quantiles:
             loss = (None, lambda: ops.tqc_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done, la, gamma,
                                                       B, Mq, drop_q, ws.dq, B * Mq, ws.q_row_loss, total))
+        elif self.critic_bins:  # (a prioritized minibatch has been refused by update_critic)
+            v_min, v_max, sigma = hlg
+            return None, lambda: ops.hlg_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done, la, gamma, B,
+                                                     Mq, v_min, v_max, sigma, ws.dq, B * Mq, ws.target_q, ws.q_row_loss,
+                                                     total, views=self.aug_views == 2)
         elif self.aug_views == 2:
             if per is not None:
                 raise ValueError("aug_views = 2: a prioritized minibatch is not supported (its rows are drawn per "
@@ -671,6 +733,10 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         if self.critic_quantiles:
             return None, lambda: ops.tqc_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, la, te, B, Mq, out, ws.dq,
                                                     B * Mq, la.grad)
+        if self.critic_bins:
+            v_min, v_max, _ = self._hlg_params()
+            return None, lambda: ops.hlg_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, la, te, B, Mq, v_min, v_max,
+                                                    ws.q_row_loss, out, ws.dq, B * Mq, la.grad)
         return (dict(kind=2, A=A, twin_stride=B, q=ws.q, log_pi=ws.log_pi, log_std=ws.log_std, log_alpha=la,
                      target_entropy=te, scalars=out, dq=ws.dq, dlog_alpha=la.grad),
                 lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, la, te, B, out, ws.dq, la.grad))
@@ -773,9 +839,17 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             if per is not None:
                 raise ValueError("critic_quantiles: a prioritized minibatch is not supported (its priorities are built "
                                  "on one scalar TD error per Q function): use ReplayBuffer(prioritized=False)")
+        hlg = None
+        if self.critic_bins:
+            hlg = self._hlg_params()  # (the range or the smoothing may have been edited: checked before anything is written)
+            if per is not None:
+                raise ValueError("critic_bins: a prioritized minibatch is not supported (its priorities are built on one "
+                                 "scalar TD error per Q function): use ReplayBuffer(prioritized=False)")
         self._restore_grad_views()
         o, no = _as_ref(obs), _as_ref(next_obs)
         ws, enc = self._ws(o.B), self.critic.encoder
+        if hlg is not None:
+            self._hlg_last_B = o.B
         self._drop_encoder_caches()
         action, reward, not_done = action.contiguous(), reward.contiguous(), not_done.contiguous()
         # -- target (no_grad block, curl_sac.py:350-355) and current Q estimates (:357-358)
@@ -786,7 +860,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             self.critic.outputs['q1'], self.critic.outputs['q2'] = ws.q[0].clone(), ws.q[1].clone()
             enc.record_from(o, ws.acts_main, ws.fc_out, ws.z_c)
         # -- loss + backward (curl_sac.py:359-367)
-        loss = self._critic_loss(ws, reward, not_done, per, drop_q)
+        loss = self._critic_loss(ws, reward, not_done, per, drop_q, hlg)
         self._twin_bwd(ws, self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial, drop=drop(3)), loss,
                        grads=True)
         if step % self.log_interval == 0:
@@ -1223,6 +1297,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             "rng": rng, "critic_dropout": float(self.critic_dropout), "utd_ratio": int(self.utd_ratio),
             "critic_quantiles": int(self.critic_quantiles), "critic_drop_quantiles": int(self.critic_drop_quantiles),
             **({"aug_views": 2} if self.aug_views == 2 else {}),  # (1: the file of an agent without the keyword)
+            **({"critic_bins": int(self.critic_bins), "critic_value_range": tuple(float(v) for v in self.critic_value_range),
+                "critic_bin_sigma": float(self.critic_bin_sigma)} if self.critic_bins else {}),  # (0: likewise)
             **self._reset_checkpoint(), **self._redo_checkpoint(),
         }, path)
 
@@ -1248,6 +1324,11 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         # loss alone and come from the file)
         if self.critic_quantiles and "critic_drop_quantiles" in ck:
             self.critic_drop_quantiles = _check_drop_quantiles(ck["critic_drop_quantiles"], self.critic_quantiles)
+        # (another critic_bins has failed above as well; the range and the smoothing are numbers of the loss alone)
+        if self.critic_bins and "critic_value_range" in ck:
+            self.critic_value_range = _check_value_range(ck["critic_value_range"])
+            self.critic_bin_sigma = _check_bin_sigma(ck.get("critic_bin_sigma", self.critic_bin_sigma))
+            self._hlg_params()
         with torch.no_grad():
             self.log_alpha.copy_(ck["log_alpha"])
         for k, o in self._optimizers().items():

@@ -112,6 +112,42 @@ def _check_drop_quantiles(d, m):
     return d
 
 
+def _check_bins(m):
+    """The bins of the categorical HL-Gauss critic: 0 (off) or an ``int`` in 2 .. ops.HLG_MAX."""
+    m = _check_int(m, 0, ops.HLG_MAX, "critic bins: %r is not an int, 0 (off) or in 2 .. %d" % (m, ops.HLG_MAX))
+    if m == 1:
+        raise ValueError("critic bins: 1 is not 0 (off) or in 2 .. %d" % ops.HLG_MAX)
+    return m
+
+
+def _check_width(quantiles, bins):
+    """(quantiles, bins) of a Q function's last layer, checked; the two are exclusive."""
+    quantiles, bins = _check_quantiles(quantiles), _check_bins(bins)
+    if quantiles and bins:
+        raise ValueError("critic quantiles = %d and critic bins = %d: a Q function's last layer is one or the other"
+                         % (quantiles, bins))
+    return quantiles, bins
+
+
+def _check_value_range(value_range):
+    """``(v_min, v_max)`` of the HL-Gauss critic's bins as two floats: finite, v_min < v_max."""
+    try:
+        v_min, v_max = (float(v) for v in value_range)
+    except (TypeError, ValueError):
+        raise ValueError("critic_value_range: %r is not a pair (v_min, v_max) of numbers" % (value_range,)) from None
+    if not (np.isfinite(v_min) and np.isfinite(v_max) and v_min < v_max):
+        raise ValueError("critic_value_range: (%r, %r) is not finite with v_min < v_max" % (v_min, v_max))
+    return v_min, v_max
+
+
+def _check_bin_sigma(s):
+    """The HL-Gauss smoothing's standard deviation in bin widths: a finite number > 0."""
+    if isinstance(s, (bool, str)) or not isinstance(s, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(s) or s <= 0:
+        raise ValueError("critic_bin_sigma: %r is not a finite number > 0" % (s,))
+    return float(s)
+
+
 def _widen_last_layers(trunks, m, init=None):
     """Replace the last Linear (hidden -> 1) of each trunk by a hidden -> ``m`` one, ``init`` applied to it.  The new
     tensors' draws are taken from a fork of torch's generator, which is put back afterwards: everything else a seed
@@ -126,14 +162,16 @@ def _widen_last_layers(trunks, m, init=None):
 
 class _QFunctionType(type):
     """``QFunction(..., quantiles=M)``: a keyword of the class call, as ``Critic(..., dropout=p)`` is (_CriticType);
-    ``QFunction.__init__`` keeps its parameter list with ``dropout`` last."""
+    ``QFunction.__init__`` keeps its parameter list with ``dropout`` last.  ``bins=M`` beside it, exclusive with it."""
 
-    def __call__(cls, *args, quantiles=0, **kwargs):
-        quantiles = _check_quantiles(quantiles)
+    def __call__(cls, *args, quantiles=0, bins=0, **kwargs):
+        quantiles, bins = _check_width(quantiles, bins)
         q = super().__call__(*args, **kwargs)
         q.quantiles = quantiles
-        if quantiles:
-            _widen_last_layers([q.trunk], quantiles)
+        if bins:
+            q.bins = bins
+        if quantiles or bins:
+            _widen_last_layers([q.trunk], quantiles or bins)
         return q
 
 
@@ -142,9 +180,10 @@ class QFunction(nn.Module, metaclass=_QFunctionType):
     between each hidden Linear and its ReLU (the Linears are then trunk.0 / .3 / .6, the LayerNorms trunk.1 / .4).
     ``dropout``: DroQ's dropout probability in front of each LayerNorm -- an attribute, no module of the trunk.
     ``QFunction(..., quantiles=M)`` (a keyword of the class call; 0: off): the last Linear has M rows, one per quantile
-    atom."""
+    atom.  ``QFunction(..., bins=M)`` (likewise; not with quantiles): M rows, the logits over the HL-Gauss critic's bins."""
 
     quantiles = 0
+    bins = 0
 
     def __init__(self, obs_dim, action_dim, hidden_dim, layer_norm=False, dropout=0.0):
         super().__init__()
@@ -198,15 +237,24 @@ class _CriticType(type):
     """``Critic(..., dropout=p)``: the class call takes the keyword, as CurlSacAgent's takes its own (_AgentType), and
     ``Critic.__init__`` keeps its parameter list with ``layer_norm`` last.  ``Critic(..., quantiles=M)`` likewise: the
     critic is built as without it and the Q functions' last layers are then replaced by M-row ones, initialised like
-    every other Linear (weight_init)."""
+    every other Linear (weight_init).  ``Critic(..., bins=M, value_range=(v_min, v_max))``: the same M-row layers as the
+    logits of the HL-Gauss critic, exclusive with quantiles (bins = 0: an instance without either attribute; the range
+    may be left out and set later)."""
 
-    def __call__(cls, *args, dropout=0.0, quantiles=0, **kwargs):
-        quantiles = _check_quantiles(quantiles)
+    def __call__(cls, *args, dropout=0.0, quantiles=0, bins=0, value_range=None, **kwargs):
+        quantiles, bins = _check_width(quantiles, bins)
+        if value_range is not None:
+            if not bins:
+                raise ValueError("Critic(value_range=...) needs bins > 0")
+            value_range = _check_value_range(value_range)
         critic = super().__call__(*args, **kwargs)
         critic.dropout = critic.Q1.dropout = critic.Q2.dropout = _check_dropout(dropout, critic.layer_norm)
         critic.quantiles = critic.Q1.quantiles = critic.Q2.quantiles = quantiles
-        if quantiles:
-            _widen_last_layers([critic.Q1.trunk, critic.Q2.trunk], quantiles, weight_init)
+        if bins:
+            critic.bins = critic.Q1.bins = critic.Q2.bins = bins
+            critic.value_range = value_range
+        if quantiles or bins:
+            _widen_last_layers([critic.Q1.trunk, critic.Q2.trunk], quantiles or bins, weight_init)
         return critic
 
 
@@ -214,15 +262,36 @@ class Critic(nn.Module, metaclass=_CriticType):
     """Critic network, employs two Q-functions (curl_sac.py:142-180).  ``layer_norm``: QFunction's; so is
     ``Critic(..., dropout=p)``, a keyword of the class call.  ``forward`` drops in training mode only
     (``critic.eval()``: the deterministic Q).  ``Critic(..., quantiles=M)`` (0: off): each Q function outputs M quantile
-    atoms and ``forward`` returns ``q1, q2`` of shape [B, M]."""
+    atoms and ``forward`` returns ``q1, q2`` of shape [B, M].  ``Critic(..., bins=M, value_range=(v_min, v_max))`` (0:
+    off; not with quantiles): the categorical HL-Gauss critic -- each Q function outputs M logits over the
+    bins of the value range, ``forward`` returns the two [B, M] logit tensors, ``expected(logits)`` turns them into Q
+    values.  ``value_range`` is an attribute that may be edited (the agent keeps its critics' in step with its own)."""
 
     dropout = 0.0
     quantiles = 0
+    bins = 0
+    value_range = None
 
     @property
     def out_dim(self):
-        """The width of a Q function's last layer: its quantile atoms, or the one Q value."""
-        return self.quantiles or 1
+        """The width of a Q function's last layer: its quantile atoms, its bins' logits, or the one Q value."""
+        return self.quantiles or self.bins or 1
+
+    def bin_centres(self):
+        """c_j = v_min + (j + 1/2) w, w = (v_max - v_min) / M: float32 [M], on the critic's device."""
+        if not self.bins:
+            raise RuntimeError("Critic.bin_centres: this critic has no bins (Critic(..., bins=M))")
+        if self.value_range is None:
+            raise RuntimeError("Critic.bin_centres: set critic.value_range = (v_min, v_max) first")
+        v_min, v_max = _check_value_range(self.value_range)
+        w = (v_max - v_min) / self.bins
+        dev = self.Q1.trunk[-1].weight.device
+        return (v_min + (torch.arange(self.bins, dtype=torch.float64) + 0.5) * w).to(torch.float32).to(dev)
+
+    def expected(self, logits):
+        """Q = sum_j softmax(logits)_j c_j of [B, M] logits, as [B, 1]: a plain torch expression, differentiable by
+        torch (what an evaluation script or a user's own loss turns ``forward``'s logits into Q values with)."""
+        return (torch.softmax(logits, dim=-1) * self.bin_centres().to(logits.device, logits.dtype)).sum(-1, keepdim=True)
 
     def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
                  layer_norm=False):

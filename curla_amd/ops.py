@@ -627,6 +627,29 @@ def tqc_actor_loss(q, sq, log_pi, log_std, A, log_alpha, target_entropy, B, M, s
          ptr(scalars4), ptr(dq), sdq, ptr(dlog_alpha), stream())
 
 
+HLG_MAX = 256  # the most bins per Q function: a lane of the row's wave holds four (csrc/hlgauss.h)
+
+
+def hlg_critic_loss(q, sq, tq, stq, log_pi, reward, not_done, log_alpha, discount, B, M, v_min, v_max, sigma, dq, sdq,
+                    target_q, row_loss, loss=None, views=False):
+    """The HL-Gauss critic's loss (curla_hlg_critic_loss): q / tq / dq [2][B][M] logits over the M bins of
+    [v_min, v_max] with twin strides sq / stq / sdq (elements), ``sigma`` the smoothing's standard deviation (a value,
+    not a share of the bin width); target_q [B] takes the clamped TD target, row_loss [B] the two cross-entropies,
+    ``loss`` [1] their fixed-order sum over N = B (None: not taken).  ``views``: positions b and b + B/2 share the mean
+    of their two targets and N = B/2 (B even)."""
+    call("curla_hlg_critic_loss", ptr(q), sq, ptr(tq), stq, ptr(log_pi), ptr(reward), ptr(not_done), ptr(log_alpha),
+         discount, B, M, v_min, v_max, sigma, 1 if views else 0, ptr(dq), sdq, ptr(target_q), ptr(row_loss), ptr(loss),
+         stream())
+
+
+def hlg_actor_loss(q, sq, log_pi, log_std, A, log_alpha, target_entropy, B, M, v_min, v_max, row_q, scalars4, dq, sdq,
+                   dlog_alpha):
+    """actor_loss over Q_n = sum_j softmax(q[n])_j c_j of the logits q [2][B][M] (curla_hlg_actor_loss): row_q [B] takes
+    min(Q_0, Q_1), dq [2][B][M] the gradient through the softmax of the smaller network (a tie splits it)."""
+    call("curla_hlg_actor_loss", ptr(q), sq, ptr(log_pi), ptr(log_std), A, ptr(log_alpha), target_entropy, B, M, v_min,
+         v_max, ptr(row_q), ptr(scalars4), ptr(dq), sdq, ptr(dlog_alpha), stream())
+
+
 def curl_head_supported(B, F_):
     return B % 128 == 0 and B <= 1024 and 49 <= F_ <= 52
 

@@ -471,6 +471,30 @@ int curla_tqc_critic_loss(const float* q, long long q_twin_stride, const float* 
 int curla_tqc_actor_loss(const float* q, long long q_twin_stride, const float* log_pi, const float* log_std, int A,
                          const double* log_alpha, float target_entropy, int B, int M, float* scalars4, float* dq,
                          long long dq_twin_stride, double* dlog_alpha, void* stream);
+/* The categorical HL-Gauss critic (Imani & White 2018; Farebrother et al. 2024) in place of curla_critic_td_loss, for Q
+ * functions whose last layer outputs M logits over the bins of [v_min, v_max] (q, tq, dq are [2][B][M], their twins the
+ * given element strides apart, each >= B M).  w = (v_max - v_min) / M, edges e_j = v_min + j w, centres
+ * c_j = v_min + (j + 1/2) w, Q = sum_j softmax(l)_j c_j.  Per row b: y = reward + not_done * discount *
+ * (min(Q'_0, Q'_1) - exp(log_alpha) * log_pi) from the target logits `tq`; with views != 0 (B even, H = B / 2) positions
+ * p and p + H both take 0.5 (y_p + y_{p+H}), one value bit for bit; y is clamped to [v_min, v_max] and written to
+ * target_q[b]; t_j = (Phi((e_{j+1} - y) / sigma) - Phi((e_j - y) / sigma)) / (Phi((e_M - y) / sigma) - Phi((e_0 - y) / sigma));
+ * row_loss[b] = -sum_n sum_j t_j log_softmax(q[n][b])_j, dq[n][b][j] = (softmax(q[n][b])_j - t_j) / N and `loss` (may be
+ * NULL) = sum_b row_loss[b] / N in a fixed order, N = B (H with views).  No atomics: a rerun writes the same bits.
+ * CURLA_ERR_ARG on a NULL required pointer, B < 1, M < 2, M > 256, a non-finite bound, v_min >= v_max, sigma <= 0 or not
+ * finite, a stride below B M, views not 0 or 1, or views with an odd B.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_hlg_critic_loss(const float* q, long long q_twin_stride, const float* tq, long long tq_twin_stride,
+                          const float* log_pi, const float* reward, const float* not_done, const double* log_alpha,
+                          float discount, int B, int M, float v_min, float v_max, float sigma, int views, float* dq,
+                          long long dq_twin_stride, float* target_q, float* row_loss, float* loss, void* stream);
+/* curla_actor_loss for the same Q functions: Q_n = sum_j softmax(q[n][b])_j c_j, the row's Q term min(Q_0, Q_1), written
+ * to row_q[b] (a [B] scratch the scalars are then summed from in a fixed order); dq[n][b][j] = g_n p_{n,j} (c_j - Q_n)
+ * with curla_actor_loss's g_n (-1 / B for the smaller network, -0.5 / B each on an exact tie, 0 for the larger); scalars4
+ * and dlog_alpha (may be NULL) as curla_actor_loss leaves them.  CURLA_ERR_ARG on a NULL required pointer, B < 1, A < 1,
+ * M < 2, M > 256, a non-finite bound, v_min >= v_max or a stride below B M.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_hlg_actor_loss(const float* q, long long q_twin_stride, const float* log_pi, const float* log_std, int A,
+                         const double* log_alpha, float target_entropy, int B, int M, float v_min, float v_max,
+                         float* row_q, float* scalars4, float* dq, long long dq_twin_stride, double* dlog_alpha,
+                         void* stream);
 /* CrossEntropyLoss(logits, arange(B)) and d/dlogits (curl_sac.py:221,411-413); `loss` (the mean of row_loss) may be
  * NULL when the scalar is not going to be logged */
 int curla_curl_ce(const float* logits, int B, int ld, float* row_loss, float* loss, float* dlogits, void* stream);
