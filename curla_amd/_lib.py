@@ -136,6 +136,14 @@ SIGNATURES = {
     "curla_fc_ln_fwd_multi": [c_int, vp, c_int, c_ll, c_int, c_int, c_int, c_float, c_int, vp],
     "curla_actor_head_bwd": [vp, vp, c_int, vp, vp, c_float, vp, vp, vp, vp, c_int, c_int, c_float, c_float, vp, vp],
     "curla_policy_head_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_float, c_float, vp, vp],
+    # the deterministic policy head
+    "curla_det_head_fwd": [vp, vp, vp, c_float, c_int, c_int, vp, vp, vp, vp, vp, c_int, vp],
+    "curla_det_head_fwd_rng": [vp, vp, c_u64, c_u64, vp, vp, c_float, c_int, c_int, vp, vp, vp, vp, vp, c_int, vp],
+    "curla_mlp_out_det_head_fwd": [vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, c_float, vp, vp, vp, vp, vp, c_int, vp],
+    "curla_mlp_out_det_head_fwd_rng": [vp, vp, vp, vp, c_int, c_int, c_int, vp, c_u64, c_u64, vp, vp, c_float, vp, vp, vp,
+                                       vp, vp, c_int, vp],
+    "curla_det_head_bwd": [vp, vp, c_int, vp, c_int, c_int, vp, vp],
+    "curla_det_policy_head_bwd": [vp, vp, vp, c_int, c_int, vp, vp],
     "curla_concat": [vp, vp, c_int, c_int, c_int, vp, vp],
     "curla_split_sum": [vp, c_ll, c_int, c_int, c_int, vp, vp, vp],
     "curla_td_target": [vp, c_ll, vp, vp, vp, vp, c_float, c_int, vp, vp],

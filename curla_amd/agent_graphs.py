@@ -138,8 +138,10 @@ class _UpdateGraphsMixin:
             ((("quantiles", self.critic_quantiles, self.critic_drop_quantiles),) if self.critic_quantiles else ()) + \
             ((("aug_views", 2),) if self.aug_views == 2 else ()) + \
             ((("bins", self.critic_bins) + tuple(float(v) for v in self.critic_value_range) +
-              (float(self.critic_bin_sigma),),) if self.critic_bins else ())
-        # (0, for any of the three, and one view: the key of an agent without the keyword)
+              (float(self.critic_bin_sigma),),) if self.critic_bins else ()) + \
+            ((("policy", "deterministic", self._policy_clip()),) if self.policy == "deterministic" else ())
+        # (0, for any of the three, one view and the Gaussian policy: the key of an agent without the keyword; the
+        # deterministic policy's std is data the head kernels read on the device and is not here, its clip is an argument)
 
     def _graph_rb_key(self):
         """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value

@@ -64,7 +64,7 @@ class _ResetMixin:
         q_kw = self._critic_width_kw()
         with torch.random.fork_rng(devices=[]):
             torch.set_rng_state(self._reset_stream())
-            actor = Actor(obs_shape, action_shape, hidden, feat, ls_min, ls_max, layers, filters)
+            actor = Actor(obs_shape, action_shape, hidden, feat, ls_min, ls_max, layers, filters, **self._actor_kw())
             critic = Critic(obs_shape, action_shape, hidden, feat, layers, filters, layer_norm=self.critic_layer_norm,
                             dropout=self.critic_dropout, **q_kw)
             W = torch.rand(feat, feat)

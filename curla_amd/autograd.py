@@ -303,7 +303,65 @@ class ActorFn(torch.autograd.Function):
         return (None, None, None, None, None, dz, *pg)
 
 
+class DetActorFn(torch.autograd.Function):
+    """(mu[, pi]) of the deterministic actor (Actor(deterministic=True)) from the features ``z``: the trunk
+    and the head on the launches of the no-grad forward.  ``noise`` is a constant; log_pi (zeros) and log_std (log(std))
+    are constants too and are written into ``keep``'s plain tensors by the same launch."""
+
+    @staticmethod
+    def forward(ctx, actor, keep, noise, z, *trunk_params):
+        ctx.set_materialize_grads(False)
+        B, A, H, F = z.shape[0], actor.action_dim, actor.hidden_dim, actor.encoder.feature_dim
+        h1, h2, out = _empty(B, H, like=z), _empty(B, H, like=z), _empty(B, A, like=z)
+        mu = _empty(B, A, like=z)
+        pi = _empty(B, A, like=z) if noise is not None else None
+        _mlp_fwd(z, 0, _Mlp(actor.trunk), 1, B, F, H, A, h1, h2, out,
+                 head=(noise, actor.std_on(z.device), None,
+                       dict(mu=mu, pi=pi, log_pi=keep.get("log_pi"), log_std=keep["log_std"]), "det"))
+        ctx.actor, ctx.h1, ctx.h2 = actor, h1, h2
+        keep.update(out=out)
+        ctx.save_for_backward(z, mu)
+        return (mu, pi) if pi is not None else mu
+
+    @staticmethod
+    @once_differentiable_hip
+    def backward(ctx, *grads):
+        actor = ctx.actor
+        z, mu = ctx.saved_tensors
+        dmu, dpi = grads if len(grads) == 2 else (grads[0], None)
+        B, A, H, F = z.shape[0], actor.action_dim, actor.hidden_dim, actor.encoder.feature_dim
+        need = ctx.needs_input_grad
+        if (dmu is None and dpi is None) or not any(need[3:]):
+            return (None,) * (4 + 6)
+        dout = _empty(B, A, like=z)
+        ops.det_policy_head_bwd(_contig(dmu), _contig(dpi), mu, B, A, dout)
+        G = _grad_mlp(_linears(actor.trunk)) if any(need[4:]) else None
+        dz = _empty(B, F, like=z) if need[3] else None
+        _mlp_bwd(z, 0, _Mlp(actor.trunk), G, 1, B, F, H, A, ctx.h1, ctx.h2, dout, _empty(B, H, like=z),
+                 _empty(B, H, like=z), dz)
+        pg = [None] * 6 if G is None else [t for i in range(3) for t in (G.W[i], G.b[i])]
+        return (None, None, None, dz, *pg)
+
+
+def _det_actor_forward(actor, z, compute_pi, compute_log_pi, noise):
+    B, A = z.shape[0], actor.action_dim
+    keep = dict(log_std=_empty(B, A, like=z))
+    if compute_pi:
+        noise = torch.randn((B, A), device=z.device) if noise is None else noise.detach().contiguous().float()
+        if compute_log_pi:
+            keep["log_pi"] = _empty(B, 1, like=z)
+    else:
+        noise = None
+    outs = DetActorFn.apply(actor, keep, noise, z, *[t for m in _linears(actor.trunk) for t in (m.weight, m.bias)])
+    mu, pi = outs if compute_pi else (outs, None)
+    actor.outputs['mu'] = keep["out"]
+    actor.outputs['std'] = keep["log_std"].exp()
+    return mu, pi, keep.get("log_pi"), keep["log_std"]
+
+
 def actor_forward(actor, z, compute_pi, compute_log_pi, noise):
+    if actor.deterministic:
+        return _det_actor_forward(actor, z, compute_pi, compute_log_pi, noise)
     B, A = z.shape[0], actor.action_dim
     if compute_pi:
         noise = torch.randn((B, A), device=z.device) if noise is None else noise.detach().contiguous().float()

@@ -69,7 +69,7 @@ int ln_bwd_launch(const float* dy, const float* dy2, int ld_dy, const float* xha
 // always are) and they fit the 48 KB a kernel may use without asking.
 // (R = 4 rows per wave to share the weight loads was measured for the actor's 8 outputs: 25 us against 14 -- the
 // layer is load latency, and 128 waves hide less of it than 512)
-template <bool HEAD>
+template <int HEAD>
 int mlp_out_fwd_launch(const float* h, long long sH, long long sH2, const float* W, long long sW, long long sW2,
                        const float* bias, long long sB, long long sB2, float* out, long long sOut, long long sOut2, int M,
                        int N, int K, int nb, int nb2, const HeadArgs& hd, void* stream) {
@@ -90,7 +90,7 @@ int head_args(const float* noise, int B, int A, float log_std_min, float log_std
   CURLA_REQUIRE(!pi_xa || (noise && xa_ld >= A));
   hd->noise = noise, hd->mu_t = mu, hd->pi_t = pi, hd->log_pi = log_pi, hd->log_std = log_std, hd->tanh_ls = tanh_ls;
   hd->pi_xa = pi_xa, hd->A = A, hd->xa_ld = xa_ld, hd->lo = log_std_min, hd->hi = log_std_max;
-  hd->noise_gen = nullptr, hd->rng_seed = 0, hd->rng_offset = 0, hd->rng_dev = nullptr;
+  hd->noise_gen = nullptr, hd->rng_seed = 0, hd->rng_offset = 0, hd->rng_dev = nullptr, hd->std = nullptr, hd->clip = 0.f;
   return CURLA_OK;
 }
 
@@ -115,7 +115,34 @@ int mlp_out_head_launch(const float* h, const float* W, const float* bias, float
                         const HeadArgs& hd, void* stream) {
   if (2 * A > kMaxOut || K % 4 != 0) return CURLA_ERR_UNSUPPORTED;
   CURLA_REQUIRE(aligned16(h) && aligned16(W));
-  return mlp_out_fwd_launch<true>(h, 0LL, 0LL, W, 0LL, 0LL, bias, 0LL, 0LL, trunk_out, 0LL, 0LL, B, 2 * A, K, 1, 1, hd, stream);
+  return mlp_out_fwd_launch<kHeadGauss>(h, 0LL, 0LL, W, 0LL, 0LL, bias, 0LL, 0LL, trunk_out, 0LL, 0LL, B, 2 * A, K, 1, 1, hd,
+                                        stream);
+}
+
+// The deterministic head's argument block (curla_det_head_fwd and its three relatives): the Gaussian head's checks, then
+// its own -- the device scalar `std` is required, the clip is >= 0 (+inf: none; false for a NaN).  `noise_out` != NULL:
+// the draws are made inside the launch (head_args_rng).
+int det_head_args(const float* noise, float* noise_out, unsigned long long seed, unsigned long long offset,
+                  const unsigned long long* rng_dev, const float* std, float clip, int B, int A, float* mu, float* pi,
+                  float* log_pi, float* log_std, float* pi_xa, int xa_ld, HeadArgs* hd) {
+  CURLA_REQUIRE(std && (reinterpret_cast<uintptr_t>(std) & 3) == 0 && clip >= 0.f);
+  const int rc = noise_out ? head_args_rng(noise_out, seed, offset, rng_dev, B, A, 0.f, 0.f, mu, pi, log_pi, log_std, nullptr,
+                                           pi_xa, xa_ld, hd)
+                           : head_args(noise, B, A, 0.f, 0.f, mu, pi, log_pi, log_std, nullptr, pi_xa, xa_ld, hd);
+  if (rc != CURLA_OK) return rc;
+  hd->std = std, hd->clip = clip;
+  return CURLA_OK;
+}
+
+int det_head_launch(const float* trunk_out, int B, const HeadArgs& hd, void* stream) {
+  return launch(det_head_fwd_kernel, dim3((B + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), trunk_out, B, hd);
+}
+
+int mlp_out_det_head_launch(const float* h, const float* W, const float* bias, float* trunk_out, int B, int A, int K,
+                            const HeadArgs& hd, void* stream) {
+  if (K % 4 != 0) return CURLA_ERR_UNSUPPORTED;  // (A <= kMaxA <= kMaxOut has been checked)
+  CURLA_REQUIRE(aligned16(h) && aligned16(W));
+  return mlp_out_fwd_launch<kHeadDet>(h, 0LL, 0LL, W, 0LL, 0LL, bias, 0LL, 0LL, trunk_out, 0LL, 0LL, B, A, K, 1, 1, hd, stream);
 }
 
 // the step-dependent factors evaluated in double, as torch's single-tensor Adam does
@@ -426,7 +453,7 @@ int curla_mlp_out_fwd(const float* h, long long strideH, const float* W, long lo
   CURLA_REQUIRE(h && W && out && M > 0 && N > 0 && K > 0 && nbatch > 0);
   if (N > kMaxOut || K % 4 != 0 || strideH % 4 != 0 || strideW % 4 != 0) return CURLA_ERR_UNSUPPORTED;
   CURLA_REQUIRE(aligned16(h) && aligned16(W));
-  return mlp_out_fwd_launch<false>(h, strideH, 0LL, W, strideW, 0LL, bias, strideBias, 0LL, out, strideOut, 0LL, M, N, K,
+  return mlp_out_fwd_launch<0>(h, strideH, 0LL, W, strideW, 0LL, bias, strideBias, 0LL, out, strideOut, 0LL, M, N, K,
                                    nbatch, 1, HeadArgs{}, stream);
 }
 
@@ -438,7 +465,7 @@ int curla_mlp_out_fwd_nested(const float* h, long long strideH, long long stride
   if (N > kMaxOut || K % 4 != 0 || strideH % 4 != 0 || strideW % 4 != 0 || strideH2 % 4 != 0 || strideW2 % 4 != 0)
     return CURLA_ERR_UNSUPPORTED;
   CURLA_REQUIRE(aligned16(h) && aligned16(W));
-  return mlp_out_fwd_launch<false>(h, strideH, strideH2, W, strideW, strideW2, bias, strideBias, strideBias2, out,
+  return mlp_out_fwd_launch<0>(h, strideH, strideH2, W, strideW, strideW2, bias, strideBias, strideBias2, out,
                                    strideOut, strideOut2, M, N, K, nbatch, nbatch2, HeadArgs{}, stream);
 }
 
@@ -544,6 +571,58 @@ int curla_policy_head_bwd(const float* dmu, const float* dpi, const float* dlog_
   CURLA_REQUIRE(!(dpi || dlog_pi) || (noise && pi && log_std));
   return launch(policy_head_bwd_kernel, dim3((B + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), dmu, dpi, dlog_pi,
                 dlog_std, noise, mu, pi, log_std, tanh_ls, B, A, log_std_min, log_std_max, dtrunk_out);
+}
+
+int curla_det_head_fwd(const float* trunk_out, const float* noise, const float* std, float clip, int B, int A, float* mu,
+                       float* pi, float* log_pi, float* log_std, float* pi_xa, int xa_ld, void* stream) {
+  CURLA_REQUIRE(trunk_out);
+  HeadArgs hd;
+  const int rc = det_head_args(noise, nullptr, 0, 0, nullptr, std, clip, B, A, mu, pi, log_pi, log_std, pi_xa, xa_ld, &hd);
+  return rc != CURLA_OK ? rc : det_head_launch(trunk_out, B, hd, stream);
+}
+
+int curla_det_head_fwd_rng(const float* trunk_out, float* noise_out, unsigned long long seed, unsigned long long offset,
+                           const unsigned long long* rng_dev, const float* std, float clip, int B, int A, float* mu,
+                           float* pi, float* log_pi, float* log_std, float* pi_xa, int xa_ld, void* stream) {
+  CURLA_REQUIRE(trunk_out && noise_out);
+  HeadArgs hd;
+  const int rc = det_head_args(nullptr, noise_out, seed, offset, rng_dev, std, clip, B, A, mu, pi, log_pi, log_std, pi_xa,
+                               xa_ld, &hd);
+  return rc != CURLA_OK ? rc : det_head_launch(trunk_out, B, hd, stream);
+}
+
+int curla_mlp_out_det_head_fwd(const float* h, const float* W, const float* bias, float* trunk_out, int B, int A, int K,
+                               const float* noise, const float* std, float clip, float* mu, float* pi, float* log_pi,
+                               float* log_std, float* pi_xa, int xa_ld, void* stream) {
+  CURLA_REQUIRE(h && W && trunk_out && K > 0);
+  HeadArgs hd;
+  const int rc = det_head_args(noise, nullptr, 0, 0, nullptr, std, clip, B, A, mu, pi, log_pi, log_std, pi_xa, xa_ld, &hd);
+  return rc != CURLA_OK ? rc : mlp_out_det_head_launch(h, W, bias, trunk_out, B, A, K, hd, stream);
+}
+
+int curla_mlp_out_det_head_fwd_rng(const float* h, const float* W, const float* bias, float* trunk_out, int B, int A, int K,
+                                   float* noise_out, unsigned long long seed, unsigned long long offset,
+                                   const unsigned long long* rng_dev, const float* std, float clip, float* mu, float* pi,
+                                   float* log_pi, float* log_std, float* pi_xa, int xa_ld, void* stream) {
+  CURLA_REQUIRE(h && W && trunk_out && K > 0 && noise_out);
+  HeadArgs hd;
+  const int rc = det_head_args(nullptr, noise_out, seed, offset, rng_dev, std, clip, B, A, mu, pi, log_pi, log_std, pi_xa,
+                               xa_ld, &hd);
+  return rc != CURLA_OK ? rc : mlp_out_det_head_launch(h, W, bias, trunk_out, B, A, K, hd, stream);
+}
+
+int curla_det_head_bwd(const float* gpi, const float* gpi2, int gpi_ld, const float* mu, int B, int A, float* dtrunk_out,
+                       void* stream) {
+  CURLA_REQUIRE(gpi && mu && dtrunk_out && B > 0 && A > 0 && A <= kMaxA && gpi_ld >= A);
+  return launch(det_head_bwd_kernel, dim3((B + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), gpi, gpi2, gpi_ld, mu,
+                B, A, dtrunk_out);
+}
+
+int curla_det_policy_head_bwd(const float* dmu, const float* dpi, const float* mu, int B, int A, float* dtrunk_out,
+                              void* stream) {
+  CURLA_REQUIRE(mu && dtrunk_out && B > 0 && A > 0 && A <= kMaxA);
+  return launch(det_policy_head_bwd_kernel, dim3((B + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), dmu, dpi, mu, B,
+                A, dtrunk_out);
 }
 
 int curla_concat(const float* z, const float* act, int B, int F, int A, float* xa, void* stream) {

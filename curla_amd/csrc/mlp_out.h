@@ -1,6 +1,7 @@
 // The small last layers of the actor / Q trunks (mlp_out_fwd_kernel, mlp_out_bwd_kernel) and the squashed-Gaussian
 // policy head, fused into the actor's last layer or as launches of its own (actor_head_fwd_kernel and the two backward
-// kernels).  Included by heads.hip inside its anonymous namespace, behind reduce.h (wave_sum).
+// kernels); beside it the deterministic DrQ-v2 head tanh(o) + clipped noise (det_head_fwd_kernel and its two backward
+// kernels), fused the same way.  Included by heads.hip inside its anonymous namespace, behind reduce.h (wave_sum).
 #pragma once
 
 // ---- last layer of the actor / Q trunks: hidden -> N outputs with N tiny (Q: 1, actor: 2|A|) ----
@@ -25,6 +26,10 @@ struct HeadArgs {
   // rng_dev != nullptr: (seed, offset) are read from device memory when the kernel RUNS (rng_dev[0], rng_dev[1]) -- a
   // captured graph is replayed with new stream positions
   const unsigned long long* rng_dev;
+  // the deterministic head (det_head_one) only: the standard deviation of its noise, read from device memory when the
+  // kernel RUNS (a schedule is data, a captured graph never holds it), and the clip of the scaled noise (+inf: none)
+  const float* std;
+  float clip;
 };
 
 // (philox4x32_10 / philox_normal: common.h, shared with the noisy-cover kernel of augment.hip)
@@ -61,14 +66,48 @@ __device__ __forceinline__ void actor_head_row(const float* out2a_row, int b, co
   if ((hd.noise || hd.noise_gen) && hd.log_pi) hd.log_pi[b] = lp - kHalfLog2Pi * hd.A - corr;
 }
 
+// ---- deterministic policy head (DrQ-v2), one element: trunk output o [B][A] -> m = tanh(o), pi = clamp(m + e, -lim, lim)
+// with e = clamp(s n, -c, c), lim = 1 - 1e-6 (DrQ-v2's TruncatedNormal.sample); log_std = log(s), a constant ----
+constexpr int kHeadGauss = 1, kHeadDet = 2;  // the HEAD kinds of mlp_out_fwd_kernel (0: none)
+__device__ __forceinline__ void det_head_one(float o, int b, int a, const HeadArgs& hd) {
+  const size_t e = (size_t)b * hd.A + a;
+  const float m = tanhf(o);
+  const float s = *hd.std;
+  if (hd.mu_t) hd.mu_t[e] = m;
+  if (hd.log_std) hd.log_std[e] = (float)log((double)s);  // (in double: the float32 nearest to log(s), whatever s)
+  if (hd.noise || hd.noise_gen) {
+    float n;
+    if (hd.noise_gen) {
+      const unsigned long long seed = hd.rng_dev ? hd.rng_dev[0] : hd.rng_seed;
+      const unsigned long long offs = hd.rng_dev ? hd.rng_dev[1] : hd.rng_offset;
+      n = philox_normal(seed, offs, (unsigned)(b * hd.A + a));
+      hd.noise_gen[e] = n;
+    } else {
+      n = hd.noise[e];
+    }
+    const float lim = 1.f - 1e-6f;
+    const float ev = fminf(fmaxf(s * n, -hd.clip), hd.clip);
+    const float p = fminf(fmaxf(m + ev, -lim), lim);
+    if (hd.pi_t) hd.pi_t[e] = p;
+    if (hd.pi_xa) hd.pi_xa[(size_t)b * hd.xa_ld + a] = p;
+  }
+}
+
+// one thread walks the row's actions; log_pi is the constant 0 (no entropy term: the critic losses' alpha * 0)
+__device__ __forceinline__ void det_head_row(const float* out_row, int b, const HeadArgs& hd) {
+  for (int a = 0; a < hd.A; ++a) det_head_one(out_row[a], b, a, hd);
+  if (hd.log_pi) hd.log_pi[b] = 0.f;
+}
+
 // out[z][m][n] = bias[z][n] + sum_k h[z][m][k] * W[z][n][k]        (curl_sac.py:73-74,132-133 forward)
 // (two-level batch: blockIdx.y = outer * nb_inner + inner; the outer level's strides end in 2)
 // HEAD: the outputs are the actor trunk's [mu | raw log_std] and the wave that produced a row also runs the policy
-// head on it (a launch of its own otherwise: a few hundred cycles of work per row behind a 5 us launch)
+// head on it (a launch of its own otherwise: a few hundred cycles of work per row behind a 5 us launch); HEAD is the
+// head's kind -- 0 none, kHeadGauss, kHeadDet (the outputs are then the A pre-squash means alone)
 // R rows per wave: a weight float4 is loaded once for R rows; a row's sums do not depend on R (R = 1 is what runs).
 // LDSW: the block first copies the N weight rows into LDS and its four waves read them from there -- with several
 // rows (the actor's 8 x 1024) every wave otherwise pulls 32 KB through the L2 for itself, 16 MB per launch.
-template <bool HEAD, int R, bool LDSW>
+template <int HEAD, int R, bool LDSW>
 __global__ __launch_bounds__(256) void mlp_out_fwd_kernel(const float* h, long long sH, long long sH2, const float* W,
                                                           long long sW, long long sW2, const float* bias, long long sB,
                                                           long long sB2, float* out, long long sOut, long long sOut2,
@@ -117,7 +156,17 @@ __global__ __launch_bounds__(256) void mlp_out_fwd_kernel(const float* h, long l
         if (lane == 0)
           out[zi * sOut + zo * sOut2 + (size_t)row * N + n] = s + (bias ? bias[zi * sB + zo * sB2 + n] : 0.f);
       }
-    if (HEAD) {
+    if (HEAD == kHeadDet) {
+      float o = 0.f;
+#pragma unroll
+      for (int n = 0; n < kMaxOut; ++n) {
+        const float v = n < N ? acc[r][n] + (bias ? bias[n] : 0.f) : 0.f;
+        if (n == lane) o = v;
+      }
+      if (lane < hd.A) det_head_one(o, row, lane, hd);
+      if (lane == 0 && hd.log_pi) hd.log_pi[row] = 0.f;
+    }
+    if (HEAD == kHeadGauss) {
       // every lane holds the row's outputs: lane a < A takes action a, the two sums over the actions are then added
       // in action order by lane 0 (the same order as the one-thread walk)
       float mu = 0.f, raw = 0.f;
@@ -378,5 +427,41 @@ __global__ void policy_head_bwd_kernel(const float* dmu, const float* dpi, const
     const float t = tanh_ls[e];
     dout2a[(size_t)b * 2 * A + a] = gmu;
     dout2a[(size_t)b * 2 * A + A + a] = gls * 0.5f * (hi - lo) * (1.f - t * t);
+  }
+}
+
+// ---- deterministic policy head, a launch of its own (acting path; training fuses it into mlp_out_fwd_kernel<kHeadDet>) ----
+__global__ void det_head_fwd_kernel(const float* out, int B, HeadArgs hd) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  det_head_row(out + (size_t)b * hd.A, b, hd);
+}
+
+// gradient of sum_a gpi[a] * pi[a] wrt the trunk output o [B][A]: d pi / d o = 1 - m^2 (straight through the outer clamp;
+// the noise depends on no parameter).  gpi is addressed as actor_head_bwd_kernel's: gpi[b*gpi_ld + a] (+ gpi2[...]), the
+// action columns of the twin-Q input gradient read in place and summed over the twin
+__global__ void det_head_bwd_kernel(const float* gpi, const float* gpi2, int gpi_ld, const float* mu_t, int B, int A,
+                                    float* dout) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  for (int a = 0; a < A; ++a) {
+    const float m = mu_t[(size_t)b * A + a];
+    float gp = gpi[(size_t)b * gpi_ld + a];
+    if (gpi2) gp += gpi2[(size_t)b * gpi_ld + a];
+    dout[(size_t)b * A + a] = gp * (1.f - m * m);
+  }
+}
+
+// general backward of the deterministic head for upstream gradients of mu and pi (NULL = zero), [B][A] each:
+// d o = (dmu + dpi)(1 - m^2); log_pi and log_std are constants
+__global__ void det_policy_head_bwd_kernel(const float* dmu, const float* dpi, const float* mu_t, int B, int A,
+                                           float* dout) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  for (int a = 0; a < A; ++a) {
+    const size_t e = (size_t)b * A + a;
+    const float m = mu_t[e];
+    const float g = (dmu ? dmu[e] : 0.f) + (dpi ? dpi[e] : 0.f);
+    dout[e] = g * (1.f - m * m);
   }
 }

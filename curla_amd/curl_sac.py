@@ -36,7 +36,7 @@ from .encoder import CNNEncoder
 from .mlp import _Mlp, _MlpLn, _linears, _mlp_bwd, _mlp_fwd  # noqa: F401
 from .networks import (CURL, LOG_FREQ, Actor, Critic, QFunction, _check_drop_quantiles,  # noqa: F401
                        _check_bin_sigma, _check_bins, _check_dropout, _check_int, _check_layer_norm_width,
-                       _check_quantiles, _check_value_range, _CriticType,
+                       _check_policy_std, _check_policy_std_clip, _check_quantiles, _check_value_range, _CriticType,
                        _device_generator, _QFunctionType, _reserve_dropout_counter, _widen_last_layers, weight_init)
 from .ops import ObsRef
 from .optim import FlatAdam, check_max_grad_norm, check_weight_decay
@@ -60,6 +60,33 @@ def _check_views(v):
 def _check_utd_ratio(g):
     """The update-to-data ratio: an ``int >= 1`` (a bool, a float or a string is not one)."""
     return _check_int(g, 1, None, "utd_ratio: %r is not an int >= 1" % (g,))
+
+
+def _check_policy(policy):
+    if policy not in ("gaussian", "deterministic"):
+        raise ValueError("policy: %r is not 'gaussian' or 'deterministic'" % (policy,))
+    return policy
+
+
+def _check_policy_std_schedule(sched):
+    """DrQ-v2's ``linear(init, final, duration)`` as a tuple of three floats: init and final finite and > 0, duration
+    finite and > 0; or None."""
+    if sched is None:
+        return None
+    try:
+        init, final, duration = (float(v) for v in sched)
+    except (TypeError, ValueError):
+        raise ValueError("policy_std_schedule: %r is not None or (init, final, duration)" % (sched,)) from None
+    if not (np.isfinite(init) and np.isfinite(final) and np.isfinite(duration) and init > 0 and final > 0 and duration > 0):
+        raise ValueError("policy_std_schedule: (%r, %r, %r) is not (init > 0, final > 0, duration > 0), all finite"
+                         % (init, final, duration))
+    return init, final, duration
+
+
+def _linear_schedule(sched, step):
+    """DrQ-v2's linear(init, final, duration) at ``step``: init + (final - init) * min(step / duration, 1)."""
+    init, final, duration = sched
+    return init + (final - init) * min(step / duration, 1.0)
 
 
 class _Workspace:
@@ -92,8 +119,9 @@ class _Workspace:
         self.w_partial = f(max(1, B // 16) * F * F) if ops.curl_head_supported(B, F) else None
         self.fc_out = f(B, F)  # pre-LayerNorm features, only written on histogram-logging steps
         # actor trunk
-        self.a_h1, self.a_h2, self.a_out = f(B, H), f(B, H), f(B, 2 * A)
-        self.a_dh1, self.a_dh2, self.a_dout = f(B, H), f(B, H), f(B, 2 * A)
+        AO = agent._actor_out_dim()  # ([mu | raw log_std]; the deterministic policy: the A means alone)
+        self.a_h1, self.a_h2, self.a_out = f(B, H), f(B, H), f(B, AO)
+        self.a_dh1, self.a_dh2, self.a_dout = f(B, H), f(B, H), f(B, AO)
         self.noise = f(B, A)
         self.mu, self.pi, self.log_std, self.tanh_ls, self.gpi = f(B, A), f(B, A), f(B, A), f(B, A), f(B, A)
         self.log_pi = f(B, 1)
@@ -132,11 +160,25 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, aug_views=1, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0,
+    def __call__(cls, *args, policy="gaussian", policy_std=0.2, policy_std_clip=0.3, policy_std_schedule=None,
+                 aug_views=1, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0,
                  reset_encoder_keep=1.0, reset_seed=0, critic_quantiles=0, critic_drop_quantiles=0, critic_bins=0,
                  critic_value_range=None, critic_bin_sigma=0.75, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0,
                  critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
+        if _check_policy(policy) == "deterministic":  # (gaussian: the instance is the one without the keyword)
+            agent.policy = "deterministic"
+            agent.policy_std_schedule = _check_policy_std_schedule(policy_std_schedule)
+            agent._policy_std = _check_policy_std(policy_std)
+            if agent.policy_std_schedule is not None:  # (the schedule's value at step 0 until the first update)
+                agent._policy_std = _check_policy_std(_linear_schedule(agent.policy_std_schedule, 0))
+            agent.policy_std_clip = _check_policy_std_clip(policy_std_clip)
+        else:
+            for name, value, default in (("policy_std", policy_std, 0.2), ("policy_std_clip", policy_std_clip, 0.3),
+                                         ("policy_std_schedule", policy_std_schedule, None)):
+                if value is not default and value != default:
+                    raise ValueError("%s = %r needs policy='deterministic' (the Gaussian policy learns its own standard "
+                                     "deviation)" % (name, value))
         agent.redo_interval = _check_redo_interval(redo_interval)
         agent.redo_tau = _check_redo_tau(redo_tau)
         agent.redo_recycle = _check_redo_recycle(redo_recycle)
@@ -212,8 +254,21 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     and the critic is trained by cross-entropy on the histogram of a Gaussian of standard deviation s bin widths around
     the clamped scalar TD target; the actor ascends min(Q1, Q2) through the softmax.  M shapes the
     networks; the range and s are attributes that may be edited between calls.  ``target_clip_fraction()`` tells whether
-    the range fits.  With ``aug_views=2``; not with ``critic_quantiles``, not with a prioritized replay buffer."""
+    the range fits.  With ``aug_views=2``; not with ``critic_quantiles``, not with a prioritized replay buffer.
+    ``policy="deterministic"`` (default "gaussian": nothing changes) with ``policy_std=0.2`` (finite, > 0),
+    ``policy_std_clip=0.3`` (finite, >= 0, or None: no clip) and ``policy_std_schedule=None`` (or ``(init, final,
+    duration)``: DrQ-v2's linear schedule in ``update``'s ``step``): DrQ-v2's policy -- the actor outputs A pre-squash
+    means, ``select_action`` returns tanh(mu), ``sample_action`` clamp(tanh(mu) + std * noise, -lim, lim), and the update
+    phases clip the scaled noise to ``policy_std_clip`` before they add it (TD3's target smoothing); log_pi is 0, so the
+    critic losses compute the entropy-free target, the actor loss is -mean Q, and log_alpha never moves.
+    The policy shapes the actor; ``policy_std`` is read through ``agent.policy_std`` and set by ``set_policy_std`` (a
+    device scalar: data to captured graphs), clip and schedule are attributes that may be edited between calls.  The
+    three ``policy_std*`` keywords raise beside the Gaussian policy."""
 
+    policy = "gaussian"
+    policy_std_clip = None
+    policy_std_schedule = None
+    _policy_std = None
     critic_layer_norm = False
     critic_dropout = 0.0
     utd_ratio = 1
@@ -285,7 +340,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
 
         # same construction order as the reference => same RNG stream => same init for a given seed
         self.actor = Actor(obs_shape, action_shape, hidden_dim, encoder_feature_dim, actor_log_std_min,
-                           actor_log_std_max, num_layers, num_filters)
+                           actor_log_std_max, num_layers, num_filters, **self._actor_kw())
         q_kw = self._critic_width_kw()
         self.critic = Critic(obs_shape, action_shape, hidden_dim, encoder_feature_dim, num_layers, num_filters,
                              layer_norm=self.critic_layer_norm, dropout=self.critic_dropout, **q_kw)
@@ -303,6 +358,12 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         self.CURL = CURL(obs_shape, encoder_feature_dim, self.critic, self.critic_target, output_type='continuous')
 
         self._to_flat_device_layout()
+        if self.policy == "deterministic":
+            # the standard deviation the head kernels read on the device, and where the actor loss launches leave their
+            # d(alpha loss)/d(log_alpha): log_alpha.grad stays all zeros, so its Adam step leaves it bit for bit alone
+            self.actor.std = torch.full((1,), self._policy_std, device=self.device, dtype=torch.float32)
+            self.actor.std_clip = self.policy_std_clip
+            self._dla_scratch = torch.zeros((), device=self.device, dtype=torch.float64)
 
         actor_own = [p for n, p in self.actor.named_parameters() if ".convs." not in n]
         enc_params = list(self.critic.encoder.parameters())
@@ -634,13 +695,48 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             self._encoder_backward(ws, obs_ref, dz, ws.xhat_c, ws.rstd_c, enc, **kw)
             self._allreduce(g[lo:hi])
 
+    # -- the deterministic policy
+    def _actor_kw(self):
+        """The keyword that shapes the actor, for every place that builds one."""
+        return dict(deterministic=True) if self.policy == "deterministic" else {}
+
+    def _actor_out_dim(self):
+        """The width of the actor trunk's last layer: [mu | raw log_std], or the deterministic policy's A means."""
+        return self.action_dim if self.policy == "deterministic" else 2 * self.action_dim
+
+    def _policy_clip(self):
+        """``policy_std_clip`` as it stands now (it may have been edited), checked; the actor's follows the agent's."""
+        clip = self.actor.std_clip = _check_policy_std_clip(self.policy_std_clip)
+        return clip
+
+    @property
+    def policy_std(self):
+        """The deterministic policy's current standard deviation (None: the Gaussian policy); ``set_policy_std``."""
+        return self._policy_std
+
+    def set_policy_std(self, value):
+        """Set the deterministic policy's standard deviation: one fill of the device scalar the head kernels read,
+        enqueued on the current stream and only when the value changes; the host is never synchronised and no captured
+        graph holds the value."""
+        if self.policy != "deterministic":
+            raise ValueError("set_policy_std needs policy='deterministic'")
+        value = _check_policy_std(value)
+        if value != self._policy_std:
+            self._policy_std = value
+            self.actor.std.fill_(value)
+
     # -- the network passes: shapes and buffers are the workspace's and the agent's, stated here and nowhere else
     def _actor_fwd(self, ws, noise=None, **outs):
         """The actor trunk over ws.z_a into ws.a_out; with ``noise``, the policy head behind it, which writes ``outs``
-        (ops.actor_head_fwd's: mu, pi, log_pi, log_std, tanh_ls, xa, rng)."""
+        (ops.actor_head_fwd's: mu, pi, log_pi, log_std, tanh_ls, xa, rng; the deterministic head has no tanh_ls and
+        clips its scaled noise to ``policy_std_clip``)."""
         B, F = ws.z_a.shape
-        head = None if noise is None else (noise, self.actor.log_std_min, self.actor.log_std_max, outs)
-        _mlp_fwd(ws.z_a, 0, _Mlp(self.actor.trunk), 1, B, F, self.hidden_dim, 2 * self.action_dim, ws.a_h1, ws.a_h2,
+        if self.policy == "deterministic":
+            outs.pop("tanh_ls", None)
+            head = None if noise is None else (noise, self.actor.std, self._policy_clip(), outs, "det")
+        else:
+            head = None if noise is None else (noise, self.actor.log_std_min, self.actor.log_std_max, outs)
+        _mlp_fwd(ws.z_a, 0, _Mlp(self.actor.trunk), 1, B, F, self.hidden_dim, self._actor_out_dim(), ws.a_h1, ws.a_h2,
                  ws.a_out, head=head)
 
     def _twin_fwd(self, ws, net, ln, out=None, outer=None):
@@ -730,16 +826,18 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         atoms in place of min(Q1, Q2), a launch of its own."""
         B, A, Mq = ws.log_pi.shape[0], self.action_dim, self.critic.out_dim
         la, te, out = self.log_alpha, float(self.target_entropy), ws.scalars[1:5]
+        # (the deterministic policy: log_pi = 0 and the temperature takes no part -- its gradient goes to a scratch word)
+        dla = self._dla_scratch if self.policy == "deterministic" else la.grad
         if self.critic_quantiles:
             return None, lambda: ops.tqc_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, la, te, B, Mq, out, ws.dq,
-                                                    B * Mq, la.grad)
+                                                    B * Mq, dla)
         if self.critic_bins:
             v_min, v_max, _ = self._hlg_params()
             return None, lambda: ops.hlg_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, la, te, B, Mq, v_min, v_max,
-                                                    ws.q_row_loss, out, ws.dq, B * Mq, la.grad)
+                                                    ws.q_row_loss, out, ws.dq, B * Mq, dla)
         return (dict(kind=2, A=A, twin_stride=B, q=ws.q, log_pi=ws.log_pi, log_std=ws.log_std, log_alpha=la,
-                     target_entropy=te, scalars=out, dq=ws.dq, dlog_alpha=la.grad),
-                lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, la, te, B, out, ws.dq, la.grad))
+                     target_entropy=te, scalars=out, dq=ws.dq, dlog_alpha=dla),
+                lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, la, te, B, out, ws.dq, dla))
 
     # -- the critic phase's forward: a' ~ pi(. | z'), the target's twins over [z' | a'], the critic's over [z | a]
     #    (curl_sac.py:350-358), by one of three routes; each returns the phase's ``drop`` (_dropout)
@@ -906,9 +1004,10 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         CNNEncoder.ln_from_partial_multi(B, lns, A)
         self._anchor_cache = obs
 
+        det = self.policy == "deterministic"
         nz, rng = self._noise(ws, noise)
-        self._actor_fwd(ws, nz, mu=ws.mu, pi=ws.pi, log_pi=ws.log_pi, log_std=ws.log_std, tanh_ls=ws.tanh_ls, xa=ws.xa,
-                        rng=rng)
+        self._actor_fwd(ws, nz, mu=ws.mu, pi=None if det else ws.pi, log_pi=ws.log_pi, log_std=ws.log_std,
+                        tanh_ls=ws.tanh_ls, xa=ws.xa, rng=rng)
         if self._records(step):  # what actor.log() histograms (curl_sac.py:92-93): pre-squash mean and std
             self.actor.outputs['mu'], self.actor.outputs['std'] = ws.a_out[:, :A].clone(), ws.log_std.exp()
         # (the data gradient through the LayerNorms needs the saves too; dropout: the critic twins under tags 5 / 6)
@@ -918,19 +1017,25 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         self._twin_bwd(ws, q_ln, self._actor_loss(ws), grads=False)
         if step % self.log_interval == 0:
             L.log('train_actor/loss', ws.scalars[1], step)
-            L.log('train_actor/target_entropy', self.target_entropy, step)
-            L.log('train_actor/entropy', ws.scalars[3], step)
+            if det:  # (no entropy term, no temperature)
+                L.log('train_actor/std', self._policy_std, step)
+            else:
+                L.log('train_actor/target_entropy', self.target_entropy, step)
+                L.log('train_actor/entropy', ws.scalars[3], step)
         # d(loss)/d(pi) = the action columns of dxa summed over the twin, read in place
         F, trunk = aenc.feature_dim, self.actor.trunk
-        ops.actor_head_bwd(None, self.log_alpha, 1.0 / B, nz, ws.pi, ws.log_std, ws.tanh_ls, B, A, self.actor.log_std_min,
-                           self.actor.log_std_max, ws.a_dout, twin_dxa=ws.dxa, F=F)
-        _mlp_bwd(ws.z_a, 0, _Mlp(trunk), _Mlp(trunk, grads=True), 1, B, F, self.hidden_dim, 2 * A, ws.a_h1, ws.a_h2,
-                 ws.a_dout, ws.a_dh2, ws.a_dh1, ws.dz)
+        if det:
+            ops.det_head_bwd(None, ws.mu, B, A, ws.a_dout, twin_dxa=ws.dxa, F=F)
+        else:
+            ops.actor_head_bwd(None, self.log_alpha, 1.0 / B, nz, ws.pi, ws.log_std, ws.tanh_ls, B, A,
+                               self.actor.log_std_min, self.actor.log_std_max, ws.a_dout, twin_dxa=ws.dxa, F=F)
+        _mlp_bwd(ws.z_a, 0, _Mlp(trunk), _Mlp(trunk, grads=True), 1, B, F, self.hidden_dim, self._actor_out_dim(), ws.a_h1,
+                 ws.a_h2, ws.a_dout, ws.a_dh2, ws.a_dh1, ws.dz)
         self._encoder_backward(ws, o, ws.dz, ws.xhat_a, ws.rstd_a, aenc, conv_grads=False)
         self._actor_reduce_and_step(L, step)
         if self.log_param_hist_imgs:
             self.actor.log(L, step)
-        if step % self.log_interval == 0:
+        if step % self.log_interval == 0 and not det:
             L.log('train_alpha/loss', ws.scalars[2], step)
             L.log('train_alpha/value', ws.scalars[4], step)
 
@@ -1127,6 +1232,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         decision) followed by the ordinary call with ``utd_ratio = 1``.  ``noise`` is a hook for one minibatch and is
         refused with G > 1."""
         self._restore_grad_views()
+        if self.policy_std_schedule is not None:  # (evaluated before the eager / graph route is chosen: std is data)
+            self.set_policy_std(_linear_schedule(_check_policy_std_schedule(self.policy_std_schedule), step))
         self._check_n_step(replay_buffer)
         self._check_aug_views(replay_buffer)
         self._maybe_reset(step)  # (reset_interval: in front of every sub-step, graphed or not)
@@ -1299,6 +1406,9 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             **({"aug_views": 2} if self.aug_views == 2 else {}),  # (1: the file of an agent without the keyword)
             **({"critic_bins": int(self.critic_bins), "critic_value_range": tuple(float(v) for v in self.critic_value_range),
                 "critic_bin_sigma": float(self.critic_bin_sigma)} if self.critic_bins else {}),  # (0: likewise)
+            **({"policy": "deterministic", "policy_std": float(self._policy_std),
+                "policy_std_clip": self.policy_std_clip, "policy_std_schedule": self.policy_std_schedule}
+               if self.policy == "deterministic" else {}),  # (gaussian: likewise)
             **self._reset_checkpoint(), **self._redo_checkpoint(),
         }, path)
 
@@ -1329,6 +1439,11 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             self.critic_value_range = _check_value_range(ck["critic_value_range"])
             self.critic_bin_sigma = _check_bin_sigma(ck.get("critic_bin_sigma", self.critic_bin_sigma))
             self._hlg_params()
+        # (a checkpoint of the other policy has failed above, on the size of actor.trunk.4)
+        if self.policy == "deterministic" and ck.get("policy") == "deterministic":
+            self.policy_std_clip = _check_policy_std_clip(ck["policy_std_clip"])
+            self.policy_std_schedule = _check_policy_std_schedule(ck["policy_std_schedule"])
+            self.set_policy_std(ck["policy_std"])
         with torch.no_grad():
             self.log_alpha.copy_(ck["log_alpha"])
         for k, o in self._optimizers().items():

@@ -68,7 +68,8 @@ def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None,
     """``outer`` = (n2, sW2): n2 such MLP groups in the same launches, their parameters sW2 floats apart (the target
     critic's and the critic's twins); x [n2][B, din] and h1 / h2 / out [n2][nb][B, .] then.
     ``head`` = (noise, lo, hi, outputs): the MLP is the actor trunk and the policy head (ops.actor_head_fwd with these
-    arguments) follows its last layer -- in the same launch when the layer is small enough.
+    arguments) follows its last layer -- in the same launch when the layer is small enough.  ``head`` = (noise, std,
+    clip, outputs, "det"): the deterministic head (ops.det_head_fwd) instead, over ``dout`` = A outputs.
     ``ln`` (_MlpLn): a LayerNorm sits between each hidden Linear and its ReLU -- the GEMM leaves the ReLU out and one
     launch per hidden layer normalises in place."""
     s = P.stride
@@ -84,7 +85,12 @@ def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None,
     if ln is not None:
         ln.fwd(1, h2, s, nb, B, H, outer)
     small = dout <= ops.MLP_OUT_MAX and H % 4 == 0 and not relu_out
-    if head is not None and small and nb == 1 and outer is None:
+    det = head is not None and len(head) == 5
+    if det and small and nb == 1 and outer is None:
+        noise, std, clip, outs, _ = head
+        ops.mlp_out_det_head_fwd(h2, P.W[2], P.b[2], out, noise, B, dout, H, std, clip, **outs)
+        return
+    if head is not None and not det and small and nb == 1 and outer is None:
         noise, lo, hi, outs = head
         ops.mlp_out_head_fwd(h2, P.W[2], P.b[2], out, noise, B, dout // 2, H, lo, hi, **outs)
         return
@@ -92,7 +98,10 @@ def _mlp_fwd(x, sx, P, nb, B, din, H, dout, h1, h2, out, relu_out=0, outer=None,
         ops.mlp_out_fwd(h2, B * H, P.W[2], s, P.b[2], s, out, B * dout, B, dout, H, nb, outer=o2)
     else:
         ops.linear_fwd(h2, B * H, P.W[2], s, P.b[2], s, out, B * dout, B, dout, H, nb, relu=relu_out, outer=o2)
-    if head is not None:
+    if det:
+        noise, std, clip, outs, _ = head
+        ops.det_head_fwd(out, noise, std, clip, B, dout, **outs)
+    elif head is not None:
         noise, lo, hi, outs = head
         ops.actor_head_fwd(out, noise, B, dout // 2, lo, hi, **outs)
 

@@ -30,8 +30,49 @@ def weight_init(m):
         nn.init.orthogonal_(m.weight.data[:, :, centre, centre], nn.init.calculate_gain('relu'))
 
 
-class Actor(nn.Module):
-    """MLP actor network (curl_sac.py:57-121)."""
+def _check_policy_std(v):
+    """The deterministic policy's standard deviation: a finite float > 0."""
+    if isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(v) or v <= 0:
+        raise ValueError("policy_std: %r is not a finite number > 0" % (v,))
+    return float(v)
+
+
+def _check_policy_std_clip(c):
+    """The clip of the deterministic policy's scaled noise inside an update: a finite float >= 0, or None (no clip)."""
+    if c is None:
+        return None
+    if isinstance(c, (bool, str)) or not isinstance(c, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(c) or c < 0:
+        raise ValueError("policy_std_clip: %r is not a finite number >= 0 or None" % (c,))
+    return float(c)
+
+
+class _ActorType(type):
+    """``Actor(..., deterministic=True)``: a keyword of the class call, as ``QFunction(..., quantiles=M)`` is;
+    ``Actor.__init__`` keeps its parameter list.  The actor is built as without it and its last Linear is then replaced
+    in place by a hidden -> A one (the key stays trunk.4), drawn from a fork of torch's generator: every other tensor a
+    seed produces, and the generator's state afterwards, are the Gaussian actor's."""
+
+    def __call__(cls, *args, deterministic=False, **kwargs):
+        actor = super().__call__(*args, **kwargs)
+        if deterministic:
+            actor.deterministic = True
+            _widen_last_layers([actor.trunk], actor.action_dim, weight_init)
+            actor.std = torch.full((1,), 0.2, dtype=torch.float32)  # (no registered buffer: the state-dict keys stay)
+            actor.std_clip = 0.3
+        return actor
+
+
+class Actor(nn.Module, metaclass=_ActorType):
+    """MLP actor network (curl_sac.py:57-121).  ``Actor(..., deterministic=True)`` (a keyword of the class call; DESIGN.md
+    7m): DrQ-v2's deterministic policy -- the trunk outputs the A pre-squash means alone, ``forward`` returns
+    ``mu = tanh(o)``, ``pi = clamp(mu + std * noise, -lim, lim)`` (no noise clip, as DrQ-v2 acts), ``log_pi`` zeros and
+    ``log_std`` filled with log(std).  ``std`` is a one-element float32 tensor read by the kernels on the device (edit it
+    in place, or through CurlSacAgent.set_policy_std); ``std_clip`` is what the agent's update phases clip the scaled noise
+    to (None: no clip)."""
+
+    deterministic = False
 
     def __init__(self, obs_shape, action_shape, hidden_dim, encoder_feature_dim, log_std_min, log_std_max,
                  num_layers, num_filters):
@@ -58,6 +99,21 @@ class Actor(nn.Module):
             return autograd.actor_forward(self, z, compute_pi, compute_log_pi, noise)
         B, A, H, F = z.shape[0], self.action_dim, self.hidden_dim, self.encoder.feature_dim
         dev = z.device
+        if self.deterministic:
+            h1, h2, out = (torch.empty(s, device=dev) for s in ((B, H), (B, H), (B, A)))
+            mu, log_std = torch.empty((B, A), device=dev), torch.empty((B, A), device=dev)
+            pi = log_pi = None
+            if compute_pi:
+                if noise is None:
+                    noise = torch.randn((B, A), device=dev)
+                pi = torch.empty((B, A), device=dev)
+                log_pi = torch.empty((B, 1), device=dev) if compute_log_pi else None
+            _mlp_fwd(z, 0, _Mlp(self.trunk), 1, B, F, H, A, h1, h2, out,
+                     head=(noise if compute_pi else None, self.std_on(dev), None,
+                           dict(mu=mu, pi=pi, log_pi=log_pi, log_std=log_std), "det"))
+            self.outputs['mu'] = out  # the pre-squash mean
+            self.outputs['std'] = log_std.exp()
+            return mu, pi, log_pi, log_std
         h1 = torch.empty((B, H), device=dev)
         h2 = torch.empty((B, H), device=dev)
         out = torch.empty((B, 2 * A), device=dev)
@@ -75,6 +131,13 @@ class Actor(nn.Module):
         self.outputs['mu'] = out[:, :A]  # the pre-squash mean, as the reference records it (curl_sac.py:92)
         self.outputs['std'] = log_std.exp()
         return mu, pi, log_pi, log_std
+
+    def std_on(self, device):
+        """The deterministic actor's ``std`` on ``device`` (moved there once: the kernels read it from device memory)."""
+        if self.std.device != torch.device(device) and not (self.std.is_cuda and torch.device(device).type == "cuda"
+                                                            and torch.device(device).index is None):
+            self.std = self.std.to(device)
+        return self.std
 
     def log(self, L, step, log_freq=LOG_FREQ):
         """Histograms of the recorded outputs and of the three trunk layers, every ``log_freq`` steps

@@ -577,6 +577,56 @@ def policy_head_bwd(dmu, dpi, dlog_pi, dlog_std, noise, mu, pi, log_std, tanh_ls
          ptr(log_std), ptr(tanh_ls), B, A, lo, hi, ptr(dtrunk_out), stream())
 
 
+def _det_clip(clip):
+    """The deterministic head's noise clip as the float the kernels take: None is +inf (no clip)."""
+    return float("inf") if clip is None else float(clip)
+
+
+def det_head_fwd(trunk_out, noise, std, clip, B, A, mu=None, pi=None, log_pi=None, log_std=None, xa=None, rng=None):
+    """The deterministic policy head over ``trunk_out`` [B, A]: mu = tanh(o), pi = clamp(mu + clamp(s noise,
+    -clip, clip), -lim, lim), log_pi = 0, log_std = log(s).  ``std``: a one-element float32 DEVICE tensor, read when the
+    kernel runs; ``clip``: a float >= 0 or None (no clip), held by value.  ``xa`` / ``rng``: as for actor_head_fwd."""
+    pi_xa, ld = (None, 0) if xa is None else (xa.data_ptr() + 4 * (xa.shape[1] - A), xa.shape[1])
+    if rng is not None:
+        call("curla_det_head_fwd_rng", ptr(trunk_out), ptr(noise), int(rng[0]) & (2 ** 64 - 1), int(rng[1]),
+             rng[2] if len(rng) > 2 else None, ptr(std), _det_clip(clip), B, A, ptr(mu), ptr(pi), ptr(log_pi), ptr(log_std),
+             pi_xa, ld, stream())
+        return
+    call("curla_det_head_fwd", ptr(trunk_out), ptr(noise), ptr(std), _det_clip(clip), B, A, ptr(mu), ptr(pi), ptr(log_pi),
+         ptr(log_std), pi_xa, ld, stream())
+
+
+def mlp_out_det_head_fwd(h, W, bias, trunk_out, noise, B, A, K, std, clip, mu=None, pi=None, log_pi=None, log_std=None,
+                         xa=None, rng=None):
+    """The deterministic actor's last layer (h [B, K] -> trunk_out [B, A]) with det_head_fwd run by the same launch; the
+    same bits as the two launches."""
+    pi_xa, ld = (None, 0) if xa is None else (xa.data_ptr() + 4 * (xa.shape[1] - A), xa.shape[1])
+    if rng is not None:
+        call("curla_mlp_out_det_head_fwd_rng", ptr(h), ptr(W), ptr(bias), ptr(trunk_out), B, A, K, ptr(noise),
+             int(rng[0]) & (2 ** 64 - 1), int(rng[1]), rng[2] if len(rng) > 2 else None, ptr(std), _det_clip(clip), ptr(mu),
+             ptr(pi), ptr(log_pi), ptr(log_std), pi_xa, ld, stream())
+        return
+    call("curla_mlp_out_det_head_fwd", ptr(h), ptr(W), ptr(bias), ptr(trunk_out), B, A, K, ptr(noise), ptr(std),
+         _det_clip(clip), ptr(mu), ptr(pi), ptr(log_pi), ptr(log_std), pi_xa, ld, stream())
+
+
+def det_head_bwd(gpi, mu, B, A, dtrunk_out, twin_dxa=None, F=0):
+    """d(trunk output [B, A]) = gpi (1 - mu^2) of the deterministic head; ``twin_dxa`` [2, B, F + A] (instead of ``gpi``
+    [B, A]): the action columns of the Q-input gradient, read in place and summed over the twin (actor_head_bwd's)."""
+    if twin_dxa is not None:
+        base = ptr(twin_dxa) + 4 * F
+        g1, g2, ld = base, base + 4 * B * (F + A), F + A
+    else:
+        g1, g2, ld = ptr(gpi), None, A
+    call("curla_det_head_bwd", g1, g2, ld, ptr(mu), B, A, ptr(dtrunk_out), stream())
+
+
+def det_policy_head_bwd(dmu, dpi, mu, B, A, dtrunk_out):
+    """d(trunk output [B, A]) = (dmu + dpi)(1 - mu^2) of the deterministic head for upstream gradients of its two
+    differentiable outputs (None = zero)."""
+    call("curla_det_policy_head_bwd", ptr(dmu), ptr(dpi), ptr(mu), B, A, ptr(dtrunk_out), stream())
+
+
 def concat(z, act, B, F, A, xa):
     call("curla_concat", ptr(z), ptr(act), B, F, A, ptr(xa), stream())
 

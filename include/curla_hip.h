@@ -420,6 +420,38 @@ int curla_policy_head_bwd(const float* dmu, const float* dpi, const float* dlog_
                           const float* tanh_ls, int B, int A, float log_std_min, float log_std_max, float* dtrunk_out,
                           void* stream);
 
+/* ---- deterministic policy head (DrQ-v2; CurlSacAgent(policy="deterministic")) ----
+ * trunk_out [B][A] = o, the A pre-squash means (no log_std half).  With s = *std, a float32 read from DEVICE memory when
+ * the kernel runs (a schedule of s is data: a captured hipGraph never holds it), c = clip >= 0 (+inf: none) and
+ * lim = float32(1 - 1e-6):   mu = tanh(o);   pi = clamp(mu + clamp(s noise, -c, c), -lim, lim);   log_pi[b] = 0;
+ * log_std = log(s) (the float32 nearest to it).  Every output is optional as in curla_actor_head_fwd, pi_xa / xa_ld and
+ * NULL noise (mu and log_std only) likewise.  The _rng forms draw the noise inside the launch from the stream of
+ * curla_actor_head_fwd_rng -- same counters, same rng_dev -- and store it to noise_out.  The mlp_out forms run the
+ * actor trunk's last layer h [B][K] @ W [A][K]^T + bias in the same launch (K % 4 == 0; CURLA_ERR_UNSUPPORTED otherwise)
+ * and write the same bits as the two-launch form.  CURLA_ERR_ARG before any launch: A < 1 or A > 8, B < 1, a NULL
+ * trunk_out / std (h / W; noise_out in the _rng forms), clip < 0 or NaN.  No atomics: a rerun writes the same bits.
+ * Additive: CURLA_ABI_VERSION stays 8. */
+int curla_det_head_fwd(const float* trunk_out, const float* noise, const float* std, float clip, int B, int A, float* mu,
+                       float* pi, float* log_pi, float* log_std, float* pi_xa, int xa_ld, void* stream);
+int curla_det_head_fwd_rng(const float* trunk_out, float* noise_out, unsigned long long seed, unsigned long long offset,
+                           const unsigned long long* rng_dev, const float* std, float clip, int B, int A, float* mu,
+                           float* pi, float* log_pi, float* log_std, float* pi_xa, int xa_ld, void* stream);
+int curla_mlp_out_det_head_fwd(const float* h, const float* W, const float* bias, float* trunk_out, int B, int A, int K,
+                               const float* noise, const float* std, float clip, float* mu, float* pi, float* log_pi,
+                               float* log_std, float* pi_xa, int xa_ld, void* stream);
+int curla_mlp_out_det_head_fwd_rng(const float* h, const float* W, const float* bias, float* trunk_out, int B, int A, int K,
+                                   float* noise_out, unsigned long long seed, unsigned long long offset,
+                                   const unsigned long long* rng_dev, const float* std, float clip, float* mu, float* pi,
+                                   float* log_pi, float* log_std, float* pi_xa, int xa_ld, void* stream);
+/* dtrunk_out [B][A] = gpi (1 - mu^2): the gradient of sum(gpi*pi) through the head above -- straight through the outer
+ * clamp, the noise a constant.  gpi is addressed as curla_actor_head_bwd's (gpi_ld, gpi2: the twin's action columns in
+ * place); mu is the forward's output. */
+int curla_det_head_bwd(const float* gpi, const float* gpi2, int gpi_ld, const float* mu, int B, int A, float* dtrunk_out,
+                       void* stream);
+/* The general form (curla_amd/autograd.py): dtrunk_out = (dmu + dpi)(1 - mu^2), dmu / dpi [B][A], either may be NULL. */
+int curla_det_policy_head_bwd(const float* dmu, const float* dpi, const float* mu, int B, int A, float* dtrunk_out,
+                              void* stream);
+
 /* torch.cat([z, action], 1) (curl_sac.py:138) and its backward summed over the twin */
 int curla_concat(const float* z, const float* act, int B, int F, int A, float* xa, void* stream);
 int curla_split_sum(const float* dxa, long long twin_stride, int B, int F, int A, float* dz, float* dact,
