@@ -135,13 +135,10 @@ class _UpdateGraphsMixin:
                 self.cpc_update_freq, self._dp_active, self._dp_overlap, id(self._dp_group) if self._dp_active else 0,
                 hyper, self._graph_rb_key(), self._max_grad_norm) + \
             ((float(self.critic_dropout),) if self.critic_dropout else ()) + \
-            ((("quantiles", self.critic_quantiles, self.critic_drop_quantiles),) if self.critic_quantiles else ()) + \
             ((("aug_views", 2),) if self.aug_views == 2 else ()) + \
-            ((("bins", self.critic_bins) + tuple(float(v) for v in self.critic_value_range) +
-              (float(self.critic_bin_sigma),),) if self.critic_bins else ()) + \
-            ((("policy", "deterministic", self._policy_clip()),) if self.policy == "deterministic" else ())
-        # (0, for any of the three, one view and the Gaussian policy: the key of an agent without the keyword; the
-        # deterministic policy's std is data the head kernels read on the device and is not here, its clip is an argument)
+            self._critic_head_graph_key() + self._policy_graph_key()
+        # (a feature that is off adds nothing: the key of an agent without the keyword.  The critic head's entry is the
+        # quantiles', which two views are not combined with, or the bins', behind the views' -- the order as it was)
 
     def _graph_rb_key(self):
         """(n_step, discount, pos_offset, n_envs) of the graphs' replay buffer: its staging launch holds them by value

@@ -39,6 +39,13 @@ def _check_redo_recycle(v):
     return bool(v)
 
 
+def _redo_keywords(agent, redo_interval, redo_tau, redo_recycle):
+    """The class call's redo keywords, checked, onto the agent under construction."""
+    agent.redo_interval = _check_redo_interval(redo_interval)
+    agent.redo_tau = _check_redo_tau(redo_tau)
+    agent.redo_recycle = _check_redo_recycle(redo_recycle)
+
+
 def _trunk_segments(seq, base, l1, l2):
     """The segments of ops.redo_recycle for a trunk Linear [- LayerNorm] - ReLU - Linear [- LayerNorm] - ReLU - Linear
     whose parameters lie in one flat buffer, offsets counted in floats from the address ``base``; ``l1`` / ``l2``: the

@@ -29,6 +29,13 @@ def _check_reset_seed(v):
     return int(v)
 
 
+def _reset_keywords(agent, reset_interval, reset_encoder_keep, reset_seed):
+    """The class call's reset keywords, checked, onto the agent under construction."""
+    agent.reset_interval = _check_reset_interval(reset_interval)
+    agent.reset_encoder_keep = _check_reset_keep(reset_encoder_keep)
+    agent.reset_seed = _check_reset_seed(reset_seed)
+
+
 def _zero_torch_adam(opt):
     """A torch.optim.Adam's state back to step 0 with zero moments, every tensor filled in place."""
     for st in opt.state.values():

@@ -28,18 +28,30 @@ import torch
 
 from . import ops
 from .agent_acting import _ActingMixin
+from .agent_checkpoint import _CheckpointMixin
+from .agent_critic_head import _critic_head_keywords, _CriticHeadMixin
 from .agent_dp import _DataParallelMixin
 from .agent_graphs import _NullLog, _UpdateGraphsMixin
-from .agent_redo import _check_redo_interval, _check_redo_recycle, _check_redo_tau, _RedoMixin
-from .agent_reset import _check_reset_interval, _check_reset_keep, _check_reset_seed, _ResetMixin
+from .agent_optim import _OptimMixin
+from .agent_policy import _policy_keywords, _PolicyMixin
+from .agent_redo import _redo_keywords, _RedoMixin
+from .agent_reset import _reset_keywords, _ResetMixin
 from .encoder import CNNEncoder
-from .mlp import _Mlp, _MlpLn, _linears, _mlp_bwd, _mlp_fwd  # noqa: F401
-from .networks import (CURL, LOG_FREQ, Actor, Critic, QFunction, _check_drop_quantiles,  # noqa: F401
-                       _check_bin_sigma, _check_bins, _check_dropout, _check_int, _check_layer_norm_width,
-                       _check_policy_std, _check_policy_std_clip, _check_quantiles, _check_value_range, _CriticType,
-                       _device_generator, _QFunctionType, _reserve_dropout_counter, _widen_last_layers, weight_init)
+from .mlp import _Mlp, _mlp_bwd, _mlp_fwd
+from .networks import (CURL, LOG_FREQ, Actor, Critic, _check_dropout, _check_int, _check_layer_norm_width,
+                       _device_generator, _reserve_dropout_counter)
 from .ops import ObsRef
-from .optim import FlatAdam, check_max_grad_norm, check_weight_decay
+from .optim import check_weight_decay
+
+# the other names this module defined before its splits, from their homes (tests/test_module_layout_host.py)
+from .agent_policy import _check_policy, _check_policy_std_schedule, _linear_schedule  # noqa: F401
+from .agent_redo import _check_redo_interval, _check_redo_recycle, _check_redo_tau  # noqa: F401
+from .agent_reset import _check_reset_interval, _check_reset_keep, _check_reset_seed  # noqa: F401
+from .mlp import _MlpLn, _linears  # noqa: F401
+from .networks import (QFunction, _check_bin_sigma, _check_bins, _check_drop_quantiles,  # noqa: F401
+                       _check_policy_std, _check_policy_std_clip, _check_quantiles, _check_value_range, _CriticType,
+                       _QFunctionType, _widen_last_layers, weight_init)
+from .optim import FlatAdam, check_max_grad_norm  # noqa: F401
 
 
 def _as_ref(obs):
@@ -60,33 +72,6 @@ def _check_views(v):
 def _check_utd_ratio(g):
     """The update-to-data ratio: an ``int >= 1`` (a bool, a float or a string is not one)."""
     return _check_int(g, 1, None, "utd_ratio: %r is not an int >= 1" % (g,))
-
-
-def _check_policy(policy):
-    if policy not in ("gaussian", "deterministic"):
-        raise ValueError("policy: %r is not 'gaussian' or 'deterministic'" % (policy,))
-    return policy
-
-
-def _check_policy_std_schedule(sched):
-    """DrQ-v2's ``linear(init, final, duration)`` as a tuple of three floats: init and final finite and > 0, duration
-    finite and > 0; or None."""
-    if sched is None:
-        return None
-    try:
-        init, final, duration = (float(v) for v in sched)
-    except (TypeError, ValueError):
-        raise ValueError("policy_std_schedule: %r is not None or (init, final, duration)" % (sched,)) from None
-    if not (np.isfinite(init) and np.isfinite(final) and np.isfinite(duration) and init > 0 and final > 0 and duration > 0):
-        raise ValueError("policy_std_schedule: (%r, %r, %r) is not (init > 0, final > 0, duration > 0), all finite"
-                         % (init, final, duration))
-    return init, final, duration
-
-
-def _linear_schedule(sched, step):
-    """DrQ-v2's linear(init, final, duration) at ``step``: init + (final - init) * min(step / duration, 1)."""
-    init, final, duration = sched
-    return init + (final - init) * min(step / duration, 1.0)
 
 
 class _Workspace:
@@ -128,7 +113,7 @@ class _Workspace:
         # twin Q
         # [0] = the target critic's pass over next_obs, [1] = the critic's over obs: one launch per layer for the four
         # Q functions (update_critic); the names without a 2 are the critic's halves, what the backward reads
-        M = agent.critic.out_dim  # (critic_quantiles: M atoms per Q function in place of the one Q value)
+        M = agent.critic.out_dim  # (a wider critic head: M atoms or logits per Q function in place of the one Q value)
         self.xa2, self.q_h1_2, self.q_h2_2, self.q2 = f(2, B, F + A), f(2, 2, B, H), f(2, 2, B, H), f(2, 2, B, M)
         self.xa, self.q_h1, self.q_h2 = self.xa2[1], self.q_h1_2[1], self.q_h2_2[1]
         self.tq, self.q = self.q2[0], self.q2[1]
@@ -143,9 +128,7 @@ class _Workspace:
             self.q_ln_saves = ([self.q_xhat1, self.q_xhat2], [self.q_rstd1, self.q_rstd2])
             self.q_ln_partial = f(ops.mlp_ln_partial_floats(B, H, 2))
         self.dq, self.target_q = f(2, B, M), f(B, 1)
-        # the quantile loss per row (ops.tqc_critic_loss); critic_bins: the cross-entropies per row (ops.hlg_critic_loss)
-        # in the critic phase, min(Q1, Q2) per row (ops.hlg_actor_loss) in the actor phase
-        self.q_row_loss = f(B) if agent.critic_quantiles or agent.critic_bins else None
+        self.q_row_loss = f(B) if agent._has_row_loss() else None  # the quantile and HL-Gauss losses' value per row
         self.per_w = self.per_value = None  # importance weights / new stored values [B]: a prioritized buffer's updates only
         # scalars: [0] critic loss, [1..4] actor_loss/alpha_loss/entropy/alpha, [5] curl loss, [6] batch reward
         self.scalars = torch.zeros(8, device=dev, dtype=torch.float32)
@@ -166,43 +149,17 @@ class _AgentType(type):
                  critic_value_range=None, critic_bin_sigma=0.75, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0,
                  critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
-        if _check_policy(policy) == "deterministic":  # (gaussian: the instance is the one without the keyword)
-            agent.policy = "deterministic"
-            agent.policy_std_schedule = _check_policy_std_schedule(policy_std_schedule)
-            agent._policy_std = _check_policy_std(policy_std)
-            if agent.policy_std_schedule is not None:  # (the schedule's value at step 0 until the first update)
-                agent._policy_std = _check_policy_std(_linear_schedule(agent.policy_std_schedule, 0))
-            agent.policy_std_clip = _check_policy_std_clip(policy_std_clip)
-        else:
-            for name, value, default in (("policy_std", policy_std, 0.2), ("policy_std_clip", policy_std_clip, 0.3),
-                                         ("policy_std_schedule", policy_std_schedule, None)):
-                if value is not default and value != default:
-                    raise ValueError("%s = %r needs policy='deterministic' (the Gaussian policy learns its own standard "
-                                     "deviation)" % (name, value))
-        agent.redo_interval = _check_redo_interval(redo_interval)
-        agent.redo_tau = _check_redo_tau(redo_tau)
-        agent.redo_recycle = _check_redo_recycle(redo_recycle)
-        agent.reset_interval = _check_reset_interval(reset_interval)
-        agent.reset_encoder_keep = _check_reset_keep(reset_encoder_keep)
-        agent.reset_seed = _check_reset_seed(reset_seed)
-        agent.critic_quantiles = _check_quantiles(critic_quantiles)
-        agent.critic_drop_quantiles = _check_drop_quantiles(critic_drop_quantiles, agent.critic_quantiles)
+        _policy_keywords(agent, policy, policy_std, policy_std_clip, policy_std_schedule)
+        _redo_keywords(agent, redo_interval, redo_tau, redo_recycle)
+        _reset_keywords(agent, reset_interval, reset_encoder_keep, reset_seed)
+        _critic_head_keywords(agent, critic_quantiles, critic_drop_quantiles, critic_bins, critic_value_range,
+                              critic_bin_sigma)
         agent.critic_layer_norm = bool(critic_layer_norm)
         agent.critic_dropout = _check_dropout(critic_dropout, agent.critic_layer_norm)
         agent.utd_ratio = _check_utd_ratio(utd_ratio)
-        bin_sigma = _check_bin_sigma(critic_bin_sigma)
-        if _check_bins(critic_bins):  # (0: the instance is the one without the keyword, down to its __dict__)
-            if agent.critic_quantiles:
-                raise ValueError("critic_bins > 0 is not combined with critic_quantiles > 0: a Q function's last layer is "
-                                 "the logits of one categorical distribution or a set of quantile atoms")
-            if critic_value_range is None:
-                raise ValueError("critic_bins = %d needs critic_value_range=(v_min, v_max), the range of the returns the "
-                                 "bins cover" % critic_bins)
-            agent.critic_bins = int(critic_bins)
-            agent.critic_value_range = _check_value_range(critic_value_range)
-            agent.critic_bin_sigma = bin_sigma
-        elif critic_value_range is not None:
-            raise ValueError("critic_value_range needs critic_bins > 0")
+        if agent.critic_bins and agent.critic_quantiles:
+            raise ValueError("critic_bins > 0 is not combined with critic_quantiles > 0: a Q function's last layer is "
+                             "the logits of one categorical distribution or a set of quantile atoms")
         if _check_views(aug_views) == 2:  # (1: the instance is the one without the keyword, down to its __dict__)
             if agent.critic_quantiles:
                 raise ValueError("aug_views = 2 is not combined with critic_quantiles > 0: the mean of two views' "
@@ -215,7 +172,8 @@ class _AgentType(type):
         return agent
 
 
-class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetMixin, _RedoMixin, metaclass=_AgentType):
+class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetMixin, _RedoMixin, _CriticHeadMixin,
+                   _PolicyMixin, _OptimMixin, _CheckpointMixin, metaclass=_AgentType):
     """CURL representation learning with SAC (curl_sac.py:224-465).
     ``CurlSacAgent(..., critic_layer_norm=True)`` (a keyword of the class call, not in the reference; default off:
     nothing changes): an ``nn.LayerNorm(hidden_dim)`` between each hidden Linear of the Q functions and its ReLU, critic
@@ -265,20 +223,10 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     device scalar: data to captured graphs), clip and schedule are attributes that may be edited between calls.  The
     three ``policy_std*`` keywords raise beside the Gaussian policy."""
 
-    policy = "gaussian"
-    policy_std_clip = None
-    policy_std_schedule = None
-    _policy_std = None
     critic_layer_norm = False
     critic_dropout = 0.0
     utd_ratio = 1
-    critic_quantiles = 0
-    critic_drop_quantiles = 0
     aug_views = 1
-    critic_bins = 0
-    critic_value_range = None
-    critic_bin_sigma = 0.75
-    _hlg_last_B = None  # critic_bins: the batch size of the last critic phase (target_clip_fraction's workspace)
 
     def __init__(
         self,
@@ -358,38 +306,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         self.CURL = CURL(obs_shape, encoder_feature_dim, self.critic, self.critic_target, output_type='continuous')
 
         self._to_flat_device_layout()
-        if self.policy == "deterministic":
-            # the standard deviation the head kernels read on the device, and where the actor loss launches leave their
-            # d(alpha loss)/d(log_alpha): log_alpha.grad stays all zeros, so its Adam step leaves it bit for bit alone
-            self.actor.std = torch.full((1,), self._policy_std, device=self.device, dtype=torch.float32)
-            self.actor.std_clip = self.policy_std_clip
-            self._dla_scratch = torch.zeros((), device=self.device, dtype=torch.float64)
-
-        actor_own = [p for n, p in self.actor.named_parameters() if ".convs." not in n]
-        enc_params = list(self.critic.encoder.parameters())
-        # Optimizers (curl_sac.py:299-313).  The reference hands Adam the tied convs (actor) and the target
-        # encoder (cpc) as well; their .grad is always None at step time there, so Adam never touches them.
-        # FlatAdam is torch.optim.Adam with its step() as one HIP launch over the flat buffer (optim.py);
-        # CURLA_TORCH_ADAM=1 keeps torch's own fused multi-tensor step (same state_dict either way).
-        if self.device.type == "cuda" and os.environ.get("CURLA_TORCH_ADAM", "0") == "1":
-            def adam(params, flat, gflat, **kw):
-                return torch.optim.Adam(params, fused=True, **kw)
-        elif self.device.type == "cuda":
-            def adam(params, flat, gflat, **kw):
-                return FlatAdam(params, flat, gflat, **kw)
-        else:
-            def adam(params, flat, gflat, **kw):
-                return torch.optim.Adam(params, **kw)
-        cf, cg = self._critic_flat, self._critic_gflat
-        self.actor_optimizer = adam(actor_own, self._actor_flat, self._actor_gflat, lr=actor_lr, betas=(actor_beta, 0.999))
-        self.critic_optimizer = adam(list(self.critic.parameters()), cf, cg, lr=critic_lr, betas=(critic_beta, 0.999))
-        # (beside a FlatAdam actor, log_alpha's step rides in the actor's launch: FlatAdam.step_with_scalar)
-        flat_actor = isinstance(self.actor_optimizer, FlatAdam)
-        self.log_alpha_optimizer = torch.optim.Adam(
-            [self.log_alpha], lr=alpha_lr, betas=(alpha_beta, 0.999),
-            **(dict(foreach=False) if flat_actor else dict(fused=True) if self.device.type == "cuda" else {}))
-        self.encoder_optimizer = adam(enc_params, cf, cg, lr=encoder_lr)
-        self.cpc_optimizer = adam([self.CURL.W] + enc_params, cf, cg, lr=encoder_lr)
+        self._place_policy_scalars()
+        self._build_optimizers(actor_lr, actor_beta, critic_lr, critic_beta, alpha_lr, alpha_beta, encoder_lr)
         self._install_grad_views()
 
         self._workspaces = {}
@@ -695,50 +613,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             self._encoder_backward(ws, obs_ref, dz, ws.xhat_c, ws.rstd_c, enc, **kw)
             self._allreduce(g[lo:hi])
 
-    # -- the deterministic policy
-    def _actor_kw(self):
-        """The keyword that shapes the actor, for every place that builds one."""
-        return dict(deterministic=True) if self.policy == "deterministic" else {}
-
-    def _actor_out_dim(self):
-        """The width of the actor trunk's last layer: [mu | raw log_std], or the deterministic policy's A means."""
-        return self.action_dim if self.policy == "deterministic" else 2 * self.action_dim
-
-    def _policy_clip(self):
-        """``policy_std_clip`` as it stands now (it may have been edited), checked; the actor's follows the agent's."""
-        clip = self.actor.std_clip = _check_policy_std_clip(self.policy_std_clip)
-        return clip
-
-    @property
-    def policy_std(self):
-        """The deterministic policy's current standard deviation (None: the Gaussian policy); ``set_policy_std``."""
-        return self._policy_std
-
-    def set_policy_std(self, value):
-        """Set the deterministic policy's standard deviation: one fill of the device scalar the head kernels read,
-        enqueued on the current stream and only when the value changes; the host is never synchronised and no captured
-        graph holds the value."""
-        if self.policy != "deterministic":
-            raise ValueError("set_policy_std needs policy='deterministic'")
-        value = _check_policy_std(value)
-        if value != self._policy_std:
-            self._policy_std = value
-            self.actor.std.fill_(value)
-
     # -- the network passes: shapes and buffers are the workspace's and the agent's, stated here and nowhere else
-    def _actor_fwd(self, ws, noise=None, **outs):
-        """The actor trunk over ws.z_a into ws.a_out; with ``noise``, the policy head behind it, which writes ``outs``
-        (ops.actor_head_fwd's: mu, pi, log_pi, log_std, tanh_ls, xa, rng; the deterministic head has no tanh_ls and
-        clips its scaled noise to ``policy_std_clip``)."""
-        B, F = ws.z_a.shape
-        if self.policy == "deterministic":
-            outs.pop("tanh_ls", None)
-            head = None if noise is None else (noise, self.actor.std, self._policy_clip(), outs, "det")
-        else:
-            head = None if noise is None else (noise, self.actor.log_std_min, self.actor.log_std_max, outs)
-        _mlp_fwd(ws.z_a, 0, _Mlp(self.actor.trunk), 1, B, F, self.hidden_dim, self._actor_out_dim(), ws.a_h1, ws.a_h2,
-                 ws.a_out, head=head)
-
     def _twin_fwd(self, ws, net, ln, out=None, outer=None):
         """The twin Q functions of ``net`` (the critic or the target) over ws.xa into ``out`` (ws.q / ws.tq), ``ln`` their
         _MlpLn.  ``outer`` = (2, floats from the target's parameters to the critic's): the target's twins over
@@ -753,91 +628,6 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         (_, B, FA), net = ws.xa2.shape, self.critic
         _mlp_bwd(ws.xa, 0, net.twin(), net.twin(grads=True) if grads else None, 2, B, FA, self.hidden_dim, net.out_dim,
                  ws.q_h1, ws.q_h2, ws.dq, ws.q_dh2, ws.q_dh1, ws.dxa, loss=loss, ln=ln)
-
-    def _critic_width_kw(self):
-        """The keywords that widen the Q functions' last layers, for every place that builds a Critic."""
-        if self.critic_bins:
-            return dict(bins=self.critic_bins, value_range=self.critic_value_range)
-        return dict(quantiles=self.critic_quantiles) if self.critic_quantiles else {}
-
-    def _hlg_params(self):
-        """(v_min, v_max, sigma) of the HL-Gauss critic as they stand now -- the range and the smoothing may have been
-        edited --, checked; the critics' own ``value_range`` (bin_centres, expected) follows the agent's."""
-        v_min, v_max = rng = _check_value_range(self.critic_value_range)
-        self.critic.value_range = self.critic_target.value_range = rng
-        return v_min, v_max, _check_bin_sigma(self.critic_bin_sigma) * (v_max - v_min) / self.critic_bins
-
-    def target_clip_fraction(self):
-        """The share of the last critic phase's TD targets that the clamp moved onto ``v_min`` or ``v_max``: near 0 with
-        a value range that fits, towards 1 with one the returns have left -- the HL-Gauss critic's own failure mode.  A
-        host read of the workspace (it waits for the device); not part of ``update()``."""
-        if not self.critic_bins:
-            raise RuntimeError("target_clip_fraction: this agent has no categorical critic (critic_bins=M)")
-        ws = self._workspaces.get(self._hlg_last_B)
-        if ws is None:
-            raise RuntimeError("target_clip_fraction: no critic phase has run yet")
-        v_min, v_max = (np.float32(v) for v in _check_value_range(self.critic_value_range))
-        t = ws.target_q.detach().reshape(-1).cpu().numpy()
-        return float(((t == v_min) | (t == v_max)).mean())
-
-    # -- the loss descriptors of _twin_bwd: (fields, launch) -- ``fields`` for the form computed inside the backward
-    #    launch of the Q functions' last layer, ``launch()`` the loss kernel on its own where that form does not apply
-    def _critic_loss(self, ws, reward, not_done, per, drop_q, hlg=None):
-        """target_Q = r + not_done * gamma * (min Q' - alpha log pi'), the two MSE terms and their gradient dq
-        (curl_sac.py:353-361).  ``critic_quantiles``: the quantile Huber loss of the critic's atoms against
-        the kept target atoms, always a launch of its own.  ``aug_views = 2``: both views' estimates against
-        the mean of the two views' targets, a launch of its own as well.  ``critic_bins``: the two
-        cross-entropies of the critic's logits against the Gaussian histogram of the clamped TD target, with or without
-        views, always a launch of its own; ``hlg`` = (v_min, v_max, sigma) as update_critic has checked them.  ``per``, a
-        prioritized minibatch: the loss is
-        launched here, the importance weights scale dq and the loss in place and the drawn rows get their new priorities
-        -- all on the device --, and the backward runs on the weighted dq it finds: no descriptor, None."""
-        B, Mq = ws.log_pi.shape[0], self.critic.out_dim
-        la, gamma, total = self.log_alpha, self.discount, ws.scalars[0:1]
-        if self.critic_quantiles:
-            loss = (None, lambda: ops.tqc_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done, la, gamma,
-                                                      B, Mq, drop_q, ws.dq, B * Mq, ws.q_row_loss, total))
-        elif self.critic_bins:  # (a prioritized minibatch has been refused by update_critic)
-            v_min, v_max, sigma = hlg
-            return None, lambda: ops.hlg_critic_loss(ws.q, B * Mq, ws.tq, B * Mq, ws.log_pi, reward, not_done, la, gamma, B,
-                                                     Mq, v_min, v_max, sigma, ws.dq, B * Mq, ws.target_q, ws.q_row_loss,
-                                                     total, views=self.aug_views == 2)
-        elif self.aug_views == 2:
-            if per is not None:
-                raise ValueError("aug_views = 2: a prioritized minibatch is not supported (its rows are drawn per "
-                                 "position): use ReplayBuffer(prioritized=False)")
-            return None, lambda: ops.critic_td_loss_views(ws.q, ws.tq, B, ws.log_pi, reward, not_done, la, gamma, B,
-                                                          ws.target_q, total, ws.dq)
-        else:
-            loss = (dict(kind=1, twin_stride=B, q=ws.q, target_q_twin=ws.tq, log_pi=ws.log_pi, reward=reward,
-                         not_done=not_done, log_alpha=la, discount=gamma, target_q=ws.target_q, scalars=total, dq=ws.dq),
-                    lambda: ops.critic_td_loss(ws.q, ws.tq, B, ws.log_pi, reward, not_done, la, gamma, B, ws.target_q,
-                                               total, ws.dq))
-        if per is None:
-            return loss
-        if ws.per_w is None:
-            ws.per_w, ws.per_value = (torch.empty(B, device=ws.dq.device, dtype=torch.float32) for _ in range(2))
-        loss[1]()
-        per.td_update(ws.q, B, ws.target_q, ws.dq, total, ws.per_w, ws.per_value)
-        return None
-
-    def _actor_loss(self, ws):
-        """The actor / alpha losses and d(loss)/dQ (curl_sac.py:377-401); ``critic_quantiles``: over the mean of all
-        atoms in place of min(Q1, Q2), a launch of its own."""
-        B, A, Mq = ws.log_pi.shape[0], self.action_dim, self.critic.out_dim
-        la, te, out = self.log_alpha, float(self.target_entropy), ws.scalars[1:5]
-        # (the deterministic policy: log_pi = 0 and the temperature takes no part -- its gradient goes to a scratch word)
-        dla = self._dla_scratch if self.policy == "deterministic" else la.grad
-        if self.critic_quantiles:
-            return None, lambda: ops.tqc_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, la, te, B, Mq, out, ws.dq,
-                                                    B * Mq, dla)
-        if self.critic_bins:
-            v_min, v_max, _ = self._hlg_params()
-            return None, lambda: ops.hlg_actor_loss(ws.q, B * Mq, ws.log_pi, ws.log_std, A, la, te, B, Mq, v_min, v_max,
-                                                    ws.q_row_loss, out, ws.dq, B * Mq, dla)
-        return (dict(kind=2, A=A, twin_stride=B, q=ws.q, log_pi=ws.log_pi, log_std=ws.log_std, log_alpha=la,
-                     target_entropy=te, scalars=out, dq=ws.dq, dlog_alpha=dla),
-                lambda: ops.actor_loss(ws.q, B, ws.log_pi, ws.log_std, A, la, te, B, out, ws.dq, dla))
 
     # -- the critic phase's forward: a' ~ pi(. | z'), the target's twins over [z' | a'], the critic's over [z | a]
     #    (curl_sac.py:350-358), by one of three routes; each returns the phase's ``drop`` (_dropout)
@@ -908,46 +698,16 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         self.critic.encoder.ln_from_partial(B, ws.z_c, **online)  # xa = cat([z, a], 1)
         self._twin_fwd(ws, self.critic, self.critic.twin_ln(*ws.q_ln_saves, drop=drop(3)), ws.q)
 
-    def _critic_step(self):
-        """critic_optimizer.step() (curl_sac.py:367) -- with the target soft update update() has announced right behind
-        it (:442-445) in the same launch where the optimizer is the flat one: the update reads what the step writes, so
-        both share one pass over the critic's flat parameters."""
-        opt, hidden, fused = self.critic_optimizer, [], False
-        if self.detach_encoder:  # convs received no gradient: Adam must skip them (grad None in the reference)
-            hidden = [(p, p.grad) for m in self.critic.encoder.convs for p in (m.weight, m.bias)]
-            for p, _ in hidden:
-                p.grad = None
-        elif self._soft_update_hint:
-            (e0, e1), (_, q1) = self._lay["enc"], self._lay["q"]
-            fused = self._soft_update_done = FlatAdam.step_with_lerp(opt, self._target_flat, e0, q1, e1 - e0,
-                                                                     self.encoder_tau, self.critic_tau)
-        if not fused:
-            self._clip_torch(0, opt)
-            opt.step()
-        for p, g in hidden:
-            p.grad = g
-
     # ------------------------------------------------------------------ phases
     def update_critic(self, obs, action, reward, next_obs, not_done, L, step, noise=None, dropout_rng=None):
         """curl_sac.py:349-371.  ``dropout_rng`` = (seed, counter): the stream position of a dropout critic's masks
         (the target twins under tags 1 / 2, the critic twins under 3 / 4) instead of the phase's own (_dropout)."""
-        per, drop_q = getattr(obs, "per", None), 0
-        if self.critic_quantiles:
-            drop_q = _check_drop_quantiles(self.critic_drop_quantiles, self.critic.out_dim)  # (it may have been edited)
-            if per is not None:
-                raise ValueError("critic_quantiles: a prioritized minibatch is not supported (its priorities are built "
-                                 "on one scalar TD error per Q function): use ReplayBuffer(prioritized=False)")
-        hlg = None
-        if self.critic_bins:
-            hlg = self._hlg_params()  # (the range or the smoothing may have been edited: checked before anything is written)
-            if per is not None:
-                raise ValueError("critic_bins: a prioritized minibatch is not supported (its priorities are built on one "
-                                 "scalar TD error per Q function): use ReplayBuffer(prioritized=False)")
+        per = getattr(obs, "per", None)
+        settings = self._critic_loss_settings(per)  # (checked before anything is written)
         self._restore_grad_views()
         o, no = _as_ref(obs), _as_ref(next_obs)
         ws, enc = self._ws(o.B), self.critic.encoder
-        if hlg is not None:
-            self._hlg_last_B = o.B
+        self._note_critic_batch(o.B)
         self._drop_encoder_caches()
         action, reward, not_done = action.contiguous(), reward.contiguous(), not_done.contiguous()
         # -- target (no_grad block, curl_sac.py:350-355) and current Q estimates (:357-358)
@@ -958,7 +718,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             self.critic.outputs['q1'], self.critic.outputs['q2'] = ws.q[0].clone(), ws.q[1].clone()
             enc.record_from(o, ws.acts_main, ws.fc_out, ws.z_c)
         # -- loss + backward (curl_sac.py:359-367)
-        loss = self._critic_loss(ws, reward, not_done, per, drop_q, hlg)
+        loss = self._critic_loss(ws, reward, not_done, per, settings)
         self._twin_bwd(ws, self.critic.twin_ln(*ws.q_ln_saves, grads=True, partial=ws.q_ln_partial, drop=drop(3)), loss,
                        grads=True)
         if step % self.log_interval == 0:
@@ -1004,10 +764,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         CNNEncoder.ln_from_partial_multi(B, lns, A)
         self._anchor_cache = obs
 
-        det = self.policy == "deterministic"
         nz, rng = self._noise(ws, noise)
-        self._actor_fwd(ws, nz, mu=ws.mu, pi=None if det else ws.pi, log_pi=ws.log_pi, log_std=ws.log_std,
-                        tanh_ls=ws.tanh_ls, xa=ws.xa, rng=rng)
+        self._actor_fwd(ws, nz, rng=rng, **self._actor_phase_outs(ws))
         if self._records(step):  # what actor.log() histograms (curl_sac.py:92-93): pre-squash mean and std
             self.actor.outputs['mu'], self.actor.outputs['std'] = ws.a_out[:, :A].clone(), ws.log_std.exp()
         # (the data gradient through the LayerNorms needs the saves too; dropout: the critic twins under tags 5 / 6)
@@ -1016,74 +774,17 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         # backward: Q -> pi -> trunk -> LN -> fc (encoder detached, curl_sac.py:375-376)
         self._twin_bwd(ws, q_ln, self._actor_loss(ws), grads=False)
         if step % self.log_interval == 0:
-            L.log('train_actor/loss', ws.scalars[1], step)
-            if det:  # (no entropy term, no temperature)
-                L.log('train_actor/std', self._policy_std, step)
-            else:
-                L.log('train_actor/target_entropy', self.target_entropy, step)
-                L.log('train_actor/entropy', ws.scalars[3], step)
-        # d(loss)/d(pi) = the action columns of dxa summed over the twin, read in place
+            self._log_actor(ws, L, step)
         F, trunk = aenc.feature_dim, self.actor.trunk
-        if det:
-            ops.det_head_bwd(None, ws.mu, B, A, ws.a_dout, twin_dxa=ws.dxa, F=F)
-        else:
-            ops.actor_head_bwd(None, self.log_alpha, 1.0 / B, nz, ws.pi, ws.log_std, ws.tanh_ls, B, A,
-                               self.actor.log_std_min, self.actor.log_std_max, ws.a_dout, twin_dxa=ws.dxa, F=F)
+        self._actor_head_bwd(ws, nz, B, A, F)
         _mlp_bwd(ws.z_a, 0, _Mlp(trunk), _Mlp(trunk, grads=True), 1, B, F, self.hidden_dim, self._actor_out_dim(), ws.a_h1,
                  ws.a_h2, ws.a_dout, ws.a_dh2, ws.a_dh1, ws.dz)
         self._encoder_backward(ws, o, ws.dz, ws.xhat_a, ws.rstd_a, aenc, conv_grads=False)
         self._actor_reduce_and_step(L, step)
         if self.log_param_hist_imgs:
             self.actor.log(L, step)
-        if step % self.log_interval == 0 and not det:
-            L.log('train_alpha/loss', ws.scalars[2], step)
-            L.log('train_alpha/value', ws.scalars[4], step)
-
-    def _actor_reduce_and_step(self, L, step):
-        """The actor phase's reduction and optimizer steps.  Data parallel: ONE collective for the phase -- the bucket
-        [fc, ln | trunk | words], log_alpha's float64 gradient riding in the words.  Overlapped schedule: the collective
-        is asynchronous and, when update() has announced that the CURL phase follows, the two optimizer steps are taken
-        only after that phase has been enqueued (_finish_actor_step): the CURL phase reads nothing they write (the
-        actor's own fc / ln / trunk and log_alpha), so the numbers are the reference order's (curl_sac.py:393-404
-        before :418-423) and the all-reduce runs underneath the CURL phase's convolutions."""
-        overlap = self._dp_active and self._dp_overlap
-        self._allreduce(self._actor_gbucket, async_op=overlap, f64_rider=(self.log_alpha.grad, self._la_words))
-        self._actor_step_pending = bool(overlap and self._defer_actor_step and not self.log_param_hist_imgs)
-        # (the norm is logged once the step that takes it has been enqueued: a deferred step is not, yet)
-        self._actor_norm_log = (L, step) if self._max_grad_norm is not None and step % self.log_interval == 0 else None
-        if not self._actor_step_pending:
-            if overlap:
-                self._allreduce_wait()
-            self._actor_steps()
-
-    def _actor_steps(self):
-        # actor_optimizer.step() ... log_alpha_optimizer.step() (curl_sac.py:393-404): nothing in between reads
-        # log_alpha (the logged alpha is the loss kernel's), so the two steps share a launch
-        # (clipping: the actor's own parameters; log_alpha has its own optimizer and loss scale and is not clipped)
-        if isinstance(self.actor_optimizer, FlatAdam):
-            FlatAdam.step_with_scalar(self.actor_optimizer, self.log_alpha_optimizer)
-        else:
-            self._clip_torch(1, self.actor_optimizer)
-            self.actor_optimizer.step()
-            self.log_alpha_optimizer.step()
-        if self._actor_norm_log is not None:
-            (L, step), self._actor_norm_log = self._actor_norm_log, None
-            L.log('train_actor/grad_norm', self.grad_clip_stats[1, 0], step)
-
-    def _finish_actor_step(self):
-        if self._actor_step_pending:
-            self._actor_step_pending = False
-            self._allreduce_wait()
-            self._actor_steps()
-
-    def _cpc_steps(self):
-        # encoder_optimizer.step() ... cpc_optimizer.step() (curl_sac.py:418-423)
-        if isinstance(self.encoder_optimizer, FlatAdam):
-            FlatAdam.step_pair(self.encoder_optimizer, self.cpc_optimizer)  # both steps in one pass over the encoder
-        else:
-            self._clip_torch(2, self.cpc_optimizer)  # [W | encoder], once: both steps consume the clipped gradient
-            self.encoder_optimizer.step()
-            self.cpc_optimizer.step()
+        if step % self.log_interval == 0:
+            self._log_actor(ws, L, step, alpha=True)
 
     def update_cpc(self, obs_anchor, obs_pos, cpc_kwargs, L, step):
         """curl_sac.py:406-423."""
@@ -1134,78 +835,6 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             if self._max_grad_norm is not None:
                 L.log('train/curl_grad_norm', self.grad_clip_stats[2, 0], step)
 
-    # ---------------------------------------------------------------- clipping by the global gradient norm
-    _max_grad_norm = None
-    grad_clip_stats = None
-
-    @property
-    def max_grad_norm(self):
-        """The threshold set by ``set_max_grad_norm`` (None: no clipping)."""
-        return self._max_grad_norm
-
-    def set_max_grad_norm(self, value):
-        """Clip every phase's gradient by its global norm right in front of the phase's optimizer steps:
-        ``torch.nn.utils.clip_grad_norm_(parameters with a gradient, value)`` where one would put it in the reference
-        -- in front of curl_sac.py:367 over ``critic.parameters()`` (without the convs under ``detach_encoder``), in
-        front of :393-404 over the actor's own parameters (``log_alpha`` is not clipped), in front of :418-423 over
-        [CURL.W | encoder], once for both optimizers; data parallel: after the gradient's all-reduce.  ``value``: None
-        (off, the default: the launches are the unclipped ones) or a positive number shared by the three phases.
-        With the flat optimizers the norm never leaves the device: one square-sum launch per phase, the coefficient
-        applied inside the Adam launch (optim.py).  ``grad_clip_stats`` (float32 device tensor [3, 2]; rows critic /
-        actor / cpc, columns norm before clipping / coefficient applied) holds each phase's last figures.
-        A hyper-parameter, not state: checkpoints do not carry it, a resumed run calls this again."""
-        value = check_max_grad_norm(value)
-        if value is not None and self.grad_clip_stats is None:
-            self.grad_clip_stats = torch.zeros(3, 2, device=self.device, dtype=torch.float32)
-        rows = ((self.critic_optimizer, 0), (self.actor_optimizer, 1), (self.encoder_optimizer, 2), (self.cpc_optimizer, 2))
-        for opt, row in rows:
-            if isinstance(opt, FlatAdam):
-                if value is not None:
-                    opt.clip_stats = self.grad_clip_stats[row]
-                opt.max_grad_norm = value
-        self._max_grad_norm = value  # (captured update graphs hold it by value: _graph_key)
-
-    # ---------------------------------------------------------------- decoupled weight decay (AdamW)
-    @property
-    def weight_decay(self):
-        """The decoupled weight decay of the network optimizers, read from the critic optimizer's param group (the four
-        carry the same value unless their groups were edited one by one); set by ``set_weight_decay``."""
-        return float(self.critic_optimizer.param_groups[0].get("weight_decay", 0))
-
-    def set_weight_decay(self, value):
-        """Decoupled weight decay on the four network optimizers: actor, critic, encoder and cpc become what
-        ``torch.optim.AdamW(..., weight_decay=value)`` is in the reference's place (curl_sac.py:299-313) -- every step
-        multiplies the parameters it steps by ``1 - lr * value`` in front of the Adam update.  log_alpha's optimizer
-        stays plain Adam.  The encoder is decayed by each optimizer that steps it (critic, encoder and cpc), as it would
-        be there; parameters without a gradient at step time (the convs under ``detach_encoder`` in the critic's step)
-        are not, as torch skips them.  ``value``: a finite number >= 0; 0 switches it off (the launches are the plain
-        ones again).  Written into the optimizers' param groups (``weight_decay``, ``decoupled_weight_decay = value !=
-        0``) as torch keeps them: it is part of their ``state_dict()`` and a checkpoint restores it.  With the flat
-        optimizers the multiply is inside the Adam launches (``curla_adamw_*``, optim.py): an update launches as many
-        optimizer kernels as without it."""
-        value = check_weight_decay(value)
-        for opt in (self.critic_optimizer, self.actor_optimizer, self.encoder_optimizer, self.cpc_optimizer):
-            for g in opt.param_groups:
-                g["weight_decay"] = value
-                g["decoupled_weight_decay"] = value != 0
-
-    def _clip_torch(self, row, opt):
-        """The clipping step of a phase whose optimizer is torch's own (CURLA_TORCH_ADAM=1, a CPU agent): FlatAdam
-        clips inside its launches."""
-        if self._max_grad_norm is None or isinstance(opt, FlatAdam):
-            return
-        params = [p for g in opt.param_groups for p in g["params"] if p.grad is not None]
-        norm = torch.nn.utils.clip_grad_norm_(params, self._max_grad_norm)
-        self.grad_clip_stats[row, 0] = norm
-        self.grad_clip_stats[row, 1] = torch.clamp(self._max_grad_norm / (norm + 1e-6), max=1.0)
-
-    def soft_update_targets(self):
-        """utils.soft_update_params x3 (curl_sac.py:442-445) as one flat lerp with two rates."""
-        lay = self._lay
-        (e0, e1), (q0, q1) = lay["enc"], lay["q"]
-        assert e1 == q0  # [encoder | Q1 | Q2] are adjacent: one launch, two rates
-        ops.soft_update2(self._critic_flat[e0:q1], self._target_flat[e0:q1], e1 - e0, self.encoder_tau, self.critic_tau)
-
     def update(self, replay_buffer, L, step, only_cpc=False, noise=None):
         """curl_sac.py:426-451.  A curla_amd ReplayBuffer hands over references
         into its HBM ring (gather + crop fused into the first conv); any other
@@ -1232,8 +861,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         decision) followed by the ordinary call with ``utd_ratio = 1``.  ``noise`` is a hook for one minibatch and is
         refused with G > 1."""
         self._restore_grad_views()
-        if self.policy_std_schedule is not None:  # (evaluated before the eager / graph route is chosen: std is data)
-            self.set_policy_std(_linear_schedule(_check_policy_std_schedule(self.policy_std_schedule), step))
+        self._policy_schedule_step(step)  # (before the eager / graph route is chosen: the policy's std is data)
         self._check_n_step(replay_buffer)
         self._check_aug_views(replay_buffer)
         self._maybe_reset(step)  # (reset_interval: in front of every sub-step, graphed or not)
@@ -1351,112 +979,3 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             obs_anchor, obs_pos = cpc_kwargs["obs_anchor"], cpc_kwargs["obs_pos"]
             self.update_cpc(obs_anchor, obs_pos, cpc_kwargs, L, step)
         self._finish_actor_step()
-
-    def save(self, model_dir, augmentation, step):
-        """curl_sac.py:453-456 (same three files, reference tensor layouts)."""
-        torch.save(self.CURL.state_dict(), '%s/%s_curl_%s.pt' % (model_dir, augmentation, step))
-        torch.save(self.actor.state_dict(), '%s/%s_actor_%s.pt' % (model_dir, augmentation, step))
-        torch.save(self.critic.state_dict(), '%s/%s_critic_%s.pt' % (model_dir, augmentation, step))
-
-    def load(self, model_dir, augmentation, step):
-        """curl_sac.py:458-465 (same files, same three progress lines on stdout)."""
-        self.CURL.load_state_dict(torch.load('%s/%s_curl_%s.pt' % (model_dir, augmentation, step)))
-        print('Loaded model %s/%s_curl_%s.pt' % (model_dir, augmentation, step))
-        self.actor.load_state_dict(torch.load('%s/%s_actor_%s.pt' % (model_dir, augmentation, step)))
-        print('Loaded model %s/%s_actor_%s.pt' % (model_dir, augmentation, step))
-        self.critic.load_state_dict(torch.load('%s/%s_critic_%s.pt' % (model_dir, augmentation, step)))
-        self.critic_target.load_state_dict(self.critic.state_dict())
-        print('Loaded model %s/%s_critic_%s.pt' % (model_dir, augmentation, step))
-
-    # -- full training state (SURVEY.md 8f rank 2: the reference only writes the three state_dicts above and
-    #    cannot resume; this adds log_alpha, the target critic, the five Adam states, the RNG streams and the step)
-    def _optimizers(self):
-        return {"actor": self.actor_optimizer, "critic": self.critic_optimizer, "log_alpha": self.log_alpha_optimizer,
-                "encoder": self.encoder_optimizer, "cpc": self.cpc_optimizer}
-
-    def _convert_opt_state(self, opt, sd, to_reference):
-        """Adam moments of an encoder fc.weight follow the weight's column order: (c,y,x) on disk like the
-        reference's Parameter, (y,x,c) in HBM."""
-        fc_of = {id(e.fc.weight): e.fc for e in (self.actor.encoder, self.critic.encoder, self.critic_target.encoder)}
-        params = [q for g in opt.param_groups for q in g["params"]]
-        state = {}
-        for i, st in sd["state"].items():
-            st = dict(st)
-            fc = fc_of.get(id(params[i]))
-            for k, v in st.items():
-                if torch.is_tensor(v):
-                    if fc is not None and v.dim() == 2:
-                        v = (fc.to_reference_layout(v) if to_reference else fc.from_reference_layout(v)).contiguous()
-                    st[k] = v.detach().cpu() if to_reference else v
-            state[i] = st
-        return {"state": state, "param_groups": sd["param_groups"]}
-
-    def save_checkpoint(self, path, step):
-        rng = {"torch": torch.get_rng_state(), "numpy": np.random.get_state()}
-        if self.device.type == "cuda":
-            rng["cuda"] = torch.cuda.get_rng_state(self.device)
-        torch.save({
-            "format": "curla_amd.checkpoint.v1", "step": int(step),
-            "actor": self.actor.state_dict(), "critic": self.critic.state_dict(),
-            "critic_target": self.critic_target.state_dict(), "curl": self.CURL.state_dict(),
-            "log_alpha": self.log_alpha.detach().cpu(),
-            "optimizers": {k: self._convert_opt_state(o, o.state_dict(), True) for k, o in self._optimizers().items()},
-            "rng": rng, "critic_dropout": float(self.critic_dropout), "utd_ratio": int(self.utd_ratio),
-            "critic_quantiles": int(self.critic_quantiles), "critic_drop_quantiles": int(self.critic_drop_quantiles),
-            **({"aug_views": 2} if self.aug_views == 2 else {}),  # (1: the file of an agent without the keyword)
-            **({"critic_bins": int(self.critic_bins), "critic_value_range": tuple(float(v) for v in self.critic_value_range),
-                "critic_bin_sigma": float(self.critic_bin_sigma)} if self.critic_bins else {}),  # (0: likewise)
-            **({"policy": "deterministic", "policy_std": float(self._policy_std),
-                "policy_std_clip": self.policy_std_clip, "policy_std_schedule": self.policy_std_schedule}
-               if self.policy == "deterministic" else {}),  # (gaussian: likewise)
-            **self._reset_checkpoint(), **self._redo_checkpoint(),
-        }, path)
-
-    def load_checkpoint(self, path, restore_rng=True):
-        """Returns the step the checkpoint was written at."""
-        ck = torch.load(path, map_location="cpu", weights_only=False)
-        if ck.get("format") != "curla_amd.checkpoint.v1":
-            raise ValueError("not a curla_amd checkpoint: %r" % (path,))
-        if float(ck.get("critic_dropout", 0.0)) != float(self.critic_dropout):
-            warnings.warn("curla_amd: the checkpoint was written with critic_dropout = %r; this agent keeps its own, %r"
-                          % (ck.get("critic_dropout", 0.0), self.critic_dropout), RuntimeWarning, stacklevel=2)
-        if ck.get("utd_ratio", 1) != self.utd_ratio:  # (a file from before the keyword: 1)
-            warnings.warn("curla_amd: the checkpoint was written with utd_ratio = %r; this agent keeps its own, %r"
-                          % (ck.get("utd_ratio", 1), self.utd_ratio), RuntimeWarning, stacklevel=2)
-        if ck.get("aug_views", 1) != self.aug_views:  # (a file from before the keyword: 1)
-            warnings.warn("curla_amd: the checkpoint was written with aug_views = %r; this agent keeps its own, %r"
-                          % (ck.get("aug_views", 1), self.aug_views), RuntimeWarning, stacklevel=2)
-        self.CURL.load_state_dict(ck["curl"])
-        self.actor.load_state_dict(ck["actor"])
-        self.critic.load_state_dict(ck["critic"])
-        self.critic_target.load_state_dict(ck["critic_target"])
-        # (another critic_quantiles has failed above, on the last layers' shapes; the dropped atoms are a number of the
-        # loss alone and come from the file)
-        if self.critic_quantiles and "critic_drop_quantiles" in ck:
-            self.critic_drop_quantiles = _check_drop_quantiles(ck["critic_drop_quantiles"], self.critic_quantiles)
-        # (another critic_bins has failed above as well; the range and the smoothing are numbers of the loss alone)
-        if self.critic_bins and "critic_value_range" in ck:
-            self.critic_value_range = _check_value_range(ck["critic_value_range"])
-            self.critic_bin_sigma = _check_bin_sigma(ck.get("critic_bin_sigma", self.critic_bin_sigma))
-            self._hlg_params()
-        # (a checkpoint of the other policy has failed above, on the size of actor.trunk.4)
-        if self.policy == "deterministic" and ck.get("policy") == "deterministic":
-            self.policy_std_clip = _check_policy_std_clip(ck["policy_std_clip"])
-            self.policy_std_schedule = _check_policy_std_schedule(ck["policy_std_schedule"])
-            self.set_policy_std(ck["policy_std"])
-        with torch.no_grad():
-            self.log_alpha.copy_(ck["log_alpha"])
-        for k, o in self._optimizers().items():
-            o.load_state_dict(self._convert_opt_state(o, ck["optimizers"][k], False))
-        if restore_rng:
-            torch.set_rng_state(ck["rng"]["torch"])
-            np.random.set_state(ck["rng"]["numpy"])
-            if self.device.type == "cuda" and "cuda" in ck["rng"]:
-                torch.cuda.set_rng_state(ck["rng"]["cuda"], self.device)
-        self._load_reset_checkpoint(ck)
-        self._load_redo_checkpoint(ck)
-        self._drop_encoder_caches()
-        # captured graphs hold the addresses of log_alpha's Adam moments, which load_state_dict has just replaced
-        self._drop_graphs()
-        return ck["step"]
-

@@ -16,11 +16,18 @@ MOVED = {
     "mlp": ["_Mlp", "_MlpLn", "_linears", "_mlp_fwd", "_mlp_bwd"],
     "networks": ["Actor", "QFunction", "Critic", "CURL", "weight_init", "LOG_FREQ", "_QFunctionType", "_CriticType",
                  "_widen_last_layers", "_check_quantiles", "_check_drop_quantiles", "_check_layer_norm_width",
-                 "_check_dropout", "_device_generator", "_reserve_dropout_counter"],
-    "agent_graphs": ["_NullLog"],
+                 "_check_dropout", "_device_generator", "_reserve_dropout_counter", "_check_int", "_check_bins",
+                 "_check_value_range", "_check_bin_sigma", "_check_policy_std", "_check_policy_std_clip"],
+    "agent_graphs": ["_NullLog", "_UpdateGraphsMixin"],
+    "agent_policy": ["_check_policy", "_check_policy_std_schedule", "_linear_schedule", "_policy_keywords", "_PolicyMixin"],
+    "agent_critic_head": ["_critic_head_keywords", "_CriticHeadMixin"],
+    "agent_optim": ["_OptimMixin"],
+    "agent_checkpoint": ["_CheckpointMixin"],
+    "agent_reset": ["_check_reset_interval", "_check_reset_keep", "_check_reset_seed", "_reset_keywords", "_ResetMixin"],
+    "agent_redo": ["_check_redo_interval", "_check_redo_tau", "_check_redo_recycle", "_redo_keywords", "_RedoMixin"],
 }
 KEPT = ["CurlSacAgent", "_AgentType", "_Workspace", "_as_ref", "_check_utd_ratio", "_no_drop", "CNNEncoder", "ObsRef",
-        "FlatAdam", "check_max_grad_norm", "check_weight_decay"]
+        "FlatAdam", "check_max_grad_norm", "check_weight_decay", "_check_views"]
 
 
 def test_every_name_of_the_one_file_module_is_importable_from_curl_sac_and_is_its_new_homes_object():
@@ -57,7 +64,17 @@ ATTRIBUTES = {
         critic_quantiles disable_update_graphs enable_data_parallel enable_update_graphs grad_clip_stats load
         load_checkpoint max_grad_norm sample_action sample_actions save save_checkpoint select_action select_actions
         set_max_grad_norm set_weight_decay soft_update_targets train update update_actor_and_alpha update_cpc
-        update_critic utd_ratio weight_decay""".split(),
+        update_critic utd_ratio weight_decay
+        _actor_fwd _actor_kw _actor_loss _actor_out_dim _actor_reduce_and_step _anchor_cache _check_aug_views _cpc_steps
+        _critic_forward _critic_loss _critic_step _critic_width_kw _draw_fresh _drop_encoder_caches
+        _encoder_backward_reduced _hlg_last_B _hlg_params _load_redo_checkpoint _load_reset_checkpoint _maybe_reset
+        _next_policy _online_q _phases _policy_clip _policy_std _pos_cache _pos_fc_done _pos_hint _q_four _q_merged
+        _q_unmerged _redo_allreduce _redo_buf _redo_buffers _redo_checkpoint _redo_due _redo_moments _redo_pass
+        _redo_scheduled _replica_check_due _reset_checkpoint _reset_epoch _reset_handover _reset_rng _reset_stage
+        _reset_staging _reset_stream _stage_fresh _stage_params _target_q _twin_bwd _twin_fwd _upload_fresh aug_views
+        critic_bin_sigma critic_bins critic_value_range dormant_counts dormant_fractions dormant_report policy policy_std
+        policy_std_clip policy_std_schedule redo_count redo_interval redo_pass redo_recycle redo_tau reset_count
+        reset_encoder_keep reset_interval reset_networks reset_seed set_policy_std target_clip_fraction""".split(),
     "Actor": MODULE + ["log"],
     "Critic": MODULE + ["DROP_TAG_FORWARD", "dropout", "log", "out_dim", "quantiles", "twin", "twin_ln"],
     "QFunction": MODULE + ["quantiles"],
@@ -80,12 +97,17 @@ package.__path__ = [sys.argv[1]]
 sys.modules["curla_amd"] = package
 import curla_amd.mlp
 import curla_amd.autograd
+import curla_amd.agent_critic_head
+import curla_amd.agent_policy
+import curla_amd.agent_optim
+import curla_amd.agent_checkpoint
 sys.exit(3 if "curla_amd.curl_sac" in sys.modules else 0)
 """
 
 
 def test_mlp_and_autograd_import_without_curl_sac():
-    for module in ("mlp.py", "autograd.py"):
+    for module in ("mlp.py", "autograd.py", "agent_critic_head.py", "agent_policy.py", "agent_optim.py",
+                   "agent_checkpoint.py"):
         with open(os.path.join(PACKAGE, module)) as f:
             assert "curl_sac import" not in f.read(), module
     child = subprocess.run([sys.executable, "-c", CHILD, PACKAGE], capture_output=True, text=True)

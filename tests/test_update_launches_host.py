@@ -5,7 +5,7 @@ blocks (``tests/update_launches.json``: per case and step the entry points in cl
 JSON of the full list; ``python -m tests.test_update_launches_host`` prints the full lists, ``--write`` stores the table).
 
 Scalars are recorded as they are.  An address is recorded as (named region, byte offset): the agent's flat and gradient
-buffers, ``log_alpha`` and its gradient, every tensor of the workspace by its storage (views resolve to one name), the
+buffers, ``log_alpha`` and its gradient, the deterministic policy's device scalars, every tensor of the workspace by its storage (views resolve to one name), the
 encoders' partial buffers, ``grad_clip_stats``, the flat optimizers' moment and partials buffers, the redo buffers and
 the replay buffer's tensors by attribute.  An address in none of them is named by the order of its first appearance
 (``ext0``, ...).  The small host arrays and structs some entry points take by address are recorded by content.
@@ -72,6 +72,15 @@ CASES = {
     "dp_overlap_b128": dict(shape="b128", dp="overlap"),
     "dp_overlap_hist": dict(dp="overlap", agent=dict(log_param_hist_imgs=True)),
     "redo": dict(agent=dict(redo_recycle=False), redo=True, steps={}),
+    "aug_views": dict(agent=dict(aug_views=2), rb=dict(aug_views=2)),
+    "bins": dict(agent=dict(critic_bins=5, critic_value_range=(-4.0, 6.0))),
+    "bins_views": dict(agent=dict(critic_bins=5, critic_value_range=(-4.0, 6.0), aug_views=2), rb=dict(aug_views=2)),
+    "deterministic": dict(agent=dict(policy="deterministic")),
+    "deterministic_schedule": dict(agent=dict(policy="deterministic", policy_std_schedule=(1.0, 0.1, 8.0))),
+    "deterministic_flat": dict(flat=True, agent=dict(policy="deterministic")),
+    "quantiles_flat": dict(flat=True, agent=dict(critic_quantiles=5, critic_drop_quantiles=1)),
+    "bins_logging": dict(agent=dict(critic_bins=5, critic_value_range=(-4.0, 6.0), log_interval=1)),
+    "deterministic_logging": dict(agent=dict(policy="deterministic", log_interval=1)),
 }
 
 
@@ -248,6 +257,8 @@ def _regions(agent, rb):
     for name in ("_target_flat", "_critic_gflat", "_actor_flat", "_actor_gbucket", "log_alpha", "grad_clip_stats"):
         walk("flat" if name == "_target_flat" else name, getattr(agent, name))  # (one allocation: [target | critic])
     walk("log_alpha.grad", agent.log_alpha.grad)
+    walk("actor.std", getattr(agent.actor, "std", None))  # (the deterministic policy's two device scalars)
+    walk("_dla_scratch", getattr(agent, "_dla_scratch", None))
     for name, opt in agent._optimizers().items():
         if isinstance(opt, FlatAdam):
             for attr in ("_m", "_v", "_clip_partials", "clip_stats"):
