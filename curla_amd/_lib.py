@@ -156,6 +156,7 @@ SIGNATURES = {
     "curla_hlg_actor_loss": [vp, c_ll, vp, vp, c_int, vp, c_float, c_int, c_int, c_float, c_float, vp, vp, vp, c_ll, vp, vp],
     "curla_curl_ce": [vp, c_int, c_int, vp, vp, vp, vp],
     "curla_curl_ce_views": [vp, c_int, c_int, vp, vp, vp, vp],
+    "curla_pred_loss": [vp, vp, c_int, c_int, vp, vp, vp, vp],
     "curla_mean": [vp, c_int, vp, vp],
     "curla_soft_update": [vp, vp, c_size_t, c_float, c_float, vp],
     "curla_crop_nchw": [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp],

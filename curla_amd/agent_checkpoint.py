@@ -23,7 +23,9 @@ class _CheckpointMixin:
 
     def load(self, model_dir, augmentation, step):
         """curl_sac.py:458-465 (same files, same three progress lines on stdout)."""
-        self.CURL.load_state_dict(torch.load('%s/%s_curl_%s.pt' % (model_dir, augmentation, step)))
+        curl = torch.load('%s/%s_curl_%s.pt' % (model_dir, augmentation, step))
+        self._check_curl_state_dict(curl)  # (the other objective's file: refused before anything is written)
+        self.CURL.load_state_dict(curl)
         print('Loaded model %s/%s_curl_%s.pt' % (model_dir, augmentation, step))
         self.actor.load_state_dict(torch.load('%s/%s_actor_%s.pt' % (model_dir, augmentation, step)))
         print('Loaded model %s/%s_actor_%s.pt' % (model_dir, augmentation, step))
@@ -45,7 +47,7 @@ class _CheckpointMixin:
             **{name: cast(getattr(self, name)) for name, cast, default, always in _WARN_ONLY
                if always or getattr(self, name) != default},
             **self._critic_head_checkpoint(), **self._policy_checkpoint(), **self._reset_checkpoint(),
-            **self._redo_checkpoint(),
+            **self._redo_checkpoint(), **self._cpc_checkpoint(),
         }, path)
 
     def load_checkpoint(self, path, restore_rng=True):
@@ -53,6 +55,7 @@ class _CheckpointMixin:
         ck = torch.load(path, map_location="cpu", weights_only=False)
         if ck.get("format") != "curla_amd.checkpoint.v1":
             raise ValueError("not a curla_amd checkpoint: %r" % (path,))
+        self._check_cpc_checkpoint(ck)  # (the other objective's file: refused before anything is written)
         for name, _, default, _ in _WARN_ONLY:
             if ck.get(name, default) != getattr(self, name):
                 warnings.warn("curla_amd: the checkpoint was written with %s = %r; this agent keeps its own, %r"

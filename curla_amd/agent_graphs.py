@@ -136,7 +136,7 @@ class _UpdateGraphsMixin:
                 hyper, self._graph_rb_key(), self._max_grad_norm) + \
             ((float(self.critic_dropout),) if self.critic_dropout else ()) + \
             ((("aug_views", 2),) if self.aug_views == 2 else ()) + \
-            self._critic_head_graph_key() + self._policy_graph_key()
+            self._critic_head_graph_key() + self._policy_graph_key() + self._cpc_graph_key()
         # (a feature that is off adds nothing: the key of an agent without the keyword.  The critic head's entry is the
         # quantiles', which two views are not combined with, or the bins', behind the views' -- the order as it was)
 

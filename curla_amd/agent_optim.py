@@ -37,7 +37,8 @@ class _OptimMixin:
             [self.log_alpha], lr=alpha_lr, betas=(alpha_beta, 0.999),
             **(dict(foreach=False) if flat_actor else dict(fused=True) if self.device.type == "cuda" else {}))
         self.encoder_optimizer = adam(enc_params, cf, cg, lr=encoder_lr)
-        self.cpc_optimizer = adam([self.CURL.W] + enc_params, cf, cg, lr=encoder_lr)
+        # (the head's parameters: CURL.W, or the predictor's with cpc_objective="predictive" -- agent_cpc.py)
+        self.cpc_optimizer = adam(self._cpc_head_params() + enc_params, cf, cg, lr=encoder_lr)
 
     def _optimizers(self):
         return {"actor": self.actor_optimizer, "critic": self.critic_optimizer, "log_alpha": self.log_alpha_optimizer,

@@ -114,6 +114,7 @@ class _ResetMixin:
         actor, critic, W = self._draw_fresh()
         c, a = stage["critic"]["host"], stage["actor"]["host"]
         self._stage_params(c, self._critic_flat, [("W", self.CURL.W)], [("W", W)])
+        self._stage_fresh_cpc(c)  # (cpc_objective="predictive": a fresh predictor behind W, from the same stream)
         self._stage_params(c, self._critic_flat, list(self.critic.named_parameters()), critic.named_parameters(),
                            fc=self.critic.encoder.fc)
         own = [(n, p) for n, p in self.actor.named_parameters() if ".convs." not in n]  # (the convs are the critic's)
@@ -140,8 +141,9 @@ class _ResetMixin:
           heads   : actor.trunk, critic.Q1 / Q2 and the target's Q functions become freshly initialised ones (the
                     target's equal the critic's)
           encoder : the critic encoder (the actor's tied convs with it), the target encoder -- same fresh values --, the
-                    actor encoder's fc / ln -- their own -- and CURL.W become ``keep * old + (1 - keep) * fresh`` with
-                    keep = ``encoder_keep`` (None: the attribute ``reset_encoder_keep``); 1 leaves them untouched
+                    actor encoder's fc / ln -- their own -- and CURL.W (CURL.predictor with it: DESIGN.md 7n) become
+                    ``keep * old + (1 - keep) * fresh`` with keep = ``encoder_keep`` (None: the attribute
+                    ``reset_encoder_keep``); 1 leaves them untouched
           state   : the four network optimizers start over -- moments zero, every step count 0; whole optimizers, also
                     where the encoder is kept: their fused launches have one step count each --, the gradient buffers
                     are zero; ``alpha=True``: log_alpha is the constructor's log(init_temperature) again and its

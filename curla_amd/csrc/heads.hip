@@ -25,6 +25,7 @@ namespace {
 #include "tqc.h"           // tqc_critic_loss_kernel, tqc_actor_loss_kernel (truncated quantile critics)
 #include "hlgauss.h"       // hlg_critic_loss_kernel<VIEWS>, hlg_actor_rows_kernel, hlg_actor_scalars_kernel (the HL-Gauss critic)
 #include "curl_head.h"     // curl_head_kernel<NTILE>
+#include "pred_loss.h"     // pred_loss_kernel<NF> (the self-predictive latent loss)
 #include "redo.h"          // dormant_colsum_kernel, dormant_mask_kernel, redo_recycle_kernel (dormant-neuron scores, ReDo)
 #include "optim.h"         // soft_update_kernel, soft_update2_kernel, shrink_perturb2_kernel, adam_step_kernel<CLIP, DECAY>, adam_step2_kernel<CLIP, DECAY>
 #include "sample_stage.h"  // a minibatch's index block and scalars: sample_stage_kernel<HOST, NSTEP, POS>, pos_walk_kernel
@@ -773,6 +774,16 @@ int curla_curl_head(const float* z_a, const float* z_pos, const float* wz, const
   if (loss) rc = launch(mean_kernel, dim3(1), 256, 0, st, row_loss, B, loss);  // only when it is logged
   *nparts = B / 16;
   return rc;
+}
+
+int curla_pred_loss(const float* p, const float* t, int B, int F, float* row_loss, float* loss, float* dp, void* stream) {
+  CURLA_REQUIRE(p && t && row_loss && dp && B > 0 && F >= 1 && F <= 1024);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = dispatch_ln_width(F, [&](auto nf) {
+    return launch(pred_loss_kernel<nf()>, dim3((B + 3) / 4), 256, 0, st, p, t, B, F, row_loss, dp);
+  });
+  if (rc != CURLA_OK || !loss) return rc;
+  return launch(mean_kernel, dim3(1), 256, 0, st, row_loss, B, loss);  // the fixed-order mean over rows, where asked for
 }
 
 int curla_f64_pack(const double* value, float* words, void* stream) {

@@ -29,6 +29,7 @@ import torch
 from . import ops
 from .agent_acting import _ActingMixin
 from .agent_checkpoint import _CheckpointMixin
+from .agent_cpc import _cpc_keywords, _CpcMixin
 from .agent_critic_head import _critic_head_keywords, _CriticHeadMixin
 from .agent_dp import _DataParallelMixin
 from .agent_graphs import _NullLog, _UpdateGraphsMixin
@@ -135,6 +136,7 @@ class _Workspace:
         # CURL
         self.WzT, self.dWzT = f(B, F), f(B, F)
         self.logits, self.dlogits, self.row_loss = f(B, B), f(B, B), f(B)
+        agent._cpc_workspace(self, f, B, F, A)  # (the predictive objective's head; nothing by default)
 
 
 class _AgentType(type):
@@ -143,12 +145,13 @@ class _AgentType(type):
     contract, tests/test_dropin_contract.py); a keyword that shapes the networks has to be known before ``__init__``
     builds them, so the class call takes it off the arguments and leaves it on the instance."""
 
-    def __call__(cls, *args, policy="gaussian", policy_std=0.2, policy_std_clip=0.3, policy_std_schedule=None,
-                 aug_views=1, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0,
+    def __call__(cls, *args, cpc_objective="infonce", predictor_hidden=None, policy="gaussian", policy_std=0.2,
+                 policy_std_clip=0.3, policy_std_schedule=None, aug_views=1, redo_interval=0, redo_tau=0.1, redo_recycle=True, reset_interval=0,
                  reset_encoder_keep=1.0, reset_seed=0, critic_quantiles=0, critic_drop_quantiles=0, critic_bins=0,
                  critic_value_range=None, critic_bin_sigma=0.75, weight_decay=0.0, utd_ratio=1, critic_dropout=0.0,
                  critic_layer_norm=False, **kwargs):
         agent = cls.__new__(cls)
+        _cpc_keywords(agent, cpc_objective, predictor_hidden)
         _policy_keywords(agent, policy, policy_std, policy_std_clip, policy_std_schedule)
         _redo_keywords(agent, redo_interval, redo_tau, redo_recycle)
         _reset_keywords(agent, reset_interval, reset_encoder_keep, reset_seed)
@@ -173,7 +176,7 @@ class _AgentType(type):
 
 
 class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetMixin, _RedoMixin, _CriticHeadMixin,
-                   _PolicyMixin, _OptimMixin, _CheckpointMixin, metaclass=_AgentType):
+                   _CpcMixin, _PolicyMixin, _OptimMixin, _CheckpointMixin, metaclass=_AgentType):
     """CURL representation learning with SAC (curl_sac.py:224-465).
     ``CurlSacAgent(..., critic_layer_norm=True)`` (a keyword of the class call, not in the reference; default off:
     nothing changes): an ``nn.LayerNorm(hidden_dim)`` between each hidden Linear of the Q functions and its ReLU, critic
@@ -221,7 +224,14 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
     critic losses compute the entropy-free target, the actor loss is -mean Q, and log_alpha never moves.
     The policy shapes the actor; ``policy_std`` is read through ``agent.policy_std`` and set by ``set_policy_std`` (a
     device scalar: data to captured graphs), clip and schedule are attributes that may be edited between calls.  The
-    three ``policy_std*`` keywords raise beside the Gaussian policy."""
+    three ``policy_std*`` keywords raise beside the Gaussian policy.
+    ``cpc_objective="predictive"`` (default "infonce": nothing changes) with ``predictor_hidden=H`` (None: hidden_dim; a
+    positive int): the self-predictive latent objective of SPR / BBF in one step -- the representation phase trains the
+    encoder, and ``CURL.predictor`` = Linear(F + A, H) - ReLU - Linear(H, F), to predict from the online latent of obs[t]
+    and action[t] the target encoder's latent of the next observation, by the squared distance of the two normalised
+    vectors (``curla_pred_loss``; agent_cpc.py).  No negatives: per row, whatever the batch size.  With a
+    ``ReplayBuffer(pos_offset=1)``, and ``update`` checks it; CURL.W keeps its slot and is never stepped; logged as
+    ``train/pred_loss``.  Fixed at construction.  Not with ``pixel_sac``."""
 
     critic_layer_norm = False
     critic_dropout = 0.0
@@ -260,6 +270,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         pixel_sac=False
     ):
         _check_layer_norm_width(self.critic_layer_norm, hidden_dim)
+        self._check_cpc_init(pixel_sac)
         self.augmentor = augmentor
         self.device = torch.device(device)
         if self.critic_dropout > 0 and self.device.type == "cuda" and \
@@ -304,6 +315,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         self.target_entropy = -np.prod(action_shape)
 
         self.CURL = CURL(obs_shape, encoder_feature_dim, self.critic, self.critic_target, output_type='continuous')
+        self._build_predictor(encoder_feature_dim)  # (cpc_objective="predictive": behind everything the reference draws)
 
         self._to_flat_device_layout()
         self._place_policy_scalars()
@@ -330,8 +342,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         """Move every parameter into flat fp32 device buffers (16-byte aligned
         slots), Q1/Q2 as two identically laid-out blocks, and give each a
         persistent .grad view into a mirror buffer.
-          critic flat : [ CURL.W | encoder (convs, fc, ln) | Q1 | Q2 ]
-          target flat : same layout (W slot unused)
+          critic flat : [ CURL.W (+ CURL.predictor: cpc_objective="predictive") | encoder (convs, fc, ln) | Q1 | Q2 ]
+          target flat : same layout (W group's slot unused)
           actor flat  : [ encoder.fc, encoder.ln | trunk ]"""
         dev = self.device
         for m in (self.actor, self.critic, self.critic_target):
@@ -354,7 +366,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             enc = [("encoder." + n, p) for n, p in critic.encoder.named_parameters()]
             q1 = [("Q1." + n, p) for n, p in critic.Q1.named_parameters()]
             q2 = [("Q2." + n, p) for n, p in critic.Q2.named_parameters()]
-            return [("W", W)] if W is not None else [], enc, q1, q2
+            return [("W", W)] + self._cpc_flat_params() if W is not None else [], enc, q1, q2
 
         wl, enc, q1, q2 = critic_groups(self.critic, self.CURL.W)
         w_sz = place(wl, True)
@@ -405,7 +417,8 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         skip them as torch's Adam does.  ``zero_grad`` of the five optimizers marks the views as possibly dropped;
         update() restores them first (_restore_grad_views) -- a flag test, not a walk, while nothing has changed."""
         views, seen = [], set()
-        for p in [self.CURL.W, self.log_alpha, *self.critic.parameters(), *self.actor.parameters()]:
+        for p in [self.CURL.W, *(p for _, p in self._cpc_flat_params()), self.log_alpha, *self.critic.parameters(),
+                  *self.actor.parameters()]:
             if id(p) not in seen and p.grad is not None:
                 seen.add(id(p))
                 views.append((p, p.grad))
@@ -786,12 +799,14 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         if step % self.log_interval == 0:
             self._log_actor(ws, L, step, alpha=True)
 
-    def update_cpc(self, obs_anchor, obs_pos, cpc_kwargs, L, step):
-        """curl_sac.py:406-423."""
-        self._restore_grad_views()
+    def update_cpc(self, obs_anchor, obs_pos, cpc_kwargs, L, step, action=None):
+        """curl_sac.py:406-423.  ``action`` (``cpc_objective="predictive"`` only, required then: the minibatch's actions):
+        the head behind the two encoders is the self-predictive one (agent_cpc.py) in place of CURL's."""
         oa, op_ = _as_ref(obs_anchor), _as_ref(obs_pos)
+        action = self._check_cpc_action(action, oa.B)  # (before anything is written)
+        self._restore_grad_views()
         B, ws = oa.B, self._ws(oa.B)
-        enc, tenc, F = self.critic.encoder, self.critic_target.encoder, self.critic.encoder.feature_dim
+        enc, tenc = self.critic.encoder, self.critic_target.encoder
         need_anchor = self._anchor_cache is None or self._anchor_cache is not obs_anchor
         need_pos = self._pos_cache is None or self._pos_cache is not obs_pos
         pos_fc_done = self._pos_fc_done and not need_pos
@@ -810,9 +825,27 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             tenc.fc_partial(ws.acts_tmp[-1])
             tenc.ln_from_partial(B, ws.z_pos)
 
-        W = self.CURL.W
-        ops.linear_fwd(ws.z_pos, 0, W, 0, None, 0, ws.WzT, 0, B, F, F)         # (W z_pos^T)^T
         logged = step % self.log_interval == 0  # the mean of the row losses is only needed when it is logged
+        if action is not None:
+            self._predictive_head(ws, oa, action, logged)
+        else:
+            self._infonce_head(ws, oa, logged)
+        self._cpc_steps()
+        if logged:
+            L.log(self._cpc_loss_key(), ws.scalars[5], step)
+            if self._max_grad_norm is not None:
+                L.log('train/curl_grad_norm', self.grad_clip_stats[2, 0], step)
+
+    # The drop-in contract pins update_cpc's parameter list to the reference's five names (tests/test_dropin_contract.py),
+    # as it pins __init__'s: introspection keeps showing those, and ``action`` is a keyword accepted behind them.
+    update_cpc.__signature__ = inspect.Signature(
+        [p for p in inspect.signature(update_cpc).parameters.values() if p.name != "action"])
+
+    def _infonce_head(self, ws, oa, logged):
+        """CURL's head behind ws.z_c / ws.z_pos (curl_sac.py:211-222, 411-417) and the encoder's backward."""
+        B, enc = oa.B, self.critic.encoder
+        F, W = enc.feature_dim, self.CURL.W
+        ops.linear_fwd(ws.z_pos, 0, W, 0, None, 0, ws.WzT, 0, B, F, F)         # (W z_pos^T)^T
         # logits, cross-entropy, d z_a, the LayerNorm backward and the partial sums of dW in ONE launch where the
         # shapes allow (and the fc backward is a streaming kernel, whose extra workgroup finishes the partial sums)
         token = None
@@ -829,11 +862,6 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
             ops.linear_dw(ws.dlogits, 0, ws.z_c, 0, ws.dWzT, 0, B, B, F)           # d (W z_pos^T)^T
             ops.linear_dw(ws.dWzT, 0, ws.z_pos, 0, W.grad, 0, B, F, F)             # d W
         self._encoder_backward_reduced(ws, oa, ws.dz, 0, self._lay["enc"][1], ln_token=token)
-        self._cpc_steps()
-        if step % self.log_interval == 0:
-            L.log('train/curl_loss', ws.scalars[5], step)
-            if self._max_grad_norm is not None:
-                L.log('train/curl_grad_norm', self.grad_clip_stats[2, 0], step)
 
     def update(self, replay_buffer, L, step, only_cpc=False, noise=None):
         """curl_sac.py:426-451.  A curla_amd ReplayBuffer hands over references
@@ -863,6 +891,7 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
         self._restore_grad_views()
         self._policy_schedule_step(step)  # (before the eager / graph route is chosen: the policy's std is data)
         self._check_n_step(replay_buffer)
+        self._check_cpc_buffer(replay_buffer)
         self._check_aug_views(replay_buffer)
         self._maybe_reset(step)  # (reset_interval: in front of every sub-step, graphed or not)
         if self.utd_ratio != 1 or type(self.utd_ratio) is not int:  # (the attribute may have been edited)
@@ -977,5 +1006,5 @@ class CurlSacAgent(_ActingMixin, _DataParallelMixin, _UpdateGraphsMixin, _ResetM
 
         if do_cpc:
             obs_anchor, obs_pos = cpc_kwargs["obs_anchor"], cpc_kwargs["obs_pos"]
-            self.update_cpc(obs_anchor, obs_pos, cpc_kwargs, L, step)
+            self.update_cpc(obs_anchor, obs_pos, cpc_kwargs, L, step, **self._cpc_call_kw(action))
         self._finish_actor_step()

@@ -298,9 +298,11 @@ def linear_fwd(x, sx, W, sW, bias, sb, out, so, M, N, K, nb=1, relu=0, outer=Non
              1.0, ptr(bias), sb, sW2, relu, None, 0, 0, 0, stream())
 
 
-def linear_dx(dy, sdy, W, sW, out, so, M, N, K, nb=1, mask=None, smask=0):
-    """out[z] = (dy[z] @ W[z]) masked;  dy [M,N], W [N,K] -> out [M,K]."""
-    gemm(dy, 0, N, sdy, W, 1, K, sW, out, K, so, M, K, N, nb, mask=mask, ldmask=K, sMask=smask)
+def linear_dx(dy, sdy, W, sW, out, so, M, N, K, nb=1, mask=None, smask=0, ldw=None):
+    """out[z] = (dy[z] @ W[z]) masked;  dy [M,N], W [N,K] -> out [M,K].
+    ``ldw`` (None: K): W's rows are ldw >= K floats long and the product takes their first K columns -- the input
+    gradient of a layer's first K inputs alone, dense in ``out``."""
+    gemm(dy, 0, N, sdy, W, 1, K if ldw is None else ldw, sW, out, K, so, M, K, N, nb, mask=mask, ldmask=K, sMask=smask)
 
 
 def linear_dw(dy, sdy, x, sx, out, so, M, N, K, nb=1, colsum=None, s_colsum=0):
@@ -724,6 +726,16 @@ def curl_ce(logits, B, ld, row_loss, loss, dlogits=None):
 def curl_ce_views(logits, B, ld, row_loss, loss, dlogits=None):
     """curl_ce without row a's partner column (a + B/2) % B among the negatives (curla_curl_ce_views; B even)."""
     call("curla_curl_ce_views", ptr(logits), B, ld, ptr(row_loss), ptr(loss), ptr(dlogits), stream())
+
+
+PRED_MAX = 1024  # the widest latent the self-predictive loss takes: the encoder's own limit (csrc/pred_loss.h)
+
+
+def pred_loss(p, t, B, F, row_loss, loss, dp):
+    """The self-predictive latent loss and its gradient in one kernel (curla_pred_loss): p (the predictor's output) and
+    t (the target encoder's latent, a constant) [B][F]; row_loss [B] = |normalize(p) - normalize(t)|^2 per row, ``loss``
+    [1] their fixed-order mean (None: not taken), dp [B][F] = d loss / d p."""
+    call("curla_pred_loss", ptr(p), ptr(t), B, F, ptr(row_loss), ptr(loss), ptr(dp), stream())
 
 
 def mean(x, n, out):

@@ -548,6 +548,16 @@ int curla_curl_ce_views(const float* logits, int B, int ld, float* row_loss, flo
 int curla_curl_head(const float* z_a, const float* z_pos, const float* wz, const float* xhat, const float* rstd,
                     const float* gamma, int B, int F, float* row_loss, float* loss, float* dfc, float* ln_partial,
                     int* nparts, float* w_partial, float* logits, float* dlogits, float* dz, void* stream);
+/* The self-predictive latent loss (SPR, Schwarzer et al. 2021; BYOL's normalised regression) of the predictor's output
+ * p against the target encoder's latent t, both [B][F], forward and gradient in one kernel.  Per row b, with eps = 1e-12:
+ * ph = p / max(|p|, eps), th = t / max(|t|, eps) (torch's F.normalize), row_loss[b] = sum_f (ph_f - th_f)^2 (= 2 - 2 cos
+ * where neither vector is zero), `loss` (may be NULL) the fixed-order mean of row_loss, dp[b] = (2 / B) (I - ph ph^T)
+ * (ph - th) / |p| for |p| >= eps and (2 / B) (ph - th) / eps below it (the clamp's branch: a zero row is defined and
+ * finite); t gets no gradient.  Norms are float32 square roots of float32 sums of squares: inputs whose squares overflow or
+ * underflow float32 are outside the contract; a non-finite input makes its own row's outputs non-finite and no other's.
+ * One wave per row, no atomics: a rerun writes the same bits.  CURLA_ERR_ARG on a NULL required pointer, B < 1, F < 1 or
+ * F > 1024.  Additive: CURLA_ABI_VERSION stays 8. */
+int curla_pred_loss(const float* p, const float* t, int B, int F, float* row_loss, float* loss, float* dp, void* stream);
 int curla_mean(const float* x, int n, float* out, void* stream);
 
 /* target <- tau*param + (1-tau)*target over a flat parameter block (utils.py:37-41) */
