@@ -231,10 +231,11 @@ def head_fwd_bounds(ref, out2a, noise, lo, hi):
                 pi=(1 - pi * pi) * b_u + N_TANH * U * pi.abs())
 
 
-def curl_ce_bounds(ref, logits):
+def curl_ce_bounds(ref, logits, adds=None):
     """Bounds for row_loss [B] and dlogits [B, B] from curl_ce's result.  se = sum_j exp(l_j - mx) in float32: the
-    subtraction rounds by u |l_j - mx| absolute, which exp makes relative, expf adds 2 u, the sum ceil(B / 64) + 6 adds
-    (a lane's serial adds, six shuffle levels); weighted by p_j the first is u E_p|l - mx| <= u log B (E_p[mx - l] =
+    subtraction rounds by u |l_j - mx| absolute, which exp makes relative, expf adds 2 u, the sum `adds` adds -- by
+    default curl_ce_kernel's ceil(B / 64) + 6 (a lane's serial adds, six shuffle levels); another kernel that evaluates
+    the same formula hands in the length of its own chain (tests/_curl_head_ref.py); weighted by p_j the first is u E_p|l - mx| <= u log B (E_p[mx - l] =
     H(p) - (lse - mx) <= log B).  log turns se's relative error into an absolute one, logf adds 2 u |lse - mx|, the sum
     with mx u |lse|.  So lse is within (adds + 6) u E, E = |mx| + |lse| + 1 + log B, doubled: n_lse.
     row_loss = lse - l_aa: one more rounding, relative to at most |lse| + |l_aa|.
@@ -243,7 +244,7 @@ def curl_ce_bounds(ref, logits):
     A p_j below the smallest normal float32 may come out as a denormal or as zero: 2^-126 absolute on top."""
     l = f64(logits)
     B = l.shape[0]
-    adds = (B + 63) // 64 + 6
+    adds = (B + 63) // 64 + 6 if adds is None else adds
     n_lse = 2 * (adds + 6)
     E = ref["mx"].abs() + ref["lse"].abs() + 1 + math.log(B)
     eye = torch.eye(B, dtype=F64)
